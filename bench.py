@@ -9,7 +9,12 @@ A "step" is one pass of the hot path over one synthetic 800x800 frame (BASELINE.
 rays are sharded over the ranks (contiguous tiles) and one RCCL all_gather reassembles it: strong
 scaling, as BASELINE.json's north_star asks.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = wall time of one timed step).  --dump-outputs DIR then also writes
+what the last timed step returned, DIR/rgb.npy (rays x 3) and DIR/depth.npy (rays), float32; the inputs
+are seeded, so two builds can be compared output for output.
+
+--full adds the extra objects below to that line; they are measured AFTER the headline's timed region:
   roofline      dominant kernel (nerf_mlp_f32_kernel: both launches of a frame), algorithmic FLOP
                 (1 186 816 per MLP point) / HIP-event time, vs 157.3 TFLOP/s fp32 MFMA
   cpu_baseline  the CPU oracle (port of the reference, its 512-point chunking) timed on this host
@@ -17,8 +22,9 @@ Extra objects on that line:
                 BASELINE.json configs[0] (1024 rays, 64 coarse samples only) on the same host
   training      BASELINE.json configs[2]: 4096 rays/iter per GPU, fused fwd+bwd HIP MLP + clip + Adam, f32 and f32x
   config5       BASELINE.json configs[4]: one 1600x1600 frame, fp16 activations / fp32 accumulate, sharded like the headline
-  world_size / per_rank_compute_ms   what torch.distributed really saw, and each rank's own render time per step
-The headline value/metric/dtype are those of configs[1] only; the extra blocks run AFTER its timed region.
+  other_precisions  the same frame in the precisions not selected (N=1 only)
+The headline value/metric/dtype are those of configs[1] only.  world_size / per_rank_compute_ms (what
+torch.distributed really saw, and each rank's own render time per step) are on every line.
 """
 import argparse
 import json
@@ -369,6 +375,77 @@ def cpu_baseline_config1(sd):
                       f"{cores} threads (os.cpu_count()={os.cpu_count()})"}, (o, d, rgb, dep)
 
 
+DUMP_BYTES_MAX = 63 * 10 ** 6            # array data of one --dump-outputs; with the .npy headers below 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """Write `arrays` (name -> tensor whose first dimension is the ray) as path/<name>.npy in float32.  If they exceed
+    DUMP_BYTES_MAX together, every array keeps the same seeded sample of rays, in ray order (fixed by the ray count alone)."""
+    import numpy as np
+    n = next(iter(arrays.values())).shape[0]
+    bytes_per_ray = sum(4 * (t.numel() // max(1, n)) for t in arrays.values())
+    rows = None
+    if n * bytes_per_ray > DUMP_BYTES_MAX:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_BYTES_MAX // bytes_per_ray].sort().values
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        np.save(os.path.join(path, name + ".npy"), (t if rows is None else t[rows]).numpy())
+
+
+def measure_roofline(pkg, net, ren, o, d, args, prec, peak, n, lo, hi, world, value, ms_per_step):
+    """--full: the roofline block of the headline line, from a separate HIP-event pass over this rank's shard."""
+    # dominant-kernel roofline on this rank's shard (HIP events on the launch stream)
+    # (the full networks -- every colour computed -- are timed beside the launches the render makes: separate template instances,
+    #  so their launches land in rows of their own in `rocprofv3 --stats`; --no-full-network-compare drops them)
+    stages = time_stages(pkg, net, ren, o, d, max(1, min(args.steps, 3)), prec, full_coarse=args.compare_full_coarse)
+    mlp_ms_per_launch = (stages["mlp_coarse"] + stages["mlp_fine"]) / 2.0
+    # FLOP actually executed: the coarse launch stops after the sigma head (feature_linear 256x256, views_linears.0
+    # 283x128 and rgb_linear 128x3 = 204 288 FLOP per point are never read by the reference's hierarchical render and are
+    # not evaluated)
+    coarse_flop_per_point = FLOP_PER_POINT - FLOP_DENSITY_SKIPPED
+    dead_tiles, fine_tiles = stages.pop("_dead_fine_tiles"), stages.pop("_fine_tiles")
+    flop_frame_executed = (hi - lo) * (64 * coarse_flop_per_point + 192 * FLOP_PER_POINT)
+    flop_frame_executed -= dead_tiles * 32 * FLOP_DENSITY_SKIPPED        # dead tiles skip the colour branch (every precision)
+    flop_frame_reference = (hi - lo) * POINTS_PER_RAY * FLOP_PER_POINT
+    flop_per_launch = flop_frame_executed / 2.0
+    achieved = flop_per_launch / (mlp_ms_per_launch * 1e-3) / 1e12
+    traffic, traffic_src = None, None
+    try:      # HBM bytes per launch come from separate rocprofv3 --pmc passes (cannot be read in-process);
+        tj = json.load(open(os.path.join(REPO, "profiles", f"traffic_{args.precision}.json")))   # only for the profiled workload
+        if world == 1 and H == 800:
+            traffic, traffic_src = tj["traffic_bytes_per_launch"], f"profiles/traffic_{args.precision}.json (rocprofv3 --pmc, not this run)"
+    except (OSError, ValueError, KeyError):
+        pass
+    roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
+                "frac": round(achieved / (peak / 1e12), 4), "traffic": traffic, "traffic_source": traffic_src,
+                "kernel": {"f32": "nerf_mlp_f32_kernel", "f16": "nerf_mlp_f16s_kernel", "f16m32": "nerf_mlp_f16_kernel", "f32x": "nerf_mlp_f32x_kernel"}[args.precision], "avg_launch_ms": round(mlp_ms_per_launch, 3),
+                "flop_per_frame_executed": flop_frame_executed, "flop_per_frame_reference_algorithm": flop_frame_reference,
+                "fine_tiles_without_density": {"tiles": dead_tiles, "of": fine_tiles,
+                                               "note": "32-sample tiles whose sigma is <= 0 throughout: weight exactly 0 in compositing; "
+                                                       "the fp32 fine launch stops them after the sigma head (scene-dependent)"},
+                "stage_ms": {k: round(v, 3) for k, v in stages.items()}}
+    # SURVEY 8(d)'s own definition: the REFERENCE algorithm's FLOP (303 824 896 per ray) over the measured time.  It exceeds what the
+    # kernels execute -- and may exceed 1 -- by exactly the skipped dead code (coarse colour branch, colours of density-free tiles)
+    roofline["frac_reference_algorithm"] = round(value * POINTS_PER_RAY * FLOP_PER_POINT / (peak * world), 4)
+    if args.compare_full_coarse:
+        # the same frame with the coarse network evaluated in full (its colour computed and dropped, as the reference
+        # does): derived from the measured step time and the two coarse launches timed side by side
+        roofline["rays_per_s_if_coarse_colour_were_computed"] = round(
+            n / ((ms_per_step + stages["mlp_coarse_full_network"] - stages["mlp_coarse"]) * 1e-3), 1)
+        # ... and with, in addition, the colours of the zero-density fine tiles computed (every FLOP of the reference's algorithm):
+        # the SCENE-INDEPENDENT figures of this line
+        full = n / ((ms_per_step + stages["mlp_coarse_full_network"] - stages["mlp_coarse"]
+                     + stages["mlp_fine_full_network"] - stages["mlp_fine"]) * 1e-3)
+        roofline["rays_per_s_if_every_colour_were_computed"] = round(full, 1)
+        roofline["rays_per_s_full_network"] = round(full, 1)
+        roofline["frac_full_network"] = round(full * POINTS_PER_RAY * FLOP_PER_POINT / (peak * world), 4)
+        # the two full-network launches by themselves (kernel time only, this rank's shard)
+        roofline["frac_full_network_kernels"] = round((hi - lo) * POINTS_PER_RAY * FLOP_PER_POINT /
+                                                      ((stages["mlp_coarse_full_network"] + stages["mlp_fine_full_network"]) * 1e-3) / peak, 4)
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -399,7 +476,17 @@ def main():
     ap.add_argument("--precision", default="f32", choices=["f32", "f16", "f32x", "f16m32"],
                     help="f32 (default, the reference's dtype: exact fp32 MFMA), f16 (BASELINE config 5: fp16 "
                          "activations, fp32 accumulate) or f32x (fp32-accurate: hi/lo split operands, 3 fp16 MFMAs per product)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline (per-kernel HIP-event pass), the CPU baselines, the other "
+                         "precisions, training (configs[2]) and config 5; --cpu-sample, --no-extras and --no-full-network-compare "
+                         "trim that part.  Off: the run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; render mode)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode != "render":
+        ap.error("--dump-outputs writes the render path's outputs: it needs --mode render")
     global H, W
     H = W = args.res
 
@@ -498,54 +585,9 @@ def main():
     if rank == 0:
         print(f"[bench] {args.steps} steps: {ms_per_step:.1f} ms/step, {value:.0f} rays/s", file=sys.stderr, flush=True)
 
-    # dominant-kernel roofline on this rank's shard (HIP events on the launch stream)
-    # (the full networks -- every colour computed -- are timed beside the launches the render makes: separate template instances,
-    #  so their launches land in rows of their own in `rocprofv3 --stats`; --no-full-network-compare drops them)
-    stages = time_stages(pkg, net, ren, o, d, max(1, min(args.steps, 3)), prec, full_coarse=args.compare_full_coarse)
-    mlp_ms_per_launch = (stages["mlp_coarse"] + stages["mlp_fine"]) / 2.0
-    # FLOP actually executed: the coarse launch stops after the sigma head (feature_linear 256x256, views_linears.0
-    # 283x128 and rgb_linear 128x3 = 204 288 FLOP per point are never read by the reference's hierarchical render and are
-    # not evaluated)
-    coarse_flop_per_point = FLOP_PER_POINT - FLOP_DENSITY_SKIPPED
-    dead_tiles, fine_tiles = stages.pop("_dead_fine_tiles"), stages.pop("_fine_tiles")
-    flop_frame_executed = (hi - lo) * (64 * coarse_flop_per_point + 192 * FLOP_PER_POINT)
-    flop_frame_executed -= dead_tiles * 32 * FLOP_DENSITY_SKIPPED        # dead tiles skip the colour branch (every precision)
-    flop_frame_reference = (hi - lo) * POINTS_PER_RAY * FLOP_PER_POINT
-    flop_per_launch = flop_frame_executed / 2.0
-    achieved = flop_per_launch / (mlp_ms_per_launch * 1e-3) / 1e12
-    traffic, traffic_src = None, None
-    try:      # HBM bytes per launch come from separate rocprofv3 --pmc passes (cannot be read in-process);
-        tj = json.load(open(os.path.join(REPO, "profiles", f"traffic_{args.precision}.json")))   # only for the profiled workload
-        if world == 1 and H == 800:
-            traffic, traffic_src = tj["traffic_bytes_per_launch"], f"profiles/traffic_{args.precision}.json (rocprofv3 --pmc, not this run)"
-    except (OSError, ValueError, KeyError):
-        pass
-    roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
-                "frac": round(achieved / (peak / 1e12), 4), "traffic": traffic, "traffic_source": traffic_src,
-                "kernel": {"f32": "nerf_mlp_f32_kernel", "f16": "nerf_mlp_f16s_kernel", "f16m32": "nerf_mlp_f16_kernel", "f32x": "nerf_mlp_f32x_kernel"}[args.precision], "avg_launch_ms": round(mlp_ms_per_launch, 3),
-                "flop_per_frame_executed": flop_frame_executed, "flop_per_frame_reference_algorithm": flop_frame_reference,
-                "fine_tiles_without_density": {"tiles": dead_tiles, "of": fine_tiles,
-                                               "note": "32-sample tiles whose sigma is <= 0 throughout: weight exactly 0 in compositing; "
-                                                       "the fp32 fine launch stops them after the sigma head (scene-dependent)"},
-                "stage_ms": {k: round(v, 3) for k, v in stages.items()}}
-    # SURVEY 8(d)'s own definition: the REFERENCE algorithm's FLOP (303 824 896 per ray) over the measured time.  It exceeds what the
-    # kernels execute -- and may exceed 1 -- by exactly the skipped dead code (coarse colour branch, colours of density-free tiles)
-    roofline["frac_reference_algorithm"] = round(value * POINTS_PER_RAY * FLOP_PER_POINT / (peak * world), 4)
-    if args.compare_full_coarse:
-        # the same frame with the coarse network evaluated in full (its colour computed and dropped, as the reference
-        # does): derived from the measured step time and the two coarse launches timed side by side
-        roofline["rays_per_s_if_coarse_colour_were_computed"] = round(
-            n / ((ms_per_step + stages["mlp_coarse_full_network"] - stages["mlp_coarse"]) * 1e-3), 1)
-        # ... and with, in addition, the colours of the zero-density fine tiles computed (every FLOP of the reference's algorithm):
-        # the SCENE-INDEPENDENT figures of this line
-        full = n / ((ms_per_step + stages["mlp_coarse_full_network"] - stages["mlp_coarse"]
-                     + stages["mlp_fine_full_network"] - stages["mlp_fine"]) * 1e-3)
-        roofline["rays_per_s_if_every_colour_were_computed"] = round(full, 1)
-        roofline["rays_per_s_full_network"] = round(full, 1)
-        roofline["frac_full_network"] = round(full * POINTS_PER_RAY * FLOP_PER_POINT / (peak * world), 4)
-        # the two full-network launches by themselves (kernel time only, this rank's shard)
-        roofline["frac_full_network_kernels"] = round((hi - lo) * POINTS_PER_RAY * FLOP_PER_POINT /
-                                                      ((stages["mlp_coarse_full_network"] + stages["mlp_fine_full_network"]) * 1e-3) / peak, 4)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rgb": rgb, "depth": dep})
+    roofline = measure_roofline(pkg, net, ren, o, d, args, prec, peak, n, lo, hi, world, value, ms_per_step) if args.full else None
 
     out = None
     if rank == 0:
@@ -562,19 +604,19 @@ def main():
                           "coarse_pass": ("density-only launch: sigma is the only coarse output the reference reads when "
                                           "N_importance > 0 (volume_renderer.py:335), rgb/depth are bit-identical to running "
                                           "the full coarse network; fp32 fine launch: 32-sample tiles without a single sigma > 0 stop after the sigma head "
-                                          "too (weight exactly 0 in compositing).  --compare-full-network times the full networks beside "
+                                          "too (weight exactly 0 in compositing).  With --full, the full networks are timed beside "
                                           "them on this line: roofline.rays_per_s_full_network / frac_full_network"
                                           ),
                           "rays_per_step": n, "parallelism": f"ray-tile shard x{world} (each rank generates and renders only "
                                                              "its tile) + 1 all_gather",
                           **({"fast_sampling": "ESS/ERT masks, weights_threshold %.2f; the roofline block times the UNMASKED "
                                                "MLP launches" % ren.weights_threshold} if args.fast_sampling else {})},
-               "roofline": roofline,
+               **({"roofline": roofline} if args.full else {}),
                # self-check for a scaling record: what torch.distributed really ran, and every rank's own render time
                "world_size": dist.get_world_size() if dist.is_initialized() else 1,
                "dist_backend": (dist.get_backend() if dist.is_initialized() else None),
                "per_rank_compute_ms": [round(x, 3) for x in per_rank_ms]}
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             base, (ids, ref_rgb, ref_dep) = cpu_baseline(sd, args.cpu_sample)
             base["value"] = round(base["value"], 1)
             out["cpu_baseline"] = base
@@ -626,7 +668,7 @@ def main():
 
     # BASELINE configs[2] and configs[4] on the same line (every rank takes part when N>1), AFTER the headline's timed
     # region; a failure here is reported in its block and never costs the headline measurement
-    if args.extras and H == 800 and not args.fast_sampling:
+    if args.full and args.extras and H == 800 and not args.fast_sampling:
         del net, ren, o, d
         extra = {}
         try:

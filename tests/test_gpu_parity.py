@@ -816,7 +816,7 @@ def test_bench_two_rank_path_on_one_gpu():
     env = dict(os.environ, NERF_BENCH_SHARE_GPU="1", NERF_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1",
                HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--res", "800"]
+           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--res", "800", "--full"]
     res = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -865,6 +865,35 @@ def test_rccl_single_rank_collectives():
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
     assert line["dist_backend"] == "nccl" and line["world_size"] == 1 and line["n_gpus"] == 1 and line["value"] > 0
+
+
+def test_bench_plain_run_dumps_what_its_last_step_rendered(amd, net, tmp_path):
+    """A plain bench run times only the headline steps: its line carries the headline fields and none of the --full blocks.
+    --dump-outputs writes the last timed step's rgb / depth, which are the render of the bench's seeded frame."""
+    import importlib.util
+    import json
+    import subprocess
+    import sys
+    from conftest import REPO
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--res", "200",
+                          "--dump-outputs", str(tmp_path)], cwd=REPO, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["unit"] == "rays/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 2
+    assert abs(out["value"] - 40000 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    assert not {"roofline", "cpu_baseline", "other_precisions", "training", "config5"} & set(out)
+    rgb, dep = np.load(tmp_path / "rgb.npy"), np.load(tmp_path / "depth.npy")
+    assert rgb.dtype == dep.dtype == np.float32 and rgb.shape == (40000, 3) and dep.shape == (40000,)
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    net.precision = "f32"
+    o, d = amd.generate_rays(bench.camera_pose_40(), 200, 200, 0.6911112070083618, "cuda")
+    with torch.no_grad():
+        want_rgb, want_dep = amd.Renderer(net).render({"rays_o": o[None], "rays_d": d[None]})
+    assert torch.equal(torch.from_numpy(rgb), want_rgb.cpu()) and torch.equal(torch.from_numpy(dep), want_dep.cpu())
 
 
 @pytest.mark.parametrize("family", ["base", "sharp", "white", "trained"])

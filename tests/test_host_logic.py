@@ -1,5 +1,6 @@
 """CPU-only checks of host-side logic that needs no GPU: the bench's camera pose is the oracle's, the bench's FLOP accounting
-follows SURVEY 8(d), the package's lazy attributes are complete, and the C header declares exactly what the ctypes binding binds."""
+follows SURVEY 8(d), its output dump is bounded and reproducible, the package's lazy attributes are complete, and the C header
+declares exactly what the ctypes binding binds."""
 import importlib.util
 import os
 import re
@@ -43,3 +44,34 @@ def test_package_lazy_attributes_are_complete():
         assert getattr(pkg, name) is not None
     assert set(pkg.__all__) <= set(dir(pkg))
     assert pkg.training.FusedAdam is not None and pkg.dist.shard_bounds(10, 1, 4) == (3, 6, 3)
+
+
+def test_bench_dump_outputs_is_float32_bounded_and_reproducible(tmp_path):
+    import numpy as np
+    b = _load_bench()
+    small = {"rgb": torch.rand(1000, 3, dtype=torch.float64), "depth": torch.rand(1000)}
+    b.dump_outputs(str(tmp_path / "small"), small)
+    for name, t in small.items():
+        got = np.load(tmp_path / "small" / f"{name}.npy")
+        assert got.dtype == np.float32 and torch.equal(torch.from_numpy(got), t.float())
+    # above the bound every array keeps the SAME seeded sample of rays, in ray order, identically on every call
+    n = 5_000_000                                                   # 80 MB of float32
+    ray = torch.arange(n, dtype=torch.float32)
+    big = {"rgb": ray[:, None].expand(n, 3), "depth": ray}
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), big)
+    files = sorted((tmp_path / "a").iterdir())
+    assert sum(f.stat().st_size for f in files) <= 64 * 10 ** 6
+    rgb, dep = np.load(tmp_path / "a" / "rgb.npy"), np.load(tmp_path / "a" / "depth.npy")
+    assert rgb.shape == (dep.shape[0], 3) and dep.shape[0] > n // 2
+    assert (rgb == dep[:, None]).all() and (np.diff(dep) > 0).all()
+    for f in files:
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+
+
+def test_bench_rejects_a_run_without_timed_steps():
+    import subprocess
+    import sys
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=300)
+    assert res.returncode == 2 and "--steps must be >= 1" in res.stderr, res.stderr[-2000:]

@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--res", type=int, default=200)
     ap.add_argument("--precision", default="f32x", choices=["f32", "f32x"])
     ap.add_argument("--out", default="nerf_train")
+    ap.add_argument("--perturb", action="store_true",
+                    help="train with the reference's stochastic sampling (task: train): jittered coarse depths, random fine u")
     args = ap.parse_args()
     dev = "cuda"
 
@@ -50,7 +52,11 @@ def main():
     torch.manual_seed(0)
     net = nerf.Network().cuda().train()                         # nn.Linear default init, as the reference
     net.precision = args.precision
-    ren = nerf.Renderer(net)
+    ren = nerf.Renderer(net)                                    # deterministic: the held-out evaluation
+    train_ren = ren
+    if args.perturb:
+        train_ren = nerf.Renderer(net)
+        train_ren.task, train_ren.perturb = "train", True
     opt = FusedAdam(net.parameters(), lr=5e-4, eps=1e-8, clip_value=40.0)
     lr0, gen = 5e-4, torch.Generator(device=dev).manual_seed(1)
 
@@ -73,7 +79,7 @@ def main():
             break
         ids = torch.randint(0, O.shape[0], (4096,), device=dev, generator=gen)
         opt.lr = FusedAdam.exponential_lr(lr0, epoch=step / 50.0)          # ExponentialLR, one "epoch" = 50 iterations here
-        loss = train_step(ren, opt, O[ids].contiguous(), D[ids].contiguous(), C[ids].contiguous())
+        loss = train_step(train_ren, opt, O[ids].contiguous(), D[ids].contiguous(), C[ids].contiguous())
     nerf.save_model(net, opt, None, None, args.out, epoch=args.steps // 50, last=True)
     print("saved", os.path.join(args.out, "latest.pth"))
 

@@ -288,6 +288,41 @@ int32_t nerf_render_forward(const float* rays_o, const float* rays_d, int64_t n_
                             float weights_threshold, void* workspace,
                             int64_t workspace_bytes, float* rgb, float* depth, void* stream);
 
+/* ---- stochastic sampling (the reference's task == "train" mode) -----------------------------------------------------
+ * Coarse jitter of volume_renderer.py:48-60: t_coarse [n,64] = lower + (upper - lower) * jitter [n,64], with mids =
+ * 0.5 (t[1:] + t[:-1]), lower = [t0, mids], upper = [mids, t63] of the host-built table t_linear [64]; every operation
+ * separately rounded, bit-equal to the CPU torch expression. */
+int32_t nerf_stratified_samples(const float* t_linear, const float* jitter, int64_t n_rays, float* t_coarse, void* stream);
+
+/* nerf_sample_fine with per-ray tables: the coarse depths of ray r are t_coarse[r * t_ray_stride + s] (stride 0 or 64) and
+ * its u are u[r * u_ray_stride + k] (stride 0 or 128, any order: random u of volume_renderer.py:143-147).  t_sorted =
+ * torch.sort(cat(t_coarse, t_fine)) of the reference's arithmetic (torch_sum62 order, index clamp to 61); the kernel sorts
+ * each ray's u first (t_sorted depends only on the multiset of fine depths).  t_fine, if given, comes back in the caller's u
+ * order.  Both strides 0: exactly nerf_sample_fine.  valid_sorted (fast_sampling) with a non-zero stride: NERF_ERR_INVALID_ARG. */
+int32_t nerf_sample_fine_rays(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                              int64_t u_ray_stride, int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
+                              float weights_threshold, float ert_threshold, void* stream);
+
+/* Adjoint of nerf_sample_fine_rays (same strides; both 0: exactly nerf_sample_fine_backward), float64 accumulation.  The
+ * jittered coarse depths get no gradient: in the reference they depend on no parameter. */
+int32_t nerf_sample_fine_rays_backward(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                                       int64_t u_ray_stride, int64_t n_rays, const float* t_sorted, const float* g_t_sorted,
+                                       float* g_raw_coarse, void* stream);
+
+/* Bytes of scratch nerf_render_forward_stochastic needs for n_rays rays. */
+int64_t nerf_render_stochastic_workspace_bytes(int64_t n_rays, int32_t n_importance);
+
+/* nerf_render_forward in the reference's training sampling mode.  jitter [n,64] (nullable: the shared t_coarse table) and
+ * u_rays [n,128] (nullable: the shared u table) are the reference's two torch.rand draws, in its order.  The output does not
+ * depend on the 2^20-ray blocking.  n_importance 0 or 128; precision NERF_PREC_F32 or NERF_PREC_F32X (fp16 and fast_sampling:
+ * NERF_ERR_INVALID_ARG).  With both draws NULL this computes exactly what nerf_render_forward does. */
+int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d, int64_t n_rays,
+                                       const void* packed_coarse, const void* packed_fine,
+                                       const float* t_coarse, const float* u, const float* jitter, const float* u_rays,
+                                       int32_t n_importance, int32_t white_bkgd, int32_t precision, int32_t fast_sampling,
+                                       float weights_threshold, void* workspace, int64_t workspace_bytes,
+                                       float* rgb, float* depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

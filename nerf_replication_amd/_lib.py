@@ -74,6 +74,14 @@ _PROTOS = {
     "nerf_render_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int32, _c.c_int32]),
     "nerf_render_forward": (_c.c_int32, [_F, _F, _c.c_int64, _F, _F, _F, _F, _c.c_int32, _c.c_int32,
                                          _c.c_int32, _c.c_int32, _c.c_float, _F, _c.c_int64, _F, _F, _c.c_void_p]),
+    # stochastic sampling (task == "train")
+    "nerf_stratified_samples": (_c.c_int32, [_F, _F, _c.c_int64, _F, _c.c_void_p]),
+    "nerf_sample_fine_rays": (_c.c_int32, [_F, _F, _c.c_int64, _F, _c.c_int64, _c.c_int64, _F, _F, _F, _c.c_float, _c.c_float,
+                                           _c.c_void_p]),
+    "nerf_sample_fine_rays_backward": (_c.c_int32, [_F, _F, _c.c_int64, _F, _c.c_int64, _c.c_int64, _F, _F, _F, _c.c_void_p]),
+    "nerf_render_stochastic_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int32]),
+    "nerf_render_forward_stochastic": (_c.c_int32, [_F, _F, _c.c_int64, _F, _F, _F, _F, _F, _F, _c.c_int32, _c.c_int32,
+                                                    _c.c_int32, _c.c_int32, _c.c_float, _F, _c.c_int64, _F, _F, _c.c_void_p]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -870,6 +870,296 @@ void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __rest
   if (ray_ok) reinterpret_cast<f32x4*>(g_raw_c)[ray * S + i] = go;
 }
 
+// ------------------------------------------------------------------------------------ stochastic sampling (task == "train")
+// Coarse jitter (volume_renderer.py:48-60): mids = 0.5 (t[1:] + t[:-1]), lower = [t0, mids], upper = [mids, t63],
+// t = lower + (upper - lower) * jitter, every operation rounded on its own as the CPU torch expression is.
+__global__ __launch_bounds__(256)
+void nerf_stratified_kernel(const float* __restrict__ t_lin, const float* __restrict__ jitter, long long n, float* __restrict__ t_out) {
+  constexpr int S = NERF_N_SAMPLES;
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n * S) return;
+  const int s = (int)(e % S);
+  const float lower = s == 0 ? t_lin[0] : __fmul_rn(0.5f, __fadd_rn(t_lin[s], t_lin[s - 1]));
+  const float upper = s == S - 1 ? t_lin[S - 1] : __fmul_rn(0.5f, __fadd_rn(t_lin[s + 1], t_lin[s]));
+  t_out[e] = __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), jitter[e]));
+}
+
+// Ascending bitonic network over one thread's 128 registers.  Fully unrolled (unroll(full): plain `#pragma unroll` left the
+// array in scratch, 528 B per lane), so every index is a constant and the array lives in VGPRs.
+__device__ __forceinline__ void sort128_ascending(float (&r)[NERF_N_IMPORTANCE]) {
+#pragma clang loop unroll(full)
+  for (int k = 2; k <= NERF_N_IMPORTANCE; k <<= 1) {
+#pragma clang loop unroll(full)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma clang loop unroll(full)
+      for (int i = 0; i < NERF_N_IMPORTANCE; ++i) {
+        const int l = i ^ j;
+        if (l > i) {
+          const float x = r[i], y = r[l];
+          const bool up = (i & k) == 0;
+          r[i] = up ? fminf(x, y) : fmaxf(x, y);
+          r[l] = up ? fmaxf(x, y) : fminf(x, y);
+        }
+      }
+    }
+  }
+}
+
+// Inverse CDF of one u given its searchsorted(right) index: the arithmetic of nerf_sample_fine_kernel's walk.
+__device__ __forceinline__ float inv_cdf_at(const float* cdf, const float* tc, float u, int ind) {
+  constexpr int S = NERF_N_SAMPLES;
+  const int below = min(max(ind - 1, 0), S - 3);
+  const int above = min(ind, S - 3);                   // clamp to 61: tail collapse
+  const float cb = cdf[below], ca = cdf[above];
+  const float bb = __fmul_rn(0.5f, __fadd_rn(tc[below + 1], tc[below]));
+  const float ba = __fmul_rn(0.5f, __fadd_rn(tc[above + 1], tc[above]));
+  float denom = __fsub_rn(ca, cb);
+  if (denom < 1e-5f) denom = 1.0f;
+  const float frac = __fdiv_rn(__fsub_rn(u, cb), denom);
+  return __fadd_rn(bb, __fmul_rn(frac, __fsub_rn(ba, bb)));
+}
+
+// nerf_sample_fine_kernel with a coarse table and a u table per ray (t of ray r at t_coarse + r * t_stride, u at
+// u + r * u_stride; stride 0 shares one table).  t_sorted depends only on the MULTISET of fine depths, so each lane sorts its
+// ray's 128 u ascending (registers, bitonic) and then runs the deterministic kernel's monotone walk, insertion repair and
+// two-way merge unchanged.  LDS: the 64 x 193-float rows of the deterministic kernel (49 408 B) + one 65-float coarse row per
+// ray (16 640 B) = 66 048 B per 64-ray workgroup.  The row's slots [0,128) hold sigma, then the ray's u (staged coalesced),
+// then the sorted u the walk overwrites in place with the fine depths (slot j <= k is written only after u[k] was read).
+constexpr int kTcPitch = 65;       // odd pitch, as kBufPitch
+struct SampleRaysArgs {
+  const float* raw_c;        // [n,64,4]
+  const float* t_coarse;     // [64] or [n,64]
+  long long t_stride;        // 0 or 64
+  const float* u;            // [128] or [n,128]
+  long long u_stride;        // 0 or 128
+  long long n_rays;
+  float* t_sorted;           // [n,192]
+  float* t_fine;             // optional [n,128], in the caller's u order
+};
+__global__ __launch_bounds__(kSampleThreads)
+void nerf_sample_fine_rays_kernel(SampleRaysArgs a) {
+  constexpr int S = NERF_N_SAMPLES, F = NERF_N_IMPORTANCE, NB = S - 1;
+  __shared__ float s_tc[kSampleThreads * kTcPitch];
+  __shared__ float s_buf[kSampleThreads * kBufPitch];
+  const int lane = threadIdx.x;
+  const long long ray0 = (long long)blockIdx.x * kSampleThreads;
+  for (int r = 0; r < kSampleThreads; ++r) {          // lane = coarse sample index
+    long long rg = ray0 + r;
+    if (rg >= a.n_rays) rg = a.n_rays - 1;
+    s_buf[r * kBufPitch + lane] = a.raw_c[rg * (S * 4) + lane * 4 + 3];
+    s_tc[r * kTcPitch + lane] = a.t_coarse[rg * a.t_stride + lane];
+  }
+  __syncthreads();
+  float* buf = s_buf + lane * kBufPitch;
+  float* cdf = buf + F;
+  const float* tc = s_tc + lane * kTcPitch;
+  float T = 1.0f;
+  for (int i = 0; i < S; ++i) {
+    const float sigma = fmaxf(buf[i], 0.0f);
+    const float delta = (i < S - 1) ? __fsub_rn(tc[i + 1], tc[i]) : 1e10f;
+    const float alpha = alpha_of(sigma, delta);
+    const float w = __fmul_rn(T, alpha);
+    if (i >= 1 && i <= S - 2) cdf[i - 1] = __fadd_rn(w, 1e-5f);
+    T = __fmul_rn(T, fminf(fmaxf(__fsub_rn(1.0f, alpha), 1e-10f), 1.0f));
+  }
+  const float wsum = torch_sum62(cdf);
+  {
+    float run = 0.0f, prev = cdf[0];
+    cdf[0] = 0.0f;
+    for (int m = 1; m < NB; ++m) {
+      run = __fadd_rn(run, __fdiv_rn(prev, wsum));
+      prev = cdf[m];
+      cdf[m] = run;
+    }
+  }
+  __syncthreads();                                     // every lane has read its sigmas: slots [0,128) take the rays' u
+  for (int r = 0; r < kSampleThreads; ++r) {
+    long long rg = ray0 + r;
+    if (rg >= a.n_rays) rg = a.n_rays - 1;
+    s_buf[r * kBufPitch + lane] = a.u[rg * a.u_stride + lane];
+    s_buf[r * kBufPitch + 64 + lane] = a.u[rg * a.u_stride + 64 + lane];
+  }
+  __syncthreads();
+  const long long ray = ray0 + lane;
+  const bool ray_ok = ray < a.n_rays;
+  if (a.t_fine && ray_ok) {                            // in the caller's order: searchsorted(right) by bisection
+    for (int k = 0; k < F; ++k) {
+      const float u = buf[k];
+      int lo = 0, hi = NB;
+      while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] <= u) lo = mid + 1; else hi = mid; }
+      a.t_fine[ray * F + k] = inv_cdf_at(cdf, tc, u, lo);
+    }
+  }
+  {
+    float r[F];
+#pragma clang loop unroll(full)
+    for (int k = 0; k < F; ++k) r[k] = buf[k];
+    sort128_ascending(r);
+#pragma clang loop unroll(full)
+    for (int k = 0; k < F; ++k) buf[k] = r[k];
+  }
+  int ind = 0;
+  for (int k = 0; k < F; ++k) {
+    const float u = buf[k];
+    while (ind < NB && cdf[ind] <= u) ++ind;
+    const float v = inv_cdf_at(cdf, tc, u, ind);
+    int j = k;
+    while (j > 0 && buf[j - 1] > v) { buf[j] = buf[j - 1]; --j; }
+    buf[j] = v;
+  }
+  {
+    int ic = S - 1, jf = F - 1;
+    for (int k = S + F - 1; k >= 0; --k) {
+      const bool take_f = (ic < 0) || (jf >= 0 && buf[jf] >= tc[ic]);
+      if (take_f) { buf[k] = buf[jf]; --jf; }
+      else { buf[k] = tc[ic]; --ic; }
+    }
+  }
+  __syncthreads();
+  for (int i = 0; i < S + F; ++i) {
+    const int e = lane + 64 * i, r = e / (S + F), k = e - r * (S + F);
+    const long long rg = ray0 + r;
+    if (rg < a.n_rays) a.t_sorted[rg * (S + F) + k] = s_buf[r * kBufPitch + k];
+  }
+}
+
+// nerf_sample_bwd_kernel with per-ray tables (strides as nerf_sample_fine_rays_kernel).  Each wave sorts its ray's u across
+// the wave first (bitonic, lane l holds elements l and l + 64): the merged-slot logic (k + ic with the running maximum, ties
+// coarse first) then holds as in the deterministic kernel.  LDS per 4-ray workgroup: 4 coarse rows, the cdf rows and the
+// float64 cdf adjoint rows, 4 352 B.
+__global__ __launch_bounds__(256)
+void nerf_sample_rays_bwd_kernel(const float* __restrict__ raw_c, const float* __restrict__ t_coarse, long long t_stride,
+                                 const float* __restrict__ u_in, long long u_stride, long long n_rays,
+                                 const float* __restrict__ g_tsorted, float* __restrict__ g_raw_c) {
+  constexpr int S = NERF_N_SAMPLES, F = NERF_N_IMPORTANCE, NB = S - 1;
+  static_assert(S == 64 && F == 128, "lane = coarse sample, two fine samples per lane");
+  __shared__ float s_tc[4][S];
+  __shared__ float s_cdf[4][S];
+  __shared__ double s_gcdf[4][S];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long ray_slot = (long long)blockIdx.x * 4 + wv;
+  const bool ray_ok = ray_slot < n_rays;
+  const long long ray = ray_ok ? ray_slot : n_rays - 1;
+  s_tc[wv][lane] = t_coarse[ray * t_stride + lane];
+  s_gcdf[wv][lane] = 0.0;
+  float us[2] = {u_in[ray * u_stride + lane], u_in[ray * u_stride + 64 + lane]};
+#pragma unroll
+  for (int k = 2; k <= F; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (j == 64) {                                   // k == 128: partners share the lane
+        const float x = us[0], y = us[1];
+        us[0] = fminf(x, y); us[1] = fmaxf(x, y);
+      } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int idx = lane + 64 * h;
+          const float p = __shfl_xor(us[h], j);
+          const bool up = (idx & k) == 0, low = (idx & j) == 0;
+          us[h] = (low == up) ? fminf(us[h], p) : fmaxf(us[h], p);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const float* tcw = s_tc[wv];
+  const int i = lane;
+  const float s_raw = raw_c[ray * (S * 4) + i * 4 + 3];
+  const float sigma = fmaxf(s_raw, 0.0f);
+  const float delta = (i < S - 1) ? __fsub_rn(tcw[i + 1], tcw[i]) : 1e10f;
+  const float e = expf(__fmul_rn(-sigma, delta));
+  const float alpha = __fsub_rn(1.0f, e);
+  const float om = __fsub_rn(1.0f, alpha);
+  const float q = fminf(fmaxf(om, 1e-10f), 1.0f);
+  float Ti = 1.0f;
+  {
+    float T = 1.0f;
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+      if (lane == j) Ti = T;
+      T = __fmul_rn(T, lane_bcast(q, j));
+    }
+  }
+  const bool inner = i >= 1 && i <= S - 2;
+  const float we = __fadd_rn(__fmul_rn(Ti, alpha), 1e-5f);
+  const float wsum = torch_sum62_of([&](int k) { return lane_bcast(we, k + 1); });
+  const float pdf = __fdiv_rn(we, wsum);
+  float cdf_m = 0.0f;
+  {
+    float run = 0.0f;
+#pragma unroll
+    for (int m = 1; m < NB; ++m) {
+      run = __fadd_rn(run, lane_bcast(pdf, m));
+      if (lane == m) cdf_m = run;
+    }
+  }
+  s_cdf[wv][lane] = cdf_m;
+  __syncthreads();
+  const float* gts = g_tsorted + ray * (S + F);
+  float* cdf = s_cdf[wv];
+  double* gcdf = s_gcdf[wv];
+  int ic_carry = 0;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int k = lane + 64 * half;                   // rank of this fine sample among the ray's (sorted) fine samples
+    const float u = us[half];
+    int ind = 0;
+    for (int m = 0; m < NB; ++m) ind += cdf[m] <= u;
+    const int below = min(max(ind - 1, 0), S - 3), above = min(ind, S - 3);
+    const float cb = cdf[below], ca = cdf[above];
+    const float bb = __fmul_rn(0.5f, __fadd_rn(tcw[below + 1], tcw[below]));
+    const float ba = __fmul_rn(0.5f, __fadd_rn(tcw[above + 1], tcw[above]));
+    const float draw_ = __fsub_rn(ca, cb);
+    const bool live = !(draw_ < 1e-5f);
+    const float denom = live ? draw_ : 1.0f;
+    const float num = __fsub_rn(u, cb);
+    const float v = __fadd_rn(bb, __fmul_rn(__fdiv_rn(num, denom), __fsub_rn(ba, bb)));
+    int ic = 0;
+    for (int j = 0; j < S; ++j) ic += tcw[j] <= v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(ic, d);
+      if (lane >= d) ic = max(ic, o);
+    }
+    ic = max(ic, ic_carry);
+    ic_carry = __shfl(ic, 63);
+    const double g = (double)gts[k + ic];
+    const double g_frac = g * (double)__fsub_rn(ba, bb);
+    double g_cb = -g_frac / (double)denom, g_ca = 0.0;
+    if (live) { const double gden = -g_frac * (double)num / ((double)denom * (double)denom); g_ca += gden; g_cb -= gden; }
+    atomicAdd(&gcdf[below], g_cb);
+    atomicAdd(&gcdf[above], g_ca);
+  }
+  __syncthreads();
+  double sfx = lane < NB ? gcdf[lane] : 0.0;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const double o = __shfl_down(sfx, d);
+    if (lane + d < 64) sfx += o;
+  }
+  double gpdf_excl = __shfl_down(sfx, 1);
+  if (lane == 63) gpdf_excl = 0.0;
+  double gpdf_i = __shfl_up(gpdf_excl, 1);
+  if (!inner) gpdf_i = 0.0;
+  double dot = inner ? gpdf_i * (double)we : 0.0;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) dot += __shfl_xor(dot, d);
+  const double g_w = inner ? (gpdf_i / (double)wsum - dot / ((double)wsum * (double)wsum)) : 0.0;
+  double sf2 = g_w * (double)alpha * (double)Ti;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const double o = __shfl_down(sf2, d);
+    if (lane + d < 64) sf2 += o;
+  }
+  double suf = __shfl_down(sf2, 1);
+  if (lane == 63) suf = 0.0;
+  double g_alpha = g_w * (double)Ti;
+  if (om >= 1e-10f && om <= 1.0f) g_alpha -= suf / (double)q;
+  f32x4 go = {0.f, 0.f, 0.f, 0.f};
+  go.w = s_raw > 0.0f ? (float)(g_alpha * (double)delta * (double)e) : 0.0f;
+  if (ray_ok) reinterpret_cast<f32x4*>(g_raw_c)[ray * S + i] = go;
+}
+
 // ------------------------------------------------------------------------------------ training: live tiles of a backward pass
 // d loss / d raw is exactly zero wherever relu(sigma) = 0 (alpha = 0, weight 0: nerf_composite_bwd_kernel writes zeros there),
 // and wherever the coarse density does not move any fine sample.  A 32-point tile (the unit of the chain kernel) whose
@@ -1426,6 +1716,54 @@ int32_t nerf_sample_fine_backward(const float* raw_coarse, const float* t_coarse
   return check_launch("nerf_sample_bwd_kernel");
 }
 
+int32_t nerf_stratified_samples(const float* t_linear, const float* jitter, int64_t n_rays, float* t_coarse, void* stream) {
+  if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_stratified_samples: bad size");
+  if (n_rays == 0) return NERF_OK;
+  if (!t_linear || !jitter || !t_coarse) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_stratified_samples: null argument");
+  const long long ne = (long long)n_rays * NERF_N_SAMPLES;
+  hipLaunchKernelGGL(nerf_stratified_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     t_linear, jitter, (long long)n_rays, t_coarse);
+  return check_launch("nerf_stratified_kernel");
+}
+
+static bool bad_strides(int64_t t_ray_stride, int64_t u_ray_stride) {
+  return (t_ray_stride != 0 && t_ray_stride != NERF_N_SAMPLES) || (u_ray_stride != 0 && u_ray_stride != NERF_N_IMPORTANCE);
+}
+
+int32_t nerf_sample_fine_rays(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                              int64_t u_ray_stride, int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
+                              float weights_threshold, float ert_threshold, void* stream) {
+  if (n_rays < 0 || bad_strides(t_ray_stride, u_ray_stride))
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: bad size or stride (t: 0 or 64, u: 0 or 128)");
+  if (t_ray_stride == 0 && u_ray_stride == 0)
+    return nerf_sample_fine(raw_coarse, t_coarse, u, n_rays, t_sorted, t_fine, valid_sorted, weights_threshold, ert_threshold, stream);
+  if (valid_sorted) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: fast_sampling needs the shared tables");
+  if (n_rays == 0) return NERF_OK;
+  if (!raw_coarse || !t_coarse || !u || !t_sorted) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: null argument");
+  SampleRaysArgs a;
+  a.raw_c = raw_coarse; a.t_coarse = t_coarse; a.t_stride = t_ray_stride; a.u = u; a.u_stride = u_ray_stride;
+  a.n_rays = n_rays; a.t_sorted = t_sorted; a.t_fine = t_fine;
+  const unsigned blocks = (unsigned)((n_rays + kSampleThreads - 1) / kSampleThreads);
+  hipLaunchKernelGGL(nerf_sample_fine_rays_kernel, dim3(blocks), dim3(kSampleThreads), 0, (hipStream_t)stream, a);
+  return check_launch("nerf_sample_fine_rays_kernel");
+}
+
+int32_t nerf_sample_fine_rays_backward(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                                       int64_t u_ray_stride, int64_t n_rays, const float* t_sorted, const float* g_t_sorted,
+                                       float* g_raw_coarse, void* stream) {
+  if (n_rays < 0 || bad_strides(t_ray_stride, u_ray_stride))
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays_backward: bad size or stride (t: 0 or 64, u: 0 or 128)");
+  if (t_ray_stride == 0 && u_ray_stride == 0)
+    return nerf_sample_fine_backward(raw_coarse, t_coarse, u, n_rays, t_sorted, g_t_sorted, g_raw_coarse, stream);
+  if (n_rays == 0) return NERF_OK;
+  if (!raw_coarse || !t_coarse || !u || !t_sorted || !g_t_sorted || !g_raw_coarse)
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays_backward: null argument");
+  hipLaunchKernelGGL(nerf_sample_rays_bwd_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                     raw_coarse, t_coarse, (long long)t_ray_stride, u, (long long)u_ray_stride, (long long)n_rays, g_t_sorted,
+                     g_raw_coarse);
+  return check_launch("nerf_sample_rays_bwd_kernel");
+}
+
 int32_t nerf_viewdirs_backward(const float* gsave, int64_t n_rays, int32_t n_samples, const float* w_views,
                                const float* viewdirs, float* g_viewdirs, void* stream) {
   if (n_rays < 0 || n_samples <= 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_viewdirs_backward: bad size");
@@ -1893,6 +2231,75 @@ static int32_t render_block(const float* rays_o, const float* rays_d, int64_t n_
     if (rc) return rc;
   }
   return nerf_composite(raw_f, t_sorted, S, n_rays, (int32_t)S, white_bkgd, rgb, depth, nullptr, stream);
+}
+
+// Stochastic render (task == "train", no grad): the deterministic block's stages with a per-ray coarse table (jittered) and a
+// per-ray u table.  Workspace per block: the deterministic one (shared tables, no fast_sampling) + the jittered depths [n,64].
+int64_t nerf_render_stochastic_workspace_bytes(int64_t n_rays_frame, int32_t n_importance) {
+  if (n_rays_frame < 0) return -1;
+  const int64_t n_rays = n_rays_frame < render_block_rays() ? n_rays_frame : render_block_rays();
+  return nerf_render_workspace_bytes(n_rays_frame, n_importance, 0) + align256(n_rays * NERF_N_SAMPLES * (int64_t)sizeof(float));
+}
+
+int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d, int64_t n_rays,
+                                       const void* packed_coarse, const void* packed_fine,
+                                       const float* t_coarse, const float* u, const float* jitter, const float* u_rays,
+                                       int32_t n_importance, int32_t white_bkgd, int32_t precision, int32_t fast_sampling,
+                                       float weights_threshold, void* workspace, int64_t workspace_bytes,
+                                       float* rgb, float* depth, void* stream) {
+  (void)weights_threshold;
+  if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: bad size");
+  if (n_importance != 0 && n_importance != NERF_N_IMPORTANCE)
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: n_importance must be 0 or 128");
+  if (precision != NERF_PREC_F32 && precision != NERF_PREC_F32X)
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: precision must be f32 or f32x");
+  if (fast_sampling) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: fast_sampling is not supported");
+  if (n_rays == 0) return NERF_OK;
+  if (!rays_o || !rays_d || !packed_coarse || !t_coarse || !rgb || !depth || !workspace ||
+      (n_importance && (!packed_fine || !u)))
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: null argument");
+  if (workspace_bytes < nerf_render_stochastic_workspace_bytes(n_rays, n_importance))
+    return fail(NERF_ERR_WORKSPACE, "%s", "nerf_render_forward_stochastic: workspace too small");
+  const int64_t B = render_block_rays();
+  const int64_t S = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
+  const int64_t nbmax = n_rays < B ? n_rays : B;
+  char* ws = (char*)workspace;
+  float* raw_c = (float*)ws;
+  char* rest = ws + align256(nbmax * NERF_N_SAMPLES * 4 * (int64_t)sizeof(float));
+  float* t_sorted = (float*)rest;
+  float* raw_f = (float*)(rest + align256(nbmax * S * (int64_t)sizeof(float)));
+  float* t_jit = (float*)(ws + nerf_render_workspace_bytes(n_rays, n_importance, 0));
+  for (int64_t r0 = 0; r0 < n_rays; r0 += B) {
+    const int64_t nb = n_rays - r0 < B ? n_rays - r0 : B;
+    const float* o = rays_o + 3 * r0;
+    const float* d = rays_d + 3 * r0;
+    const float* tc = t_coarse;
+    int64_t tcs = 0;
+    int rc;
+    if (jitter) {
+      rc = nerf_stratified_samples(t_coarse, jitter + NERF_N_SAMPLES * r0, nb, t_jit, stream);
+      if (rc) return rc;
+      tc = t_jit; tcs = NERF_N_SAMPLES;
+    }
+    if (n_importance == 0) {
+      rc = nerf_mlp_forward_rays(o, d, tc, tcs, nb, NERF_N_SAMPLES, packed_coarse, raw_c, precision, stream);
+      if (rc) return rc;
+      rc = nerf_composite(raw_c, tc, tcs, nb, NERF_N_SAMPLES, white_bkgd, rgb + 3 * r0, depth + r0, nullptr, stream);
+      if (rc) return rc;
+      continue;
+    }
+    rc = nerf_mlp_forward_rays_density(o, d, tc, tcs, nb, NERF_N_SAMPLES, packed_coarse, raw_c, precision, stream);
+    if (rc) return rc;
+    rc = u_rays ? nerf_sample_fine_rays(raw_c, tc, tcs, u_rays + NERF_N_IMPORTANCE * r0, NERF_N_IMPORTANCE, nb, t_sorted, nullptr,
+                                        nullptr, 0.f, 0.f, stream)
+                : nerf_sample_fine_rays(raw_c, tc, tcs, u, 0, nb, t_sorted, nullptr, nullptr, 0.f, 0.f, stream);
+    if (rc) return rc;
+    rc = nerf_mlp_forward_rays_for_compositing(o, d, t_sorted, S, nb, (int32_t)S, packed_fine, raw_f, precision, stream);
+    if (rc) return rc;
+    rc = nerf_composite(raw_f, t_sorted, S, nb, (int32_t)S, white_bkgd, rgb + 3 * r0, depth + r0, nullptr, stream);
+    if (rc) return rc;
+  }
+  return NERF_OK;
 }
 
 }  // extern "C"

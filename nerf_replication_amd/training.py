@@ -6,6 +6,10 @@ coarse weights -- the coarse network learns through the sample positions (SURVEY
 forward runs the SAVE-mode fused kernels and the backward is the chain of adjoint kernels behind the
 C ABI (nerf_composite_backward, nerf_mlp_backward, nerf_sample_fine_backward); torch.autograd only
 carries the 48 parameter gradients back to the optimizer.  No ATen op computes on this path.
+
+In the reference's training sampling mode (Renderer.task == "train") the step takes the two draws of Renderer._draws: the
+jittered coarse depths (nerf_stratified_samples) go to the coarse forward / backward and the sampler with a per-ray stride of
+64, the per-ray u to the sampler and its adjoint with a stride of 128.  Without draws every launch is the deterministic one.
 """
 import ctypes
 
@@ -20,7 +24,7 @@ def _ptr_array(tensors):
 
 class RenderFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, renderer, rays_o, rays_d, *params):
+    def forward(ctx, renderer, rays_o, rays_d, draws, *params):
         lib = _lib.load()
         net = renderer.net
         dev = rays_o.device
@@ -28,6 +32,17 @@ class RenderFunction(torch.autograd.Function):
         st = _lib.stream_of(dev)
         t_c, u = renderer._get_tables(dev)
         S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
+        jitter, u_rays = draws if draws is not None else (None, None)
+        t_cs, u_s = 0, 0                          # per-ray strides of the coarse table and of u (0: the shared tables)
+        if jitter is not None:
+            t_lin = t_c
+            t_c = torch.empty((n, S_c), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.nerf_stratified_samples(_lib.ptr(t_lin), _lib.ptr(jitter), n, _lib.ptr(t_c), st),
+                           "nerf_stratified_samples")
+            t_cs = S_c
+        if u_rays is not None:
+            u, u_s = u_rays, _lib.N_IMPORTANCE
         pk_c, pk_f = net.packed(""), net.packed("fine")
         prec = _lib.PRECISIONS[getattr(net, "precision", "f32")]
         f32 = dict(dtype=torch.float32, device=dev)
@@ -40,10 +55,14 @@ class RenderFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             # coarse pass: only its sigma is ever used (it places the fine samples; the coarse colour is never
             # composited) -> the density-only forward / backward pair
-            _lib.check(lib.nerf_mlp_forward_rays_save_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c,
+            _lib.check(lib.nerf_mlp_forward_rays_save_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), t_cs, n, S_c,
                                                               pk_c.data_ptr(), _lib.ptr(raw_c), _lib.ptr(save_c), prec, st), "forward(coarse)")
-            _lib.check(lib.nerf_sample_fine(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted), None, None,
-                                            0.0, 0.0, st), "nerf_sample_fine")
+            if draws is None:
+                _lib.check(lib.nerf_sample_fine(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted), None, None,
+                                                0.0, 0.0, st), "nerf_sample_fine")
+            else:
+                _lib.check(lib.nerf_sample_fine_rays(_lib.ptr(raw_c), _lib.ptr(t_c), t_cs, _lib.ptr(u), u_s, n, _lib.ptr(t_sorted),
+                                                     None, None, 0.0, 0.0, st), "nerf_sample_fine_rays")
             # fine pass: its raw goes to compositing only, and its gradient will come from compositing's adjoint (zero
             # wherever sigma <= 0): tiles without density skip the colour branch and its stores (exact, see the header)
             _lib.check(lib.nerf_mlp_forward_rays_save_for_compositing(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
@@ -54,6 +73,7 @@ class RenderFunction(torch.autograd.Function):
         ctx.prec = prec
         ctx.n = n
         ctx.params = params
+        ctx.stochastic = (t_c, t_cs, u, u_s) if draws is not None else None
         ctx.save_for_backward(rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f)
         return rgb, depth
 
@@ -65,6 +85,9 @@ class RenderFunction(torch.autograd.Function):
         dev = rays_o.device
         st = _lib.stream_of(dev)
         t_c, u = renderer._get_tables(dev)
+        t_cs, u_s = 0, 0
+        if ctx.stochastic is not None:
+            t_c, t_cs, u, u_s = ctx.stochastic
         S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
         f32 = dict(dtype=torch.float32, device=dev)
         g_rgb = g_rgb.contiguous().to(torch.float32)
@@ -98,15 +121,20 @@ class RenderFunction(torch.autograd.Function):
                 cnt_f = gsave[int(lib.nerf_train_live_count_offset(n * S_f))].view(torch.int32).clone()
             # coarse pass: depths -> coarse density -> coarse MLP parameters
             g_raw_c = torch.empty((n, S_c, 4), **f32)
-            _lib.check(lib.nerf_sample_fine_backward(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted),
-                                                     _lib.ptr(g_t), _lib.ptr(g_raw_c), st), "nerf_sample_fine_backward")
+            if ctx.stochastic is None:
+                _lib.check(lib.nerf_sample_fine_backward(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted),
+                                                         _lib.ptr(g_t), _lib.ptr(g_raw_c), st), "nerf_sample_fine_backward")
+            else:
+                _lib.check(lib.nerf_sample_fine_rays_backward(_lib.ptr(raw_c), _lib.ptr(t_c), t_cs, _lib.ptr(u), u_s, n,
+                                                              _lib.ptr(t_sorted), _lib.ptr(g_t), _lib.ptr(g_raw_c), st),
+                           "nerf_sample_fine_rays_backward")
             cap = getattr(renderer, "capture_adjoints", None)
             if cap is not None:       # tests: the per-ray sampler adjoint d loss / d raw_coarse and d loss / d t_sorted (parity attribution)
                 cap["g_raw_coarse"], cap["g_t_sorted"], cap["raw_coarse"] = g_raw_c.clone(), g_t.clone(), raw_c.clone()
                 cap["t_sorted"] = t_sorted.clone()
             _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params[:24]]), pk_b.data_ptr(), prec, st))
             gsave_c = gsave[: int(lib.nerf_train_grad_floats(n * S_c))]
-            _lib.check(lib.nerf_mlp_backward_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c,
+            _lib.check(lib.nerf_mlp_backward_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), t_cs, n, S_c,
                                                      pk_b.data_ptr(), _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave_c),
                                                      None, _ptr_array(grads[:24]), prec, st), "nerf_mlp_backward(coarse)")
             stats = getattr(renderer, "live_tile_stats", None)
@@ -115,12 +143,13 @@ class RenderFunction(torch.autograd.Function):
                 # count was cloned above, before its gsave was reused
                 cnt_c = gsave_c[int(lib.nerf_train_live_count_offset(n * S_c))].view(torch.int32).clone()
                 stats.append((cnt_f, n * S_f // 32, cnt_c, n * S_c // 32))
-        return (None, None, None) + tuple(g.to(p.dtype) for g, p in zip(grads, params))
+        return (None, None, None, None) + tuple(g.to(p.dtype) for g, p in zip(grads, params))
 
 
-def render_with_grad(renderer, rays_o, rays_d):
+def render_with_grad(renderer, rays_o, rays_d, jitter=None, u=None):
     """rays [n,3] (contiguous fp32, on the GPU) -> (rgb [n,3], depth [n]) attached to the autograd graph of
-    the 48 network parameters (coarse sub-model first, then fine, state_dict order)."""
+    the 48 network parameters (coarse sub-model first, then fine, state_dict order).  `jitter` [n,64] / `u` [n,128]:
+    the reference's training-mode draws (Renderer._draws); None keeps the shared deterministic table."""
     net = renderer.net
     if getattr(net, "precision", "f32") not in ("f32", "f32x"):
         raise NotImplementedError("training runs on the fp32-accurate paths: precision 'f32' (exact fp32 MFMA) or 'f32x' "
@@ -128,7 +157,8 @@ def render_with_grad(renderer, rays_o, rays_d):
     if renderer.N_importance != _lib.N_IMPORTANCE or renderer.fast_sampling:
         raise NotImplementedError("training path is built for N_importance=128 without fast_sampling")
     params = tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
-    return RenderFunction.apply(renderer, rays_o, rays_d, *params)
+    draws = (jitter, u) if (jitter is not None or u is not None) else None
+    return RenderFunction.apply(renderer, rays_o, rays_d, draws, *params)
 
 
 class FusedAdam(torch.optim.Optimizer):

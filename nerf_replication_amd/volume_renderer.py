@@ -4,7 +4,9 @@ kernels behind include/nerf_mi355x.h.
 
 Loadable through the reference's loader (src/models/nerf/renderer/make_renderer.py:4-8), see
 INTEGRATION.md.  Hyper-parameters follow the reference's *effective* behaviour:
-N_samples 64, N_importance 128, near/far 2/6, deterministic sampling, white background.
+N_samples 64, N_importance 128, near/far 2/6, white background.  Sampling is deterministic unless the reference's
+training mode is selected (cfg.task == "train": jittered coarse depths if perturb, random inverse-CDF u); its random numbers
+are the one ATen op on that path (Renderer._rand, see README "Stochastic sampling").
 """
 import os
 import sys
@@ -55,9 +57,6 @@ class Renderer:
         self._workspace = None
         if self.N_samples != _lib.N_SAMPLES or self.N_importance not in (0, _lib.N_IMPORTANCE):
             raise ValueError("HIP renderer is built for N_samples=64 and N_importance in {0,128}")
-        if self.perturb or self.task == "train":
-            raise NotImplementedError("stochastic (task=='train') sampling is unreachable from the reference's "
-                                      "configs (SURVEY F2) and is not built")
 
     # host-built, bit-sensitive tables: torch.linspace on the CPU, then copied
     def _get_tables(self, dev):
@@ -67,6 +66,21 @@ class Renderer:
             u = torch.linspace(0.0, 1.0, steps=_lib.N_IMPORTANCE).to(dev)
             tabs = self._tables[dev] = (t_c, u)
         return tabs
+
+    def _rand(self, shape, device):
+        """The reference's random draws (volume_renderer.py:59, :145): torch.rand on the rays' device, so torch.manual_seed
+        controls the samples.  Overridable: tests replay recorded draws through it."""
+        return torch.rand(*shape, device=device)
+
+    def _draws(self, n, dev):
+        """(jitter [n,64] or None, u [n,128] or None) of one render() call, drawn in the reference's order: the coarse jitter
+        first (if perturb), then the fine u (if task == "train" and there is a fine pass).  Read from the instance at
+        render() time, as the reference does."""
+        jitter = self._rand((n, self.N_samples), dev).to(torch.float32).contiguous() if self.perturb else None
+        u = None
+        if self.task == "train" and self.N_importance > 0:
+            u = self._rand((n, self.N_importance), dev).to(torch.float32).contiguous()
+        return jitter, u
 
     def _get_workspace(self, nbytes, dev):
         ws = self._workspace
@@ -85,6 +99,16 @@ class Renderer:
         n = B * N
         o = rays_o.detach().reshape(n, 3).to(torch.float32).contiguous()
         d = rays_d.detach().reshape(n, 3).to(torch.float32).contiguous()
+        stochastic = bool(self.perturb) or self.task == "train"
+        if stochastic:
+            prec_name = getattr(self.net, "precision", "f32")
+            if _lib.PRECISIONS[prec_name] not in (_lib.PREC_F32, _lib.PREC_F32X):
+                raise NotImplementedError(f"stochastic sampling (task={self.task!r}, perturb={bool(self.perturb)}) runs in "
+                                          f"precision 'f32' or 'f32x', not {prec_name!r}")
+            if self.fast_sampling:
+                raise NotImplementedError(f"stochastic sampling (task={self.task!r}, perturb={bool(self.perturb)}) is not "
+                                          "built with fast_sampling")
+            jitter, u_rays = self._draws(n, dev)
         if torch.is_grad_enabled() and getattr(self.net, "training", False) and \
                 any(p.requires_grad for p in self.net.parameters()):
             # training call (trainers/nerf.py:27 under trainer.py:53-60): forward with activation save,
@@ -92,6 +116,8 @@ class Renderer:
             render_with_grad = _sibling("training").render_with_grad
             if n == 0:
                 return torch.empty((0, 3), device=dev), torch.empty((0,), device=dev)
+            if stochastic:
+                return render_with_grad(self, o, d, jitter, u_rays)
             return render_with_grad(self, o, d)
         t_c, u = self._get_tables(dev)
         pk_c = self.net.packed("")
@@ -99,6 +125,17 @@ class Renderer:
         rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
         depth = torch.empty((n,), dtype=torch.float32, device=dev)
         if n == 0:
+            return rgb, depth
+        if stochastic:
+            nbytes = int(lib.nerf_render_stochastic_workspace_bytes(n, self.N_importance))
+            ws = self._get_workspace(nbytes, dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.nerf_render_forward_stochastic(
+                    _lib.ptr(o), _lib.ptr(d), n, pk_c.data_ptr(), pk_f.data_ptr() if pk_f is not None else None,
+                    _lib.ptr(t_c), _lib.ptr(u), _lib.ptr(jitter), _lib.ptr(u_rays),
+                    int(self.N_importance), int(bool(self.white_bkgd)), _lib.PRECISIONS[prec_name], 0,
+                    float(self.weights_threshold), ws.data_ptr(), ws.numel(),
+                    _lib.ptr(rgb), _lib.ptr(depth), _lib.stream_of(dev)), "nerf_render_forward_stochastic")
             return rgb, depth
         fast = int(bool(self.fast_sampling) and self.N_importance > 0)
         nbytes = int(lib.nerf_render_workspace_bytes(n, self.N_importance, fast))

@@ -31,7 +31,7 @@ extern "C" {
  *     past the last point write the pad32 padding rows of every region;
  *   - with dead-tile skipping (default; NERF_DEAD_TILE_SKIP=0 in the environment disables it) the g_z rows of tiles whose incoming
  *     gradient is zero throughout are left unwritten in `gsave` (point mode zero-fills the g_zv region, which
- *     nerf_viewdirs_backward sums over);
+ *     nerf_viewdirs_backward sums over; ray mode leaves them unwritten, and nerf_rays_viewdirs_backward skips them by their flag);
  *   - nerf_mlp_forward_rays_save_for_compositing may omit the rows of density-free tiles; it stamps the buffer, and a backward pass
  *     that runs without the live-tile list on such a buffer poisons grads[alpha_linear.bias] with NaN instead of reading them;
  *   - nerf_composite_backward refuses more than 192 samples per ray. */
@@ -196,6 +196,33 @@ int32_t nerf_mlp_backward_points(const float* pts, int64_t n_rays, int32_t n_sam
  * views_linears.0.weight [128,283] (nn.Linear layout), `viewdirs` the forward's [n_rays,3]. */
 int32_t nerf_viewdirs_backward(const float* gsave, int64_t n_rays, int32_t n_samples, const float* w_views,
                                const float* viewdirs, float* g_viewdirs, void* stream);
+
+/* Gradients with respect to the rays (Renderer.render with rays_o / rays_d requiring grad; DESIGN section 2, "Gradients with
+ * respect to the rays").  Three steps per training-style backward:
+ *  1. nerf_mlp_backward_rays_x: nerf_mlp_backward (density_only == 0) / nerf_mlp_backward_density (density_only != 0) that, in
+ *     addition, writes g_x [P,3] = d loss / d (o + d t) of every point when g_x is non-null (next to g_t, which stays optional;
+ *     zero for the tiles that dead-tile skipping drops).  grads == NULL: the data-gradient chain alone -- no weight-gradient
+ *     launch, nothing written to any gradient array (a frozen network).  g_t, g_x and the g_z rows in `gsave` are bit-identical
+ *     to a call with grads, and to a call without g_x.
+ *  2. nerf_rays_viewdirs_backward, right after the FINE pass's call 1 and before anything reuses its `gsave`: the fine pass's view
+ *     direction v = d / |d| (rounded as the forward kernels round it) takes sum_s g_zv[ray, s] through views_linears.0's 27
+ *     direction columns (`w_views`: the fine views_linears.0.weight [128,283]) and the normalisation:
+ *     g_rays_d_view [n,3] = (g_v - v (v . g_v)) / |d|.  Reads the tile flags of `gsave`: dead tiles' unwritten rows are skipped.
+ *  3. nerf_rays_backward: per ray, with the 64 coarse depths t_coarse (t_ray_stride 0: one shared table; 64: one row per ray),
+ *     the coarse pass's g_x_coarse [n,64,3] (its incoming gradient is the sampler adjoint's), the merged depths t_sorted [n,192]
+ *     and the fine pass's g_x_fine [n,192,3]:
+ *       g_rays_o = sum_s g_x_coarse + sum_s g_x_fine,  g_rays_d = sum_s t_coarse g_x_coarse + sum_s t_sorted g_x_fine + g_rays_d_view.
+ *     One wave per ray, fixed summation order (no atomics): deterministic.  g_x_coarse, g_x_fine, g_rays_d_view may be NULL
+ *     (term left out).  f32 / f32x chains only, like nerf_mlp_backward. */
+int32_t nerf_mlp_backward_rays_x(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
+                                 int64_t n_rays, int32_t n_samples, const void* packed_bwd, const float* draw,
+                                 const float* save, float* gsave, float* g_t, float* g_x, float* const grads[24],
+                                 int32_t density_only, int32_t precision, void* stream);
+int32_t nerf_rays_viewdirs_backward(const float* rays_d, int64_t n_rays, int32_t n_samples, const float* gsave,
+                                    const float* w_views, float* g_rays_d_view, void* stream);
+int32_t nerf_rays_backward(int64_t n_rays, const float* t_coarse, int64_t t_ray_stride, const float* g_x_coarse,
+                           const float* t_sorted, const float* g_x_fine, const float* g_rays_d_view, float* g_rays_o,
+                           float* g_rays_d, void* stream);
 
 /* Adjoint of nerf_composite (autograd of volume_renderer.py:414-432 with :67-96): g_rgb [n,3], g_depth [n]
  * (nullable) -> g_raw [n,S,4] and, if given, g_t [n,S] (the direct dependence of the image on the sample

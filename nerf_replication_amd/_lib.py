@@ -82,6 +82,11 @@ _PROTOS = {
     "nerf_render_stochastic_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int32]),
     "nerf_render_forward_stochastic": (_c.c_int32, [_F, _F, _c.c_int64, _F, _F, _F, _F, _F, _F, _c.c_int32, _c.c_int32,
                                                     _c.c_int32, _c.c_int32, _c.c_float, _F, _c.c_int64, _F, _F, _c.c_void_p]),
+    # gradients with respect to the rays
+    "nerf_mlp_backward_rays_x": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F, _F,
+                                              _c.POINTER(_c.c_void_p), _c.c_int32, _c.c_int32, _c.c_void_p]),
+    "nerf_rays_viewdirs_backward": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_void_p]),
+    "nerf_rays_backward": (_c.c_int32, [_c.c_int64, _F, _c.c_int64, _F, _F, _F, _F, _F, _F, _c.c_void_p]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -1329,6 +1329,32 @@ void nerf_ssim_kernel(const float* __restrict__ pred, const float* __restrict__ 
 // The view direction of a ray enters views_linears.0 through its 27-channel encoding (network.py:224-225, :63-66) and is
 // shared by the ray's samples: g_dir_enc = W_v[:, 256:283]^T (sum_s g_zv[ray, s]), then the chain rule through
 // [d, sin(2^k d), cos(2^k d)] (freq.py:31-32).  One 128-thread workgroup per ray; 3.5 k MACs per ray -- negligible.
+// viewdir_grad_block: the part after the sum, shared by the point-mode and the ray-mode entry.  Thread o brings column o of
+// sum_s g_zv (`acc`) and, for o < 3, component o of the direction the forward encoded (`dir`); threads 0..2 get component o
+// of d loss / d dir back.
+__device__ __forceinline__ float viewdir_grad_block(float acc, float dir, const float* __restrict__ w_views, float* G, float* E) {
+  const int o = threadIdx.x;
+  G[o] = acc;
+  __syncthreads();
+  if (o < 27) {
+    float e = 0.0f;
+    for (int k = 0; k < 128; ++k) e = fmaf(G[k], w_views[k * 283 + 256 + o], e);
+    E[o] = e;
+  }
+  __syncthreads();
+  float g = 0.0f;
+  if (o < 3) {
+    g = E[o];
+    for (int k = 0; k < 4; ++k) {
+      const float f = (float)(1 << k);
+      float sv, cv;
+      sincosf(dir * f, &sv, &cv);
+      g += f * (cv * E[3 + 6 * k + o] - sv * E[3 + 6 * k + 3 + o]);
+    }
+  }
+  return g;
+}
+
 __global__ __launch_bounds__(128)
 void nerf_viewdirs_bwd_kernel(const float* __restrict__ gzv, long long n_rays, int n_samples, const float* __restrict__ w_views,
                               const float* __restrict__ viewdirs, float* __restrict__ g_viewdirs) {
@@ -1338,24 +1364,99 @@ void nerf_viewdirs_bwd_kernel(const float* __restrict__ gzv, long long n_rays, i
   const int o = threadIdx.x;
   float acc = 0.0f;
   for (int s = 0; s < n_samples; ++s) acc += gzv[(ray * n_samples + s) * 128 + o];
-  G[o] = acc;
-  __syncthreads();
-  if (o < 27) {
-    float e = 0.0f;
-    for (int k = 0; k < 128; ++k) e = fmaf(G[k], w_views[k * 283 + 256 + o], e);
-    E[o] = e;
+  const float g = viewdir_grad_block(acc, o < 3 ? viewdirs[ray * 3 + o] : 0.0f, w_views, G, E);
+  if (o < 3) g_viewdirs[ray * 3 + o] = g;
+}
+
+// ------------------------------------------------------------------------------------ d loss / d rays (Renderer.render under autograd)
+// The rays adjoint ("Gradients with respect to the rays").  Ray mode: the fine pass encodes v = d / |d|, rounded
+// as the forward kernels do, so g_d gets J_norm(d)^T g_v = (g_v - v (v . g_v)) / |d| from the fine pass's g_zv rows.  A dead tile
+// (flag 0 in the list of the pass, TrainGrad::off_flags) has no workgroup and unwritten g_zv rows: it is skipped here, exactly (its
+// rows would be zero).  Without a list (*count == -1) every row was written.
+__global__ __launch_bounds__(128)
+void nerf_rays_viewdirs_bwd_kernel(const float* __restrict__ gzv, const int* __restrict__ flags, const int* __restrict__ count,
+                                   int n_samples, const float* __restrict__ w_views, const float* __restrict__ rays_d,
+                                   float* __restrict__ g_dview) {
+  __shared__ float G[128];
+  __shared__ float E[27];
+  const long long ray = blockIdx.x;
+  const int o = threadIdx.x;
+  const bool list = *count >= 0;
+  float acc = 0.0f;
+  for (int s = 0; s < n_samples; ++s) {
+    const long long p = ray * n_samples + s;
+    if (list && flags[p >> 5] == 0) continue;          // (uniform)
+    acc += gzv[p * 128 + o];
   }
-  __syncthreads();
+  float nrm = 1.0f, v = 0.0f;
   if (o < 3) {
-    const float d = viewdirs[ray * 3 + o];
-    float g = E[o];
-    for (int k = 0; k < 4; ++k) {
-      const float f = (float)(1 << k);
-      float sv, cv;
-      sincosf(d * f, &sv, &cv);
-      g += f * (cv * E[3 + 6 * k + o] - sv * E[3 + 6 * k + 3 + o]);
+    const float d0 = rays_d[ray * 3 + 0], d1 = rays_d[ray * 3 + 1], d2 = rays_d[ray * 3 + 2];
+    nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+    v = __fdiv_rn(o == 0 ? d0 : o == 1 ? d1 : d2, nrm);
+  }
+  const float gv = viewdir_grad_block(acc, v, w_views, G, E);
+  const float vg = __shfl(v, 0) * __shfl(gv, 0) + __shfl(v, 1) * __shfl(gv, 1) + __shfl(v, 2) * __shfl(gv, 2);
+  if (o < 3) g_dview[ray * 3 + o] = (gv - v * vg) / nrm;
+}
+
+// g_t [P] = g_x . d of the point's ray, after a chain that wrote g_x (BwdArgs::g_t bit 0): the arithmetic of the chain's own
+// g_t store (gt = 0; gt += g_x[c] * d[c], c = 0..2), so the result is bit-identical to a call without g_x.
+__global__ __launch_bounds__(256)
+void nerf_gt_of_gx_kernel(const float* __restrict__ gx, const float* __restrict__ rays_d, int n_samples, long long P,
+                          float* __restrict__ g_t) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const long long ray = p / n_samples;
+  float gt = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) gt += gx[p * 3 + c] * rays_d[ray * 3 + c];
+  g_t[p] = gt;
+}
+
+// Per-ray sums of the rays adjoint: x = o + d t at the 64 coarse and the 192 merged fine samples, so
+//   g_o = sum_s gx_c + sum_s gx_f,   g_d = sum_s t_c gx_c + sum_s t_s gx_f + g_dview.
+// One wave per ray: lane l takes coarse sample l and fine samples l, l + 64, l + 128; a fixed xor butterfly finishes the sums
+// (no atomics: the result does not depend on scheduling).  gx_c / gx_f / g_dview may each be null (term left out).
+__global__ __launch_bounds__(256)
+void nerf_rays_bwd_kernel(long long n_rays, const float* __restrict__ t_c, long long t_stride, const float* __restrict__ gx_c,
+                          const float* __restrict__ t_s, const float* __restrict__ gx_f, const float* __restrict__ g_dview,
+                          float* __restrict__ g_o, float* __restrict__ g_d) {
+  constexpr int S_C = NERF_N_SAMPLES, S_F = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
+  static_assert(S_C == 64 && S_F % 64 == 0, "one coarse sample per lane");
+  const int lane = threadIdx.x & 63;
+  const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ray >= n_rays) return;                           // (whole waves; no barrier below)
+  float so[3] = {0.f, 0.f, 0.f}, sd[3] = {0.f, 0.f, 0.f};
+  if (gx_c != nullptr) {
+    const float t = t_c[ray * t_stride + lane];
+    const long long p = ray * S_C + lane;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float g = gx_c[p * 3 + c];
+      so[c] += g; sd[c] += t * g;
     }
-    g_viewdirs[ray * 3 + o] = g;
+  }
+  if (gx_f != nullptr) {
+#pragma unroll
+    for (int k = 0; k < S_F / 64; ++k) {
+      const long long p = ray * S_F + k * 64 + lane;
+      const float t = t_s[p];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float g = gx_f[p * 3 + c];
+        so[c] += g; sd[c] += t * g;
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { so[c] += __shfl_xor(so[c], off); sd[c] += __shfl_xor(sd[c], off); }
+  if (lane < 3) {
+    const float o_l = lane == 0 ? so[0] : lane == 1 ? so[1] : so[2];
+    const float d_l = lane == 0 ? sd[0] : lane == 1 ? sd[1] : sd[2];
+    g_o[ray * 3 + lane] = o_l;
+    g_d[ray * 3 + lane] = g_dview != nullptr ? d_l + g_dview[ray * 3 + lane] : d_l;
   }
 }
 
@@ -1775,6 +1876,34 @@ int32_t nerf_viewdirs_backward(const float* gsave, int64_t n_rays, int32_t n_sam
   return check_launch("nerf_viewdirs_bwd_kernel");
 }
 
+int32_t nerf_rays_viewdirs_backward(const float* rays_d, int64_t n_rays, int32_t n_samples, const float* gsave,
+                                    const float* w_views, float* g_rays_d_view, void* stream) {
+  if (n_rays < 0 || n_samples <= 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_viewdirs_backward: bad size");
+  if (n_rays == 0) return NERF_OK;
+  if (!rays_d || !gsave || !w_views || !g_rays_d_view) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_viewdirs_backward: null argument");
+  if (n_rays > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_viewdirs_backward: too many rays for one launch");
+  const long long P = n_rays * n_samples;
+  hipLaunchKernelGGL(nerf_rays_viewdirs_bwd_kernel, dim3((unsigned)n_rays), dim3(128), 0, (hipStream_t)stream,
+                     gsave + TrainGrad::off_gzv(P), reinterpret_cast<const int*>(gsave + TrainGrad::off_flags(P)),
+                     reinterpret_cast<const int*>(gsave + TrainGrad::off_count(P)), n_samples, w_views, rays_d, g_rays_d_view);
+  return check_launch("nerf_rays_viewdirs_bwd_kernel");
+}
+
+int32_t nerf_rays_backward(int64_t n_rays, const float* t_coarse, int64_t t_ray_stride, const float* g_x_coarse,
+                           const float* t_sorted, const float* g_x_fine, const float* g_rays_d_view, float* g_rays_o,
+                           float* g_rays_d, void* stream) {
+  if (n_rays < 0 || (t_ray_stride != 0 && t_ray_stride != NERF_N_SAMPLES))
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_backward: bad size or stride (t: 0 or 64)");
+  if (n_rays == 0) return NERF_OK;
+  if (!g_rays_o || !g_rays_d || (g_x_coarse && !t_coarse) || (g_x_fine && !t_sorted))
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_backward: null argument");
+  const long long blocks = (n_rays + 3) / 4;
+  if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_backward: too many rays for one launch");
+  hipLaunchKernelGGL(nerf_rays_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long long)n_rays,
+                     t_coarse, (long long)t_ray_stride, g_x_coarse, t_sorted, g_x_fine, g_rays_d_view, g_rays_o, g_rays_d);
+  return check_launch("nerf_rays_bwd_kernel");
+}
+
 int32_t nerf_adam_step(int32_t n_tensors, float* const params[], const float* const grads[], float* const exp_avg[],
                        float* const exp_avg_sq[], const int64_t numel[], float lr, float beta1, float beta2, float eps,
                        float weight_decay, float clip_value, int64_t step, void* stream) {
@@ -1830,12 +1959,21 @@ int32_t nerf_pack_model_bwd(const float* const params[24], void* packed_bwd_v, i
   return check_launch("nerf_pack_bwd_kernel");
 }
 
-// grads[24]: device pointers in state_dict order (nn.Linear layouts), accumulated into (caller zeroes them)
+// grads[24]: device pointers in state_dict order (nn.Linear layouts), accumulated into (caller zeroes them); nullptr: the
+// data-gradient chain alone (a frozen network: no weight-gradient launch, nothing to poison)
 // shared by the ray-mode and the point-mode entry: data-gradient chain, then the weight / bias gradients
 static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* const grads[24], int32_t precision, void* stream) {
   // density only: both chains skip the colour branch in the kernel (ray mode), and its three weight-gradient jobs are skipped
   // here: their result is exactly zero
   BwdArgs a = a_in;
+  // ray mode with g_x: the chain writes g_x through its one output pointer (BwdArgs::g_t, bit 0 set), g_t follows from it
+  float* const g_t_out = a.g_t;
+  float* const g_x_out = a.g_x;
+  const bool ray_x = !pts_mode && g_x_out != nullptr;
+  if (ray_x) {
+    a.g_t = reinterpret_cast<float*>(reinterpret_cast<uintptr_t>(g_x_out) | 1);
+    a.g_x = nullptr;
+  }
   const bool dens = a.density_only != 0;
   const long long P = a.n_points;
   const float* draw = a.draw; const float* save = a.save; float* gsave = a.gsave;
@@ -1857,12 +1995,12 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
       rc = check_launch("nerf_tile_scan_kernel");
       if (rc) return rc;
       // dead tiles have no workgroup: their g_t / g_x is the zero written here
-      if (!pts_mode && a.g_t && hipMemsetAsync(a.g_t, 0, (size_t)P * sizeof(float), (hipStream_t)stream) != hipSuccess)
+      if (!pts_mode && !ray_x && g_t_out && hipMemsetAsync(g_t_out, 0, (size_t)P * sizeof(float), (hipStream_t)stream) != hipSuccess)
         return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward: memset failed");
-      if (pts_mode && a.g_x && hipMemsetAsync(a.g_x, 0, (size_t)P * 3 * sizeof(float), (hipStream_t)stream) != hipSuccess)
+      if (g_x_out && hipMemsetAsync(g_x_out, 0, (size_t)P * 3 * sizeof(float), (hipStream_t)stream) != hipSuccess)
         return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward: memset failed");
       // point mode has one more consumer of gsave: nerf_viewdirs_backward sums the g_zv rows of ALL samples of a ray, dead
-      // tiles included -- their rows are the zeros written here (ray mode: nothing reads a dead tile's rows)
+      // tiles included -- their rows are the zeros written here (ray mode: nerf_rays_viewdirs_backward skips dead tiles by their flag)
       if (pts_mode && hipMemsetAsync(gsave + TrainGrad::off_gzv(P), 0, (size_t)TrainSave::pad32(P) * 128 * sizeof(float), (hipStream_t)stream) != hipSuccess)
         return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward: memset failed");
       live = lv; n_live = cnt;
@@ -1871,9 +2009,12 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
       if (hipMemsetAsync(gsave + TrainGrad::off_count(P), 0xFF, sizeof(int), (hipStream_t)stream) != hipSuccess)   // count = -1: no list
         return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward: memset failed");
       // a dense backward needs every row of `save`: refuse (NaN in the alpha-bias gradient) a buffer whose forward skipped rows
-      hipLaunchKernelGGL(nerf_check_stamp_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, save + TrainSave::off_stamp(P), grads[nerf::P_BA]);
-      rc = check_launch("nerf_check_stamp_kernel");
-      if (rc) return rc;
+      // (chain only: the skipped tiles' incoming gradient is zero by the forward's contract, so is all the chain makes of them)
+      if (grads) {
+        hipLaunchKernelGGL(nerf_check_stamp_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, save + TrainSave::off_stamp(P), grads[nerf::P_BA]);
+        rc = check_launch("nerf_check_stamp_kernel");
+        if (rc) return rc;
+      }
     }
   }
   if (precision == NERF_PREC_F32X) {
@@ -1892,6 +2033,13 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
     rc = check_launch("nerf_mlp_bwd_f32_kernel");
   } else return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_mlp_backward: f32 or f32x only");
   if (rc) return rc;
+  if (ray_x && g_t_out) {
+    hipLaunchKernelGGL(nerf_gt_of_gx_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g_x_out, a.rays_d,
+                       a.n_samples, P, g_t_out);
+    rc = check_launch("nerf_gt_of_gx_kernel");
+    if (rc) return rc;
+  }
+  if (!grads) return NERF_OK;                       // chain only
   // weight / bias gradients: grad_W = g_z^T @ input, grad_b = sum g_z   (network.py:22-47 layers)
   const float* pe = save + TrainSave::off_pe(P);
   const float* dpe = save + TrainSave::off_dpe(P);
@@ -1992,6 +2140,23 @@ int32_t nerf_mlp_backward_density(const float* rays_o, const float* rays_d, cons
   a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride; a.n_points = n_rays * n_samples;
   a.n_samples = n_samples; a.packed_bwd = (const float*)packed_bwd_v; a.draw = draw; a.save = save; a.gsave = gsave; a.g_t = g_t;
   a.density_only = 1;
+  return mlp_backward_impl(a, false, grads, precision, stream);
+}
+
+int32_t nerf_mlp_backward_rays_x(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
+                                 int64_t n_rays, int32_t n_samples, const void* packed_bwd_v, const float* draw,
+                                 const float* save, float* gsave, float* g_t, float* g_x, float* const grads[24],
+                                 int32_t density_only, int32_t precision, void* stream) {
+  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_rays_x: bad size");
+  if (n_rays == 0) return NERF_OK;
+  if (!rays_o || !rays_d || !tvals || !packed_bwd_v || !draw || !save || !gsave)
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_rays_x: null argument");
+  if (grads)
+    for (int i = 0; i < 24; ++i) if (!grads[i]) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_rays_x: null gradient pointer");
+  BwdArgs a{};
+  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride; a.n_points = n_rays * n_samples;
+  a.n_samples = n_samples; a.packed_bwd = (const float*)packed_bwd_v; a.draw = draw; a.save = save; a.gsave = gsave; a.g_t = g_t;
+  a.g_x = g_x; a.density_only = density_only != 0;
   return mlp_backward_impl(a, false, grads, precision, stream);
 }
 

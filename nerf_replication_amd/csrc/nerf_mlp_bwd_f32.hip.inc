@@ -17,7 +17,10 @@ struct BwdArgs {
   const float* draw;         // [P,4] gradient of raw (r,g,b,sigma)
   const float* save;         // TrainSave of the forward
   float* gsave;              // TrainGrad: g_zv [P,128], g_f [P,256], g_z7..g_z0 [P,256] each
-  float* g_t;                // optional [P]: d loss / d t through the points (= g_x . rays_d)
+  float* g_t;                // optional [P]: d loss / d t through the points (= g_x . rays_d).  Ray mode, bit 0 set: the address
+                             // (bit cleared) of g_x [P,3] = d loss / d (o + d t) instead, written in place of g_t (the launcher's
+                             // encoding, mlp_backward_impl: ONE output pointer stays live across the chain, as before; a second
+                             // one cost the f32x density chain an SGPR spill to scratch)
   // point mode (Network.forward under autograd, network.py:199-258: explicit points instead of o + d*t)
   const float* pts;          // [P,3]
   float* g_x;                // optional [P,3]: d loss / d points
@@ -198,6 +201,13 @@ void nerf_mlp_bwd_f32_kernel(BwdArgs a) {
         const float gc = gx[c] + __shfl_xor(gx[c], 32);
         if (valid && h == 0) a.g_x[p * 3 + c] = gc;
       }
+    }
+  } else if (reinterpret_cast<uintptr_t>(a.g_t) & 1) {       // g_x (see BwdArgs::g_t)
+    float* const gxp = reinterpret_cast<float*>(reinterpret_cast<uintptr_t>(a.g_t) - 1);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float gc = gx[c] + __shfl_xor(gx[c], 32);
+      if (valid && h == 0) gxp[p * 3 + c] = gc;
     }
   } else if (a.g_t != nullptr) {
     float gt = 0.0f;

@@ -393,10 +393,23 @@ void nerf_mlp_bwd_f32x_kernel(BwdArgs a) {
         }
       }
     } else if (a.g_t != nullptr) {
-      float gt = 0.0f;
+      uintptr_t out = reinterpret_cast<uintptr_t>(a.g_t);
+      // (opaque here: hoisted out of the tile loop, the decoded g_x address was one more SGPR pair live across the chain, and the
+      //  density instance spilled to scratch)
+      asm volatile("" : "+s"(out));
+      if (out & 1) {                                    // g_x (see BwdArgs::g_t)
+        float* const gxp = reinterpret_cast<float*>(out - 1);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) gt += (gx[c] + __shfl_xor(gx[c], 32)) * rd[c];
-      if (valid && h == 0) a.g_t[p] = gt;
+        for (int c = 0; c < 3; ++c) {
+          const float gc = gx[c] + __shfl_xor(gx[c], 32);
+          if (valid && h == 0) gxp[p * 3 + c] = gc;
+        }
+      } else {
+        float gt = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gt += (gx[c] + __shfl_xor(gx[c], 32)) * rd[c];
+        if (valid && h == 0) reinterpret_cast<float*>(out)[p] = gt;
+      }
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -7,6 +7,11 @@ forward runs the SAVE-mode fused kernels and the backward is the chain of adjoin
 C ABI (nerf_composite_backward, nerf_mlp_backward, nerf_sample_fine_backward); torch.autograd only
 carries the 48 parameter gradients back to the optimizer.  No ATen op computes on this path.
 
+The rays are differentiable inputs too (camera-pose refinement, iNeRF-style pose estimation): when rays_o / rays_d require grad,
+both MLP chains also emit the point gradients (nerf_mlp_backward_rays_x) and nerf_rays_viewdirs_backward / nerf_rays_backward
+reduce them per ray.  Parameters that do not require grad get None; with none at all the chains run alone (no weight-gradient
+launch).  A step whose rays do not require grad runs exactly the launches it ran before.
+
 In the reference's training sampling mode (Renderer.task == "train") the step takes the two draws of Renderer._draws: the
 jittered coarse depths (nerf_stratified_samples) go to the coarse forward / backward and the sampler with a per-ray stride of
 64, the per-ray u to the sampler and its adjoint with a stride of 128.  Without draws every launch is the deterministic one.
@@ -92,12 +97,19 @@ class RenderFunction(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         g_rgb = g_rgb.contiguous().to(torch.float32)
         g_depth = None if g_depth is None else g_depth.contiguous().to(torch.float32)
-        # 24 coarse + 24 fine gradient tensors as views of one zeroed buffer (one memset instead of 48)
-        flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
-        grads, off = [], 0
-        for p in params:
-            grads.append(flat[off:off + p.numel()].view(p.shape))
-            off += p.numel()
+        need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        need_params = ctx.needs_input_grad[4:]
+        grads, off = None, 0
+        if any(need_params):
+            # 24 coarse + 24 fine gradient tensors as views of one zeroed buffer (one memset instead of 48)
+            flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
+            grads = []
+            for p in params:
+                grads.append(flat[off:off + p.numel()].view(p.shape))
+                off += p.numel()
+        # no parameter needs grad: NULL gradient arrays, the chains run alone
+        grads_f = None if grads is None else _ptr_array(grads[24:])
+        grads_c = None if grads is None else _ptr_array(grads[:24])
         prec = ctx.prec
         nbwd = int(lib.nerf_packed_bwd_bytes(prec))
         with torch.cuda.device(dev):
@@ -112,9 +124,21 @@ class RenderFunction(torch.autograd.Function):
             _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params[24:]]), pk_b.data_ptr(), prec, st))
             gsave = torch.empty(int(lib.nerf_train_grad_floats(n * S_f)), **f32)
             g_t_pts = torch.empty((n, S_f), **f32)
-            _lib.check(lib.nerf_mlp_backward(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
-                                             pk_b.data_ptr(), _lib.ptr(g_raw_f), _lib.ptr(save_f), _lib.ptr(gsave),
-                                             _lib.ptr(g_t_pts), _ptr_array(grads[24:]), prec, st), "nerf_mlp_backward(fine)")
+            if not need_rays:
+                _lib.check(lib.nerf_mlp_backward(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
+                                                 pk_b.data_ptr(), _lib.ptr(g_raw_f), _lib.ptr(save_f), _lib.ptr(gsave),
+                                                 _lib.ptr(g_t_pts), grads_f, prec, st), "nerf_mlp_backward(fine)")
+            else:
+                g_x_f = torch.empty((n, S_f, 3), **f32)
+                g_dview = torch.empty((n, 3), **f32)
+                _lib.check(lib.nerf_mlp_backward_rays_x(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
+                                                        pk_b.data_ptr(), _lib.ptr(g_raw_f), _lib.ptr(save_f), _lib.ptr(gsave),
+                                                        _lib.ptr(g_t_pts), _lib.ptr(g_x_f), grads_f, 0, prec, st),
+                           "nerf_mlp_backward_rays_x(fine)")
+                # the view-direction term reads the fine g_zv rows: before the coarse pass reuses gsave
+                w_views = params[24 + 16].detach().contiguous()           # model_fine views_linears.0.weight [128,283]
+                _lib.check(lib.nerf_rays_viewdirs_backward(_lib.ptr(rays_d), n, S_f, _lib.ptr(gsave), _lib.ptr(w_views),
+                                                           _lib.ptr(g_dview), st), "nerf_rays_viewdirs_backward")
             g_t.add_(g_t_pts)                     # plumbing: one elementwise add of two [n,192] buffers
             cnt_f = None
             if getattr(renderer, "live_tile_stats", None) is not None:
@@ -134,28 +158,46 @@ class RenderFunction(torch.autograd.Function):
                 cap["t_sorted"] = t_sorted.clone()
             _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params[:24]]), pk_b.data_ptr(), prec, st))
             gsave_c = gsave[: int(lib.nerf_train_grad_floats(n * S_c))]
-            _lib.check(lib.nerf_mlp_backward_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), t_cs, n, S_c,
-                                                     pk_b.data_ptr(), _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave_c),
-                                                     None, _ptr_array(grads[:24]), prec, st), "nerf_mlp_backward(coarse)")
+            if not need_rays:
+                _lib.check(lib.nerf_mlp_backward_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), t_cs, n, S_c,
+                                                         pk_b.data_ptr(), _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave_c),
+                                                         None, grads_c, prec, st), "nerf_mlp_backward(coarse)")
+            else:
+                g_x_c = torch.empty((n, S_c, 3), **f32)
+                _lib.check(lib.nerf_mlp_backward_rays_x(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), t_cs, n, S_c,
+                                                        pk_b.data_ptr(), _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave_c),
+                                                        None, _lib.ptr(g_x_c), grads_c, 1, prec, st),
+                           "nerf_mlp_backward_rays_x(coarse)")
+                g_o, g_d = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32)
+                _lib.check(lib.nerf_rays_backward(n, _lib.ptr(t_c), t_cs, _lib.ptr(g_x_c), _lib.ptr(t_sorted), _lib.ptr(g_x_f),
+                                                  _lib.ptr(g_dview), _lib.ptr(g_o), _lib.ptr(g_d), st), "nerf_rays_backward")
             stats = getattr(renderer, "live_tile_stats", None)
             if stats is not None:
                 # (live tiles, tiles) of the coarse pass as 1-element device tensors: no host sync here; the fine pass's
                 # count was cloned above, before its gsave was reused
                 cnt_c = gsave_c[int(lib.nerf_train_live_count_offset(n * S_c))].view(torch.int32).clone()
                 stats.append((cnt_f, n * S_f // 32, cnt_c, n * S_c // 32))
-        return (None, None, None, None) + tuple(g.to(p.dtype) for g, p in zip(grads, params))
+        g_rays = (g_o if need_rays and ctx.needs_input_grad[1] else None, g_d if need_rays and ctx.needs_input_grad[2] else None)
+        return (None,) + g_rays + (None,) + tuple(g.to(p.dtype) if need else None
+                                                  for g, p, need in zip(grads or [None] * len(params), params, need_params))
 
 
-def render_with_grad(renderer, rays_o, rays_d, jitter=None, u=None):
-    """rays [n,3] (contiguous fp32, on the GPU) -> (rgb [n,3], depth [n]) attached to the autograd graph of
-    the 48 network parameters (coarse sub-model first, then fine, state_dict order).  `jitter` [n,64] / `u` [n,128]:
-    the reference's training-mode draws (Renderer._draws); None keeps the shared deterministic table."""
-    net = renderer.net
-    if getattr(net, "precision", "f32") not in ("f32", "f32x"):
+def check_differentiable(renderer):
+    """Raise NotImplementedError for the modes without adjoint kernels (fp16 precisions, fast_sampling, N_importance == 0)."""
+    if getattr(renderer.net, "precision", "f32") not in ("f32", "f32x"):
         raise NotImplementedError("training runs on the fp32-accurate paths: precision 'f32' (exact fp32 MFMA) or 'f32x' "
                                   "(forward on split-fp16 MFMA; the backward kernels are fp32 MFMA either way)")
     if renderer.N_importance != _lib.N_IMPORTANCE or renderer.fast_sampling:
         raise NotImplementedError("training path is built for N_importance=128 without fast_sampling")
+
+
+def render_with_grad(renderer, rays_o, rays_d, jitter=None, u=None):
+    """rays [n,3] (contiguous fp32, on the GPU) -> (rgb [n,3], depth [n]) attached to the autograd graph of
+    the 48 network parameters (coarse sub-model first, then fine, state_dict order) and of the rays, each where it
+    requires grad.  `jitter` [n,64] / `u` [n,128]: the reference's training-mode draws (Renderer._draws); None keeps the
+    shared deterministic table."""
+    net = renderer.net
+    check_differentiable(renderer)
     params = tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
     draws = (jitter, u) if (jitter is not None or u is not None) else None
     return RenderFunction.apply(renderer, rays_o, rays_d, draws, *params)

@@ -97,8 +97,15 @@ class Renderer:
         lib = _lib.load()
         B, N, _ = rays_o.shape
         n = B * N
-        o = rays_o.detach().reshape(n, 3).to(torch.float32).contiguous()
-        d = rays_d.detach().reshape(n, 3).to(torch.float32).contiguous()
+        # rays that require grad stay in the graph (pose refinement): reshape / cast / contiguous map the gradient back to [B,N,3]
+        rays_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+        if not rays_grad:
+            rays_o, rays_d = rays_o.detach(), rays_d.detach()
+        o = rays_o.reshape(n, 3).to(torch.float32).contiguous()
+        d = rays_d.reshape(n, 3).to(torch.float32).contiguous()
+        if rays_grad:
+            # refused before any launch: never a detached result for rays that require grad
+            _sibling("training").check_differentiable(self)
         stochastic = bool(self.perturb) or self.task == "train"
         if stochastic:
             prec_name = getattr(self.net, "precision", "f32")
@@ -109,10 +116,10 @@ class Renderer:
                 raise NotImplementedError(f"stochastic sampling (task={self.task!r}, perturb={bool(self.perturb)}) is not "
                                           "built with fast_sampling")
             jitter, u_rays = self._draws(n, dev)
-        if torch.is_grad_enabled() and getattr(self.net, "training", False) and \
-                any(p.requires_grad for p in self.net.parameters()):
-            # training call (trainers/nerf.py:27 under trainer.py:53-60): forward with activation save,
-            # backward through the adjoint HIP kernels (training.py)
+        if rays_grad or (torch.is_grad_enabled() and getattr(self.net, "training", False) and
+                         any(p.requires_grad for p in self.net.parameters())):
+            # training call (trainers/nerf.py:27 under trainer.py:53-60), or rays that require grad: forward with activation
+            # save, backward through the adjoint HIP kernels (training.py)
             render_with_grad = _sibling("training").render_with_grad
             if n == 0:
                 return torch.empty((0, 3), device=dev), torch.empty((0,), device=dev)

@@ -34,7 +34,14 @@ def main():
     ap.add_argument("--out", default="nerf_train")
     ap.add_argument("--perturb", action="store_true",
                     help="train with the reference's stochastic sampling (task: train): jittered coarse depths, random fine u")
+    ap.add_argument("--fast-sampling", action="store_true",
+                    help="train with the reference's ESS / ERT masked fine pass (fast_sampling): the fine network runs on, stores and "
+                         "back-propagates the valid merged samples only; deterministic sampling (not with --perturb)")
+    ap.add_argument("--weights-threshold", type=float, default=0.25,
+                    help="ESS threshold on the coarse weights with --fast-sampling (reference default 0.25; 0.02 keeps far more fine samples)")
     args = ap.parse_args()
+    if args.fast_sampling and args.perturb:
+        ap.error("--fast-sampling trains with deterministic sampling: leave --perturb out")
     dev = "cuda"
 
     teacher = nerf.Network(); nerf.load_network(teacher, args.teacher); teacher = teacher.cuda().eval()
@@ -57,6 +64,9 @@ def main():
     if args.perturb:
         train_ren = nerf.Renderer(net)
         train_ren.task, train_ren.perturb = "train", True
+    if args.fast_sampling:
+        train_ren = nerf.Renderer(net)
+        train_ren.fast_sampling, train_ren.weights_threshold = True, args.weights_threshold
     opt = FusedAdam(net.parameters(), lr=5e-4, eps=1e-8, clip_value=40.0)
     lr0, gen = 5e-4, torch.Generator(device=dev).manual_seed(1)
 

@@ -224,6 +224,41 @@ int32_t nerf_rays_backward(int64_t n_rays, const float* t_coarse, int64_t t_ray_
                            const float* t_sorted, const float* g_x_fine, const float* g_rays_d_view, float* g_rays_o,
                            float* g_rays_d, void* stream);
 
+/* ---- masked (fast_sampling) fine pass of a training step ------------------------------------------------------------
+ * The reference evaluates the fine network on the merged samples that survive ESS / ERT only (boolean indexing of
+ * network.py:207-214, results scattered back into zeros :238-253, mask from volume_renderer.py:132-244, :359-369) and
+ * autograd follows: masked samples give no parameter gradient and no gradient through their point.  Here the valid ids
+ * are compacted on the device and the forward / backward work on the M compact rows; M never reaches the host.
+ *
+ * nerf_compact_valid: valid [n_points] (uint8, nerf_sample_fine's valid_sorted) -> index[0..M) = the ids with valid != 0 in
+ * ASCENDING order, *count = M.  The fixed order makes the save layout, the live-tile lists and every sum repeatable
+ * (nerf_render_forward's own compaction is atomic and unordered).  n_points <= 2^31 - 1 (NERF_ERR_INVALID_ARG beyond);
+ * `workspace`: nerf_compact_valid_workspace_bytes(n_points) bytes. */
+int64_t nerf_compact_valid_workspace_bytes(int64_t n_points);
+int32_t nerf_compact_valid(const uint8_t* valid, int64_t n_points, int32_t* index, int32_t* count, void* workspace,
+                           void* stream);
+/* nerf_mlp_forward_rays_save_for_compositing on the listed points: `raw` rows are written at the point ids index[j] (the
+ * caller zero-fills `raw`: a masked sample has raw = 0, network.py:238-253), the activation rows and the ReLU sign-bit
+ * blocks at the COMPACT slot j, in the nerf_train_save_floats(n_rays * n_samples) layout.  Rows >= M are not
+ * written, M need not be a multiple of 32 (the idle lanes of the last tile store duplicates behind row M - 1).  The
+ * for-compositing rule applies per compact tile.  index / count as nerf_compact_valid leaves them (ids < n_rays * n_samples,
+ * count <= n_rays * n_samples).  n_rays * n_samples <= 2^31 - 1 (NERF_ERR_INVALID_ARG beyond).  f32 / f32x. */
+int32_t nerf_mlp_forward_rays_save_masked(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
+                                          int64_t n_rays, int32_t n_samples, const int32_t* index, const int32_t* count,
+                                          const void* packed, float* raw, float* save, int32_t precision, void* stream);
+/* nerf_mlp_backward for a `save` of nerf_mlp_forward_rays_save_masked (same index / count).  `draw` [P,4] and g_t [P]
+ * (nullable) are in the global layout, P = n_rays * n_samples: the rows of the listed points are gathered to compact rows
+ * (rows >= M zero) together with the points o + d t, the chain and every weight-gradient kernel run in point mode over the
+ * live compact tiles (tiles behind row M - 1 are never live; with NERF_DEAD_TILE_SKIP=0 every occupied tile is), and g_t of a
+ * listed point = g_x . d is scattered back; g_t is 0 at unlisted ids.  `gsave`: nerf_train_grad_floats(P) floats (rows in the
+ * compact layout), `workspace`: nerf_mlp_backward_masked_workspace_bytes(P) bytes.  P must be a multiple of 32
+ * (NERF_ERR_UNSUPPORTED otherwise; n_samples = 192 always is) and <= 2^31 - 1 (NERF_ERR_INVALID_ARG). */
+int64_t nerf_mlp_backward_masked_workspace_bytes(int64_t n_points);
+int32_t nerf_mlp_backward_masked(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
+                                 int64_t n_rays, int32_t n_samples, const int32_t* index, const int32_t* count,
+                                 const void* packed_bwd, const float* draw, const float* save, float* gsave, float* g_t,
+                                 float* const grads[24], int32_t precision, void* workspace, void* stream);
+
 /* Adjoint of nerf_composite (autograd of volume_renderer.py:414-432 with :67-96): g_rgb [n,3], g_depth [n]
  * (nullable) -> g_raw [n,S,4] and, if given, g_t [n,S] (the direct dependence of the image on the sample
  * depths through delta_k = t_{k+1}-t_k and the depth sum).  S <= 192.  Rows of g_raw are exactly zero wherever

@@ -87,6 +87,14 @@ _PROTOS = {
                                               _c.POINTER(_c.c_void_p), _c.c_int32, _c.c_int32, _c.c_void_p]),
     "nerf_rays_viewdirs_backward": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_void_p]),
     "nerf_rays_backward": (_c.c_int32, [_c.c_int64, _F, _c.c_int64, _F, _F, _F, _F, _F, _F, _c.c_void_p]),
+    # masked (fast_sampling) fine pass of a training step
+    "nerf_compact_valid_workspace_bytes": (_c.c_int64, [_c.c_int64]),
+    "nerf_compact_valid": (_c.c_int32, [_F, _c.c_int64, _F, _F, _F, _c.c_void_p]),
+    "nerf_mlp_forward_rays_save_masked": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F,
+                                                       _c.c_int32, _c.c_void_p]),
+    "nerf_mlp_backward_masked_workspace_bytes": (_c.c_int64, [_c.c_int64]),
+    "nerf_mlp_backward_masked": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F, _F, _F,
+                                              _c.POINTER(_c.c_void_p), _c.c_int32, _F, _c.c_void_p]),
 }
 EXPORTS = tuple(_PROTOS)
 

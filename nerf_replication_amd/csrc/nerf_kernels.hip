@@ -1203,6 +1203,120 @@ void nerf_tile_scan_kernel(const int* __restrict__ flags, int n_tiles, int* __re
   if (tid == 1023) *count = s_cnt[1023];
 }
 
+// ------------------------------------------------------------------------------------ training: the masked (fast_sampling) fine pass
+// Ordered stream compaction of the valid (ray, sample) ids: index[0..M) = the ids with valid != 0 in ASCENDING order, *count = M.
+// Unlike nerf_compact_kernel (one atomic per wave, arbitrary order: fine for inference, where results are scattered back by id)
+// the order here is fixed, because the training forward stores the activations of index[j] at row j of the save buffer: a
+// repeatable layout gives repeatable tiles, live-tile lists and gradient sums.  Three launches: per-block counts (256 ids per
+// block), one-workgroup exclusive scan of the block counts, ordered scatter.  No atomics.
+constexpr int kCompactBlock = 256;
+__device__ __forceinline__ int compact_block_rank(bool v, int* s_wave, int& block_total) {
+  const unsigned long long m = __builtin_amdgcn_ballot_w64(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) s_wave[wave] = (int)__popcll(m);
+  __syncthreads();
+  int before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < kCompactBlock / 64; ++w) {
+    const int c = s_wave[w];
+    if (w < wave) before += c;
+    total += c;
+  }
+  block_total = total;
+  return before + (int)__popcll(m & ((1ull << lane) - 1ull));
+}
+__global__ __launch_bounds__(kCompactBlock)
+void nerf_compact_count_kernel(const unsigned char* __restrict__ valid, long long n, int* __restrict__ block_count) {
+  __shared__ int s_wave[kCompactBlock / 64];
+  const long long i = (long long)blockIdx.x * kCompactBlock + threadIdx.x;
+  int total;
+  compact_block_rank(i < n && valid[i] != 0, s_wave, total);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+// block counts -> exclusive offsets in place, *count = their sum; one workgroup (3072 blocks for a 4096-ray step)
+__global__ __launch_bounds__(1024)
+void nerf_compact_scan_kernel(int* __restrict__ block_count, long long n_blocks, int* __restrict__ count) {
+  __shared__ int s_cnt[1024];
+  const int tid = threadIdx.x;
+  const long long per = (n_blocks + 1023) / 1024;
+  const long long b0 = tid * per, b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
+  int c = 0;
+  for (long long b = b0; b < b1; ++b) c += block_count[b];
+  s_cnt[tid] = c;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {                 // inclusive Hillis-Steele scan
+    const int v = tid >= d ? s_cnt[tid - d] : 0;
+    __syncthreads();
+    s_cnt[tid] += v;
+    __syncthreads();
+  }
+  int pos = s_cnt[tid] - c;
+  for (long long b = b0; b < b1; ++b) {
+    const int cb = block_count[b];
+    block_count[b] = pos;
+    pos += cb;
+  }
+  if (tid == 1023) *count = s_cnt[1023];
+}
+__global__ __launch_bounds__(kCompactBlock)
+void nerf_compact_scatter_kernel(const unsigned char* __restrict__ valid, long long n, const int* __restrict__ block_offset,
+                                 int* __restrict__ index) {
+  __shared__ int s_wave[kCompactBlock / 64];
+  const long long i = (long long)blockIdx.x * kCompactBlock + threadIdx.x;
+  const bool v = i < n && valid[i] != 0;
+  int total;
+  const int rank = compact_block_rank(v, s_wave, total);
+  if (v) index[block_offset[blockIdx.x] + rank] = (int)i;       // offset + rank <= number of valid ids before i <= i < n
+}
+
+// Masked backward, step 1: the compact rows the chain works on.  Row j < M (= *count) takes d loss / d raw of point index[j]
+// and the point itself, x = o + d t with the two roundings of the forward kernels; rows >= M are zero: their tiles are never
+// live (nerf_tile_flags_kernel), and the idle rows of the ragged tile behind row M - 1 add exactly nothing.
+__global__ __launch_bounds__(256)
+void nerf_masked_gather_kernel(const int* __restrict__ index, const int* __restrict__ count, long long P,
+                               const f32x4* __restrict__ draw, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                               const float* __restrict__ tvals, long long t_ray_stride, int n_samples,
+                               f32x4* __restrict__ draw_c, float* __restrict__ pts_c) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= P) return;
+  f32x4 g = {0.f, 0.f, 0.f, 0.f};
+  float x[3] = {0.f, 0.f, 0.f};
+  const long long id = j < (long long)*count ? (long long)index[j] : -1;
+  if (id >= 0 && id < P) {
+    g = draw[id];
+    const long long ray = id / n_samples;
+    const float t = tvals[ray * t_ray_stride + (id - ray * n_samples)];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) x[c] = __fadd_rn(rays_o[ray * 3 + c], __fmul_rn(rays_d[ray * 3 + c], t));
+  }
+  draw_c[j] = g;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) pts_c[j * 3 + c] = x[c];
+}
+// NERF_DEAD_TILE_SKIP=0 with a compact buffer: every tile that holds a listed point is live, whatever its gradient; the tiles
+// behind row M - 1 were never written by the forward and stay out.
+__global__ __launch_bounds__(256)
+void nerf_tile_occupied_kernel(const int* __restrict__ count, long long n_tiles, int* __restrict__ flags) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t < n_tiles) flags[t] = t * 32 < (long long)*count;
+}
+// Masked backward, last step: g_t [P] of the listed points from the chain's compact g_x rows, with the arithmetic of the
+// chain's own g_t store (nerf_gt_of_gx_kernel); the caller has zeroed g_t, so unlisted ids keep 0.
+__global__ __launch_bounds__(256)
+void nerf_masked_gt_scatter_kernel(const int* __restrict__ index, const int* __restrict__ count, long long P,
+                                   const float* __restrict__ gx_c, const float* __restrict__ rays_d, int n_samples,
+                                   float* __restrict__ g_t) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= P || j >= (long long)*count) return;
+  const long long id = index[j];
+  if (id < 0 || id >= P) return;
+  const long long ray = id / n_samples;
+  float gt = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) gt += gx_c[j * 3 + c] * rays_d[ray * 3 + c];
+  g_t[id] = gt;
+}
+
 // ------------------------------------------------------------------------------------ fused clip + Adam (section 8f-4)
 // One launch over all 48 parameter tensors: clip_grad_value_ (trainer.py:59) + torch.optim.Adam's update
 // (optimizer.py:21-24: Adam(lr, weight_decay, eps), betas (0.9, 0.999), no amsgrad) in torch's operation
@@ -1962,7 +2076,10 @@ int32_t nerf_pack_model_bwd(const float* const params[24], void* packed_bwd_v, i
 // grads[24]: device pointers in state_dict order (nn.Linear layouts), accumulated into (caller zeroes them); nullptr: the
 // data-gradient chain alone (a frozen network: no weight-gradient launch, nothing to poison)
 // shared by the ray-mode and the point-mode entry: data-gradient chain, then the weight / bias gradients
-static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* const grads[24], int32_t precision, void* stream) {
+// occupied (masked backward, point mode on compact rows): device count M of the rows the forward filled.  Tiles behind row
+// M - 1 hold nothing, so a live-tile list is built even with NERF_DEAD_TILE_SKIP=0 -- then of every occupied tile.
+static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* const grads[24], int32_t precision, void* stream,
+                                 const int* occupied = nullptr) {
   // density only: both chains skip the colour branch in the kernel (ray mode), and its three weight-gradient jobs are skipped
   // here: their result is exactly zero
   BwdArgs a = a_in;
@@ -1983,13 +2100,20 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
   // NERF_DEAD_TILE_SKIP=0 in the environment turns it off (tests compare the two).
   const int* live = nullptr; const int* n_live = nullptr;
   {
-    if (dead_tile_list_available(P, precision)) {
+    const bool by_gradient = dead_tile_list_available(P, precision);
+    if (by_gradient || occupied) {
       int* flags = reinterpret_cast<int*>(gsave + TrainGrad::off_flags(P));
       int* lv = reinterpret_cast<int*>(gsave + TrainGrad::off_live(P));
       int* cnt = reinterpret_cast<int*>(gsave + TrainGrad::off_count(P));
-      hipLaunchKernelGGL(nerf_tile_flags_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                         reinterpret_cast<const f32x4*>(draw), P, a.density_only, flags);
-      rc = check_launch("nerf_tile_flags_kernel");
+      if (by_gradient) {
+        hipLaunchKernelGGL(nerf_tile_flags_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const f32x4*>(draw), P, a.density_only, flags);
+        rc = check_launch("nerf_tile_flags_kernel");
+      } else {
+        hipLaunchKernelGGL(nerf_tile_occupied_kernel, dim3((unsigned)((P / 32 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           occupied, P / 32, flags);
+        rc = check_launch("nerf_tile_occupied_kernel");
+      }
       if (rc) return rc;
       hipLaunchKernelGGL(nerf_tile_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, flags, (int)(P / 32), lv, cnt);
       rc = check_launch("nerf_tile_scan_kernel");
@@ -2001,7 +2125,8 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
         return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward: memset failed");
       // point mode has one more consumer of gsave: nerf_viewdirs_backward sums the g_zv rows of ALL samples of a ray, dead
       // tiles included -- their rows are the zeros written here (ray mode: nerf_rays_viewdirs_backward skips dead tiles by their flag)
-      if (pts_mode && hipMemsetAsync(gsave + TrainGrad::off_gzv(P), 0, (size_t)TrainSave::pad32(P) * 128 * sizeof(float), (hipStream_t)stream) != hipSuccess)
+      // (masked backward: its g_zv rows are read by the weight-gradient kernels alone, live tiles only)
+      if (pts_mode && !occupied && hipMemsetAsync(gsave + TrainGrad::off_gzv(P), 0, (size_t)TrainSave::pad32(P) * 128 * sizeof(float), (hipStream_t)stream) != hipSuccess)
         return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward: memset failed");
       live = lv; n_live = cnt;
       a.live_tiles = lv; a.n_live = cnt;
@@ -2179,7 +2304,7 @@ int64_t nerf_train_save_floats(int64_t n_points) { return n_points < 0 ? -1 : Tr
 static int32_t forward_rays_save_impl(const float* rays_o, const float* rays_d, const float* tvals,
                                       int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                                       const void* packed, float* raw, float* save, int32_t precision, void* stream, int density_only,
-                                      int skip_dead = 0) {
+                                      int skip_dead = 0, const int* index = nullptr, const int* count = nullptr) {
   if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_save: bad size");
   if (n_rays == 0) return NERF_OK;
   if (!rays_o || !rays_d || !tvals || !packed || !raw || !save) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_save: null argument");
@@ -2187,6 +2312,7 @@ static int32_t forward_rays_save_impl(const float* rays_o, const float* rays_d, 
   a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride;
   a.n_points = n_rays * n_samples; a.n_samples = n_samples; a.packed = (const float*)packed; a.raw = raw; a.save = save;
   a.density_only = density_only;
+  a.index = index; a.count = count;      // masked: rows of index[j] at slot j, `raw` at the id (every SAVE instance honours both)
   // stamp: 1 = the rows of density-free tiles are NOT stored (for-compositing entry with the list available)
   const bool rows_skipped = (precision == NERF_PREC_F32 || precision == NERF_PREC_F32X) && !density_only && skip_dead;
   if (hipMemsetAsync(save + TrainSave::off_stamp(a.n_points), rows_skipped ? 0x01 : 0x00, 4 * sizeof(float), (hipStream_t)stream) != hipSuccess)
@@ -2226,6 +2352,86 @@ int32_t nerf_mlp_forward_rays_save_density(const float* rays_o, const float* ray
                                            int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                                            const void* packed, float* raw, float* save, int32_t precision, void* stream) {
   return forward_rays_save_impl(rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, save, precision, stream, 1);
+}
+
+// ---- masked (fast_sampling) fine pass of a training step
+static bool masked_sizes_ok(int64_t n_rays, int32_t n_samples, int64_t t_ray_stride) {
+  return n_rays >= 0 && n_samples > 0 && t_ray_stride >= 0 && n_rays <= (int64_t)0x7fffffff / n_samples;     // point ids are int32
+}
+int64_t nerf_compact_valid_workspace_bytes(int64_t n_points) {
+  if (n_points < 0 || n_points > 0x7fffffffLL) return -1;
+  return align256(((n_points + kCompactBlock - 1) / kCompactBlock) * (int64_t)sizeof(int));
+}
+int32_t nerf_compact_valid(const uint8_t* valid, int64_t n_points, int32_t* index, int32_t* count, void* workspace, void* stream) {
+  if (n_points < 0 || n_points > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_compact_valid: point ids are int32");
+  if (!count) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_compact_valid: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_points == 0) {
+    if (hipMemsetAsync(count, 0, sizeof(int), st) != hipSuccess) return fail(NERF_ERR_HIP, "%s", "nerf_compact_valid: memset failed");
+    return NERF_OK;
+  }
+  if (!valid || !index || !workspace) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_compact_valid: null argument");
+  const long long n_blocks = (n_points + kCompactBlock - 1) / kCompactBlock;
+  int* block = (int*)workspace;
+  hipLaunchKernelGGL(nerf_compact_count_kernel, dim3((unsigned)n_blocks), dim3(kCompactBlock), 0, st, valid, (long long)n_points, block);
+  int rc = check_launch("nerf_compact_count_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(nerf_compact_scan_kernel, dim3(1), dim3(1024), 0, st, block, n_blocks, count);
+  rc = check_launch("nerf_compact_scan_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(nerf_compact_scatter_kernel, dim3((unsigned)n_blocks), dim3(kCompactBlock), 0, st, valid, (long long)n_points, block, index);
+  return check_launch("nerf_compact_scatter_kernel");
+}
+
+int32_t nerf_mlp_forward_rays_save_masked(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
+                                          int64_t n_rays, int32_t n_samples, const int32_t* index, const int32_t* count,
+                                          const void* packed, float* raw, float* save, int32_t precision, void* stream) {
+  if (!masked_sizes_ok(n_rays, n_samples, t_ray_stride)) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_save_masked: bad size");
+  if (n_rays == 0) return NERF_OK;
+  if (!index || !count) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_save_masked: null argument");
+  // the fine pass of a step: `raw` goes to compositing, so the rule of nerf_mlp_forward_rays_save_for_compositing holds per
+  // compact tile (and the same helper decides for the backward pass)
+  const int skip = dead_tile_list_available(n_rays * (int64_t)n_samples, precision);
+  return forward_rays_save_impl(rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, save, precision, stream, 0, skip,
+                                index, count);
+}
+
+int64_t nerf_mlp_backward_masked_workspace_bytes(int64_t n_points) {
+  if (n_points < 0 || n_points > 0x7fffffffLL) return -1;
+  return align256(n_points * 4 * (int64_t)sizeof(float)) + 2 * align256(n_points * 3 * (int64_t)sizeof(float));
+}
+int32_t nerf_mlp_backward_masked(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
+                                 int64_t n_rays, int32_t n_samples, const int32_t* index, const int32_t* count,
+                                 const void* packed_bwd_v, const float* draw, const float* save, float* gsave, float* g_t,
+                                 float* const grads[24], int32_t precision, void* workspace, void* stream) {
+  if (!masked_sizes_ok(n_rays, n_samples, t_ray_stride)) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_masked: bad size");
+  if (n_rays == 0) return NERF_OK;
+  if (!rays_o || !rays_d || !tvals || !index || !count || !packed_bwd_v || !draw || !save || !gsave || !grads || !workspace)
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_masked: null argument");
+  for (int i = 0; i < 24; ++i) if (!grads[i]) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_masked: null gradient pointer");
+  if (precision != NERF_PREC_F32 && precision != NERF_PREC_F32X) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_mlp_backward_masked: f32 or f32x only");
+  const long long P = n_rays * (int64_t)n_samples;
+  // compact rows past the count are kept out by the live-tile list alone: the list-mode kernels must exist (whole 32-point tiles)
+  if (!(NERF_WGRAD_ASM && NERF_WGVEC_ASM) || P % 32 != 0)
+    return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_mlp_backward_masked: needs the live-tile kernels and a point count that is a multiple of 32");
+  hipStream_t st = (hipStream_t)stream;
+  float* draw_c = (float*)workspace;
+  float* pts_c = (float*)((char*)draw_c + align256(P * 4 * (int64_t)sizeof(float)));
+  float* gx_c = (float*)((char*)pts_c + align256(P * 3 * (int64_t)sizeof(float)));
+  const unsigned blocks = (unsigned)((P + 255) / 256);
+  hipLaunchKernelGGL(nerf_masked_gather_kernel, dim3(blocks), dim3(256), 0, st, index, count, P, reinterpret_cast<const f32x4*>(draw),
+                     rays_o, rays_d, tvals, (long long)t_ray_stride, n_samples, reinterpret_cast<f32x4*>(draw_c), pts_c);
+  int rc = check_launch("nerf_masked_gather_kernel");
+  if (rc) return rc;
+  // the chain and the weight-gradient kernels in point mode over the compact rows (live tiles only)
+  BwdArgs a{};
+  a.pts = pts_c; a.g_x = g_t ? gx_c : nullptr; a.n_points = P; a.n_samples = n_samples;
+  a.packed_bwd = (const float*)packed_bwd_v; a.draw = draw_c; a.save = save; a.gsave = gsave;
+  rc = mlp_backward_impl(a, true, grads, precision, stream, count);
+  if (rc || !g_t) return rc;
+  if (hipMemsetAsync(g_t, 0, (size_t)P * sizeof(float), st) != hipSuccess) return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward_masked: memset failed");
+  hipLaunchKernelGGL(nerf_masked_gt_scatter_kernel, dim3(blocks), dim3(256), 0, st, index, count, P, gx_c, rays_d, n_samples, g_t);
+  return check_launch("nerf_masked_gt_scatter_kernel");
 }
 
 int32_t nerf_mlp_forward_points_save(const float* pts, const float* viewdirs, int64_t n_rays, int32_t n_samples,

@@ -15,6 +15,11 @@ launch).  A step whose rays do not require grad runs exactly the launches it ran
 In the reference's training sampling mode (Renderer.task == "train") the step takes the two draws of Renderer._draws: the
 jittered coarse depths (nerf_stratified_samples) go to the coarse forward / backward and the sampler with a per-ray stride of
 64, the per-ray u to the sampler and its adjoint with a stride of 128.  Without draws every launch is the deterministic one.
+
+Two more modes train, with deterministic sampling and parameter gradients: fast_sampling (MaskedRenderFunction: the reference's
+ESS / ERT mask, volume_renderer.py:132-244 / :359-369 / network.py:207-253 -- the fine network, its activation store and its
+backward run on the valid merged samples only, compacted on the device) and N_importance == 0 (CoarseRenderFunction: the coarse
+network alone, composited over its 64 samples).  The unmasked step above issues exactly the launches it issued before.
 """
 import ctypes
 
@@ -182,13 +187,201 @@ class RenderFunction(torch.autograd.Function):
                                                   for g, p, need in zip(grads or [None] * len(params), params, need_params))
 
 
-def check_differentiable(renderer):
-    """Raise NotImplementedError for the modes without adjoint kernels (fp16 precisions, fast_sampling, N_importance == 0)."""
+def _zeroed_grads(params, dev):
+    """One gradient tensor per parameter as views of one zeroed buffer (one memset)."""
+    flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
+    grads, off = [], 0
+    for p in params:
+        grads.append(flat[off:off + p.numel()].view(p.shape))
+        off += p.numel()
+    return grads
+
+
+class MaskedRenderFunction(torch.autograd.Function):
+    """The step with fast_sampling: the sampler also yields the validity of the 192 merged samples (coarse samples always valid,
+    fine ones unless ESS / ERT / the empty-ray test drop them); the fine network runs on the M valid samples, raw_fine is exactly 0
+    at the others (network.py:238-253).  The mask is made of comparisons, a constant for autograd: compositing's adjoint runs over
+    all 192 samples, the fine MLP's backward over the M compact rows, and g_t of a masked sample has no point term."""
+
+    @staticmethod
+    def forward(ctx, renderer, rays_o, rays_d, *params):
+        lib = _lib.load()
+        net = renderer.net
+        dev = rays_o.device
+        n = rays_o.shape[0]
+        st = _lib.stream_of(dev)
+        t_c, u = renderer._get_tables(dev)
+        S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
+        P = n * S_f
+        pk_c, pk_f = net.packed(""), net.packed("fine")
+        prec = _lib.PRECISIONS[getattr(net, "precision", "f32")]
+        f32 = dict(dtype=torch.float32, device=dev)
+        raw_c = torch.empty((n, S_c, 4), **f32)
+        save_c = torch.empty(int(lib.nerf_train_save_floats(n * S_c)), **f32)
+        t_sorted = torch.empty((n, S_f), **f32)
+        valid = torch.empty((n, S_f), dtype=torch.uint8, device=dev)
+        index = torch.empty(P, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(lib.nerf_compact_valid_workspace_bytes(P)), dtype=torch.uint8, device=dev)
+        raw_f = torch.zeros((n, S_f, 4), **f32)           # masked samples keep raw = 0
+        save_f = torch.empty(int(lib.nerf_train_save_floats(P)), **f32)
+        rgb, depth = torch.empty((n, 3), **f32), torch.empty((n,), **f32)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_mlp_forward_rays_save_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c,
+                                                              pk_c.data_ptr(), _lib.ptr(raw_c), _lib.ptr(save_c), prec, st), "forward(coarse)")
+            _lib.check(lib.nerf_sample_fine(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted), None,
+                                            _lib.ptr(valid, torch.uint8), float(renderer.weights_threshold), 0.45, st), "nerf_sample_fine")
+            _lib.check(lib.nerf_compact_valid(_lib.ptr(valid, torch.uint8), P, _lib.ptr(index, torch.int32), _lib.ptr(count, torch.int32),
+                                              ws.data_ptr(), st), "nerf_compact_valid")
+            _lib.check(lib.nerf_mlp_forward_rays_save_masked(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
+                                                             _lib.ptr(index, torch.int32), _lib.ptr(count, torch.int32), pk_f.data_ptr(),
+                                                             _lib.ptr(raw_f), _lib.ptr(save_f), prec, st), "forward(fine, masked)")
+            _lib.check(lib.nerf_composite(_lib.ptr(raw_f), _lib.ptr(t_sorted), S_f, n, S_f, int(bool(renderer.white_bkgd)),
+                                          _lib.ptr(rgb), _lib.ptr(depth), None, st), "nerf_composite")
+        stats = getattr(renderer, "masked_stats", None)
+        if stats is not None:         # (points the fine network evaluated as a 1-element device tensor, capacity): no host sync here
+            stats.append((count.clone(), P))
+        cap = getattr(renderer, "capture_adjoints", None)
+        if cap is not None:
+            cap["valid_sorted"] = valid.clone()
+        ctx.renderer, ctx.prec, ctx.n, ctx.params = renderer, prec, n, params
+        ctx.save_for_backward(rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f, index, count)
+        return rgb, depth
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth):
+        lib = _lib.load()
+        renderer, n, params, prec = ctx.renderer, ctx.n, ctx.params, ctx.prec
+        rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f, index, count = ctx.saved_tensors
+        dev = rays_o.device
+        st = _lib.stream_of(dev)
+        t_c, u = renderer._get_tables(dev)
+        S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
+        P = n * S_f
+        f32 = dict(dtype=torch.float32, device=dev)
+        g_rgb = g_rgb.contiguous().to(torch.float32)
+        g_depth = None if g_depth is None else g_depth.contiguous().to(torch.float32)
+        need_params = ctx.needs_input_grad[3:]
+        if not any(need_params):
+            return (None,) * (3 + len(params))
+        grads = _zeroed_grads(params, dev)
+        nbwd = int(lib.nerf_packed_bwd_bytes(prec))
+        with torch.cuda.device(dev):
+            # fine pass: image -> raw_fine and depths (all 192 samples; g_raw is exactly zero at the masked ones: sigma = 0)
+            g_raw_f = torch.empty((n, S_f, 4), **f32)
+            g_t = torch.empty((n, S_f), **f32)
+            _lib.check(lib.nerf_composite_backward(_lib.ptr(raw_f), _lib.ptr(t_sorted), S_f, n, S_f,
+                                                   int(bool(renderer.white_bkgd)), _lib.ptr(g_rgb),
+                                                   None if g_depth is None else _lib.ptr(g_depth),
+                                                   _lib.ptr(g_raw_f), _lib.ptr(g_t), st), "nerf_composite_backward")
+            pk_b = torch.empty(nbwd, dtype=torch.uint8, device=dev)
+            _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params[24:]]), pk_b.data_ptr(), prec, st))
+            gsave = torch.empty(int(lib.nerf_train_grad_floats(P)), **f32)
+            g_t_pts = torch.empty((n, S_f), **f32)
+            ws = torch.empty(int(lib.nerf_mlp_backward_masked_workspace_bytes(P)), dtype=torch.uint8, device=dev)
+            # MLP backward over the compact rows of the valid samples; their g_t scattered back, 0 at the masked ones
+            _lib.check(lib.nerf_mlp_backward_masked(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
+                                                    _lib.ptr(index, torch.int32), _lib.ptr(count, torch.int32), pk_b.data_ptr(),
+                                                    _lib.ptr(g_raw_f), _lib.ptr(save_f), _lib.ptr(gsave), _lib.ptr(g_t_pts),
+                                                    _ptr_array(grads[24:]), prec, ws.data_ptr(), st), "nerf_mlp_backward_masked(fine)")
+            g_t.add_(g_t_pts)
+            stats = getattr(renderer, "live_tile_stats", None)
+            cnt_f = None
+            if stats is not None:
+                cnt_f = gsave[int(lib.nerf_train_live_count_offset(P))].view(torch.int32).clone()
+            # coarse pass: depths -> coarse density -> coarse MLP parameters, as in the unmasked step
+            g_raw_c = torch.empty((n, S_c, 4), **f32)
+            _lib.check(lib.nerf_sample_fine_backward(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted),
+                                                     _lib.ptr(g_t), _lib.ptr(g_raw_c), st), "nerf_sample_fine_backward")
+            cap = getattr(renderer, "capture_adjoints", None)
+            if cap is not None:       # tests: as in the unmasked step
+                cap["g_raw_coarse"], cap["g_t_sorted"], cap["raw_coarse"] = g_raw_c.clone(), g_t.clone(), raw_c.clone()
+                cap["t_sorted"] = t_sorted.clone()
+            _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params[:24]]), pk_b.data_ptr(), prec, st))
+            gsave_c = gsave[: int(lib.nerf_train_grad_floats(n * S_c))]
+            _lib.check(lib.nerf_mlp_backward_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c,
+                                                     pk_b.data_ptr(), _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave_c),
+                                                     None, _ptr_array(grads[:24]), prec, st), "nerf_mlp_backward(coarse)")
+            if stats is not None:
+                cnt_c = gsave_c[int(lib.nerf_train_live_count_offset(n * S_c))].view(torch.int32).clone()
+                stats.append((cnt_f, P // 32, cnt_c, n * S_c // 32))
+        return (None, None, None) + tuple(g.to(p.dtype) if need else None for g, p, need in zip(grads, params, need_params))
+
+
+class CoarseRenderFunction(torch.autograd.Function):
+    """The step with N_importance == 0 (volume_renderer.py:306-345 returning the coarse outputs): the full coarse network on the
+    64 table depths, compositing over them, and the adjoints of both.  The depths are constants, so the MLP backward is asked
+    for no g_t.  Only the 24 coarse tensors are inputs: the fine sub-model is unused, its .grad stays None as in the reference."""
+
+    @staticmethod
+    def forward(ctx, renderer, rays_o, rays_d, *params):
+        lib = _lib.load()
+        net = renderer.net
+        dev = rays_o.device
+        n = rays_o.shape[0]
+        st = _lib.stream_of(dev)
+        t_c, _ = renderer._get_tables(dev)
+        S_c = _lib.N_SAMPLES
+        prec = _lib.PRECISIONS[getattr(net, "precision", "f32")]
+        f32 = dict(dtype=torch.float32, device=dev)
+        raw_c = torch.empty((n, S_c, 4), **f32)
+        save_c = torch.empty(int(lib.nerf_train_save_floats(n * S_c)), **f32)
+        rgb, depth = torch.empty((n, 3), **f32), torch.empty((n,), **f32)
+        with torch.cuda.device(dev):
+            # its raw goes to compositing only: tiles without density skip the colour branch and its stores
+            _lib.check(lib.nerf_mlp_forward_rays_save_for_compositing(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c,
+                                                                      net.packed("").data_ptr(), _lib.ptr(raw_c), _lib.ptr(save_c), prec, st),
+                       "forward(coarse)")
+            _lib.check(lib.nerf_composite(_lib.ptr(raw_c), _lib.ptr(t_c), 0, n, S_c, int(bool(renderer.white_bkgd)),
+                                          _lib.ptr(rgb), _lib.ptr(depth), None, st), "nerf_composite")
+        ctx.renderer, ctx.prec, ctx.n, ctx.params = renderer, prec, n, params
+        ctx.save_for_backward(rays_o, rays_d, raw_c, save_c)
+        return rgb, depth
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth):
+        lib = _lib.load()
+        renderer, n, params, prec = ctx.renderer, ctx.n, ctx.params, ctx.prec
+        rays_o, rays_d, raw_c, save_c = ctx.saved_tensors
+        dev = rays_o.device
+        st = _lib.stream_of(dev)
+        t_c, _ = renderer._get_tables(dev)
+        S_c = _lib.N_SAMPLES
+        f32 = dict(dtype=torch.float32, device=dev)
+        g_rgb = g_rgb.contiguous().to(torch.float32)
+        g_depth = None if g_depth is None else g_depth.contiguous().to(torch.float32)
+        need_params = ctx.needs_input_grad[3:]
+        if not any(need_params):
+            return (None,) * (3 + len(params))
+        grads = _zeroed_grads(params, dev)
+        with torch.cuda.device(dev):
+            g_raw_c = torch.empty((n, S_c, 4), **f32)
+            _lib.check(lib.nerf_composite_backward(_lib.ptr(raw_c), _lib.ptr(t_c), 0, n, S_c, int(bool(renderer.white_bkgd)),
+                                                   _lib.ptr(g_rgb), None if g_depth is None else _lib.ptr(g_depth),
+                                                   _lib.ptr(g_raw_c), None, st), "nerf_composite_backward")
+            pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device=dev)
+            _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params]), pk_b.data_ptr(), prec, st))
+            gsave = torch.empty(int(lib.nerf_train_grad_floats(n * S_c)), **f32)
+            _lib.check(lib.nerf_mlp_backward(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c, pk_b.data_ptr(),
+                                             _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave), None, _ptr_array(grads), prec, st),
+                       "nerf_mlp_backward(coarse)")
+            stats = getattr(renderer, "live_tile_stats", None)
+            if stats is not None:
+                cnt_c = gsave[int(lib.nerf_train_live_count_offset(n * S_c))].view(torch.int32).clone()
+                stats.append((None, 0, cnt_c, n * S_c // 32))
+        return (None, None, None) + tuple(g.to(p.dtype) if need else None for g, p, need in zip(grads, params, need_params))
+
+
+def check_differentiable(renderer, rays_grad=False):
+    """Raise NotImplementedError for the modes without adjoint kernels: fp16 precisions, and gradients with respect to the rays
+    (`rays_grad`) with fast_sampling or N_importance == 0 -- those two modes train their parameters only."""
     if getattr(renderer.net, "precision", "f32") not in ("f32", "f32x"):
         raise NotImplementedError("training runs on the fp32-accurate paths: precision 'f32' (exact fp32 MFMA) or 'f32x' "
                                   "(forward on split-fp16 MFMA; the backward kernels are fp32 MFMA either way)")
-    if renderer.N_importance != _lib.N_IMPORTANCE or renderer.fast_sampling:
-        raise NotImplementedError("training path is built for N_importance=128 without fast_sampling")
+    if renderer.N_importance not in (0, _lib.N_IMPORTANCE):
+        raise NotImplementedError("training path is built for N_importance in {0, 128}")
+    if rays_grad and (renderer.N_importance != _lib.N_IMPORTANCE or renderer.fast_sampling):
+        raise NotImplementedError("gradients with respect to the rays are built for N_importance=128 without fast_sampling")
 
 
 def render_with_grad(renderer, rays_o, rays_d, jitter=None, u=None):
@@ -197,9 +390,17 @@ def render_with_grad(renderer, rays_o, rays_d, jitter=None, u=None):
     requires grad.  `jitter` [n,64] / `u` [n,128]: the reference's training-mode draws (Renderer._draws); None keeps the
     shared deterministic table."""
     net = renderer.net
-    check_differentiable(renderer)
-    params = tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
+    rays_grad = rays_o.requires_grad or rays_d.requires_grad
+    check_differentiable(renderer, rays_grad)
     draws = (jitter, u) if (jitter is not None or u is not None) else None
+    if renderer.N_importance == 0 or renderer.fast_sampling:
+        if draws is not None:
+            raise NotImplementedError("stochastic sampling trains with N_importance=128 without fast_sampling only")
+        if renderer.N_importance == 0:
+            return CoarseRenderFunction.apply(renderer, rays_o, rays_d, *net.model.ordered_params())
+        params = tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
+        return MaskedRenderFunction.apply(renderer, rays_o, rays_d, *params)
+    params = tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
     return RenderFunction.apply(renderer, rays_o, rays_d, draws, *params)
 
 

@@ -105,7 +105,7 @@ class Renderer:
         d = rays_d.reshape(n, 3).to(torch.float32).contiguous()
         if rays_grad:
             # refused before any launch: never a detached result for rays that require grad
-            _sibling("training").check_differentiable(self)
+            _sibling("training").check_differentiable(self, True)
         stochastic = bool(self.perturb) or self.task == "train"
         if stochastic:
             prec_name = getattr(self.net, "precision", "f32")

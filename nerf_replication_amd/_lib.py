@@ -153,6 +153,22 @@ def ptr(t, dtype=torch.float32):
     return t.data_ptr()
 
 
+def ptr_array(tensors, dtype=None):
+    """ctypes array of the device pointers of `tensors`; with `dtype`, each one checked as by ptr()."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if dtype is None else ptr(t, dtype) for t in tensors])
+
+
+def zeroed_grads(params, device):
+    """One fp32 gradient tensor per parameter, in order, as views of one zeroed buffer: one memset instead of one per tensor, and
+    the layout dist.allreduce_gradients reduces in place."""
+    flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=device)
+    grads, off = [], 0
+    for p in params:
+        grads.append(flat[off:off + p.numel()].view(p.shape))
+        off += p.numel()
+    return grads
+
+
 def stream_of(device):
     return torch.cuda.current_stream(device).cuda_stream
 

@@ -25,10 +25,12 @@
 // nerf_build_flags(), which the Python loader (and any other binder) checks -- so a stray -D can no longer produce a
 // library that passes nerf_abi_version() and computes garbage.
 #define NERF_ANY_TIMING_HACK (NERF_F32_HACK_NOLOAD || NERF_F32_HACK_NOBIAS || NERF_F32_HACK_NORELU || NERF_F32_HACK_NOPE || \
-                              0 || NERF_F32_ASM_OVERRUN || NERF_F32_HACK_NOSAVE || NERF_BWD_HACK_NOMASK || 0 || NERF_F16_HACK_NOADV || NERF_F16_HACK_NOBARRIER || NERF_WG_HACK_NOATOMIC || NERF_F16_HACK_NOEPI || 0 || NERF_F16_HACK_NORELU || NERF_F32X_HACK_NOADV || \
-                              NERF_F32X_HACK_NOPE || NERF_F32X_HACK_NOEPI || NERF_F32X_HACK_SAVE_NOSTORE || NERF_XB_HACK_NOSTORE)
-// (two structural knobs of the SAVE forward also break results when switched off: no rows / no sign bits stored)
-#if (NERF_ANY_TIMING_HACK || NERF_SAVE_TAPS == 0 || 2 == 0) && !defined(NERF_TIMING_BUILD)
+                              NERF_F32_ASM_OVERRUN || NERF_F32_HACK_NOSAVE || NERF_BWD_HACK_NOMASK || NERF_F16_HACK_NOADV || \
+                              NERF_F16_HACK_NOBARRIER || NERF_WG_HACK_NOATOMIC || NERF_F16_HACK_NOEPI || NERF_F16_HACK_NORELU || \
+                              NERF_F32X_HACK_NOADV || NERF_F32X_HACK_NOPE || NERF_F32X_HACK_NOEPI || NERF_F32X_HACK_SAVE_NOSTORE || \
+                              NERF_XB_HACK_NOSTORE)
+// (a structural knob of the SAVE forward also breaks results when switched off: no rows stored)
+#if (NERF_ANY_TIMING_HACK || NERF_SAVE_TAPS == 0) && !defined(NERF_TIMING_BUILD)
 #error "a NERF_*_HACK_* / NERF_F32_ASM_OVERRUN timing switch is set: such a library computes wrong results; build it with -DNERF_TIMING_BUILD (tools/ab_bench.py does) so that nerf_build_flags() reports it"
 #endif
 
@@ -1602,60 +1604,84 @@ int num_cus() {
   return cus;
 }
 
-int launch_mlp(const MlpArgs& a, bool ray_mode, int precision, hipStream_t st) {
-  if (precision != NERF_PREC_F32 && precision != NERF_PREC_F16 && precision != NERF_PREC_F32X && precision != NERF_PREC_F16S)
-    return fail(NERF_ERR_UNSUPPORTED, "%s", "precision not built");
-  if (a.n_points <= 0) return NERF_OK;
-  if (a.index && a.n_points > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "index mode: point ids are int32");
-  if (precision == NERF_PREC_F32X) {       // persistent workgroups of 4 waves, one per CU
-    const long long n_tiles = (a.n_points + kXTilePts - 1) / kXTilePts;
-    const unsigned blocks = (unsigned)(n_tiles < num_cus() ? n_tiles : num_cus());
-    if (ray_mode && a.density_only) hipLaunchKernelGGL((nerf_mlp_f32x_kernel<true, false, true>), dim3(blocks), dim3(kXThreads), 0, st, a);
-    else if (ray_mode && a.skip_dead_colour) hipLaunchKernelGGL((nerf_mlp_f32x_kernel<true, false, false, true>), dim3(blocks), dim3(kXThreads), 0, st, a);
-    else if (ray_mode) hipLaunchKernelGGL(nerf_mlp_f32x_kernel<true>, dim3(blocks), dim3(kXThreads), 0, st, a);
-    else hipLaunchKernelGGL(nerf_mlp_f32x_kernel<false>, dim3(blocks), dim3(kXThreads), 0, st, a);
-    return check_launch("nerf_mlp_f32x_kernel");
-  }
-  if (precision == NERF_PREC_F16S) {       // the fp16 path on 16x16x32 MFMA tiles: same workgroup shape and LDS ring
-    const long long n_tiles = (a.n_points + kF16TilePts - 1) / kF16TilePts;
-    const unsigned blocks = (unsigned)(n_tiles < num_cus() ? n_tiles : num_cus());
-    if (ray_mode && a.density_only) hipLaunchKernelGGL((nerf_mlp_f16s_kernel<true, true>), dim3(blocks), dim3(kF16Threads), 0, st, a);
-    else if (ray_mode && a.skip_dead_colour) hipLaunchKernelGGL((nerf_mlp_f16s_kernel<true, false, true>), dim3(blocks), dim3(kF16Threads), 0, st, a);
-    else if (ray_mode) hipLaunchKernelGGL(nerf_mlp_f16s_kernel<true>, dim3(blocks), dim3(kF16Threads), 0, st, a);
-    else hipLaunchKernelGGL(nerf_mlp_f16s_kernel<false>, dim3(blocks), dim3(kF16Threads), 0, st, a);
-    return check_launch("nerf_mlp_f16s_kernel");
-  }
-  if (precision == NERF_PREC_F16) {        // persistent workgroups, one per CU (147 KB of LDS each)
-    const long long n_tiles = (a.n_points + kF16TilePts - 1) / kF16TilePts;
-    const unsigned blocks = (unsigned)(n_tiles < num_cus() ? n_tiles : num_cus());
-    if (ray_mode && a.density_only) hipLaunchKernelGGL((nerf_mlp_f16_kernel<true, true>), dim3(blocks), dim3(kF16Threads), 0, st, a);
-    else if (ray_mode && a.skip_dead_colour) hipLaunchKernelGGL((nerf_mlp_f16_kernel<true, false, true>), dim3(blocks), dim3(kF16Threads), 0, st, a);
-    else if (ray_mode) hipLaunchKernelGGL(nerf_mlp_f16_kernel<true>, dim3(blocks), dim3(kF16Threads), 0, st, a);
-    else hipLaunchKernelGGL(nerf_mlp_f16_kernel<false>, dim3(blocks), dim3(kF16Threads), 0, st, a);
-    return check_launch("nerf_mlp_f16_kernel");
-  }
-#ifndef NERF_F32_WG_WAVES
-#define NERF_F32_WG_WAVES 1                 // waves per workgroup of the (barrier-free) inference instance: with one-wave
-                                            // workgroups every SIMD is refilled on its own (+0.9 % over 4-wave workgroups, A/B)
-#endif
-  const long long tiles = (a.n_points + nerf::kTilePts - 1) / nerf::kTilePts;
-  long long blocks = (tiles + NERF_F32_WG_WAVES - 1) / NERF_F32_WG_WAVES;
-  if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "too many points for one launch");
-  // density_only (ray mode): every precision has an instance that stops after the sigma head
-  if (ray_mode && a.density_only) hipLaunchKernelGGL((nerf_mlp_f32_kernel<true, false, true>), dim3((unsigned)blocks), dim3(64 * NERF_F32_WG_WAVES), 0, st, a);
-  else if (ray_mode && a.skip_dead_colour)
-    hipLaunchKernelGGL((nerf_mlp_f32_kernel<true, false, false, true>), dim3((unsigned)blocks), dim3(64 * NERF_F32_WG_WAVES), 0, st, a);
-  else if (ray_mode) hipLaunchKernelGGL(nerf_mlp_f32_kernel<true>, dim3((unsigned)blocks), dim3(64 * NERF_F32_WG_WAVES), 0, st, a);
-  else hipLaunchKernelGGL(nerf_mlp_f32_kernel<false>, dim3((unsigned)blocks), dim3(64 * NERF_F32_WG_WAVES), 0, st, a);
-  return check_launch("nerf_mlp_f32_kernel");
-}
-
 inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 }  // namespace
 
 // ===================================================================================== C ABI
 extern "C" {
+
+// The MLP forward instances of one precision, inference or SAVE (training forward), and their launch shape.
+using MlpKernel = void (*)(MlpArgs);
+struct MlpFamily {
+  const char* name;
+  int wg_pts, threads;       // points and threads of one workgroup tile
+  bool persistent;           // one workgroup per CU walks the tiles; otherwise one workgroup per tile
+  MlpKernel inst[4];         // rays, density only | rays, dead-colour skip | rays | points
+};
+// hipcc emits the instances in the order of their first use, and the library's device code is kept byte for byte: the inference
+// families stand here, the SAVE families behind mlp_backward_impl (their place before there was a table)
+#define NERF_MLP_INFERENCE_3(K) {K<true, true>, K<true, false, true>, K<true>, K<false>}
+#define NERF_MLP_INFERENCE_4(K) {K<true, false, true>, K<true, false, false, true>, K<true>, K<false>}
+#define NERF_MLP_SAVE(K) {K<true, true, true>, K<true, true, false, true>, K<true, true>, K<false, true>}
+static const MlpFamily kMlpF32x = {"nerf_mlp_f32x_kernel", kXTilePts, kXThreads, true, NERF_MLP_INFERENCE_4(nerf_mlp_f32x_kernel)};
+// the fp16 path on 16x16x32 MFMA tiles: same workgroup shape and LDS ring as f16 (147 KB of LDS per workgroup)
+static const MlpFamily kMlpF16s = {"nerf_mlp_f16s_kernel", kF16TilePts, kF16Threads, true, NERF_MLP_INFERENCE_3(nerf_mlp_f16s_kernel)};
+static const MlpFamily kMlpF16 = {"nerf_mlp_f16_kernel", kF16TilePts, kF16Threads, true, NERF_MLP_INFERENCE_3(nerf_mlp_f16_kernel)};
+// barrier-free: workgroups of NERF_F32_WG_WAVES one-tile waves (nerf_mlp_f32.hip.inc says why one)
+static const MlpFamily kMlpF32 = {"nerf_mlp_f32_kernel", nerf::kTilePts * NERF_F32_WG_WAVES, 64 * NERF_F32_WG_WAVES, false,
+                           NERF_MLP_INFERENCE_4(nerf_mlp_f32_kernel)};
+static const MlpFamily* mlp_family(int precision, bool save);
+
+// persistent kernels: one workgroup per CU, fewer when there are fewer tiles
+static unsigned persistent_blocks(long long n_points, int wg_pts) {
+  const long long n_tiles = (n_points + wg_pts - 1) / wg_pts;
+  return (unsigned)(n_tiles < num_cus() ? n_tiles : num_cus());
+}
+
+// every MLP forward launch: the family from (precision, save), the instance from (ray_mode, density_only, skip_dead_colour).
+// `entry`: the public function that was called (error texts)
+static int launch_mlp(const MlpArgs& a, bool ray_mode, bool save, int precision, hipStream_t st, const char* entry) {
+  if (!mlp_family(precision, false)) return fail(NERF_ERR_UNSUPPORTED, "%s: precision not built", entry);
+  if (a.n_points <= 0) return NERF_OK;
+  if (a.index && a.n_points > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s: index mode: point ids are int32", entry);
+  const MlpFamily* f = mlp_family(precision, save);
+  if (!f) return fail(NERF_ERR_UNSUPPORTED, "%s: f32 or f32x only", entry);
+  // density_only (ray mode): every precision has an instance that stops after the sigma head
+  const MlpKernel k = f->inst[!ray_mode ? 3 : a.density_only ? 0 : a.skip_dead_colour ? 1 : 2];
+  if (f->persistent) {
+    hipLaunchKernelGGL(k, dim3(persistent_blocks(a.n_points, f->wg_pts)), dim3(f->threads), 0, st, a);
+  } else {
+    const long long blocks = (a.n_points + f->wg_pts - 1) / f->wg_pts;
+    if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s: too many points for one launch", entry);
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(f->threads), 0, st, a);
+  }
+  return check_launch(f->name);
+}
+
+// The ray-mode forward entries.  for_compositing: `raw` only ever reaches nerf_composite, where the colours of zero-density
+// samples are multiplied by exactly 0, so tiles without density skip the colour branch (DSKIP).  want_save: the training forward.
+// index / count (masked): rows of index[j] at slot j, `raw` at the id (every instance honours both).
+static int forward_rays(const char* entry, const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride, int64_t n_rays,
+                        int32_t n_samples, const void* packed, float* raw, bool want_save, float* save, bool density_only,
+                        bool for_compositing, int32_t precision, void* stream, const int* index = nullptr, const int* count = nullptr) {
+  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s: bad size", entry);
+  if (n_rays == 0) return NERF_OK;
+  if (!rays_o || !rays_d || !tvals || !packed || !raw || (want_save && !save)) return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
+  MlpArgs a{};
+  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride;
+  a.n_points = n_rays * n_samples; a.n_samples = n_samples; a.packed = (const float*)packed; a.raw = raw; a.save = save;
+  a.density_only = density_only; a.skip_dead_colour = for_compositing;
+  a.index = index; a.count = count;
+  if (want_save) {
+    // without dead-tile skipping in the backward pass every row must exist: fall back to the full store (the SAME helper decides
+    // for the backward pass).  The buffer is stamped with what is done here: 1 = the rows of density-free tiles are NOT stored
+    a.skip_dead_colour = for_compositing && dead_tile_list_available(a.n_points, precision);
+    if (hipMemsetAsync(save + TrainSave::off_stamp(a.n_points), a.skip_dead_colour ? 0x01 : 0x00, 4 * sizeof(float), (hipStream_t)stream) != hipSuccess)
+      return fail(NERF_ERR_HIP, "%s: memset failed", entry);
+  }
+  return launch_mlp(a, true, want_save, precision, (hipStream_t)stream, entry);
+}
 
 int32_t nerf_abi_version(void) { return NERF_ABI_VERSION; }
 
@@ -1664,7 +1690,7 @@ int32_t nerf_build_flags(void) {
 #ifdef NERF_TIMING_BUILD
   f |= NERF_BUILD_TIMING;
 #endif
-#if NERF_ANY_TIMING_HACK || NERF_SAVE_TAPS == 0 || 2 == 0
+#if NERF_ANY_TIMING_HACK || NERF_SAVE_TAPS == 0
   f |= NERF_BUILD_WRONG_NUMERICS;
 #endif
   return f;
@@ -1679,14 +1705,20 @@ int64_t nerf_packed_model_bytes(int32_t precision) {
   return -1;
 }
 
-int32_t nerf_pack_model(const float* const params[24], void* packed, int32_t precision, void* stream) {
-  if (!params || !packed) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_pack_model: null argument");
-  PackArgs a;
+// the PackArgs of every pack entry (`entry`: its name for the error text)
+static int32_t fill_pack_args(const char* entry, const float* const params[24], void* out, PackArgs& a) {
+  if (!params || !out) return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
   for (int i = 0; i < nerf::P_COUNT; ++i) {
-    if (!params[i]) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_pack_model: null parameter pointer");
+    if (!params[i]) return fail(NERF_ERR_INVALID_ARG, "%s: null parameter pointer", entry);
     a.p[i] = params[i];
   }
-  a.out = (float*)packed;
+  a.out = (float*)out;
+  return NERF_OK;
+}
+
+int32_t nerf_pack_model(const float* const params[24], void* packed, int32_t precision, void* stream) {
+  PackArgs a;
+  if (const int rc = fill_pack_args("nerf_pack_model", params, packed, a)) return rc;
   const int threads = 256;
   if (precision == NERF_PREC_F16 || precision == NERF_PREC_F32X || precision == NERF_PREC_F16S) {
     const long long n = nerf::kF16ConstBytes / 4 + (long long)nerf::kF16Frags * 512;
@@ -1724,45 +1756,28 @@ int32_t nerf_mlp_forward(const float* pts, const float* viewdirs, int64_t n_rays
   MlpArgs a{};
   a.pts = pts; a.viewdirs = viewdirs; a.n_points = n_rays * n_samples; a.n_samples = n_samples;
   a.packed = (const float*)packed; a.raw = raw;
-  return launch_mlp(a, false, precision, (hipStream_t)stream);
+  return launch_mlp(a, false, false, precision, (hipStream_t)stream, "nerf_mlp_forward");
 }
 
 int32_t nerf_mlp_forward_rays(const float* rays_o, const float* rays_d, const float* tvals,
                               int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                               const void* packed, float* raw, int32_t precision, void* stream) {
-  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays: bad size");
-  if (n_rays == 0) return NERF_OK;
-  if (!rays_o || !rays_d || !tvals || !packed || !raw) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays: null argument");
-  MlpArgs a{};
-  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride;
-  a.n_points = n_rays * n_samples; a.n_samples = n_samples; a.packed = (const float*)packed; a.raw = raw;
-  return launch_mlp(a, true, precision, (hipStream_t)stream);
+  return forward_rays("nerf_mlp_forward_rays", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, false, nullptr,
+                      false, false, precision, stream);
 }
 
 int32_t nerf_mlp_forward_rays_for_compositing(const float* rays_o, const float* rays_d, const float* tvals,
                                               int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                                               const void* packed, float* raw, int32_t precision, void* stream) {
-  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_for_compositing: bad size");
-  if (n_rays == 0) return NERF_OK;
-  if (!rays_o || !rays_d || !tvals || !packed || !raw) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_for_compositing: null argument");
-  MlpArgs a{};
-  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride;
-  a.n_points = n_rays * n_samples; a.n_samples = n_samples; a.packed = (const float*)packed; a.raw = raw;
-  a.skip_dead_colour = 1;
-  return launch_mlp(a, true, precision, (hipStream_t)stream);
+  return forward_rays("nerf_mlp_forward_rays_for_compositing", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw,
+                      false, nullptr, false, true, precision, stream);
 }
 
 int32_t nerf_mlp_forward_rays_density(const float* rays_o, const float* rays_d, const float* tvals,
                                       int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                                       const void* packed, float* raw, int32_t precision, void* stream) {
-  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_density: bad size");
-  if (n_rays == 0) return NERF_OK;
-  if (!rays_o || !rays_d || !tvals || !packed || !raw) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_density: null argument");
-  MlpArgs a{};
-  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride;
-  a.n_points = n_rays * n_samples; a.n_samples = n_samples; a.packed = (const float*)packed; a.raw = raw;
-  a.density_only = 1;
-  return launch_mlp(a, true, precision, (hipStream_t)stream);
+  return forward_rays("nerf_mlp_forward_rays_density", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, false,
+                      nullptr, true, false, precision, stream);
 }
 
 int32_t nerf_sample_fine(const float* raw_coarse, const float* t_coarse, const float* u,
@@ -1842,11 +1857,8 @@ static int32_t wgrad_impl(const float* dz, int64_t ldz, int32_t zc0, int32_t n_o
   long long blocks = (pairs + 255) / 256;            // >= 256 point pairs per workgroup
   if (blocks > num_cus()) blocks = num_cus();
   if (blocks < 1) blocks = 1;
-  // the small-layer (vector-load) kernels: one workgroup per CU (more resident waves measured no faster)
-  long long vblocks = (pairs + 255) / 256;
-  if (vblocks > (long long)num_cus()) vblocks = (long long)num_cus();
-  if (vblocks < 1) vblocks = 1;
-  const dim3 grid((unsigned)blocks), vgrid((unsigned)vblocks), blk(256);
+  // (the small-layer vector-load kernels too: one workgroup per CU, more resident waves measured no faster)
+  const dim3 grid((unsigned)blocks), blk(256);
   hipStream_t st = (hipStream_t)stream;
   const bool aligned = ldz % 4 == 0 && ldh % 4 == 0 && zc0 % 4 == 0 && hc0 % 4 == 0 &&
                        (uintptr_t)dz % 16 == 0 && (uintptr_t)hin % 16 == 0;
@@ -1884,7 +1896,7 @@ static int32_t wgrad_impl(const float* dz, int64_t ldz, int32_t zc0, int32_t n_o
       long long g = n_points / (2 * PF); \
       if (g > num_cus()) g = num_cus(); \
       hipLaunchKernelGGL((nerf_wgrad_vec_f32_asm_kernel<AV, BV, PF>), dim3((unsigned)g), blk, 0, st, a); \
-    } else hipLaunchKernelGGL((nerf_wgrad_vec_f32_kernel<AV, BV>), vgrid, blk, 0, st, a); \
+    } else hipLaunchKernelGGL((nerf_wgrad_vec_f32_kernel<AV, BV>), grid, blk, 0, st, a); \
   } while (0)
   else if (n_out == 256 && n_in <= 64 && aligned) VEC(4, 1, NERF_WGVEC_PF41, 2, 2);         // PE -> 256 (layers 0 and 5)
   else if (n_out == 128 && n_in == 256 && aligned) VEC(4, 2, 16, 1, 4);        // views_linears.0, feature part
@@ -2049,26 +2061,14 @@ int64_t nerf_packed_bwd_bytes(int32_t precision) {
 }
 
 int32_t nerf_pack_model_bwd(const float* const params[24], void* packed_bwd_v, int32_t precision, void* stream) {
-  float* packed_bwd = (float*)packed_bwd_v;
-  if (!params || !packed_bwd) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_pack_model_bwd: null argument");
+  PackArgs a;
+  if (const int rc = fill_pack_args("nerf_pack_model_bwd", params, packed_bwd_v, a)) return rc;
   if (precision == NERF_PREC_F32X) {
-    PackArgs a;
-    for (int i = 0; i < nerf::P_COUNT; ++i) {
-      if (!params[i]) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_pack_model_bwd: null parameter pointer");
-      a.p[i] = params[i];
-    }
-    a.out = packed_bwd;
     const long long n = nerf::kF16ConstBytes / 4 + (long long)nerf::kXbSteps * 512;
     hipLaunchKernelGGL(nerf_pack_bwd_f32x_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("nerf_pack_bwd_f32x_kernel");
   }
   if (precision != NERF_PREC_F32) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_pack_model_bwd: f32 or f32x only");
-  PackArgs a;
-  for (int i = 0; i < nerf::P_COUNT; ++i) {
-    if (!params[i]) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_pack_model_bwd: null parameter pointer");
-    a.p[i] = params[i];
-  }
-  a.out = packed_bwd;
   hipLaunchKernelGGL(nerf_pack_bwd_kernel, dim3((unsigned)((nerf::kBwdPackedFloats + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("nerf_pack_bwd_kernel");
 }
@@ -2143,8 +2143,7 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
     }
   }
   if (precision == NERF_PREC_F32X) {
-    const long long n_tiles = (P + kXTilePts - 1) / kXTilePts;
-    const unsigned blocks = (unsigned)(n_tiles < num_cus() ? n_tiles : num_cus());
+    const unsigned blocks = persistent_blocks(P, kXTilePts);
     if (pts_mode) hipLaunchKernelGGL(nerf_mlp_bwd_f32x_kernel<true>, dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
     else if (dens) hipLaunchKernelGGL((nerf_mlp_bwd_f32x_kernel<false, true>), dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(nerf_mlp_bwd_f32x_kernel<false>, dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
@@ -2185,104 +2184,106 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
   }
   WG(GZ(5), 256, 0, 256, pe, 64, 0, 63, grads[10], 319, 0, grads[11]);                  // skip layer, PE part (+ bias)
   WG(GZ(0), 256, 0, 256, pe, 64, 0, 63, grads[P_W0], 63, 0, grads[P_B0]);
+  // the eight 256 x 256 blocks: feature_linear (unless density only), then layers 7..1 with the skip layer's hidden part
+  struct { const float* dz; const float* hin; float* dw; int ldw, wc0; float* db; } job[8];
+  int n_jobs = 0;
+  if (!dens) job[n_jobs++] = {gf, H(7), grads[P_WF], 256, 0, grads[P_BF]};
+  for (int l = 7; l >= 1; --l) {
+    if (l == 5) job[n_jobs++] = {GZ(5), H(4), grads[10], 319, 63, nullptr};
+    else job[n_jobs++] = {GZ(l), H(l - 1), grads[2 * l], 256, 0, grads[2 * l + 1]};
+  }
   if (precision == NERF_PREC_F32X) {
-    // the eight 256 x 256 blocks in one launch on the bf16x3 path (nerf_wgrad_bf16x3.hip.inc)
+    // in one launch on the bf16x3 path (nerf_wgrad_bf16x3.hip.inc)
     WgradXArgs w;
-    w.n_points = P; w.n_jobs = 0; w.live_tiles = live; w.n_live = n_live;
-    auto job = [&](const float* dz, const float* hin, float* dw, int ldw, int wc0, float* db) {
-      WgradXJob& j = w.job[w.n_jobs++];
-      j.dz = dz; j.hin = hin; j.dw = dw; j.db = db; j.ldz = 256; j.zc0 = 0; j.ldh = 256; j.hc0 = 0; j.ldw = ldw; j.wc0 = wc0;   // ld 256: the kernel assumes 1-KiB rows
-    };
-    if (!dens) job(gf, H(7), grads[P_WF], 256, 0, grads[P_BF]);
-    for (int l = 7; l >= 1; --l) {
-      if (l == 5) job(GZ(5), H(4), grads[10], 319, 63, nullptr);
-      else job(GZ(l), H(l - 1), grads[2 * l], 256, 0, grads[2 * l + 1]);
+    w.n_points = P; w.n_jobs = n_jobs; w.live_tiles = live; w.n_live = n_live;
+    for (int i = 0; i < n_jobs; ++i) {
+      WgradXJob& j = w.job[i];
+      j.dz = job[i].dz; j.hin = job[i].hin; j.dw = job[i].dw; j.db = job[i].db; j.ldw = job[i].ldw; j.wc0 = job[i].wc0;
+      j.ldz = 256; j.zc0 = 0; j.ldh = 256; j.hc0 = 0;                                  // ld 256: the kernel assumes 1-KiB rows
     }
     const long long steps = (P + 15) / 16;
-    long long slices = num_cus() / w.n_jobs;
+    long long slices = num_cus() / n_jobs;
     if (slices > steps) slices = steps;
     if (slices < 1) slices = 1;
-    hipLaunchKernelGGL(nerf_wgrad256_bf16x3_kernel, dim3((unsigned)(slices * w.n_jobs)), dim3(256), 0, (hipStream_t)stream, w);
+    hipLaunchKernelGGL(nerf_wgrad256_bf16x3_kernel, dim3((unsigned)(slices * n_jobs)), dim3(256), 0, (hipStream_t)stream, w);
     rc = check_launch("nerf_wgrad256_bf16x3_kernel");
     if (rc) return rc;
   } else if (NERF_WGRAD_ASM && P % 16 == 0 && P / 16 >= num_cus() / 8) {
-    // fp32 MFMA, the eight 256 x 256 blocks in one launch of the asm-load kernel
+    // fp32 MFMA, in one launch of the asm-load kernel
     WgradBatch wb;
-    wb.n_jobs = 0;
-    auto job = [&](const float* dz, const float* hin, float* dw, int ldw, int wc0, float* db) {
-      WgradArgs& j = wb.job[wb.n_jobs++];
-      j.dz = dz; j.ldz = 256; j.zc0 = 0; j.n_out = 256; j.hin = hin; j.ldh = 256; j.hc0 = 0; j.n_in = 256;
-      j.dw = dw; j.ldw = ldw; j.wc0 = wc0; j.db = db; j.n_points = P; j.osplit = 2; j.isplit = 2;
+    wb.n_jobs = n_jobs;
+    for (int i = 0; i < n_jobs; ++i) {
+      WgradArgs& j = wb.job[i];
+      j.dz = job[i].dz; j.ldz = 256; j.zc0 = 0; j.n_out = 256; j.hin = job[i].hin; j.ldh = 256; j.hc0 = 0; j.n_in = 256;
+      j.dw = job[i].dw; j.ldw = job[i].ldw; j.wc0 = job[i].wc0; j.db = job[i].db; j.n_points = P; j.osplit = 2; j.isplit = 2;
       j.live_tiles = live; j.n_live = n_live;
-    };
-    if (!dens) job(gf, H(7), grads[P_WF], 256, 0, grads[P_BF]);
-    for (int l = 7; l >= 1; --l) {
-      if (l == 5) job(GZ(5), H(4), grads[10], 319, 63, nullptr);
-      else job(GZ(l), H(l - 1), grads[2 * l], 256, 0, grads[2 * l + 1]);
     }
-    long long slices = num_cus() / wb.n_jobs;
+    long long slices = num_cus() / n_jobs;
     if (slices < 1) slices = 1;                       // a device with fewer CUs than jobs still gets a non-empty grid
-    if (live) hipLaunchKernelGGL(nerf_wgrad256_f32_asm_kernel<true>, dim3((unsigned)(slices * wb.n_jobs)), dim3(256), 0, (hipStream_t)stream, wb);
-    else hipLaunchKernelGGL(nerf_wgrad256_f32_asm_kernel<false>, dim3((unsigned)(slices * wb.n_jobs)), dim3(256), 0, (hipStream_t)stream, wb);
+    if (live) hipLaunchKernelGGL(nerf_wgrad256_f32_asm_kernel<true>, dim3((unsigned)(slices * n_jobs)), dim3(256), 0, (hipStream_t)stream, wb);
+    else hipLaunchKernelGGL(nerf_wgrad256_f32_asm_kernel<false>, dim3((unsigned)(slices * n_jobs)), dim3(256), 0, (hipStream_t)stream, wb);
     rc = check_launch("nerf_wgrad256_f32_asm_kernel");
     if (rc) return rc;
   } else {
-    if (!dens) WG(gf, 256, 0, 256, H(7), 256, 0, 256, grads[P_WF], 256, 0, grads[P_BF]);   // feature_linear
-    for (int l = 7; l >= 1; --l) {
-      if (l == 5) WG(GZ(5), 256, 0, 256, H(4), 256, 0, 256, grads[10], 319, 63, nullptr);   // skip layer, hidden part
-      else WG(GZ(l), 256, 0, 256, H(l - 1), 256, 0, 256, grads[2 * l], 256, 0, grads[2 * l + 1]);
-    }
+    for (int i = 0; i < n_jobs; ++i) WG(job[i].dz, 256, 0, 256, job[i].hin, 256, 0, 256, job[i].dw, job[i].ldw, job[i].wc0, job[i].db);
   }
 #undef WG
   return NERF_OK;
+}
+
+// the SAVE families (see kMlpF32 for their place): one-wave workgroups for f32
+static const MlpFamily kMlpSaveF32x = {"nerf_mlp_f32x_kernel", kXTilePts, kXThreads, true, NERF_MLP_SAVE(nerf_mlp_f32x_kernel)};
+static const MlpFamily kMlpSaveF32 = {"nerf_mlp_f32_kernel", nerf::kTilePts, 64, false, NERF_MLP_SAVE(nerf_mlp_f32_kernel)};
+static const MlpFamily* mlp_family(int precision, bool save) {
+  switch (precision) {
+    case NERF_PREC_F32: return save ? &kMlpSaveF32 : &kMlpF32;
+    case NERF_PREC_F32X: return save ? &kMlpSaveF32x : &kMlpF32x;
+    case NERF_PREC_F16: return save ? nullptr : &kMlpF16;
+    case NERF_PREC_F16S: return save ? nullptr : &kMlpF16s;
+  }
+  return nullptr;
+}
+
+// the ray-mode backward entries (grads == nullptr where `grads_optional`: the chain alone)
+static int32_t backward_rays(const char* entry, const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
+                             int64_t n_rays, int32_t n_samples, const void* packed_bwd_v, const float* draw, const float* save,
+                             float* gsave, float* g_t, float* g_x, float* const grads[24], bool grads_optional, bool density_only,
+                             int32_t precision, void* stream) {
+  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s: bad size", entry);
+  if (n_rays == 0) return NERF_OK;
+  if (!rays_o || !rays_d || !tvals || !packed_bwd_v || !draw || !save || !gsave || (!grads && !grads_optional))
+    return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
+  if (grads)
+    for (int i = 0; i < 24; ++i) if (!grads[i]) return fail(NERF_ERR_INVALID_ARG, "%s: null gradient pointer", entry);
+  BwdArgs a{};
+  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride; a.n_points = n_rays * n_samples;
+  a.n_samples = n_samples; a.packed_bwd = (const float*)packed_bwd_v; a.draw = draw; a.save = save; a.gsave = gsave; a.g_t = g_t;
+  a.g_x = g_x; a.density_only = density_only;
+  return mlp_backward_impl(a, false, grads, precision, stream);
 }
 
 int32_t nerf_mlp_backward(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
                           int64_t n_rays, int32_t n_samples, const void* packed_bwd_v, const float* draw,
                           const float* save, float* gsave, float* g_t, float* const grads[24], int32_t precision,
                           void* stream) {
-  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward: bad size");
-  if (n_rays == 0) return NERF_OK;
-  if (!rays_o || !rays_d || !tvals || !packed_bwd_v || !draw || !save || !gsave || !grads)
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward: null argument");
-  for (int i = 0; i < 24; ++i) if (!grads[i]) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward: null gradient pointer");
-  BwdArgs a{};
-  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride; a.n_points = n_rays * n_samples;
-  a.n_samples = n_samples; a.packed_bwd = (const float*)packed_bwd_v; a.draw = draw; a.save = save; a.gsave = gsave; a.g_t = g_t;
-  return mlp_backward_impl(a, false, grads, precision, stream);
+  return backward_rays("nerf_mlp_backward", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed_bwd_v, draw, save, gsave,
+                       g_t, nullptr, grads, false, false, precision, stream);
 }
 
 int32_t nerf_mlp_backward_density(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
                                   int64_t n_rays, int32_t n_samples, const void* packed_bwd_v, const float* draw,
                                   const float* save, float* gsave, float* g_t, float* const grads[24], int32_t precision,
                                   void* stream) {
-  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_density: bad size");
-  if (n_rays == 0) return NERF_OK;
-  if (!rays_o || !rays_d || !tvals || !packed_bwd_v || !draw || !save || !gsave || !grads)
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_density: null argument");
-  for (int i = 0; i < 24; ++i) if (!grads[i]) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_density: null gradient pointer");
-  BwdArgs a{};
-  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride; a.n_points = n_rays * n_samples;
-  a.n_samples = n_samples; a.packed_bwd = (const float*)packed_bwd_v; a.draw = draw; a.save = save; a.gsave = gsave; a.g_t = g_t;
-  a.density_only = 1;
-  return mlp_backward_impl(a, false, grads, precision, stream);
+  return backward_rays("nerf_mlp_backward_density", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed_bwd_v, draw, save,
+                       gsave, g_t, nullptr, grads, false, true, precision, stream);
 }
 
 int32_t nerf_mlp_backward_rays_x(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
                                  int64_t n_rays, int32_t n_samples, const void* packed_bwd_v, const float* draw,
                                  const float* save, float* gsave, float* g_t, float* g_x, float* const grads[24],
                                  int32_t density_only, int32_t precision, void* stream) {
-  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_rays_x: bad size");
-  if (n_rays == 0) return NERF_OK;
-  if (!rays_o || !rays_d || !tvals || !packed_bwd_v || !draw || !save || !gsave)
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_rays_x: null argument");
-  if (grads)
-    for (int i = 0; i < 24; ++i) if (!grads[i]) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward_rays_x: null gradient pointer");
-  BwdArgs a{};
-  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride; a.n_points = n_rays * n_samples;
-  a.n_samples = n_samples; a.packed_bwd = (const float*)packed_bwd_v; a.draw = draw; a.save = save; a.gsave = gsave; a.g_t = g_t;
-  a.g_x = g_x; a.density_only = density_only != 0;
-  return mlp_backward_impl(a, false, grads, precision, stream);
+  return backward_rays("nerf_mlp_backward_rays_x", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed_bwd_v, draw, save,
+                       gsave, g_t, g_x, grads, true, density_only != 0, precision, stream);
 }
 
 int32_t nerf_mlp_backward_points(const float* pts, int64_t n_rays, int32_t n_samples, const void* packed_bwd_v,
@@ -2301,57 +2302,23 @@ int32_t nerf_mlp_backward_points(const float* pts, int64_t n_rays, int32_t n_sam
 
 int64_t nerf_train_save_floats(int64_t n_points) { return n_points < 0 ? -1 : TrainSave::floats(n_points); }
 
-static int32_t forward_rays_save_impl(const float* rays_o, const float* rays_d, const float* tvals,
-                                      int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
-                                      const void* packed, float* raw, float* save, int32_t precision, void* stream, int density_only,
-                                      int skip_dead = 0, const int* index = nullptr, const int* count = nullptr) {
-  if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_save: bad size");
-  if (n_rays == 0) return NERF_OK;
-  if (!rays_o || !rays_d || !tvals || !packed || !raw || !save) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_save: null argument");
-  MlpArgs a{};
-  a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = tvals; a.t_ray_stride = t_ray_stride;
-  a.n_points = n_rays * n_samples; a.n_samples = n_samples; a.packed = (const float*)packed; a.raw = raw; a.save = save;
-  a.density_only = density_only;
-  a.index = index; a.count = count;      // masked: rows of index[j] at slot j, `raw` at the id (every SAVE instance honours both)
-  // stamp: 1 = the rows of density-free tiles are NOT stored (for-compositing entry with the list available)
-  const bool rows_skipped = (precision == NERF_PREC_F32 || precision == NERF_PREC_F32X) && !density_only && skip_dead;
-  if (hipMemsetAsync(save + TrainSave::off_stamp(a.n_points), rows_skipped ? 0x01 : 0x00, 4 * sizeof(float), (hipStream_t)stream) != hipSuccess)
-    return fail(NERF_ERR_HIP, "%s", "nerf_mlp_forward_rays_save: memset failed");
-  if (precision == NERF_PREC_F32X) {
-    const long long n_tiles = (a.n_points + kXTilePts - 1) / kXTilePts;
-    const unsigned blocks = (unsigned)(n_tiles < num_cus() ? n_tiles : num_cus());
-    if (density_only) hipLaunchKernelGGL((nerf_mlp_f32x_kernel<true, true, true>), dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
-    else if (skip_dead) hipLaunchKernelGGL((nerf_mlp_f32x_kernel<true, true, false, true>), dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((nerf_mlp_f32x_kernel<true, true>), dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
-    return check_launch("nerf_mlp_f32x_kernel<save>");
-  }
-  if (precision != NERF_PREC_F32) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_mlp_forward_rays_save: f32 or f32x only");
-  const long long tiles = (a.n_points + nerf::kTilePts - 1) / nerf::kTilePts;
-  if (tiles > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_save: too many points for one launch");
-  // barrier-free: one-wave workgroups
-  if (density_only) hipLaunchKernelGGL((nerf_mlp_f32_kernel<true, true, true>), dim3((unsigned)tiles), dim3(64), 0, (hipStream_t)stream, a);
-  else if (skip_dead) hipLaunchKernelGGL((nerf_mlp_f32_kernel<true, true, false, true>), dim3((unsigned)tiles), dim3(64), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((nerf_mlp_f32_kernel<true, true>), dim3((unsigned)tiles), dim3(64), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_mlp_f32_kernel<save>");
-}
-
 int32_t nerf_mlp_forward_rays_save(const float* rays_o, const float* rays_d, const float* tvals,
                                    int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                                    const void* packed, float* raw, float* save, int32_t precision, void* stream) {
-  return forward_rays_save_impl(rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, save, precision, stream, 0);
+  return forward_rays("nerf_mlp_forward_rays_save", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, true, save,
+                      false, false, precision, stream);
 }
 int32_t nerf_mlp_forward_rays_save_for_compositing(const float* rays_o, const float* rays_d, const float* tvals,
                                                    int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                                                    const void* packed, float* raw, float* save, int32_t precision, void* stream) {
-  // without dead-tile skipping in the backward pass every row must exist: fall back to the full store (the SAME helper decides
-  // for the backward pass, and the buffer is stamped with what was done here)
-  const int skip = n_rays > 0 && n_samples > 0 && dead_tile_list_available(n_rays * (int64_t)n_samples, precision);
-  return forward_rays_save_impl(rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, save, precision, stream, 0, skip);
+  return forward_rays("nerf_mlp_forward_rays_save_for_compositing", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed,
+                      raw, true, save, false, true, precision, stream);
 }
 int32_t nerf_mlp_forward_rays_save_density(const float* rays_o, const float* rays_d, const float* tvals,
                                            int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                                            const void* packed, float* raw, float* save, int32_t precision, void* stream) {
-  return forward_rays_save_impl(rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, save, precision, stream, 1);
+  return forward_rays("nerf_mlp_forward_rays_save_density", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, true,
+                      save, true, false, precision, stream);
 }
 
 // ---- masked (fast_sampling) fine pass of a training step
@@ -2390,10 +2357,9 @@ int32_t nerf_mlp_forward_rays_save_masked(const float* rays_o, const float* rays
   if (n_rays == 0) return NERF_OK;
   if (!index || !count) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_rays_save_masked: null argument");
   // the fine pass of a step: `raw` goes to compositing, so the rule of nerf_mlp_forward_rays_save_for_compositing holds per
-  // compact tile (and the same helper decides for the backward pass)
-  const int skip = dead_tile_list_available(n_rays * (int64_t)n_samples, precision);
-  return forward_rays_save_impl(rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, save, precision, stream, 0, skip,
-                                index, count);
+  // compact tile
+  return forward_rays("nerf_mlp_forward_rays_save_masked", rays_o, rays_d, tvals, t_ray_stride, n_rays, n_samples, packed, raw, true,
+                      save, false, true, precision, stream, index, count);
 }
 
 int64_t nerf_mlp_backward_masked_workspace_bytes(int64_t n_points) {
@@ -2444,17 +2410,7 @@ int32_t nerf_mlp_forward_points_save(const float* pts, const float* viewdirs, in
   a.packed = (const float*)packed; a.raw = raw; a.save = save;
   if (hipMemsetAsync(save + TrainSave::off_stamp(a.n_points), 0, 4 * sizeof(float), (hipStream_t)stream) != hipSuccess)      // every row stored
     return fail(NERF_ERR_HIP, "%s", "nerf_mlp_forward_points_save: memset failed");
-  if (precision == NERF_PREC_F32X) {
-    const long long n_tiles = (a.n_points + kXTilePts - 1) / kXTilePts;
-    const unsigned blocks = (unsigned)(n_tiles < num_cus() ? n_tiles : num_cus());
-    hipLaunchKernelGGL((nerf_mlp_f32x_kernel<false, true>), dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
-    return check_launch("nerf_mlp_f32x_kernel<points,save>");
-  }
-  if (precision != NERF_PREC_F32) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_mlp_forward_points_save: f32 or f32x only");
-  const long long tiles = (a.n_points + nerf::kTilePts - 1) / nerf::kTilePts;
-  if (tiles > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_forward_points_save: too many points for one launch");
-  hipLaunchKernelGGL((nerf_mlp_f32_kernel<false, true>), dim3((unsigned)tiles), dim3(64), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_mlp_f32_kernel<points,save>");
+  return launch_mlp(a, false, true, precision, (hipStream_t)stream, "nerf_mlp_forward_points_save");
 }
 
 int32_t nerf_image_ssim(const float* pred, const float* gt, int32_t H, int32_t W, double* sum1, void* stream) {
@@ -2483,21 +2439,138 @@ static int64_t render_block_rays() {
   return kRenderBlockRays;
 }
 
-int64_t nerf_render_workspace_bytes(int64_t n_rays_frame, int32_t n_importance, int32_t fast_sampling) {
+// The workspace of one block of `n_rays` rays, carved in this order, every piece 256-byte aligned.  index / count: with fast_sampling
+// the compacted ids of the valid merged samples and their number, otherwise the last-sample ids of the fp16 far-plane guard and
+// their number.  t_jit: the jittered coarse depths [n,64] of a stochastic render.
+struct RenderWorkspace {
+  float* raw_c; float* t_sorted = nullptr; float* raw_f = nullptr; uint8_t* valid = nullptr; int* index; int* count; float* t_jit = nullptr;
+  int64_t bytes;
+  RenderWorkspace(void* base, int64_t n_rays, int32_t n_importance, int32_t fast_sampling, bool stochastic) {
+    uintptr_t p = (uintptr_t)base;
+    auto take = [&p](int64_t n) { void* q = (void*)p; p += (uintptr_t)align256(n); return q; };
+    const int64_t S = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
+    raw_c = (float*)take(n_rays * NERF_N_SAMPLES * 4 * (int64_t)sizeof(float));
+    if (n_importance) {
+      t_sorted = (float*)take(n_rays * S * (int64_t)sizeof(float));
+      raw_f = (float*)take(n_rays * S * 4 * (int64_t)sizeof(float));
+    }
+    if (n_importance && fast_sampling) {
+      valid = (uint8_t*)take(n_rays * S);
+      index = (int*)take(n_rays * S * (int64_t)sizeof(int));
+    } else {
+      index = (int*)take(n_rays * (int64_t)sizeof(int));
+    }
+    count = (int*)take(sizeof(int));
+    if (stochastic) t_jit = (float*)take(n_rays * NERF_N_SAMPLES * (int64_t)sizeof(float));
+    bytes = (int64_t)(p - (uintptr_t)base);
+  }
+};
+static int64_t render_workspace_bytes(int64_t n_rays_frame, int32_t n_importance, int32_t fast_sampling, bool stochastic) {
   if (n_rays_frame < 0) return -1;
   const int64_t n_rays = n_rays_frame < render_block_rays() ? n_rays_frame : render_block_rays();
-  const int64_t raw_c = align256(n_rays * NERF_N_SAMPLES * 4 * (int64_t)sizeof(float));
-  if (n_importance == 0) return raw_c + align256(n_rays * (int64_t)sizeof(int)) + 256;
-  const int64_t S = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
-  int64_t total = raw_c + align256(n_rays * S * (int64_t)sizeof(float)) + align256(n_rays * S * 4 * (int64_t)sizeof(float));
-  if (fast_sampling) total += align256(n_rays * S) + align256(n_rays * S * (int64_t)sizeof(int)) + 256;   // mask, index, count
-  else total += align256(n_rays * (int64_t)sizeof(int)) + 256;                                            // last-sample ids, count (fp16 far-plane guard)
-  return total;
+  return RenderWorkspace(nullptr, n_rays, n_importance, fast_sampling, stochastic).bytes;
+}
+int64_t nerf_render_workspace_bytes(int64_t n_rays_frame, int32_t n_importance, int32_t fast_sampling) {
+  return render_workspace_bytes(n_rays_frame, n_importance, fast_sampling, false);
+}
+int64_t nerf_render_stochastic_workspace_bytes(int64_t n_rays_frame, int32_t n_importance) {
+  return render_workspace_bytes(n_rays_frame, n_importance, 0, true);
 }
 
-static int32_t render_block(const float* rays_o, const float* rays_d, int64_t n_rays, const void* packed_coarse, const void* packed_fine,
-                            const float* t_coarse, const float* u, int32_t n_importance, int32_t white_bkgd, int32_t precision,
-                            int32_t fast_sampling, float weights_threshold, void* workspace, float* rgb, float* depth, void* stream);
+// One frame, block by block through the four stages.  jitter / u_rays (stochastic render: task == "train", no grad) give every ray
+// its own coarse depths (nerf_stratified_samples of the block, stride 64) and its own u (stride 128); without them the shared
+// tables go through with stride 0, and nerf_sample_fine_rays then launches nerf_sample_fine_kernel.
+static int32_t render_frame(const char* entry, const float* rays_o, const float* rays_d, int64_t n_rays, const void* packed_coarse,
+                            const void* packed_fine, const float* t_coarse, const float* u, const float* jitter, const float* u_rays,
+                            bool stochastic, int32_t n_importance, int32_t white_bkgd, int32_t precision, int32_t fast_sampling,
+                            float weights_threshold, void* workspace, int64_t workspace_bytes, float* rgb, float* depth, void* stream) {
+  if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s: bad size", entry);
+  if (n_importance != 0 && n_importance != NERF_N_IMPORTANCE)
+    return fail(NERF_ERR_INVALID_ARG, "%s: n_importance must be 0 or 128", entry);
+  if (n_rays == 0) return NERF_OK;
+  if (!rays_o || !rays_d || !packed_coarse || !t_coarse || !rgb || !depth || !workspace ||
+      (n_importance && (!packed_fine || !u)))
+    return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
+  if (workspace_bytes < render_workspace_bytes(n_rays, n_importance, fast_sampling, stochastic))
+    return fail(NERF_ERR_WORKSPACE, "%s: workspace too small", entry);
+  // the masked fine pass addresses (ray, sample) pairs by 32-bit ids (nerf_compact_kernel, MlpArgs::index)
+  const int64_t S = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
+  if (fast_sampling && n_importance && n_rays > (int64_t)0x7fffffff / S)
+    return fail(NERF_ERR_INVALID_ARG, "%s: fast_sampling handles at most 11 184 810 rays per call "
+                                      "(n_rays * 192 point ids must fit in int32): split the frame", entry);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t B = render_block_rays();
+  for (int64_t r0 = 0; r0 < n_rays; r0 += B) {
+    const int64_t nb = n_rays - r0 < B ? n_rays - r0 : B;
+    const float* o = rays_o + 3 * r0;
+    const float* d = rays_d + 3 * r0;
+    float* rgb_b = rgb + 3 * r0;
+    float* depth_b = depth + r0;
+    const RenderWorkspace w(workspace, nb, n_importance, fast_sampling, stochastic);
+    const float* tc = t_coarse;
+    int64_t tcs = 0;
+    int rc;
+    if (jitter) {
+      rc = nerf_stratified_samples(t_coarse, jitter + NERF_N_SAMPLES * r0, nb, w.t_jit, stream);
+      if (rc) return rc;
+      tc = w.t_jit; tcs = NERF_N_SAMPLES;
+    }
+    // hierarchical render: the coarse network only places the fine samples -- nothing but its sigma is read
+    // (volume_renderer.py:335; the returned rgb/depth come from the fine outputs, :414-437), so the coarse pass stops after
+    // the sigma head.  With n_importance == 0 the coarse outputs ARE the frame and the full network runs.
+    rc = forward_rays(entry, o, d, tc, tcs, nb, NERF_N_SAMPLES, packed_coarse, w.raw_c, false, nullptr, n_importance != 0, false, precision, stream);
+    if (rc) return rc;
+    // fp16 far-plane guard.  The last sample of a ray has delta = 1e10 (volume_renderer.py:85-86): ANY sigma > 0 there makes alpha = 1, so
+    // an fp16 rounding that flips the sign of a sigma within 1e-2 of zero turns a background ray into a full far-plane hit (round 2:
+    // single rays off by 0.64 in rgb and 6.0 in depth, which alone set the fp16 PSNR).  Every other sample's alpha moves by
+    // |d sigma| * delta ~ 1e-4.  So the fp16 precisions re-evaluate exactly that sample of every ray (0.5 % of the points) with the
+    // split-fp16 stream that rides behind their packed model: fp32-accurate sigma and colour where it matters, ~1.5 % of the frame.
+    const bool guard = (precision == NERF_PREC_F16 || precision == NERF_PREC_F16S) && nb <= (int64_t)0x7fffffff / S;
+    auto far_plane_guard = [&](const float* tvals, int64_t stride, int32_t S_, const void* packed_f16, float* raw) -> int {
+      hipLaunchKernelGGL(nerf_last_sample_index_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, w.index, w.count, (long long)nb, S_);
+      const int r2 = check_launch("nerf_last_sample_index_kernel");
+      if (r2) return r2;
+      return forward_rays(entry, o, d, tvals, stride, nb, S_, (const char*)packed_f16 + nerf::kF16PackedBytes, raw, false, nullptr, false,
+                          false, NERF_PREC_F32X, stream, w.index, w.count);
+    };
+    if (n_importance == 0) {
+      if (guard) {
+        rc = far_plane_guard(tc, tcs, NERF_N_SAMPLES, packed_coarse, w.raw_c);
+        if (rc) return rc;
+      }
+      rc = nerf_composite(w.raw_c, tc, tcs, nb, NERF_N_SAMPLES, white_bkgd, rgb_b, depth_b, nullptr, stream);
+      if (rc) return rc;
+      continue;
+    }
+    // fast_sampling, ESS/ERT (volume_renderer.py:359-369, network.py:207-253): the sampler also marks the valid merged samples
+    rc = nerf_sample_fine_rays(w.raw_c, tc, tcs, u_rays ? u_rays + NERF_N_IMPORTANCE * r0 : u, u_rays ? NERF_N_IMPORTANCE : 0, nb, w.t_sorted,
+                               nullptr, w.valid, fast_sampling ? weights_threshold : 0.f, fast_sampling ? 0.45f : 0.f, stream);
+    if (rc) return rc;
+    if (!fast_sampling) {
+      rc = forward_rays(entry, o, d, w.t_sorted, S, nb, (int32_t)S, packed_fine, w.raw_f, false, nullptr, false, true, precision, stream);
+      if (rc) return rc;
+      if (guard) {
+        rc = far_plane_guard(w.t_sorted, S, (int32_t)S, packed_fine, w.raw_f);
+        if (rc) return rc;
+      }
+    } else {
+      // only the valid merged samples go through the fine network; the others keep raw = 0 (sigma 0 -> weight 0)
+      if (hipMemsetAsync(w.count, 0, sizeof(int), st) != hipSuccess ||
+          hipMemsetAsync(w.raw_f, 0, (size_t)(nb * S * 4 * (int64_t)sizeof(float)), st) != hipSuccess)
+        return fail(NERF_ERR_HIP, "%s: memset failed", entry);
+      const long long np = nb * S;
+      hipLaunchKernelGGL(nerf_compact_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, w.valid, np, w.index, w.count);
+      rc = check_launch("nerf_compact_kernel");
+      if (rc) return rc;
+      rc = forward_rays(entry, o, d, w.t_sorted, S, nb, (int32_t)S, packed_fine, w.raw_f, false, nullptr, false, true, precision, stream,
+                        w.index, w.count);
+      if (rc) return rc;
+    }
+    rc = nerf_composite(w.raw_f, w.t_sorted, S, nb, (int32_t)S, white_bkgd, rgb_b, depth_b, nullptr, stream);
+    if (rc) return rc;
+  }
+  return NERF_OK;
+}
 
 int32_t nerf_render_forward(const float* rays_o, const float* rays_d, int64_t n_rays,
                             const void* packed_coarse, const void* packed_fine,
@@ -2505,111 +2578,8 @@ int32_t nerf_render_forward(const float* rays_o, const float* rays_d, int64_t n_
                             int32_t white_bkgd, int32_t precision, int32_t fast_sampling,
                             float weights_threshold, void* workspace,
                             int64_t workspace_bytes, float* rgb, float* depth, void* stream) {
-  if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward: bad size");
-  if (n_importance != 0 && n_importance != NERF_N_IMPORTANCE)
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward: n_importance must be 0 or 128");
-  if (n_rays == 0) return NERF_OK;
-  if (!rays_o || !rays_d || !packed_coarse || !t_coarse || !rgb || !depth || !workspace ||
-      (n_importance && (!packed_fine || !u)))
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward: null argument");
-  if (workspace_bytes < nerf_render_workspace_bytes(n_rays, n_importance, fast_sampling))
-    return fail(NERF_ERR_WORKSPACE, "%s", "nerf_render_forward: workspace too small");
-  // the masked fine pass addresses (ray, sample) pairs by 32-bit ids (nerf_compact_kernel, MlpArgs::index)
-  if (fast_sampling && n_importance && n_rays > (int64_t)0x7fffffff / (NERF_N_SAMPLES + NERF_N_IMPORTANCE))
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward: fast_sampling handles at most 11 184 810 rays per call "
-                                            "(n_rays * 192 point ids must fit in int32): split the frame");
-  const int64_t B = render_block_rays();
-  for (int64_t r0 = 0; r0 < n_rays; r0 += B) {
-    const int64_t nb = n_rays - r0 < B ? n_rays - r0 : B;
-    const int rc = render_block(rays_o + 3 * r0, rays_d + 3 * r0, nb, packed_coarse, packed_fine, t_coarse, u, n_importance, white_bkgd,
-                                precision, fast_sampling, weights_threshold, workspace, rgb + 3 * r0, depth + r0, stream);
-    if (rc) return rc;
-  }
-  return NERF_OK;
-}
-
-// one block of rays through the four stages (workspace: nerf_render_workspace_bytes of the block)
-static int32_t render_block(const float* rays_o, const float* rays_d, int64_t n_rays, const void* packed_coarse, const void* packed_fine,
-                            const float* t_coarse, const float* u, int32_t n_importance, int32_t white_bkgd, int32_t precision,
-                            int32_t fast_sampling, float weights_threshold, void* workspace, float* rgb, float* depth, void* stream) {
-  char* ws = (char*)workspace;
-  float* raw_c = (float*)ws;
-  // hierarchical render: the coarse network only places the fine samples -- nothing but its sigma is read
-  // (volume_renderer.py:335; the returned rgb/depth come from the fine outputs, :414-437), so the coarse pass stops after
-  // the sigma head.  With n_importance == 0 the coarse outputs ARE the frame and the full network runs.
-  int rc = n_importance ? nerf_mlp_forward_rays_density(rays_o, rays_d, t_coarse, 0, n_rays, NERF_N_SAMPLES, packed_coarse, raw_c, precision, stream)
-                        : nerf_mlp_forward_rays(rays_o, rays_d, t_coarse, 0, n_rays, NERF_N_SAMPLES, packed_coarse, raw_c, precision, stream);
-  if (rc) return rc;
-  // fp16 far-plane guard.  The last sample of a ray has delta = 1e10 (volume_renderer.py:85-86): ANY sigma > 0 there makes alpha = 1, so
-  // an fp16 rounding that flips the sign of a sigma within 1e-2 of zero turns a background ray into a full far-plane hit (round 2:
-  // single rays off by 0.64 in rgb and 6.0 in depth, which alone set the fp16 PSNR).  Every other sample's alpha moves by
-  // |d sigma| * delta ~ 1e-4.  So the fp16 precisions re-evaluate exactly that sample of every ray (0.5 % of the points) with the
-  // split-fp16 stream that rides behind their packed model: fp32-accurate sigma and colour where it matters, ~1.5 % of the frame.
-  const bool guard = (precision == NERF_PREC_F16 || precision == NERF_PREC_F16S) && n_rays <= (int64_t)0x7fffffff / (NERF_N_SAMPLES + NERF_N_IMPORTANCE);
-  auto far_plane_guard = [&](const float* tvals, int64_t stride, int32_t S_, const void* packed_f16, float* raw, char* ids_base) -> int {
-    int* index = (int*)ids_base;
-    int* count = (int*)(ids_base + align256(n_rays * (int64_t)sizeof(int)));
-    hipLaunchKernelGGL(nerf_last_sample_index_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream, index, count,
-                       (long long)n_rays, S_);
-    int r2 = check_launch("nerf_last_sample_index_kernel");
-    if (r2) return r2;
-    MlpArgs g{};
-    g.rays_o = rays_o; g.rays_d = rays_d; g.tvals = tvals; g.t_ray_stride = stride; g.n_points = n_rays * S_;
-    g.n_samples = S_; g.packed = (const float*)((const char*)packed_f16 + nerf::kF16PackedBytes); g.raw = raw; g.index = index; g.count = count;
-    return launch_mlp(g, true, NERF_PREC_F32X, (hipStream_t)stream);
-  };
-  if (n_importance == 0) {
-    if (guard) {
-      rc = far_plane_guard(t_coarse, 0, NERF_N_SAMPLES, packed_coarse, raw_c, ws + align256(n_rays * NERF_N_SAMPLES * 4 * (int64_t)sizeof(float)));
-      if (rc) return rc;
-    }
-    return nerf_composite(raw_c, t_coarse, 0, n_rays, NERF_N_SAMPLES, white_bkgd, rgb, depth, nullptr, stream);
-  }
-  const int64_t S = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
-  float* t_sorted = (float*)(ws + align256(n_rays * NERF_N_SAMPLES * 4 * (int64_t)sizeof(float)));
-  float* raw_f = (float*)((char*)t_sorted + align256(n_rays * S * (int64_t)sizeof(float)));
-  if (!fast_sampling) {
-    rc = nerf_sample_fine(raw_c, t_coarse, u, n_rays, t_sorted, nullptr, nullptr, 0.f, 0.f, stream);
-    if (rc) return rc;
-    // the fine outputs only ever reach nerf_composite: colours of zero-density samples are multiplied by exactly 0 there
-    rc = nerf_mlp_forward_rays_for_compositing(rays_o, rays_d, t_sorted, S, n_rays, (int32_t)S, packed_fine, raw_f, precision, stream);
-    if (rc) return rc;
-    if (guard) {
-      rc = far_plane_guard(t_sorted, S, (int32_t)S, packed_fine, raw_f, (char*)raw_f + align256(n_rays * S * 4 * (int64_t)sizeof(float)));
-      if (rc) return rc;
-    }
-  } else {
-    // ESS/ERT (volume_renderer.py:359-369, network.py:207-253): only the valid merged samples go through
-    // the fine network; the others keep raw = 0 (sigma 0 -> weight 0)
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* valid = (uint8_t*)((char*)raw_f + align256(n_rays * S * 4 * (int64_t)sizeof(float)));
-    int* index = (int*)((char*)valid + align256(n_rays * S));
-    int* count = (int*)((char*)index + align256(n_rays * S * (int64_t)sizeof(int)));
-    rc = nerf_sample_fine(raw_c, t_coarse, u, n_rays, t_sorted, nullptr, valid, weights_threshold, 0.45f, stream);
-    if (rc) return rc;
-    if (hipMemsetAsync(count, 0, sizeof(int), st) != hipSuccess ||
-        hipMemsetAsync(raw_f, 0, (size_t)(n_rays * S * 4 * (int64_t)sizeof(float)), st) != hipSuccess)
-      return fail(NERF_ERR_HIP, "%s", "nerf_render_forward: memset failed");
-    const long long np = n_rays * S;
-    hipLaunchKernelGGL(nerf_compact_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, valid, np, index, count);
-    rc = check_launch("nerf_compact_kernel");
-    if (rc) return rc;
-    MlpArgs a{};
-    a.rays_o = rays_o; a.rays_d = rays_d; a.tvals = t_sorted; a.t_ray_stride = S; a.n_points = np;
-    a.n_samples = (int)S; a.packed = (const float*)packed_fine; a.raw = raw_f; a.index = index; a.count = count;
-    a.skip_dead_colour = 1;
-    rc = launch_mlp(a, true, precision, st);
-    if (rc) return rc;
-  }
-  return nerf_composite(raw_f, t_sorted, S, n_rays, (int32_t)S, white_bkgd, rgb, depth, nullptr, stream);
-}
-
-// Stochastic render (task == "train", no grad): the deterministic block's stages with a per-ray coarse table (jittered) and a
-// per-ray u table.  Workspace per block: the deterministic one (shared tables, no fast_sampling) + the jittered depths [n,64].
-int64_t nerf_render_stochastic_workspace_bytes(int64_t n_rays_frame, int32_t n_importance) {
-  if (n_rays_frame < 0) return -1;
-  const int64_t n_rays = n_rays_frame < render_block_rays() ? n_rays_frame : render_block_rays();
-  return nerf_render_workspace_bytes(n_rays_frame, n_importance, 0) + align256(n_rays * NERF_N_SAMPLES * (int64_t)sizeof(float));
+  return render_frame("nerf_render_forward", rays_o, rays_d, n_rays, packed_coarse, packed_fine, t_coarse, u, nullptr, nullptr, false,
+                      n_importance, white_bkgd, precision, fast_sampling, weights_threshold, workspace, workspace_bytes, rgb, depth, stream);
 }
 
 int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d, int64_t n_rays,
@@ -2618,59 +2588,11 @@ int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d,
                                        int32_t n_importance, int32_t white_bkgd, int32_t precision, int32_t fast_sampling,
                                        float weights_threshold, void* workspace, int64_t workspace_bytes,
                                        float* rgb, float* depth, void* stream) {
-  (void)weights_threshold;
-  if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: bad size");
-  if (n_importance != 0 && n_importance != NERF_N_IMPORTANCE)
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: n_importance must be 0 or 128");
   if (precision != NERF_PREC_F32 && precision != NERF_PREC_F32X)
     return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: precision must be f32 or f32x");
   if (fast_sampling) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: fast_sampling is not supported");
-  if (n_rays == 0) return NERF_OK;
-  if (!rays_o || !rays_d || !packed_coarse || !t_coarse || !rgb || !depth || !workspace ||
-      (n_importance && (!packed_fine || !u)))
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_render_forward_stochastic: null argument");
-  if (workspace_bytes < nerf_render_stochastic_workspace_bytes(n_rays, n_importance))
-    return fail(NERF_ERR_WORKSPACE, "%s", "nerf_render_forward_stochastic: workspace too small");
-  const int64_t B = render_block_rays();
-  const int64_t S = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
-  const int64_t nbmax = n_rays < B ? n_rays : B;
-  char* ws = (char*)workspace;
-  float* raw_c = (float*)ws;
-  char* rest = ws + align256(nbmax * NERF_N_SAMPLES * 4 * (int64_t)sizeof(float));
-  float* t_sorted = (float*)rest;
-  float* raw_f = (float*)(rest + align256(nbmax * S * (int64_t)sizeof(float)));
-  float* t_jit = (float*)(ws + nerf_render_workspace_bytes(n_rays, n_importance, 0));
-  for (int64_t r0 = 0; r0 < n_rays; r0 += B) {
-    const int64_t nb = n_rays - r0 < B ? n_rays - r0 : B;
-    const float* o = rays_o + 3 * r0;
-    const float* d = rays_d + 3 * r0;
-    const float* tc = t_coarse;
-    int64_t tcs = 0;
-    int rc;
-    if (jitter) {
-      rc = nerf_stratified_samples(t_coarse, jitter + NERF_N_SAMPLES * r0, nb, t_jit, stream);
-      if (rc) return rc;
-      tc = t_jit; tcs = NERF_N_SAMPLES;
-    }
-    if (n_importance == 0) {
-      rc = nerf_mlp_forward_rays(o, d, tc, tcs, nb, NERF_N_SAMPLES, packed_coarse, raw_c, precision, stream);
-      if (rc) return rc;
-      rc = nerf_composite(raw_c, tc, tcs, nb, NERF_N_SAMPLES, white_bkgd, rgb + 3 * r0, depth + r0, nullptr, stream);
-      if (rc) return rc;
-      continue;
-    }
-    rc = nerf_mlp_forward_rays_density(o, d, tc, tcs, nb, NERF_N_SAMPLES, packed_coarse, raw_c, precision, stream);
-    if (rc) return rc;
-    rc = u_rays ? nerf_sample_fine_rays(raw_c, tc, tcs, u_rays + NERF_N_IMPORTANCE * r0, NERF_N_IMPORTANCE, nb, t_sorted, nullptr,
-                                        nullptr, 0.f, 0.f, stream)
-                : nerf_sample_fine_rays(raw_c, tc, tcs, u, 0, nb, t_sorted, nullptr, nullptr, 0.f, 0.f, stream);
-    if (rc) return rc;
-    rc = nerf_mlp_forward_rays_for_compositing(o, d, t_sorted, S, nb, (int32_t)S, packed_fine, raw_f, precision, stream);
-    if (rc) return rc;
-    rc = nerf_composite(raw_f, t_sorted, S, nb, (int32_t)S, white_bkgd, rgb + 3 * r0, depth + r0, nullptr, stream);
-    if (rc) return rc;
-  }
-  return NERF_OK;
+  return render_frame("nerf_render_forward_stochastic", rays_o, rays_d, n_rays, packed_coarse, packed_fine, t_coarse, u, jitter, u_rays,
+                      true, n_importance, white_bkgd, precision, 0, weights_threshold, workspace, workspace_bytes, rgb, depth, stream);
 }
 
 }  // extern "C"

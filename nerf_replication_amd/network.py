@@ -4,7 +4,6 @@ state_dict keys (src/models/nerf/network.py:9-74, :126-258), backed by the fused
 Loadable through the reference's plugin loader (src/models/make_network.py:4-8:
 ``imp.load_source(cfg.network_module, cfg.network_path).Network()``), see INTEGRATION.md.
 """
-import ctypes
 import os
 import sys
 
@@ -117,8 +116,7 @@ class Network(nn.Module):
             return hit[1]
         lib = _lib.load()
         out = torch.empty(_lib.packed_model_bytes(prec), dtype=torch.uint8, device=dev)
-        srcs = [p.detach().contiguous() for p in params]
-        arr = (ctypes.c_void_p * 24)(*[_lib.ptr(t) for t in srcs])
+        arr = _lib.ptr_array([p.detach().contiguous() for p in params], torch.float32)
         with torch.cuda.device(dev):
             _lib.check(lib.nerf_pack_model(arr, out.data_ptr(), prec, _lib.stream_of(dev)), "nerf_pack_model")
         self._packed[tag] = (key, out)
@@ -213,17 +211,12 @@ class _MlpFunction(torch.autograd.Function):
         (n, s), prec = ctx.shape, ctx.prec
         dev = pts.device
         st = _lib.stream_of(dev)
-        flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
-        grads, off = [], 0
-        for p in params:
-            grads.append(flat[off:off + p.numel()].view(p.shape))
-            off += p.numel()
+        grads = _lib.zeroed_grads(params, dev)
         g_pts = torch.zeros((n, s, 3), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
         if n * s > 0:
             g_raw = g_raw.contiguous().to(torch.float32)
-            srcs = [p.detach().contiguous() for p in params]
-            arr = (ctypes.c_void_p * 24)(*[t.data_ptr() for t in srcs])
-            garr = (ctypes.c_void_p * 24)(*[g.data_ptr() for g in grads])
+            arr = _lib.ptr_array([p.detach().contiguous() for p in params])
+            garr = _lib.ptr_array(grads)
             with torch.cuda.device(dev):
                 pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device=dev)
                 _lib.check(lib.nerf_pack_model_bwd(arr, pk_b.data_ptr(), prec, st), "nerf_pack_model_bwd")

@@ -28,173 +28,223 @@ import torch
 from . import _lib
 
 
-def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+class _Step:
+    """The stages of a training step.  Each stage owns the buffers it fills and knows the C entry that fills them; the autograd
+    functions below order the stages and carry tensors from forward to backward.  All of it is enqueued on the current stream."""
+
+    S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
+
+    def __init__(self, renderer, rays_o, rays_d, prec=None, stochastic=None):
+        self.lib = _lib.load()
+        self.renderer, self.rays_o, self.rays_d = renderer, rays_o, rays_d
+        self.dev, self.n = rays_o.device, rays_o.shape[0]
+        self.st = _lib.stream_of(self.dev)
+        self.prec = _lib.PRECISIONS[getattr(renderer.net, "precision", "f32")] if prec is None else prec
+        self.white = int(bool(renderer.white_bkgd))
+        # the coarse depths and u with their per-ray strides (0: the shared tables)
+        self.t_c, self.u = renderer._get_tables(self.dev)
+        self.t_cs, self.u_s = 0, 0
+        if stochastic is not None:
+            self.t_c, self.t_cs, self.u, self.u_s = stochastic
+        self.pk_b = self.gsave = None
+
+    def empty(self, *shape, dtype=torch.float32):
+        return torch.empty(shape, dtype=dtype, device=self.dev)
+
+    def _rays(self, tvals, stride, S):
+        return _lib.ptr(self.rays_o), _lib.ptr(self.rays_d), _lib.ptr(tvals), stride, self.n, S
+
+    # ---- forward stages
+    def use_draws(self, jitter, u_rays):
+        """The reference's training-mode draws: jittered coarse depths [n,64] and / or a per-ray u [n,128]."""
+        if jitter is not None:
+            t_lin, self.t_c, self.t_cs = self.t_c, self.empty(self.n, self.S_c), self.S_c
+            _lib.check(self.lib.nerf_stratified_samples(_lib.ptr(t_lin), _lib.ptr(jitter), self.n, _lib.ptr(self.t_c), self.st),
+                       "nerf_stratified_samples")
+        if u_rays is not None:
+            self.u, self.u_s = u_rays, _lib.N_IMPORTANCE
+        return self.t_c, self.t_cs, self.u, self.u_s
+
+    def forward_save(self, packed, tvals, stride, S, density_only=False, masked=None, raw=None):
+        """SAVE forward of the packed model over S samples per ray -> (raw [n,S,4], save).  density_only: the sigma head alone.
+        Otherwise raw goes to compositing only and its gradient will come from compositing's adjoint (zero wherever sigma <= 0):
+        tiles without density skip the colour branch and its stores (exact, see the header).  masked = (index, count): the compact
+        rows of those samples alone; the others keep what `raw` holds."""
+        raw = self.empty(self.n, S, 4) if raw is None else raw
+        save = self.empty(int(self.lib.nerf_train_save_floats(self.n * S)))
+        tail = (packed.data_ptr(), _lib.ptr(raw), _lib.ptr(save), self.prec, self.st)
+        if masked is not None:
+            rc = self.lib.nerf_mlp_forward_rays_save_masked(*self._rays(tvals, stride, S), _lib.ptr(masked[0], torch.int32),
+                                                            _lib.ptr(masked[1], torch.int32), *tail)
+        elif density_only:
+            rc = self.lib.nerf_mlp_forward_rays_save_density(*self._rays(tvals, stride, S), *tail)
+        else:
+            rc = self.lib.nerf_mlp_forward_rays_save_for_compositing(*self._rays(tvals, stride, S), *tail)
+        _lib.check(rc, "SAVE forward over %d samples" % S)
+        return raw, save
+
+    def sample_fine(self, raw_c, fast_sampling=False):
+        """Coarse sigma -> the 192 merged depths t_sorted [n,192]; fast_sampling: and their validity (ESS / ERT) as uint8."""
+        t_sorted = self.empty(self.n, self.S_f)
+        valid = self.empty(self.n, self.S_f, dtype=torch.uint8) if fast_sampling else None
+        thresholds = (float(self.renderer.weights_threshold), 0.45) if fast_sampling else (0.0, 0.0)
+        _lib.check(self.lib.nerf_sample_fine_rays(_lib.ptr(raw_c), _lib.ptr(self.t_c), self.t_cs, _lib.ptr(self.u), self.u_s, self.n,
+                                                  _lib.ptr(t_sorted), None, _lib.ptr(valid, torch.uint8), *thresholds, self.st),
+                   "nerf_sample_fine_rays")
+        return t_sorted, valid
+
+    def compact(self, valid):
+        """-> (ids of the valid samples, their number), both on the device."""
+        P = valid.numel()
+        index, count = self.empty(P, dtype=torch.int32), self.empty(1, dtype=torch.int32)
+        ws = self.empty(int(self.lib.nerf_compact_valid_workspace_bytes(P)), dtype=torch.uint8)
+        _lib.check(self.lib.nerf_compact_valid(_lib.ptr(valid, torch.uint8), P, _lib.ptr(index, torch.int32),
+                                               _lib.ptr(count, torch.int32), ws.data_ptr(), self.st), "nerf_compact_valid")
+        return index, count
+
+    def composite(self, raw, tvals, stride, S):
+        rgb, depth = self.empty(self.n, 3), self.empty(self.n)
+        _lib.check(self.lib.nerf_composite(_lib.ptr(raw), _lib.ptr(tvals), stride, self.n, S, self.white, _lib.ptr(rgb),
+                                           _lib.ptr(depth), None, self.st), "nerf_composite")
+        return rgb, depth
+
+    # ---- backward stages
+    def begin_backward(self, ctx, g_rgb, g_depth, n_inputs):
+        """The incoming gradients as contiguous fp32, and one gradient tensor per parameter (inputs from `n_inputs` on) as views
+        of one zeroed buffer; no buffer when no parameter needs grad."""
+        self.g_rgb = g_rgb.contiguous().to(torch.float32)
+        self.g_depth = None if g_depth is None else g_depth.contiguous().to(torch.float32)
+        self.params, self.need_params = ctx.params, ctx.needs_input_grad[n_inputs:]
+        self.grads = _lib.zeroed_grads(self.params, self.dev) if any(self.need_params) else None
+
+    def param_grads(self):
+        return tuple(g.to(p.dtype) if need else None
+                     for g, p, need in zip(self.grads or [None] * len(self.params), self.params, self.need_params))
+
+    def composite_backward(self, raw, tvals, stride, S, depths=True):
+        """image -> (g_raw [n,S,4], g_t [n,S] | None: the depths are constants)"""
+        g_raw = self.empty(self.n, S, 4)
+        g_t = self.empty(self.n, S) if depths else None
+        _lib.check(self.lib.nerf_composite_backward(_lib.ptr(raw), _lib.ptr(tvals), stride, self.n, S, self.white, _lib.ptr(self.g_rgb),
+                                                    _lib.ptr(self.g_depth), _lib.ptr(g_raw), _lib.ptr(g_t), self.st),
+                   "nerf_composite_backward")
+        return g_raw, g_t
+
+    def _pack_bwd(self, params):
+        if self.pk_b is None:
+            self.pk_b = self.empty(int(self.lib.nerf_packed_bwd_bytes(self.prec)), dtype=torch.uint8)
+        _lib.check(self.lib.nerf_pack_model_bwd(_lib.ptr_array([p.detach().contiguous() for p in params]), self.pk_b.data_ptr(),
+                                                self.prec, self.st), "nerf_pack_model_bwd")
+        return self.pk_b.data_ptr()
+
+    def _gsave(self, S):
+        """The chain's buffer: allocated by the first (fine) pass, its head reused by the coarse one."""
+        floats = int(self.lib.nerf_train_grad_floats(self.n * S))
+        if self.gsave is None:
+            self.gsave = self.empty(floats)
+        return self.gsave[:floats]
+
+    def live_count(self, S):
+        """For the renderer.live_tile_stats hook: the live-tile count the backward over S samples left in gsave, as a 1-element
+        device tensor (no host sync here).  A clone: the next pass reuses gsave."""
+        if getattr(self.renderer, "live_tile_stats", None) is None:
+            return None
+        return self._gsave(S)[int(self.lib.nerf_train_live_count_offset(self.n * S))].view(torch.int32).clone()
+
+    def mlp_backward(self, params, grads, tvals, stride, S, g_raw, save, density_only=False, depths=True, points=False):
+        """g_raw -> the gradients of `params` accumulated into `grads` (None: no parameter needs grad, the chain runs alone),
+        g_t [n,S] of the sample points (if `depths`) and g_x [n,S,3] (if `points`: the rays require grad)."""
+        pk_b = self._pack_bwd(params)
+        g_t = self.empty(self.n, S) if depths else None
+        g_x = self.empty(self.n, S, 3) if points else None
+        head = self._rays(tvals, stride, S) + (pk_b, _lib.ptr(g_raw), _lib.ptr(save), _lib.ptr(self._gsave(S)), _lib.ptr(g_t))
+        garr = None if grads is None else _lib.ptr_array(grads)
+        if points:
+            rc = self.lib.nerf_mlp_backward_rays_x(*head, _lib.ptr(g_x), garr, int(density_only), self.prec, self.st)
+        elif density_only:
+            rc = self.lib.nerf_mlp_backward_density(*head, garr, self.prec, self.st)
+        else:
+            rc = self.lib.nerf_mlp_backward(*head, garr, self.prec, self.st)
+        _lib.check(rc, "MLP backward over %d samples" % S)
+        return g_t, g_x
+
+    def mlp_backward_masked(self, params, grads, tvals, S, masked, g_raw, save):
+        """The MLP backward over the compact rows of the valid samples -> their g_t scattered back, 0 at the masked ones."""
+        pk_b = self._pack_bwd(params)
+        g_t = self.empty(self.n, S)
+        ws = self.empty(int(self.lib.nerf_mlp_backward_masked_workspace_bytes(self.n * S)), dtype=torch.uint8)
+        _lib.check(self.lib.nerf_mlp_backward_masked(*self._rays(tvals, S, S), _lib.ptr(masked[0], torch.int32),
+                                                     _lib.ptr(masked[1], torch.int32), pk_b, _lib.ptr(g_raw), _lib.ptr(save),
+                                                     _lib.ptr(self._gsave(S)), _lib.ptr(g_t), _lib.ptr_array(grads), self.prec,
+                                                     ws.data_ptr(), self.st), "nerf_mlp_backward_masked(fine)")
+        return g_t
+
+    def coarse_backward(self, raw_c, save_c, t_sorted, g_t, cnt_f, ray_terms=None):
+        """The coarse pass of a hierarchical step: depths -> coarse density -> coarse MLP parameters.  ray_terms = (g_x_fine,
+        g_dview) when the rays require grad: -> (g_rays_o, g_rays_d)."""
+        g_raw_c = self.empty(self.n, self.S_c, 4)
+        _lib.check(self.lib.nerf_sample_fine_rays_backward(_lib.ptr(raw_c), _lib.ptr(self.t_c), self.t_cs, _lib.ptr(self.u), self.u_s,
+                                                           self.n, _lib.ptr(t_sorted), _lib.ptr(g_t), _lib.ptr(g_raw_c), self.st),
+                   "nerf_sample_fine_rays_backward")
+        cap = getattr(self.renderer, "capture_adjoints", None)
+        if cap is not None:       # tests: the per-ray sampler adjoint d loss / d raw_coarse and d loss / d t_sorted (parity attribution)
+            cap["g_raw_coarse"], cap["g_t_sorted"], cap["raw_coarse"] = g_raw_c.clone(), g_t.clone(), raw_c.clone()
+            cap["t_sorted"] = t_sorted.clone()
+        # only the coarse sigma was ever used: the density-only backward
+        _, g_x_c = self.mlp_backward(self.params[:24], None if self.grads is None else self.grads[:24], self.t_c, self.t_cs, self.S_c,
+                                     g_raw_c, save_c, density_only=True, depths=False, points=ray_terms is not None)
+        g_rays = None
+        if ray_terms is not None:
+            g_rays = self.empty(self.n, 3), self.empty(self.n, 3)
+            _lib.check(self.lib.nerf_rays_backward(self.n, _lib.ptr(self.t_c), self.t_cs, _lib.ptr(g_x_c), _lib.ptr(t_sorted),
+                                                   _lib.ptr(ray_terms[0]), _lib.ptr(ray_terms[1]), _lib.ptr(g_rays[0]),
+                                                   _lib.ptr(g_rays[1]), self.st), "nerf_rays_backward")
+        stats = getattr(self.renderer, "live_tile_stats", None)
+        if stats is not None:     # (live tiles, tiles) of the fine and of the coarse pass
+            stats.append((cnt_f, self.n * self.S_f // 32, self.live_count(self.S_c), self.n * self.S_c // 32))
+        return g_rays
 
 
 class RenderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, renderer, rays_o, rays_d, draws, *params):
-        lib = _lib.load()
-        net = renderer.net
-        dev = rays_o.device
-        n = rays_o.shape[0]
-        st = _lib.stream_of(dev)
-        t_c, u = renderer._get_tables(dev)
-        S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
-        jitter, u_rays = draws if draws is not None else (None, None)
-        t_cs, u_s = 0, 0                          # per-ray strides of the coarse table and of u (0: the shared tables)
-        if jitter is not None:
-            t_lin = t_c
-            t_c = torch.empty((n, S_c), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.nerf_stratified_samples(_lib.ptr(t_lin), _lib.ptr(jitter), n, _lib.ptr(t_c), st),
-                           "nerf_stratified_samples")
-            t_cs = S_c
-        if u_rays is not None:
-            u, u_s = u_rays, _lib.N_IMPORTANCE
-        pk_c, pk_f = net.packed(""), net.packed("fine")
-        prec = _lib.PRECISIONS[getattr(net, "precision", "f32")]
-        f32 = dict(dtype=torch.float32, device=dev)
-        raw_c = torch.empty((n, S_c, 4), **f32)
-        save_c = torch.empty(int(lib.nerf_train_save_floats(n * S_c)), **f32)
-        t_sorted = torch.empty((n, S_f), **f32)
-        raw_f = torch.empty((n, S_f, 4), **f32)
-        save_f = torch.empty(int(lib.nerf_train_save_floats(n * S_f)), **f32)
-        rgb, depth = torch.empty((n, 3), **f32), torch.empty((n,), **f32)
-        with torch.cuda.device(dev):
+        s = _Step(renderer, rays_o, rays_d)
+        with torch.cuda.device(s.dev):
+            ctx.stochastic = s.use_draws(*draws) if draws is not None else None
+            pk_c, pk_f = renderer.net.packed(""), renderer.net.packed("fine")
             # coarse pass: only its sigma is ever used (it places the fine samples; the coarse colour is never
             # composited, SURVEY F6/F10) -> the density-only forward / backward pair
-            _lib.check(lib.nerf_mlp_forward_rays_save_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), t_cs, n, S_c,
-                                                              pk_c.data_ptr(), _lib.ptr(raw_c), _lib.ptr(save_c), prec, st), "forward(coarse)")
-            if draws is None:
-                _lib.check(lib.nerf_sample_fine(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted), None, None,
-                                                0.0, 0.0, st), "nerf_sample_fine")
-            else:
-                _lib.check(lib.nerf_sample_fine_rays(_lib.ptr(raw_c), _lib.ptr(t_c), t_cs, _lib.ptr(u), u_s, n, _lib.ptr(t_sorted),
-                                                     None, None, 0.0, 0.0, st), "nerf_sample_fine_rays")
-            # fine pass: its raw goes to compositing only, and its gradient will come from compositing's adjoint (zero
-            # wherever sigma <= 0): tiles without density skip the colour branch and its stores (exact, see the header)
-            _lib.check(lib.nerf_mlp_forward_rays_save_for_compositing(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
-                                                      pk_f.data_ptr(), _lib.ptr(raw_f), _lib.ptr(save_f), prec, st), "forward(fine)")
-            _lib.check(lib.nerf_composite(_lib.ptr(raw_f), _lib.ptr(t_sorted), S_f, n, S_f, int(bool(renderer.white_bkgd)),
-                                          _lib.ptr(rgb), _lib.ptr(depth), None, st), "nerf_composite")
-        ctx.renderer = renderer
-        ctx.prec = prec
-        ctx.n = n
-        ctx.params = params
-        ctx.stochastic = (t_c, t_cs, u, u_s) if draws is not None else None
+            raw_c, save_c = s.forward_save(pk_c, s.t_c, s.t_cs, s.S_c, density_only=True)
+            t_sorted, _ = s.sample_fine(raw_c)
+            raw_f, save_f = s.forward_save(pk_f, t_sorted, s.S_f, s.S_f)
+            rgb, depth = s.composite(raw_f, t_sorted, s.S_f, s.S_f)
+        ctx.renderer, ctx.prec, ctx.params = renderer, s.prec, params
         ctx.save_for_backward(rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f)
         return rgb, depth
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth):
-        lib = _lib.load()
-        renderer, n, params = ctx.renderer, ctx.n, ctx.params
         rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f = ctx.saved_tensors
-        dev = rays_o.device
-        st = _lib.stream_of(dev)
-        t_c, u = renderer._get_tables(dev)
-        t_cs, u_s = 0, 0
-        if ctx.stochastic is not None:
-            t_c, t_cs, u, u_s = ctx.stochastic
-        S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
-        f32 = dict(dtype=torch.float32, device=dev)
-        g_rgb = g_rgb.contiguous().to(torch.float32)
-        g_depth = None if g_depth is None else g_depth.contiguous().to(torch.float32)
+        s = _Step(ctx.renderer, rays_o, rays_d, ctx.prec, ctx.stochastic)
         need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        need_params = ctx.needs_input_grad[4:]
-        grads, off = None, 0
-        if any(need_params):
-            # 24 coarse + 24 fine gradient tensors as views of one zeroed buffer (one memset instead of 48)
-            flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
-            grads = []
-            for p in params:
-                grads.append(flat[off:off + p.numel()].view(p.shape))
-                off += p.numel()
-        # no parameter needs grad: NULL gradient arrays, the chains run alone
-        grads_f = None if grads is None else _ptr_array(grads[24:])
-        grads_c = None if grads is None else _ptr_array(grads[:24])
-        prec = ctx.prec
-        nbwd = int(lib.nerf_packed_bwd_bytes(prec))
-        with torch.cuda.device(dev):
+        s.begin_backward(ctx, g_rgb, g_depth, 4)
+        with torch.cuda.device(s.dev):
             # fine pass: image -> raw_fine and depths; MLP backward; points -> depths
-            g_raw_f = torch.empty((n, S_f, 4), **f32)
-            g_t = torch.empty((n, S_f), **f32)
-            _lib.check(lib.nerf_composite_backward(_lib.ptr(raw_f), _lib.ptr(t_sorted), S_f, n, S_f,
-                                                   int(bool(renderer.white_bkgd)), _lib.ptr(g_rgb),
-                                                   None if g_depth is None else _lib.ptr(g_depth),
-                                                   _lib.ptr(g_raw_f), _lib.ptr(g_t), st), "nerf_composite_backward")
-            pk_b = torch.empty(nbwd, dtype=torch.uint8, device=dev)
-            _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params[24:]]), pk_b.data_ptr(), prec, st))
-            gsave = torch.empty(int(lib.nerf_train_grad_floats(n * S_f)), **f32)
-            g_t_pts = torch.empty((n, S_f), **f32)
-            if not need_rays:
-                _lib.check(lib.nerf_mlp_backward(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
-                                                 pk_b.data_ptr(), _lib.ptr(g_raw_f), _lib.ptr(save_f), _lib.ptr(gsave),
-                                                 _lib.ptr(g_t_pts), grads_f, prec, st), "nerf_mlp_backward(fine)")
-            else:
-                g_x_f = torch.empty((n, S_f, 3), **f32)
-                g_dview = torch.empty((n, 3), **f32)
-                _lib.check(lib.nerf_mlp_backward_rays_x(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
-                                                        pk_b.data_ptr(), _lib.ptr(g_raw_f), _lib.ptr(save_f), _lib.ptr(gsave),
-                                                        _lib.ptr(g_t_pts), _lib.ptr(g_x_f), grads_f, 0, prec, st),
-                           "nerf_mlp_backward_rays_x(fine)")
+            g_raw_f, g_t = s.composite_backward(raw_f, t_sorted, s.S_f, s.S_f)
+            g_t_pts, g_x_f = s.mlp_backward(s.params[24:], None if s.grads is None else s.grads[24:], t_sorted, s.S_f, s.S_f,
+                                            g_raw_f, save_f, points=need_rays)
+            ray_terms = None
+            if need_rays:
                 # the view-direction term reads the fine g_zv rows: before the coarse pass reuses gsave
-                w_views = params[24 + 16].detach().contiguous()           # model_fine views_linears.0.weight [128,283]
-                _lib.check(lib.nerf_rays_viewdirs_backward(_lib.ptr(rays_d), n, S_f, _lib.ptr(gsave), _lib.ptr(w_views),
-                                                           _lib.ptr(g_dview), st), "nerf_rays_viewdirs_backward")
+                g_dview = s.empty(s.n, 3)
+                w_views = s.params[24 + 16].detach().contiguous()           # model_fine views_linears.0.weight [128,283]
+                _lib.check(s.lib.nerf_rays_viewdirs_backward(_lib.ptr(rays_d), s.n, s.S_f, _lib.ptr(s.gsave), _lib.ptr(w_views),
+                                                             _lib.ptr(g_dview), s.st), "nerf_rays_viewdirs_backward")
+                ray_terms = (g_x_f, g_dview)
             g_t.add_(g_t_pts)                     # plumbing: one elementwise add of two [n,192] buffers
-            cnt_f = None
-            if getattr(renderer, "live_tile_stats", None) is not None:
-                cnt_f = gsave[int(lib.nerf_train_live_count_offset(n * S_f))].view(torch.int32).clone()
-            # coarse pass: depths -> coarse density -> coarse MLP parameters
-            g_raw_c = torch.empty((n, S_c, 4), **f32)
-            if ctx.stochastic is None:
-                _lib.check(lib.nerf_sample_fine_backward(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted),
-                                                         _lib.ptr(g_t), _lib.ptr(g_raw_c), st), "nerf_sample_fine_backward")
-            else:
-                _lib.check(lib.nerf_sample_fine_rays_backward(_lib.ptr(raw_c), _lib.ptr(t_c), t_cs, _lib.ptr(u), u_s, n,
-                                                              _lib.ptr(t_sorted), _lib.ptr(g_t), _lib.ptr(g_raw_c), st),
-                           "nerf_sample_fine_rays_backward")
-            cap = getattr(renderer, "capture_adjoints", None)
-            if cap is not None:       # tests: the per-ray sampler adjoint d loss / d raw_coarse and d loss / d t_sorted (parity attribution)
-                cap["g_raw_coarse"], cap["g_t_sorted"], cap["raw_coarse"] = g_raw_c.clone(), g_t.clone(), raw_c.clone()
-                cap["t_sorted"] = t_sorted.clone()
-            _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params[:24]]), pk_b.data_ptr(), prec, st))
-            gsave_c = gsave[: int(lib.nerf_train_grad_floats(n * S_c))]
-            if not need_rays:
-                _lib.check(lib.nerf_mlp_backward_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), t_cs, n, S_c,
-                                                         pk_b.data_ptr(), _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave_c),
-                                                         None, grads_c, prec, st), "nerf_mlp_backward(coarse)")
-            else:
-                g_x_c = torch.empty((n, S_c, 3), **f32)
-                _lib.check(lib.nerf_mlp_backward_rays_x(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), t_cs, n, S_c,
-                                                        pk_b.data_ptr(), _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave_c),
-                                                        None, _lib.ptr(g_x_c), grads_c, 1, prec, st),
-                           "nerf_mlp_backward_rays_x(coarse)")
-                g_o, g_d = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32)
-                _lib.check(lib.nerf_rays_backward(n, _lib.ptr(t_c), t_cs, _lib.ptr(g_x_c), _lib.ptr(t_sorted), _lib.ptr(g_x_f),
-                                                  _lib.ptr(g_dview), _lib.ptr(g_o), _lib.ptr(g_d), st), "nerf_rays_backward")
-            stats = getattr(renderer, "live_tile_stats", None)
-            if stats is not None:
-                # (live tiles, tiles) of the coarse pass as 1-element device tensors: no host sync here; the fine pass's
-                # count was cloned above, before its gsave was reused
-                cnt_c = gsave_c[int(lib.nerf_train_live_count_offset(n * S_c))].view(torch.int32).clone()
-                stats.append((cnt_f, n * S_f // 32, cnt_c, n * S_c // 32))
-        g_rays = (g_o if need_rays and ctx.needs_input_grad[1] else None, g_d if need_rays and ctx.needs_input_grad[2] else None)
-        return (None,) + g_rays + (None,) + tuple(g.to(p.dtype) if need else None
-                                                  for g, p, need in zip(grads or [None] * len(params), params, need_params))
-
-
-def _zeroed_grads(params, dev):
-    """One gradient tensor per parameter as views of one zeroed buffer (one memset)."""
-    flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
-    grads, off = [], 0
-    for p in params:
-        grads.append(flat[off:off + p.numel()].view(p.shape))
-        off += p.numel()
-    return grads
+            g_rays = s.coarse_backward(raw_c, save_c, t_sorted, g_t, s.live_count(s.S_f), ray_terms)
+        g_rays = (g_rays[0] if need_rays and ctx.needs_input_grad[1] else None, g_rays[1] if need_rays and ctx.needs_input_grad[2] else None)
+        return (None,) + g_rays + (None,) + s.param_grads()
 
 
 class MaskedRenderFunction(torch.autograd.Function):
@@ -205,107 +255,39 @@ class MaskedRenderFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, renderer, rays_o, rays_d, *params):
-        lib = _lib.load()
-        net = renderer.net
-        dev = rays_o.device
-        n = rays_o.shape[0]
-        st = _lib.stream_of(dev)
-        t_c, u = renderer._get_tables(dev)
-        S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
-        P = n * S_f
-        pk_c, pk_f = net.packed(""), net.packed("fine")
-        prec = _lib.PRECISIONS[getattr(net, "precision", "f32")]
-        f32 = dict(dtype=torch.float32, device=dev)
-        raw_c = torch.empty((n, S_c, 4), **f32)
-        save_c = torch.empty(int(lib.nerf_train_save_floats(n * S_c)), **f32)
-        t_sorted = torch.empty((n, S_f), **f32)
-        valid = torch.empty((n, S_f), dtype=torch.uint8, device=dev)
-        index = torch.empty(P, dtype=torch.int32, device=dev)
-        count = torch.empty(1, dtype=torch.int32, device=dev)
-        ws = torch.empty(int(lib.nerf_compact_valid_workspace_bytes(P)), dtype=torch.uint8, device=dev)
-        raw_f = torch.zeros((n, S_f, 4), **f32)           # masked samples keep raw = 0
-        save_f = torch.empty(int(lib.nerf_train_save_floats(P)), **f32)
-        rgb, depth = torch.empty((n, 3), **f32), torch.empty((n,), **f32)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_mlp_forward_rays_save_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c,
-                                                              pk_c.data_ptr(), _lib.ptr(raw_c), _lib.ptr(save_c), prec, st), "forward(coarse)")
-            _lib.check(lib.nerf_sample_fine(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted), None,
-                                            _lib.ptr(valid, torch.uint8), float(renderer.weights_threshold), 0.45, st), "nerf_sample_fine")
-            _lib.check(lib.nerf_compact_valid(_lib.ptr(valid, torch.uint8), P, _lib.ptr(index, torch.int32), _lib.ptr(count, torch.int32),
-                                              ws.data_ptr(), st), "nerf_compact_valid")
-            _lib.check(lib.nerf_mlp_forward_rays_save_masked(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
-                                                             _lib.ptr(index, torch.int32), _lib.ptr(count, torch.int32), pk_f.data_ptr(),
-                                                             _lib.ptr(raw_f), _lib.ptr(save_f), prec, st), "forward(fine, masked)")
-            _lib.check(lib.nerf_composite(_lib.ptr(raw_f), _lib.ptr(t_sorted), S_f, n, S_f, int(bool(renderer.white_bkgd)),
-                                          _lib.ptr(rgb), _lib.ptr(depth), None, st), "nerf_composite")
+        s = _Step(renderer, rays_o, rays_d)
+        pk_c, pk_f = renderer.net.packed(""), renderer.net.packed("fine")
+        raw_f = torch.zeros((s.n, s.S_f, 4), dtype=torch.float32, device=s.dev)           # masked samples keep raw = 0
+        with torch.cuda.device(s.dev):
+            raw_c, save_c = s.forward_save(pk_c, s.t_c, 0, s.S_c, density_only=True)
+            t_sorted, valid = s.sample_fine(raw_c, fast_sampling=True)
+            index, count = s.compact(valid)
+            raw_f, save_f = s.forward_save(pk_f, t_sorted, s.S_f, s.S_f, masked=(index, count), raw=raw_f)
+            rgb, depth = s.composite(raw_f, t_sorted, s.S_f, s.S_f)
         stats = getattr(renderer, "masked_stats", None)
         if stats is not None:         # (points the fine network evaluated as a 1-element device tensor, capacity): no host sync here
-            stats.append((count.clone(), P))
+            stats.append((count.clone(), s.n * s.S_f))
         cap = getattr(renderer, "capture_adjoints", None)
         if cap is not None:
             cap["valid_sorted"] = valid.clone()
-        ctx.renderer, ctx.prec, ctx.n, ctx.params = renderer, prec, n, params
+        ctx.renderer, ctx.prec, ctx.params = renderer, s.prec, params
         ctx.save_for_backward(rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f, index, count)
         return rgb, depth
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth):
-        lib = _lib.load()
-        renderer, n, params, prec = ctx.renderer, ctx.n, ctx.params, ctx.prec
         rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f, index, count = ctx.saved_tensors
-        dev = rays_o.device
-        st = _lib.stream_of(dev)
-        t_c, u = renderer._get_tables(dev)
-        S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
-        P = n * S_f
-        f32 = dict(dtype=torch.float32, device=dev)
-        g_rgb = g_rgb.contiguous().to(torch.float32)
-        g_depth = None if g_depth is None else g_depth.contiguous().to(torch.float32)
-        need_params = ctx.needs_input_grad[3:]
-        if not any(need_params):
-            return (None,) * (3 + len(params))
-        grads = _zeroed_grads(params, dev)
-        nbwd = int(lib.nerf_packed_bwd_bytes(prec))
-        with torch.cuda.device(dev):
+        s = _Step(ctx.renderer, rays_o, rays_d, ctx.prec)
+        s.begin_backward(ctx, g_rgb, g_depth, 3)
+        if s.grads is None:
+            return (None,) * (3 + len(s.params))
+        with torch.cuda.device(s.dev):
             # fine pass: image -> raw_fine and depths (all 192 samples; g_raw is exactly zero at the masked ones: sigma = 0)
-            g_raw_f = torch.empty((n, S_f, 4), **f32)
-            g_t = torch.empty((n, S_f), **f32)
-            _lib.check(lib.nerf_composite_backward(_lib.ptr(raw_f), _lib.ptr(t_sorted), S_f, n, S_f,
-                                                   int(bool(renderer.white_bkgd)), _lib.ptr(g_rgb),
-                                                   None if g_depth is None else _lib.ptr(g_depth),
-                                                   _lib.ptr(g_raw_f), _lib.ptr(g_t), st), "nerf_composite_backward")
-            pk_b = torch.empty(nbwd, dtype=torch.uint8, device=dev)
-            _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params[24:]]), pk_b.data_ptr(), prec, st))
-            gsave = torch.empty(int(lib.nerf_train_grad_floats(P)), **f32)
-            g_t_pts = torch.empty((n, S_f), **f32)
-            ws = torch.empty(int(lib.nerf_mlp_backward_masked_workspace_bytes(P)), dtype=torch.uint8, device=dev)
-            # MLP backward over the compact rows of the valid samples; their g_t scattered back, 0 at the masked ones
-            _lib.check(lib.nerf_mlp_backward_masked(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_sorted), S_f, n, S_f,
-                                                    _lib.ptr(index, torch.int32), _lib.ptr(count, torch.int32), pk_b.data_ptr(),
-                                                    _lib.ptr(g_raw_f), _lib.ptr(save_f), _lib.ptr(gsave), _lib.ptr(g_t_pts),
-                                                    _ptr_array(grads[24:]), prec, ws.data_ptr(), st), "nerf_mlp_backward_masked(fine)")
-            g_t.add_(g_t_pts)
-            stats = getattr(renderer, "live_tile_stats", None)
-            cnt_f = None
-            if stats is not None:
-                cnt_f = gsave[int(lib.nerf_train_live_count_offset(P))].view(torch.int32).clone()
-            # coarse pass: depths -> coarse density -> coarse MLP parameters, as in the unmasked step
-            g_raw_c = torch.empty((n, S_c, 4), **f32)
-            _lib.check(lib.nerf_sample_fine_backward(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), n, _lib.ptr(t_sorted),
-                                                     _lib.ptr(g_t), _lib.ptr(g_raw_c), st), "nerf_sample_fine_backward")
-            cap = getattr(renderer, "capture_adjoints", None)
-            if cap is not None:       # tests: as in the unmasked step
-                cap["g_raw_coarse"], cap["g_t_sorted"], cap["raw_coarse"] = g_raw_c.clone(), g_t.clone(), raw_c.clone()
-                cap["t_sorted"] = t_sorted.clone()
-            _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params[:24]]), pk_b.data_ptr(), prec, st))
-            gsave_c = gsave[: int(lib.nerf_train_grad_floats(n * S_c))]
-            _lib.check(lib.nerf_mlp_backward_density(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c,
-                                                     pk_b.data_ptr(), _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave_c),
-                                                     None, _ptr_array(grads[:24]), prec, st), "nerf_mlp_backward(coarse)")
-            if stats is not None:
-                cnt_c = gsave_c[int(lib.nerf_train_live_count_offset(n * S_c))].view(torch.int32).clone()
-                stats.append((cnt_f, P // 32, cnt_c, n * S_c // 32))
-        return (None, None, None) + tuple(g.to(p.dtype) if need else None for g, p, need in zip(grads, params, need_params))
+            g_raw_f, g_t = s.composite_backward(raw_f, t_sorted, s.S_f, s.S_f)
+            g_t.add_(s.mlp_backward_masked(s.params[24:], s.grads[24:], t_sorted, s.S_f, (index, count), g_raw_f, save_f))
+            # coarse pass, as in the unmasked step
+            s.coarse_backward(raw_c, save_c, t_sorted, g_t, s.live_count(s.S_f))
+        return (None, None, None) + s.param_grads()
 
 
 class CoarseRenderFunction(torch.autograd.Function):
@@ -315,61 +297,28 @@ class CoarseRenderFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, renderer, rays_o, rays_d, *params):
-        lib = _lib.load()
-        net = renderer.net
-        dev = rays_o.device
-        n = rays_o.shape[0]
-        st = _lib.stream_of(dev)
-        t_c, _ = renderer._get_tables(dev)
-        S_c = _lib.N_SAMPLES
-        prec = _lib.PRECISIONS[getattr(net, "precision", "f32")]
-        f32 = dict(dtype=torch.float32, device=dev)
-        raw_c = torch.empty((n, S_c, 4), **f32)
-        save_c = torch.empty(int(lib.nerf_train_save_floats(n * S_c)), **f32)
-        rgb, depth = torch.empty((n, 3), **f32), torch.empty((n,), **f32)
-        with torch.cuda.device(dev):
-            # its raw goes to compositing only: tiles without density skip the colour branch and its stores
-            _lib.check(lib.nerf_mlp_forward_rays_save_for_compositing(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c,
-                                                                      net.packed("").data_ptr(), _lib.ptr(raw_c), _lib.ptr(save_c), prec, st),
-                       "forward(coarse)")
-            _lib.check(lib.nerf_composite(_lib.ptr(raw_c), _lib.ptr(t_c), 0, n, S_c, int(bool(renderer.white_bkgd)),
-                                          _lib.ptr(rgb), _lib.ptr(depth), None, st), "nerf_composite")
-        ctx.renderer, ctx.prec, ctx.n, ctx.params = renderer, prec, n, params
+        s = _Step(renderer, rays_o, rays_d)
+        with torch.cuda.device(s.dev):
+            raw_c, save_c = s.forward_save(renderer.net.packed(""), s.t_c, 0, s.S_c)
+            rgb, depth = s.composite(raw_c, s.t_c, 0, s.S_c)
+        ctx.renderer, ctx.prec, ctx.params = renderer, s.prec, params
         ctx.save_for_backward(rays_o, rays_d, raw_c, save_c)
         return rgb, depth
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth):
-        lib = _lib.load()
-        renderer, n, params, prec = ctx.renderer, ctx.n, ctx.params, ctx.prec
         rays_o, rays_d, raw_c, save_c = ctx.saved_tensors
-        dev = rays_o.device
-        st = _lib.stream_of(dev)
-        t_c, _ = renderer._get_tables(dev)
-        S_c = _lib.N_SAMPLES
-        f32 = dict(dtype=torch.float32, device=dev)
-        g_rgb = g_rgb.contiguous().to(torch.float32)
-        g_depth = None if g_depth is None else g_depth.contiguous().to(torch.float32)
-        need_params = ctx.needs_input_grad[3:]
-        if not any(need_params):
-            return (None,) * (3 + len(params))
-        grads = _zeroed_grads(params, dev)
-        with torch.cuda.device(dev):
-            g_raw_c = torch.empty((n, S_c, 4), **f32)
-            _lib.check(lib.nerf_composite_backward(_lib.ptr(raw_c), _lib.ptr(t_c), 0, n, S_c, int(bool(renderer.white_bkgd)),
-                                                   _lib.ptr(g_rgb), None if g_depth is None else _lib.ptr(g_depth),
-                                                   _lib.ptr(g_raw_c), None, st), "nerf_composite_backward")
-            pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device=dev)
-            _lib.check(lib.nerf_pack_model_bwd(_ptr_array([p.detach().contiguous() for p in params]), pk_b.data_ptr(), prec, st))
-            gsave = torch.empty(int(lib.nerf_train_grad_floats(n * S_c)), **f32)
-            _lib.check(lib.nerf_mlp_backward(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_c), 0, n, S_c, pk_b.data_ptr(),
-                                             _lib.ptr(g_raw_c), _lib.ptr(save_c), _lib.ptr(gsave), None, _ptr_array(grads), prec, st),
-                       "nerf_mlp_backward(coarse)")
-            stats = getattr(renderer, "live_tile_stats", None)
+        s = _Step(ctx.renderer, rays_o, rays_d, ctx.prec)
+        s.begin_backward(ctx, g_rgb, g_depth, 3)
+        if s.grads is None:
+            return (None,) * (3 + len(s.params))
+        with torch.cuda.device(s.dev):
+            g_raw_c, _ = s.composite_backward(raw_c, s.t_c, 0, s.S_c, depths=False)
+            s.mlp_backward(s.params, s.grads, s.t_c, 0, s.S_c, g_raw_c, save_c, depths=False)
+            stats = getattr(ctx.renderer, "live_tile_stats", None)
             if stats is not None:
-                cnt_c = gsave[int(lib.nerf_train_live_count_offset(n * S_c))].view(torch.int32).clone()
-                stats.append((None, 0, cnt_c, n * S_c // 32))
-        return (None, None, None) + tuple(g.to(p.dtype) if need else None for g, p, need in zip(grads, params, need_params))
+                stats.append((None, 0, s.live_count(s.S_c), s.n * s.S_c // 32))
+        return (None, None, None) + s.param_grads()
 
 
 def check_differentiable(renderer, rays_grad=False):
@@ -474,7 +423,7 @@ class FusedAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
-        arr = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        arr = _lib.ptr_array
         bump = getattr(torch.autograd.graph, "increment_version", None)
         for g in self.param_groups:
             if g.get("amsgrad", False) or g.get("maximize", False):

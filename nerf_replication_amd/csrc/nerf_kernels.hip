@@ -82,6 +82,26 @@ __device__ __forceinline__ float pack_weight_elem(const PackArgs& a, long long r
   }
 }
 
+// Element `rel` of a [h][t*16 + r] block (1 << LOG2 slots per lane-half h) over the features of x in act_feat order
+template <int LOG2>
+__device__ __forceinline__ float act_order_value(const float* x, int rel) {
+  const int h = rel >> LOG2, slot = rel & ((1 << LOG2) - 1);
+  return x[nerf::act_feat(slot >> 4, slot & 15, h)];
+}
+// The blocks the streams share beside w_alpha (act_order_value<7>): biases [layer 0..8][h][j*16 + r], w_rgb [c][h][t*16 + r] (t < 4)
+// and the head biases b_rgb[3], b_alpha.  (The weight pointer, not PackArgs, where a kernel also picks a weight matrix by a
+// run-time index: a reference to the arguments there made the compiler copy them to scratch.)
+__device__ __forceinline__ float pack_bias_value(const PackArgs& a, int rel) {
+  const int layer = rel >> 8;
+  return act_order_value<7>(layer < 8 ? a.p[2 * layer + 1] : a.p[nerf::P_BF], rel & 255);
+}
+__device__ __forceinline__ float pack_w_rgb_value(const float* w_rgb, int rel) {
+  return act_order_value<6>(w_rgb + 128 * (rel >> 7), rel & 127);
+}
+__device__ __forceinline__ float pack_head_bias_value(const PackArgs& a, int rel) {
+  return rel < 3 ? a.p[nerf::P_BR][rel] : a.p[nerf::P_BA][0];
+}
+
 __global__ void nerf_pack_kernel(PackArgs a) {
   using namespace nerf;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -95,23 +115,11 @@ __global__ void nerf_pack_kernel(PackArgs a) {
   else if (i < kOffFeat) { const long long rel = i - kOffL6; v = pack_weight_elem(a, rel % WS, 8, 1, 6 + (int)(rel / WS)); }
   else if (i < kOffViews) v = pack_weight_elem(a, i - kOffFeat, 8, 4, 0);
   else if (i < kOffBias) v = pack_weight_elem(a, i - kOffViews, 4, 5, 0);
-  else if (i < kOffBiasViews) {          // [layer 0..8][h][j*16 + r]
-    const int rel = (int)(i - kOffBias), layer = rel >> 8, h = (rel >> 7) & 1, slot = rel & 127;
-    const float* b = layer < 8 ? a.p[2 * layer + 1] : a.p[P_BF];
-    v = b[act_feat(slot >> 4, slot & 15, h)];
-  } else if (i < kOffWAlpha) {           // [h][j*16 + r], j < 4
-    const int rel = (int)(i - kOffBiasViews), h = rel >> 6, slot = rel & 63;
-    v = a.p[P_BV][act_feat(slot >> 4, slot & 15, h)];
-  } else if (i < kOffWRgb) {             // [h][t*16 + r]
-    const int rel = (int)(i - kOffWAlpha), h = rel >> 7, slot = rel & 127;
-    v = a.p[P_WA][act_feat(slot >> 4, slot & 15, h)];
-  } else if (i < kOffHeadBias) {         // [c][h][t*16 + r], t < 4
-    const int rel = (int)(i - kOffWRgb), c = rel >> 7, h = (rel >> 6) & 1, slot = rel & 63;
-    v = a.p[P_WR][c * 128 + act_feat(slot >> 4, slot & 15, h)];
-  } else {
-    const int rel = (int)(i - kOffHeadBias);
-    v = rel < 3 ? a.p[P_BR][rel] : a.p[P_BA][0];
-  }
+  else if (i < kOffBiasViews) v = pack_bias_value(a, (int)(i - kOffBias));
+  else if (i < kOffWAlpha) v = act_order_value<6>(a.p[P_BV], (int)(i - kOffBiasViews));      // [h][j*16 + r], j < 4
+  else if (i < kOffWRgb) v = act_order_value<7>(a.p[P_WA], (int)(i - kOffWAlpha));
+  else if (i < kOffHeadBias) v = pack_w_rgb_value(a.p[P_WR], (int)(i - kOffWRgb));
+  else v = pack_head_bias_value(a, (int)(i - kOffHeadBias));
   a.out[i] = v;
 }
 
@@ -145,86 +153,75 @@ __global__ void nerf_pack_bwd_kernel(PackArgs a) {
       const int c = pe_xyz_feat(16 * j + rp, hp);
       v = c < 0 ? 0.0f : W[(long long)krow * ld + c];
     }
-  } else if (i < kBwdOffWRgb) {
-    const int rel = (int)(i - kBwdOffWAlpha), h = rel >> 7, slot = rel & 127;
-    v = a.p[P_WA][act_feat(slot >> 4, slot & 15, h)];
-  } else if (i < kBwdOffWRgb + 384) {
-    const int rel = (int)(i - kBwdOffWRgb), c = rel >> 7, h = (rel >> 6) & 1, slot = rel & 63;
-    v = a.p[P_WR][c * 128 + act_feat(slot >> 4, slot & 15, h)];
-  }
+  } else if (i < kBwdOffWRgb) v = act_order_value<7>(a.p[P_WA], (int)(i - kBwdOffWAlpha));
+  else if (i < kBwdOffWRgb + 384) v = pack_w_rgb_value(a.p[P_WR], (int)(i - kBwdOffWRgb));
   a.out[i] = v;
 }
 
-// fp32 value of element (fragment F, lane, j) of the fp16 fragment stream (nerf_layout.h)
-__device__ __forceinline__ float f16_stream_value(const PackArgs& a, int F, int lane, int j) {
+// The two tilings of the fp16 fragment streams (nerf_layout.h): an A fragment is kRows out-features x kStep input features, lane =
+// (row, g); feat / pe_xyz / pe_dir map (k-step, element j, lane group g) to the input feature.  The ranges up to the sigma head
+// are the same fragment numbers in both streams.
+struct Frag32x16 {             // v_mfma_f32_32x32x16_f16, "fp16-activation path"
+  static constexpr int kRows = 32, kStep = 16;
+  static constexpr int kFragFeat = nerf::kF16FragFeat, kFragViews = nerf::kF16FragViews, kFragRgb = nerf::kF16FragRgb, kFragEnd = nerf::kF16Frags;
+  static __device__ constexpr int feat(int s, int j, int g) { return nerf::act16_feat(s, j, g); }
+  static __device__ constexpr int pe_xyz(int n, int g) { return nerf::pe_xyz_feat(n, g); }
+  static __device__ constexpr int pe_dir(int n, int g) { return nerf::pe_dir_feat(n, g); }
+};
+struct Frag16x32 {             // v_mfma_f32_16x16x32_f16, "f16s" (its tail up to kF16Frags: zero pad fragments)
+  static constexpr int kRows = 16, kStep = 32;
+  static constexpr int kFragFeat = nerf::kF16sFragFeat, kFragViews = nerf::kF16sFragViews, kFragRgb = nerf::kF16sFragRgb, kFragEnd = nerf::kF16sFragEnd;
+  static __device__ constexpr int feat(int s, int j, int g) { return nerf::act16s_feat(s, j, g); }
+  static __device__ constexpr int pe_xyz(int n, int g) { return nerf::pe16s_xyz_feat(n, g); }
+  static __device__ constexpr int pe_dir(int n, int g) { return nerf::pe16s_dir_feat(n, g); }
+};
+static_assert(nerf::kF16sFragL1 == nerf::kF16FragL1 && nerf::kF16sFragL5 == nerf::kF16FragL5 && nerf::kF16sFragL6 == nerf::kF16FragL6,
+              "frag_stream_value: one set of fragment ranges for L0..L7");
+
+// fp32 value of element (fragment F, lane, j) of an fp16 fragment stream with tiling T
+template <class T>
+__device__ __forceinline__ float frag_stream_value(const PackArgs& a, int F, int lane, int j) {
   using namespace nerf;
-  const int h = lane >> 5, row = lane & 31;
-  const int cj = (j & 3) + 8 * (j >> 2) + 4 * h;              // act16_feat(s,j,h) - 16 s
+  constexpr int R = T::kRows, HS = 256 / T::kStep, PS = 64 / T::kStep, DS = 32 / T::kStep;   // hidden / xyz PE / dir PE k-steps per out-tile
+  const int g = lane / R, row = lane % R;
+  const int cj = T::feat(0, j, g);                             // feature inside its k-step
   float v = 0.0f;
-  if (F < kF16FragL1) {                                       // L0: 8 m x 4 PE k-steps
-    const int m = F >> 2, s = F & 3, c = pe_xyz_feat(8 * s + j, h);
-    if (c >= 0) v = a.p[P_W0][(32 * m + row) * 63 + c];
+  if (F < kF16FragL1) {                                       // L0: 256 / R m x PS PE k-steps
+    const int m = F / PS, s = F % PS, c = T::pe_xyz(8 * s + j, g);
+    if (c >= 0) v = a.p[P_W0][(R * m + row) * 63 + c];
   } else if (F < kF16FragL5) {                                // L1..L4
-    const int f = F - kF16FragL1, li = 1 + (f >> 7), m = (f & 127) >> 4, s = f & 15;
-    v = a.p[2 * li][(32 * m + row) * 256 + 16 * s + cj];
-  } else if (F < kF16FragL6) {                                // L5: 4 PE + 16 hidden k-steps per m
-    const int f = F - kF16FragL5, m = f / 20, s = f % 20;
-    if (s < 4) { const int c = pe_xyz_feat(8 * s + j, h); if (c >= 0) v = a.p[10][(32 * m + row) * 319 + c]; }
-    else v = a.p[10][(32 * m + row) * 319 + 63 + 16 * (s - 4) + cj];
+    const int f = F - kF16FragL1, li = 1 + (f >> 7), m = (f & 127) / HS, s = f % HS;
+    v = a.p[2 * li][(R * m + row) * 256 + T::kStep * s + cj];
+  } else if (F < kF16FragL6) {                                // L5: PS PE + HS hidden k-steps per m
+    const int f = F - kF16FragL5, m = f / (PS + HS), s = f % (PS + HS);
+    if (s < PS) { const int c = T::pe_xyz(8 * s + j, g); if (c >= 0) v = a.p[10][(R * m + row) * 319 + c]; }
+    else v = a.p[10][(R * m + row) * 319 + 63 + T::kStep * (s - PS) + cj];
   } else if (F < kF16FragSigma) {                             // L6, L7
-    const int f = F - kF16FragL6, li = 6 + (f >> 7), m = (f & 127) >> 4, s = f & 15;
-    v = a.p[2 * li][(32 * m + row) * 256 + 16 * s + cj];
-  } else if (F < kF16FragFeat) {                              // sigma head: row 0 only
+    const int f = F - kF16FragL6, li = 6 + (f >> 7), m = (f & 127) / HS, s = f % HS;
+    v = a.p[2 * li][(R * m + row) * 256 + T::kStep * s + cj];
+  } else if (F < T::kFragFeat) {                              // sigma head: row 0 only
     const int s = F - kF16FragSigma;
-    if (row == 0) v = a.p[P_WA][16 * s + cj];
-  } else if (F < kF16FragViews) {                             // feature
-    const int f = F - kF16FragFeat, m = f >> 4, s = f & 15;
-    v = a.p[P_WF][(32 * m + row) * 256 + 16 * s + cj];
-  } else if (F < kF16FragRgb) {                               // views: 16 feature + 2 dir k-steps per m
-    const int f = F - kF16FragViews, m = f / 18, s = f % 18;
-    if (s < 16) v = a.p[P_WV][(32 * m + row) * 283 + 16 * s + cj];
-    else { const int c = pe_dir_feat(8 * (s - 16) + j, h); if (c >= 0) v = a.p[P_WV][(32 * m + row) * 283 + 256 + c]; }
-  } else {                                                    // rgb head: rows 0..2
-    const int s = F - kF16FragRgb;
-    if (row < 3) v = a.p[P_WR][row * 128 + 16 * s + cj];
+    if (row == 0) v = a.p[P_WA][T::kStep * s + cj];
+  } else if (F < T::kFragViews) {                             // feature
+    const int f = F - T::kFragFeat, m = f / HS, s = f % HS;
+    v = a.p[P_WF][(R * m + row) * 256 + T::kStep * s + cj];
+  } else if (F < T::kFragRgb) {                               // views: HS feature + DS dir k-steps per m
+    const int f = F - T::kFragViews, m = f / (HS + DS), s = f % (HS + DS);
+    if (s < HS) v = a.p[P_WV][(R * m + row) * 283 + T::kStep * s + cj];
+    else { const int c = T::pe_dir(8 * (s - HS) + j, g); if (c >= 0) v = a.p[P_WV][(R * m + row) * 283 + 256 + c]; }
+  } else if (F < T::kFragEnd) {                               // rgb head: rows 0..2
+    const int s = F - T::kFragRgb;
+    if (row < 3) v = a.p[P_WR][row * 128 + T::kStep * s + cj];
   }
   return v;
 }
 
-// fp32 value of element (fragment F, lane, j) of the f16s fragment stream (16x16x32 tiling, nerf_layout.h "f16s")
-__device__ __forceinline__ float f16s_stream_value(const PackArgs& a, int F, int lane, int j) {
-  using namespace nerf;
-  const int g = lane >> 4, row = lane & 15;
-  const int cj = 16 * (j >> 2) + 4 * g + (j & 3);             // act16s_feat(s,j,g) - 32 s
-  float v = 0.0f;
-  if (F < kF16sFragL1) {                                      // L0: 16 m x 2 PE k-steps
-    const int m = F >> 1, s = F & 1, c = pe16s_xyz_feat(8 * s + j, g);
-    if (c >= 0) v = a.p[P_W0][(16 * m + row) * 63 + c];
-  } else if (F < kF16sFragL5) {                               // L1..L4
-    const int f = F - kF16sFragL1, li = 1 + (f >> 7), m = (f & 127) >> 3, s = f & 7;
-    v = a.p[2 * li][(16 * m + row) * 256 + 32 * s + cj];
-  } else if (F < kF16sFragL6) {                               // L5: 2 PE + 8 hidden k-steps per m
-    const int f = F - kF16sFragL5, m = f / 10, s = f % 10;
-    if (s < 2) { const int c = pe16s_xyz_feat(8 * s + j, g); if (c >= 0) v = a.p[10][(16 * m + row) * 319 + c]; }
-    else v = a.p[10][(16 * m + row) * 319 + 63 + 32 * (s - 2) + cj];
-  } else if (F < kF16sFragSigma) {                            // L6, L7
-    const int f = F - kF16sFragL6, li = 6 + (f >> 7), m = (f & 127) >> 3, s = f & 7;
-    v = a.p[2 * li][(16 * m + row) * 256 + 32 * s + cj];
-  } else if (F < kF16sFragFeat) {                             // sigma head: row 0 only
-    const int s = F - kF16sFragSigma;
-    if (row == 0) v = a.p[P_WA][32 * s + cj];
-  } else if (F < kF16sFragViews) {                            // feature
-    const int f = F - kF16sFragFeat, m = f >> 3, s = f & 7;
-    v = a.p[P_WF][(16 * m + row) * 256 + 32 * s + cj];
-  } else if (F < kF16sFragRgb) {                              // views: 8 feature + 1 dir k-step per m
-    const int f = F - kF16sFragViews, m = f / 9, s = f % 9;
-    if (s < 8) v = a.p[P_WV][(16 * m + row) * 283 + 32 * s + cj];
-    else { const int c = pe16s_dir_feat(j, g); if (c >= 0) v = a.p[P_WV][(16 * m + row) * 283 + 256 + c]; }
-  } else if (F < kF16sFragEnd) {                              // rgb head: rows 0..2
-    const int s = F - kF16sFragRgb;
-    if (row < 3) v = a.p[P_WR][row * 128 + 32 * s + cj];
-  }                                                           // (tail: zero pad fragments)
-  return v;
+// (hi, lo) fragment pair of the split streams: element e of fragment F holds w_h, the fragment behind it w_l (w = w_h + 2^-11 w_l)
+__device__ __forceinline__ void store_split_f16(_Float16* out, int F, long long e, float v) {
+  const _Float16 hi = (_Float16)v;
+  const long long base = ((long long)(2 * F) << 9) + (e & 511);
+  out[base] = hi;
+  out[base + 512] = (_Float16)((v - (float)hi) * 2048.0f);
 }
 
 // f16s stream: const region (fp32 biases in NATURAL order) + A fragments
@@ -239,14 +236,14 @@ __global__ void nerf_pack_f16s_kernel(PackArgs a) {
       const int layer = (int)i >> 8, c = (int)i & 255;
       v = (layer < 8 ? a.p[2 * layer + 1] : a.p[P_BF])[c];
     } else if (i < kF16sOffHeadBias) v = a.p[P_BV][(int)i - kF16sOffBiasViews];
-    else if (i < kF16sOffHeadBias + 4) { const int rel = (int)i - kF16sOffHeadBias; v = rel < 3 ? a.p[P_BR][rel] : a.p[P_BA][0]; }
+    else if (i < kF16sOffHeadBias + 4) v = pack_head_bias_value(a, (int)i - kF16sOffHeadBias);
     a.out[i] = v;
     return;
   }
   const long long e = i - n_const;
   if (e >= n_half) return;
   const int F = (int)(e >> 9), lane = (int)((e >> 3) & 63), j = (int)(e & 7);
-  reinterpret_cast<_Float16*>(reinterpret_cast<char*>(a.out) + kF16ConstBytes)[e] = (_Float16)f16s_stream_value(a, F, lane, j);
+  reinterpret_cast<_Float16*>(reinterpret_cast<char*>(a.out) + kF16ConstBytes)[e] = (_Float16)frag_stream_value<Frag16x32>(a, F, lane, j);
 }
 
 // backward f32x stream: transposed weights as (hi, lo) fragment pairs + w_alpha / w_rgb in the const region
@@ -257,9 +254,8 @@ __global__ void nerf_pack_bwd_f32x_kernel(PackArgs a) {
   constexpr long long n_el = (long long)kXbSteps * 512;
   if (i < n_const) {
     float v = 0.0f;
-    if (i < 256) { const int h = (int)i >> 7, slot = (int)i & 127; v = a.p[P_WA][act_feat(slot >> 4, slot & 15, h)]; }
-    else if (i < 256 + 384) { const int rel = (int)i - 256, c = rel >> 7, h = (rel >> 6) & 1, slot = rel & 63;
-                              v = a.p[P_WR][c * 128 + act_feat(slot >> 4, slot & 15, h)]; }
+    if (i < 256) v = act_order_value<7>(a.p[P_WA], (int)i);
+    else if (i < 256 + 384) v = pack_w_rgb_value(a.p[P_WR], (int)i - 256);
     a.out[i] = v;
     return;
   }
@@ -285,15 +281,11 @@ __global__ void nerf_pack_bwd_f32x_kernel(PackArgs a) {
     const int c = pe_xyz_feat(16 * m + rp, hp);
     v = c < 0 ? 0.0f : W[(long long)krow * ld + c];
   }
-  _Float16* out = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(a.out) + kF16ConstBytes);
-  const _Float16 hi = (_Float16)v;
-  const long long base = ((long long)(2 * F) << 9) + (e & 511);
-  out[base] = hi;
-  out[base + 512] = (_Float16)((v - (float)hi) * 2048.0f);
+  store_split_f16(reinterpret_cast<_Float16*>(reinterpret_cast<char*>(a.out) + kF16ConstBytes), F, e, v);
 }
 
 // fp16 stream (nerf_layout.h "fp16-activation path"): const region (fp32 biases) + A fragments; with SPLIT the
-// "f32x" stream: every fragment followed by its low-part fragment (w = w_h + 2^-11 w_l)
+// "f32x" stream: every fragment followed by its low-part fragment
 template <bool SPLIT>
 __global__ void nerf_pack_f16_kernel(PackArgs a) {
   using namespace nerf;
@@ -302,30 +294,19 @@ __global__ void nerf_pack_f16_kernel(PackArgs a) {
   constexpr long long n_half = (long long)kF16Frags * 512;
   if (i < n_const) {                     // const region, floats
     float v = 0.0f;
-    if (i < kF16OffBiasViews) {
-      const int rel = (int)i, layer = rel >> 8, h = (rel >> 7) & 1, slot = rel & 127;
-      const float* b = layer < 8 ? a.p[2 * layer + 1] : a.p[P_BF];
-      v = b[act_feat(slot >> 4, slot & 15, h)];
-    } else if (i < kF16OffHeadBias) {
-      const int rel = (int)i - kF16OffBiasViews, h = rel >> 6, slot = rel & 63;
-      v = a.p[P_BV][act_feat(slot >> 4, slot & 15, h)];
-    } else if (i < kF16OffHeadBias + 4) {
-      const int rel = (int)i - kF16OffHeadBias;
-      v = rel < 3 ? a.p[P_BR][rel] : a.p[P_BA][0];
-    }
+    if (i < kF16OffBiasViews) v = pack_bias_value(a, (int)i);
+    else if (i < kF16OffHeadBias) v = act_order_value<6>(a.p[P_BV], (int)i - kF16OffBiasViews);
+    else if (i < kF16OffHeadBias + 4) v = pack_head_bias_value(a, (int)i - kF16OffHeadBias);
     a.out[i] = v;
     return;
   }
   const long long e = i - n_const;
   if (e >= n_half) return;
   const int F = (int)(e >> 9), lane = (int)((e >> 3) & 63), j = (int)(e & 7);
-  const float v = f16_stream_value(a, F, lane, j);
+  const float v = frag_stream_value<Frag32x16>(a, F, lane, j);
   _Float16* out = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(a.out) + kF16ConstBytes);
-  if (!SPLIT) { out[e] = (_Float16)v; return; }
-  const _Float16 hi = (_Float16)v;
-  const long long base = ((long long)(2 * F) << 9) + (e & 511);
-  out[base] = hi;
-  out[base + 512] = (_Float16)((v - (float)hi) * 2048.0f);
+  if (SPLIT) store_split_f16(out, F, e, v);
+  else out[e] = (_Float16)v;
 }
 
 // ------------------------------------------------------------------------------------ PE (test entry)
@@ -350,20 +331,31 @@ __global__ void nerf_pe_kernel(const float* __restrict__ x, long long n, int n_f
 // sequential in torch CPU too).  A 64-ray block stages its I/O through LDS: the coarse sigmas are
 // loaded cooperatively, every lane then owns one padded 192-float LDS row (sigma -> fine depths in
 // [0,128) with the cdf in [128,191) -> the merged depths), and the 64 x 192 sorted depths are
-// written back coalesced.  Optionally (fast_sampling) also the ESS/ERT validity of every merged
-// sample (volume_renderer.py:116-123, :132-133, :158-193, :359-369), carried through the merge as
-// the sign of the depth.
+// written back coalesced.
+// Two instances of one body, which is what keeps them bit-compatible on the same tables:
+//  <false> one coarse table and one ascending u table for all rays (s_tab = t[64] | u[128]); t_fine comes out of the walk;
+//          optionally (fast_sampling) also the ESS/ERT validity of every merged sample (volume_renderer.py:116-123, :132-133,
+//          :158-193, :359-369), carried through the merge as the sign of the depth.
+//  <true>  a coarse table and a u table per ray (t of ray r at t_coarse + r * t_stride, u at u + r * u_stride; stride 0 shares one
+//          table): s_tab = one 65-float coarse row per ray.  t_sorted depends only on the MULTISET of fine depths, so each lane
+//          sorts its ray's 128 u ascending (registers, bitonic) and then runs the same monotone walk.  The row's slots [0,128)
+//          hold sigma, then the ray's u (staged coalesced), then the sorted u the walk overwrites in place with the fine depths
+//          (slot j <= k is written only after u[k] was read); t_fine is in the caller's u order, by bisection.  No masks.
+// LDS per 64-ray workgroup: the 64 x 193-float rows (49 408 B) + 768 B of shared tables, or + 16 640 B of coarse rows.
 constexpr int kSampleThreads = 64;
 constexpr int kBufPitch = 193;     // odd pitch: lanes walking their own rows never share a bank
+constexpr int kTcPitch = 65;       // odd pitch, as kBufPitch
 
 struct SampleArgs {
   const float* raw_c;        // [n,64,4]
-  const float* t_coarse;     // [64]
-  const float* u_tab;        // [128]
+  const float* t_coarse;     // [64] or [n,64]
+  long long t_stride;        // 0 or 64
+  const float* u;            // [128] or [n,128]
+  long long u_stride;        // 0 or 128
   long long n_rays;
   float* t_sorted;           // [n,192]
-  float* t_fine;             // optional [n,128]
-  unsigned char* valid_sorted;   // optional [n,192], 1 = evaluate with the fine network
+  float* t_fine;             // optional [n,128], in the caller's u order
+  unsigned char* valid_sorted;   // optional [n,192], 1 = evaluate with the fine network (shared tables only)
   int fast_sampling;
   float weights_threshold, ert_threshold;
 };
@@ -399,47 +391,89 @@ __device__ __forceinline__ float torch_sum62_of(Get x) {
 }
 __device__ __forceinline__ float torch_sum62(const float* w) { return torch_sum62_of([&](int k) { return w[k]; }); }
 
+// Ascending bitonic network over one thread's 128 registers.  Fully unrolled (unroll(full): plain `#pragma unroll` left the
+// array in scratch, 528 B per lane), so every index is a constant and the array lives in VGPRs.
+__device__ __forceinline__ void sort128_ascending(float (&r)[NERF_N_IMPORTANCE]) {
+#pragma clang loop unroll(full)
+  for (int k = 2; k <= NERF_N_IMPORTANCE; k <<= 1) {
+#pragma clang loop unroll(full)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma clang loop unroll(full)
+      for (int i = 0; i < NERF_N_IMPORTANCE; ++i) {
+        const int l = i ^ j;
+        if (l > i) {
+          const float x = r[i], y = r[l];
+          const bool up = (i & k) == 0;
+          r[i] = up ? fminf(x, y) : fmaxf(x, y);
+          r[l] = up ? fmaxf(x, y) : fminf(x, y);
+        }
+      }
+    }
+  }
+}
+
+// Inverse CDF of one u given its searchsorted(right) index; also the two bins it interpolates between.
+__device__ __forceinline__ float inv_cdf_at(const float* cdf, const float* tc, float u, int ind, int& below, int& above) {
+  constexpr int S = NERF_N_SAMPLES;
+  below = min(max(ind - 1, 0), S - 3);
+  above = min(ind, S - 3);                             // clamp to 61: tail collapse
+  const float cb = cdf[below], ca = cdf[above];
+  const float bb = __fmul_rn(0.5f, __fadd_rn(tc[below + 1], tc[below]));
+  const float ba = __fmul_rn(0.5f, __fadd_rn(tc[above + 1], tc[above]));
+  float denom = __fsub_rn(ca, cb);
+  if (denom < 1e-5f) denom = 1.0f;
+  const float frac = __fdiv_rn(__fsub_rn(u, cb), denom);
+  return __fadd_rn(bb, __fmul_rn(frac, __fsub_rn(ba, bb)));
+}
+
+template <bool RAYS>
 __global__ __launch_bounds__(kSampleThreads)
 void nerf_sample_fine_kernel(SampleArgs a) {
   constexpr int S = NERF_N_SAMPLES, F = NERF_N_IMPORTANCE, NB = S - 1;   // 63 cdf entries / bins
-  __shared__ float s_tc[S];
-  __shared__ float s_u[F];
+  __shared__ float s_tab[RAYS ? kSampleThreads * kTcPitch : S + F];
   __shared__ float s_buf[kSampleThreads * kBufPitch];
   const int lane = threadIdx.x;
   const long long ray0 = (long long)blockIdx.x * kSampleThreads;
-  s_tc[lane] = a.t_coarse[lane];
-  s_u[lane] = a.u_tab[lane];
-  s_u[lane + 64] = a.u_tab[lane + 64];
+  if (!RAYS) {
+    s_tab[lane] = a.t_coarse[lane];
+    s_tab[S + lane] = a.u[lane];
+    s_tab[S + lane + 64] = a.u[lane + 64];
+  }
   for (int r = 0; r < kSampleThreads; ++r) {          // lane = coarse sample index
     long long rg = ray0 + r;
     if (rg >= a.n_rays) rg = a.n_rays - 1;
     s_buf[r * kBufPitch + lane] = a.raw_c[rg * (S * 4) + lane * 4 + 3];
+    if (RAYS) s_tab[r * kTcPitch + lane] = a.t_coarse[rg * a.t_stride + lane];
   }
   __syncthreads();
   float* buf = s_buf + lane * kBufPitch;
   float* cdf = buf + F;        // slots 128..190: free until the merge, which no longer needs the cdf
+  const float* tc = RAYS ? s_tab + lane * kTcPitch : s_tab;
+  const float* us = RAYS ? buf : s_tab + S;            // the ascending u the walk reads
+  auto depth_of = [](float v) { return RAYS ? v : fabsf(v); };      // shared tables: the sign carries "masked out"
 
   // weights of the coarse pass (volume_renderer.py:67-96), inner 62 + eps, running sum
-  float T = 1.0f, wsum = 0.0f, dsum = 0.0f, dmax = 0.0f;
+  float T = 1.0f, dsum = 0.0f, dmax = 0.0f;
   unsigned long long empty_bits = 0, ert_bits = 0;
   bool ert_seen = false;
   for (int i = 0; i < S; ++i) {
     const float sigma = fmaxf(buf[i], 0.0f);
-    dsum = __fadd_rn(dsum, sigma);
-    dmax = fmaxf(dmax, sigma);
-    const float delta = (i < S - 1) ? __fsub_rn(s_tc[i + 1], s_tc[i]) : 1e10f;
+    const float delta = (i < S - 1) ? __fsub_rn(tc[i + 1], tc[i]) : 1e10f;
     const float alpha = alpha_of(sigma, delta);
     const float w = __fmul_rn(T, alpha);
-    if (i >= 1 && i <= S - 2) {
-      const float we = __fadd_rn(w, 1e-5f);
-      cdf[i - 1] = we;                                  // stash w+eps in cdf slots 0..61 (summed below, in torch's order)
-      if (w < a.weights_threshold) empty_bits |= 1ull << (i - 1);
-      ert_seen = ert_seen || (T < a.ert_threshold);     // cummax of (T < thr) over the inner bins
-      if (ert_seen) ert_bits |= 1ull << (i - 1);
+    if (i >= 1 && i <= S - 2) cdf[i - 1] = __fadd_rn(w, 1e-5f);     // stash w+eps in cdf slots 0..61 (summed below, in torch's order)
+    if (!RAYS) {
+      dsum = __fadd_rn(dsum, sigma);
+      dmax = fmaxf(dmax, sigma);
+      if (i >= 1 && i <= S - 2) {
+        if (w < a.weights_threshold) empty_bits |= 1ull << (i - 1);
+        ert_seen = ert_seen || (T < a.ert_threshold);     // cummax of (T < thr) over the inner bins
+        if (ert_seen) ert_bits |= 1ull << (i - 1);
+      }
     }
     T = __fmul_rn(T, fminf(fmaxf(__fsub_rn(1.0f, alpha), 1e-10f), 1.0f));
   }
-  wsum = torch_sum62(cdf);
+  const float wsum = torch_sum62(cdf);
   const bool empty_ray = dsum < 1e-3f;
   const bool object_ray = dmax > 0.5f;
   // cdf = [0, cumsum(pdf)]  (63 entries)
@@ -452,31 +486,50 @@ void nerf_sample_fine_kernel(SampleArgs a) {
       cdf[m] = run;
     }
   }
-  // inverse CDF at the fixed u table; u ascending -> the searchsorted(right=True) index only grows
   const long long ray = ray0 + lane;
   const bool ray_ok = ray < a.n_rays;
+  int below, above;
+  if (RAYS) {
+    __syncthreads();                                   // every lane has read its sigmas: slots [0,128) take the rays' u
+    for (int r = 0; r < kSampleThreads; ++r) {
+      long long rg = ray0 + r;
+      if (rg >= a.n_rays) rg = a.n_rays - 1;
+      s_buf[r * kBufPitch + lane] = a.u[rg * a.u_stride + lane];
+      s_buf[r * kBufPitch + 64 + lane] = a.u[rg * a.u_stride + 64 + lane];
+    }
+    __syncthreads();
+    if (a.t_fine && ray_ok) {                          // in the caller's order: searchsorted(right) by bisection
+      for (int k = 0; k < F; ++k) {
+        const float u = buf[k];
+        int lo = 0, hi = NB;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] <= u) lo = mid + 1; else hi = mid; }
+        a.t_fine[ray * F + k] = inv_cdf_at(cdf, tc, u, lo, below, above);
+      }
+    }
+    float r[F];
+#pragma clang loop unroll(full)
+    for (int k = 0; k < F; ++k) r[k] = buf[k];
+    sort128_ascending(r);
+#pragma clang loop unroll(full)
+    for (int k = 0; k < F; ++k) buf[k] = r[k];
+  }
+  // inverse CDF at the ascending u; u ascending -> the searchsorted(right=True) index only grows
   int ind = 0;
   for (int k = 0; k < F; ++k) {
-    const float u = s_u[k];
+    const float u = us[k];
     while (ind < NB && cdf[ind] <= u) ++ind;
-    const int below = min(max(ind - 1, 0), S - 3);
-    const int above = min(ind, S - 3);                 // clamp to 61: tail collapse
-    const float cb = cdf[below], ca = cdf[above];
-    const float bb = __fmul_rn(0.5f, __fadd_rn(s_tc[below + 1], s_tc[below]));
-    const float ba = __fmul_rn(0.5f, __fadd_rn(s_tc[above + 1], s_tc[above]));
-    float denom = __fsub_rn(ca, cb);
-    if (denom < 1e-5f) denom = 1.0f;
-    const float frac = __fdiv_rn(__fsub_rn(u, cb), denom);
-    float v = __fadd_rn(bb, __fmul_rn(frac, __fsub_rn(ba, bb)));
-    if (a.t_fine && ray_ok) a.t_fine[ray * F + k] = v;
-    if (a.fast_sampling) {
-      const bool be = (empty_bits >> below) & 1, ae = (empty_bits >> above) & 1, ert = (ert_bits >> below) & 1;
-      const bool ess_nv = object_ray ? (be && ae) : (be || ae);
-      if (ess_nv || ert || empty_ray) v = -v;           // depths are > 0: the sign carries "masked out"
+    float v = inv_cdf_at(cdf, tc, u, ind, below, above);
+    if (!RAYS) {
+      if (a.t_fine && ray_ok) a.t_fine[ray * F + k] = v;
+      if (a.fast_sampling) {
+        const bool be = (empty_bits >> below) & 1, ae = (empty_bits >> above) & 1, ert = (ert_bits >> below) & 1;
+        const bool ess_nv = object_ray ? (be && ae) : (be || ae);
+        if (ess_nv || ert || empty_ray) v = -v;           // depths are > 0: the sign carries "masked out"
+      }
     }
     // keep the fine depths sorted even if rounding ever produced a 1-ulp inversion (torch.sort would fix it too)
     int j = k;
-    while (j > 0 && fabsf(buf[j - 1]) > fabsf(v)) { buf[j] = buf[j - 1]; --j; }
+    while (j > 0 && depth_of(buf[j - 1]) > depth_of(v)) { buf[j] = buf[j - 1]; --j; }
     buf[j] = v;
   }
   // in-place two-way merge from the back of (sorted coarse table, sorted fine depths) = cat + torch.sort;
@@ -484,9 +537,9 @@ void nerf_sample_fine_kernel(SampleArgs a) {
   {
     int ic = S - 1, jf = F - 1;
     for (int k = S + F - 1; k >= 0; --k) {
-      const bool take_f = (ic < 0) || (jf >= 0 && fabsf(buf[jf]) >= s_tc[ic]);
+      const bool take_f = (ic < 0) || (jf >= 0 && depth_of(buf[jf]) >= tc[ic]);
       if (take_f) { buf[k] = buf[jf]; --jf; }
-      else { buf[k] = s_tc[ic]; --ic; }
+      else { buf[k] = tc[ic]; --ic; }
     }
   }
   __syncthreads();
@@ -495,8 +548,8 @@ void nerf_sample_fine_kernel(SampleArgs a) {
     const long long rg = ray0 + r;
     if (rg < a.n_rays) {
       const float v = s_buf[r * kBufPitch + k];
-      a.t_sorted[rg * (S + F) + k] = fabsf(v);
-      if (a.valid_sorted) a.valid_sorted[rg * (S + F) + k] = v > 0.0f;
+      a.t_sorted[rg * (S + F) + k] = depth_of(v);
+      if (!RAYS && a.valid_sorted) a.valid_sorted[rg * (S + F) + k] = v > 0.0f;
     }
   }
 }
@@ -525,6 +578,34 @@ void nerf_last_sample_index_kernel(int* __restrict__ index, int* __restrict__ co
 }
 
 // ------------------------------------------------------------------------------------ compositing
+__device__ __forceinline__ float sigmoid_rn(float x) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x))); }
+
+// Running state of one ray and the per-sample step of volume_renderer.py:67-96, :414-432; the rounding sequence of `add` and
+// `store` is what both forward kernels (and every stored result) agree on bit for bit.
+struct CompositeAcc {
+  float T = 1.0f, r = 0.f, g = 0.f, b = 0.f, d = 0.f, w = 0.f;
+  __device__ __forceinline__ float add(f32x4 v, float t_cur, float delta) {      // returns the sample's weight
+    const float alpha = alpha_of(fmaxf(v.w, 0.0f), delta);
+    const float wk = __fmul_rn(T, alpha);
+    T = __fmul_rn(T, fminf(fmaxf(__fsub_rn(1.0f, alpha), 1e-10f), 1.0f));
+    const float cr = sigmoid_rn(v.x), cg = sigmoid_rn(v.y), cb = sigmoid_rn(v.z);
+    r = __fadd_rn(r, __fmul_rn(wk, cr));
+    g = __fadd_rn(g, __fmul_rn(wk, cg));
+    b = __fadd_rn(b, __fmul_rn(wk, cb));
+    d = __fadd_rn(d, __fmul_rn(wk, t_cur));
+    w = __fadd_rn(w, wk);
+    return wk;
+  }
+  __device__ __forceinline__ void store(long long ray, int white_bkgd, float* __restrict__ rgb_out, float* __restrict__ depth_out) {
+    if (white_bkgd) {
+      const float bg = __fsub_rn(1.0f, w);
+      r = __fadd_rn(r, bg); g = __fadd_rn(g, bg); b = __fadd_rn(b, bg);
+    }
+    rgb_out[ray * 3 + 0] = r; rgb_out[ray * 3 + 1] = g; rgb_out[ray * 3 + 2] = b;
+    depth_out[ray] = d;
+  }
+};
+
 __global__ __launch_bounds__(256)
 void nerf_composite_kernel(const float* __restrict__ raw, const float* __restrict__ tvals,
                            long long t_ray_stride, long long n_rays, int S, int white_bkgd,
@@ -534,32 +615,16 @@ void nerf_composite_kernel(const float* __restrict__ raw, const float* __restric
   if (ray >= n_rays) return;
   const f32x4* r4 = reinterpret_cast<const f32x4*>(raw) + ray * S;
   const float* t = tvals + ray * t_ray_stride;
-  float T = 1.0f, acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f, acc_w = 0.f;
+  CompositeAcc acc;
   float t_cur = t[0];
   for (int k = 0; k < S; ++k) {
     const f32x4 v = r4[k];
     const float t_next = (k < S - 1) ? t[k + 1] : 0.0f;
-    const float delta = (k < S - 1) ? __fsub_rn(t_next, t_cur) : 1e10f;
-    const float alpha = alpha_of(fmaxf(v.w, 0.0f), delta);
-    const float w = __fmul_rn(T, alpha);
-    T = __fmul_rn(T, fminf(fmaxf(__fsub_rn(1.0f, alpha), 1e-10f), 1.0f));
-    const float cr = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v.x)));     // sigmoid
-    const float cg = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v.y)));
-    const float cb = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v.z)));
-    acc_r = __fadd_rn(acc_r, __fmul_rn(w, cr));
-    acc_g = __fadd_rn(acc_g, __fmul_rn(w, cg));
-    acc_b = __fadd_rn(acc_b, __fmul_rn(w, cb));
-    acc_d = __fadd_rn(acc_d, __fmul_rn(w, t_cur));
-    acc_w = __fadd_rn(acc_w, w);
+    const float w = acc.add(v, t_cur, (k < S - 1) ? __fsub_rn(t_next, t_cur) : 1e10f);
     if (weights_out) weights_out[ray * S + k] = w;
     t_cur = t_next;
   }
-  if (white_bkgd) {
-    const float bg = __fsub_rn(1.0f, acc_w);
-    acc_r = __fadd_rn(acc_r, bg); acc_g = __fadd_rn(acc_g, bg); acc_b = __fadd_rn(acc_b, bg);
-  }
-  rgb_out[ray * 3 + 0] = acc_r; rgb_out[ray * 3 + 1] = acc_g; rgb_out[ray * 3 + 2] = acc_b;
-  depth_out[ray] = acc_d;
+  acc.store(ray, white_bkgd, rgb_out, depth_out);
 }
 
 // Same arithmetic, same order, but HBM-friendly: one wave per 64 rays; each 16-sample chunk of the
@@ -579,21 +644,11 @@ void nerf_composite_staged_kernel(const float* __restrict__ raw, const float* __
   const long long ray = ray0 + lane;
   const bool valid = ray < n_rays;
   const f32x4* r4 = reinterpret_cast<const f32x4*>(raw);
-  float T = 1.0f, acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f, acc_w = 0.f;
+  CompositeAcc acc;
   f32x4 pv = {0.f, 0.f, 0.f, 0.f};      // pending sample (its delta needs the next depth)
   float pt = 0.0f;
   auto emit = [&](f32x4 v, float t_cur, float delta, int k) {
-    const float alpha = alpha_of(fmaxf(v.w, 0.0f), delta);
-    const float w = __fmul_rn(T, alpha);
-    T = __fmul_rn(T, fminf(fmaxf(__fsub_rn(1.0f, alpha), 1e-10f), 1.0f));
-    const float cr = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v.x)));
-    const float cg = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v.y)));
-    const float cb = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v.z)));
-    acc_r = __fadd_rn(acc_r, __fmul_rn(w, cr));
-    acc_g = __fadd_rn(acc_g, __fmul_rn(w, cg));
-    acc_b = __fadd_rn(acc_b, __fmul_rn(w, cb));
-    acc_d = __fadd_rn(acc_d, __fmul_rn(w, t_cur));
-    acc_w = __fadd_rn(acc_w, w);
+    const float w = acc.add(v, t_cur, delta);
     if (weights_out && valid) weights_out[ray * S + k] = w;
   };
   for (int c0 = 0; c0 < S; c0 += kCompChunk) {
@@ -624,13 +679,7 @@ void nerf_composite_staged_kernel(const float* __restrict__ raw, const float* __
     }
   }
   emit(pv, pt, 1e10f, S - 1);
-  if (!valid) return;
-  if (white_bkgd) {
-    const float bg = __fsub_rn(1.0f, acc_w);
-    acc_r = __fadd_rn(acc_r, bg); acc_g = __fadd_rn(acc_g, bg); acc_b = __fadd_rn(acc_b, bg);
-  }
-  rgb_out[ray * 3 + 0] = acc_r; rgb_out[ray * 3 + 1] = acc_g; rgb_out[ray * 3 + 2] = acc_b;
-  depth_out[ray] = acc_d;
+  if (valid) acc.store(ray, white_bkgd, rgb_out, depth_out);
 }
 
 // ------------------------------------------------------------------------------------ training: backward of compositing / sampling
@@ -645,6 +694,28 @@ void nerf_composite_staged_kernel(const float* __restrict__ raw, const float* __
 // load and store is one coalesced row segment.  (The scans associate differently from the forward's sequential product:
 // rounding-level differences in T, as between any two summation orders.)
 constexpr int kCbMaxSamples = 192;
+
+// Inclusive scan over the 64 lanes of a wave: UP: lane l gets op over lanes 0..l (prefix), else over lanes l..63 (suffix)
+template <bool UP, class T, class Op>
+__device__ __forceinline__ T wave_scan(T x, int lane, Op op) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T o = UP ? __shfl_up(x, d) : __shfl_down(x, d);
+    if (UP ? lane >= d : lane + d < 64) x = op(x, o);
+  }
+  return x;
+}
+// The value of the neighbouring lane (UP: lane - 1, else lane + 1); the lane at the end of the wave gets `edge`: turns an
+// inclusive scan into the exclusive one
+template <bool UP, class T>
+__device__ __forceinline__ T wave_shift(T x, int lane, T edge) {
+  const T o = UP ? __shfl_up(x, 1) : __shfl_down(x, 1);
+  return lane == (UP ? 0 : 63) ? edge : o;
+}
+constexpr auto op_sum = [](auto x, auto y) { return x + y; };
+constexpr auto op_prod = [](auto x, auto y) { return x * y; };
+constexpr auto op_max = [](auto x, auto y) { return max(x, y); };
+
 __global__ __launch_bounds__(256)
 void nerf_composite_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ tvals, long long t_ray_stride,
                                long long n_rays, int S, int white_bkgd, const float* __restrict__ g_rgb,
@@ -679,15 +750,8 @@ void nerf_composite_bwd_kernel(const float* __restrict__ raw, const float* __res
     alpha[c] = __fsub_rn(1.0f, e[c]);
     om[c] = __fsub_rn(1.0f, alpha[c]);
     q[c] = live ? fminf(fmaxf(om[c], 1e-10f), 1.0f) : 1.0f;
-    float p = q[c];                                            // inclusive prefix product over the 64 lanes
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const float o = __shfl_up(p, d);
-      if (lane >= d) p *= o;
-    }
-    float excl = __shfl_up(p, 1);
-    if (lane == 0) excl = 1.0f;
-    Tk[c] = carry * excl;
+    const float p = wave_scan<true>(q[c], lane, op_prod);
+    Tk[c] = carry * wave_shift<true>(p, lane, 1.0f);
     carry *= __shfl(p, 63);
   }
   // reverse sweep: suf_k = sum_{m>k} g_w_m a_m T_m;  g_q_k = suf_k / q_k
@@ -697,20 +761,11 @@ void nerf_composite_bwd_kernel(const float* __restrict__ raw, const float* __res
     const int k = 64 * c + lane;
     const bool live = k < S;
     const float sig = fmaxf(v[c].w, 0.0f);
-    const float cr = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v[c].x)));
-    const float cg = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v[c].y)));
-    const float cb = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v[c].z)));
+    const float cr = sigmoid_rn(v[c].x), cg = sigmoid_rn(v[c].y), cb = sigmoid_rn(v[c].z);
     const float g_w = gr * (cr - wb) + gg * (cg - wb) + gb * (cb - wb) + gd * tk[c];
     const float w = Tk[c] * alpha[c];
-    float sfx = live ? g_w * alpha[c] * Tk[c] : 0.0f;           // inclusive suffix sum over the 64 lanes
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const float o = __shfl_down(sfx, d);
-      if (lane + d < 64) sfx += o;
-    }
-    float excl = __shfl_down(sfx, 1);
-    if (lane == 63) excl = 0.0f;
-    const float suf = excl + carry_s;
+    const float sfx = wave_scan<false>(live ? g_w * alpha[c] * Tk[c] : 0.0f, lane, op_sum);
+    const float suf = wave_shift<false>(sfx, lane, 0.0f) + carry_s;
     carry_s += __shfl(sfx, 0);
     float g_alpha = g_w * Tk[c];
     if (om[c] >= 1e-10f && om[c] <= 1.0f) g_alpha -= suf / q[c];      // clamp passes the gradient inside its range
@@ -728,10 +783,8 @@ void nerf_composite_bwd_kernel(const float* __restrict__ raw, const float* __res
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const int k = 64 * c + lane;
-      float prev = __shfl_up(g_delta[c], 1);
       const float last_of_prev_chunk = c > 0 ? __shfl(g_delta[c > 0 ? c - 1 : 0], 63) : 0.0f;
-      if (lane == 0) prev = last_of_prev_chunk;
-      if (k < S) gt[k] = gt_own[c] + prev;
+      if (k < S) gt[k] = gt_own[c] + wave_shift<true>(g_delta[c], lane, last_of_prev_chunk);
     }
   }
 }
@@ -745,33 +798,65 @@ void nerf_composite_bwd_kernel(const float* __restrict__ raw, const float* __res
 // v_readlane walk over the lanes with the forward's rounding intrinsics: bit-identical bins); everything downstream of the
 // decisions is a gradient and uses wave scans / LDS atomics.  (One thread per ray took 131 us for the 4096 rays of a step:
 // 64 lonely waves whose data-dependent while-loops also ran in lockstep.)
+// The two instances are those of nerf_sample_fine_kernel: <false> one coarse table and one ascending u table (s_tab = t[64] |
+// u[128]), <true> tables per ray with the forward's strides (s_tab = one coarse row per wave), where each wave first sorts its
+// ray's u: the merged-slot logic (k + ic with the running maximum, ties coarse first) needs the fine samples in ascending order.
 __device__ __forceinline__ float lane_bcast(float v, int lane_const) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_const));
 }
+// Ascending bitonic sort of 128 values across a wave: lane l holds elements l and l + 64
+__device__ __forceinline__ void wave_sort128_ascending(float (&us)[2], int lane) {
+#pragma unroll
+  for (int k = 2; k <= 128; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (j == 64) {                                   // k == 128: partners share the lane
+        const float x = us[0], y = us[1];
+        us[0] = fminf(x, y); us[1] = fmaxf(x, y);
+      } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int idx = lane + 64 * h;
+          const float p = __shfl_xor(us[h], j);
+          const bool up = (idx & k) == 0, low = (idx & j) == 0;
+          us[h] = (low == up) ? fminf(us[h], p) : fmaxf(us[h], p);
+        }
+      }
+    }
+  }
+}
+template <bool RAYS>
 __global__ __launch_bounds__(256)
-void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __restrict__ t_coarse,
-                            const float* __restrict__ u_tab, long long n_rays, const float* __restrict__ t_sorted,
+void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __restrict__ t_coarse, long long t_stride,
+                            const float* __restrict__ u_in, long long u_stride, long long n_rays,
                             const float* __restrict__ g_tsorted, float* __restrict__ g_raw_c) {
   constexpr int S = NERF_N_SAMPLES, F = NERF_N_IMPORTANCE, NB = S - 1;
   static_assert(S == 64 && F == 128, "lane = coarse sample, two fine samples per lane");
-  __shared__ float s_tc[S];
-  __shared__ float s_u[F];
+  __shared__ float s_tab[RAYS ? 4 * S : S + F];
   __shared__ float s_cdf[4][S];
   __shared__ double s_gcdf[4][S];          // adjoint of the cdf, accumulated in float64 (see below)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x < S) s_tc[threadIdx.x] = t_coarse[threadIdx.x];
-  if (threadIdx.x < F) s_u[threadIdx.x] = u_tab[threadIdx.x];
-  s_gcdf[wv][lane] = 0.0;
-  __syncthreads();
   const long long ray_slot = (long long)blockIdx.x * 4 + wv;
   const bool ray_ok = ray_slot < n_rays;                       // a wave past the end recomputes the last ray and stores nothing
-  const long long ray = ray_ok ? ray_slot : n_rays - 1;        // (it has to reach the two workgroup barriers below)
-  (void)t_sorted;
+  const long long ray = ray_ok ? ray_slot : n_rays - 1;        // (it has to reach the workgroup barriers below)
+  float us[2];
+  if (RAYS) {
+    s_tab[wv * S + lane] = t_coarse[ray * t_stride + lane];
+    us[0] = u_in[ray * u_stride + lane];
+    us[1] = u_in[ray * u_stride + 64 + lane];
+    wave_sort128_ascending(us, lane);
+  } else {
+    if (threadIdx.x < S) s_tab[threadIdx.x] = t_coarse[threadIdx.x];
+    if (threadIdx.x < F) s_tab[S + threadIdx.x] = u_in[threadIdx.x];
+  }
+  s_gcdf[wv][lane] = 0.0;
+  __syncthreads();
+  const float* tc = RAYS ? s_tab + wv * S : s_tab;
   const int i = lane;
   // ---- forward recompute, in the forward's order and rounding (nerf_sample_fine_kernel)
   const float s_raw = raw_c[ray * (S * 4) + i * 4 + 3];
   const float sigma = fmaxf(s_raw, 0.0f);
-  const float delta = (i < S - 1) ? __fsub_rn(s_tc[i + 1], s_tc[i]) : 1e10f;
+  const float delta = (i < S - 1) ? __fsub_rn(tc[i + 1], tc[i]) : 1e10f;
   const float e = expf(__fmul_rn(-sigma, delta));
   const float alpha = __fsub_rn(1.0f, e);                      // = alpha_of(sigma, delta)
   const float om = __fsub_rn(1.0f, alpha);
@@ -811,28 +896,23 @@ void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __rest
   int ic_carry = 0;
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
-    const int k = lane + 64 * half;
-    const float u = s_u[k];
+    const int k = lane + 64 * half;                             // rank of this fine sample among the ray's (ascending) fine samples
+    const float u = RAYS ? us[half] : s_tab[S + k];
     int ind = 0;
     for (int m = 0; m < NB; ++m) ind += cdf[m] <= u;            // cdf is non-decreasing: = the forward's searchsorted(right)
     const int below = min(max(ind - 1, 0), S - 3), above = min(ind, S - 3);
     const float cb = cdf[below], ca = cdf[above];
-    const float bb = __fmul_rn(0.5f, __fadd_rn(s_tc[below + 1], s_tc[below]));
-    const float ba = __fmul_rn(0.5f, __fadd_rn(s_tc[above + 1], s_tc[above]));
+    const float bb = __fmul_rn(0.5f, __fadd_rn(tc[below + 1], tc[below]));
+    const float ba = __fmul_rn(0.5f, __fadd_rn(tc[above + 1], tc[above]));
     const float draw_ = __fsub_rn(ca, cb);
     const bool live = !(draw_ < 1e-5f);
     const float denom = live ? draw_ : 1.0f;
     const float num = __fsub_rn(u, cb);
     const float v = __fadd_rn(bb, __fmul_rn(__fdiv_rn(num, denom), __fsub_rn(ba, bb)));
     int ic = 0;                                                 // coarse entries sorted before this fine sample (ties: coarse first)
-    for (int j = 0; j < S; ++j) ic += s_tc[j] <= v;
+    for (int j = 0; j < S; ++j) ic += tc[j] <= v;
     // the forward's merge pointer never moves back: running maximum over the fine samples in order
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(ic, d);
-      if (lane >= d) ic = max(ic, o);
-    }
-    ic = max(ic, ic_carry);
+    ic = max(wave_scan<true>(ic, lane, op_max), ic_carry);
     ic_carry = __shfl(ic, 63);
     const double g = (double)gts[k + ic];                       // its slot in the merged array
     const double g_frac = g * (double)__fsub_rn(ba, bb);
@@ -843,28 +923,16 @@ void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __rest
   }
   __syncthreads();
   // ---- cdf[m] = sum_{j<m} pdf_j  ->  g_pdf_j = sum_{m>j} g_cdf[m];  pdf = we / W
-  double sfx = lane < NB ? gcdf[lane] : 0.0;                    // inclusive suffix sum over the lanes
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_down(sfx, d);
-    if (lane + d < 64) sfx += o;
-  }
-  double gpdf_excl = __shfl_down(sfx, 1);                       // lane j: g_pdf_j = sum_{m>j} g_cdf[m]
-  if (lane == 63) gpdf_excl = 0.0;
+  const double sfx = wave_scan<false>(lane < NB ? gcdf[lane] : 0.0, lane, op_sum);
+  const double gpdf_excl = wave_shift<false>(sfx, lane, 0.0);   // lane j: g_pdf_j = sum_{m>j} g_cdf[m]
   double gpdf_i = __shfl_up(gpdf_excl, 1);                      // lane i: g_pdf of bin i - 1 (the bin of sample i)
   if (!inner) gpdf_i = 0.0;
   double dot = inner ? gpdf_i * (double)we : 0.0;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) dot += __shfl_xor(dot, d);
   const double g_w = inner ? (gpdf_i / (double)wsum - dot / ((double)wsum * (double)wsum)) : 0.0;
-  double sf2 = g_w * (double)alpha * (double)Ti;                // suf_i = sum_{m>i} g_w_m a_m T_m
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_down(sf2, d);
-    if (lane + d < 64) sf2 += o;
-  }
-  double suf = __shfl_down(sf2, 1);
-  if (lane == 63) suf = 0.0;
+  const double sf2 = wave_scan<false>(g_w * (double)alpha * (double)Ti, lane, op_sum);     // suf_i = sum_{m>i} g_w_m a_m T_m
+  const double suf = wave_shift<false>(sf2, lane, 0.0);
   double g_alpha = g_w * (double)Ti;
   if (om >= 1e-10f && om <= 1.0f) g_alpha -= suf / (double)q;
   f32x4 go = {0.f, 0.f, 0.f, 0.f};
@@ -884,282 +952,6 @@ void nerf_stratified_kernel(const float* __restrict__ t_lin, const float* __rest
   const float lower = s == 0 ? t_lin[0] : __fmul_rn(0.5f, __fadd_rn(t_lin[s], t_lin[s - 1]));
   const float upper = s == S - 1 ? t_lin[S - 1] : __fmul_rn(0.5f, __fadd_rn(t_lin[s + 1], t_lin[s]));
   t_out[e] = __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), jitter[e]));
-}
-
-// Ascending bitonic network over one thread's 128 registers.  Fully unrolled (unroll(full): plain `#pragma unroll` left the
-// array in scratch, 528 B per lane), so every index is a constant and the array lives in VGPRs.
-__device__ __forceinline__ void sort128_ascending(float (&r)[NERF_N_IMPORTANCE]) {
-#pragma clang loop unroll(full)
-  for (int k = 2; k <= NERF_N_IMPORTANCE; k <<= 1) {
-#pragma clang loop unroll(full)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma clang loop unroll(full)
-      for (int i = 0; i < NERF_N_IMPORTANCE; ++i) {
-        const int l = i ^ j;
-        if (l > i) {
-          const float x = r[i], y = r[l];
-          const bool up = (i & k) == 0;
-          r[i] = up ? fminf(x, y) : fmaxf(x, y);
-          r[l] = up ? fmaxf(x, y) : fminf(x, y);
-        }
-      }
-    }
-  }
-}
-
-// Inverse CDF of one u given its searchsorted(right) index: the arithmetic of nerf_sample_fine_kernel's walk.
-__device__ __forceinline__ float inv_cdf_at(const float* cdf, const float* tc, float u, int ind) {
-  constexpr int S = NERF_N_SAMPLES;
-  const int below = min(max(ind - 1, 0), S - 3);
-  const int above = min(ind, S - 3);                   // clamp to 61: tail collapse
-  const float cb = cdf[below], ca = cdf[above];
-  const float bb = __fmul_rn(0.5f, __fadd_rn(tc[below + 1], tc[below]));
-  const float ba = __fmul_rn(0.5f, __fadd_rn(tc[above + 1], tc[above]));
-  float denom = __fsub_rn(ca, cb);
-  if (denom < 1e-5f) denom = 1.0f;
-  const float frac = __fdiv_rn(__fsub_rn(u, cb), denom);
-  return __fadd_rn(bb, __fmul_rn(frac, __fsub_rn(ba, bb)));
-}
-
-// nerf_sample_fine_kernel with a coarse table and a u table per ray (t of ray r at t_coarse + r * t_stride, u at
-// u + r * u_stride; stride 0 shares one table).  t_sorted depends only on the MULTISET of fine depths, so each lane sorts its
-// ray's 128 u ascending (registers, bitonic) and then runs the deterministic kernel's monotone walk, insertion repair and
-// two-way merge unchanged.  LDS: the 64 x 193-float rows of the deterministic kernel (49 408 B) + one 65-float coarse row per
-// ray (16 640 B) = 66 048 B per 64-ray workgroup.  The row's slots [0,128) hold sigma, then the ray's u (staged coalesced),
-// then the sorted u the walk overwrites in place with the fine depths (slot j <= k is written only after u[k] was read).
-constexpr int kTcPitch = 65;       // odd pitch, as kBufPitch
-struct SampleRaysArgs {
-  const float* raw_c;        // [n,64,4]
-  const float* t_coarse;     // [64] or [n,64]
-  long long t_stride;        // 0 or 64
-  const float* u;            // [128] or [n,128]
-  long long u_stride;        // 0 or 128
-  long long n_rays;
-  float* t_sorted;           // [n,192]
-  float* t_fine;             // optional [n,128], in the caller's u order
-};
-__global__ __launch_bounds__(kSampleThreads)
-void nerf_sample_fine_rays_kernel(SampleRaysArgs a) {
-  constexpr int S = NERF_N_SAMPLES, F = NERF_N_IMPORTANCE, NB = S - 1;
-  __shared__ float s_tc[kSampleThreads * kTcPitch];
-  __shared__ float s_buf[kSampleThreads * kBufPitch];
-  const int lane = threadIdx.x;
-  const long long ray0 = (long long)blockIdx.x * kSampleThreads;
-  for (int r = 0; r < kSampleThreads; ++r) {          // lane = coarse sample index
-    long long rg = ray0 + r;
-    if (rg >= a.n_rays) rg = a.n_rays - 1;
-    s_buf[r * kBufPitch + lane] = a.raw_c[rg * (S * 4) + lane * 4 + 3];
-    s_tc[r * kTcPitch + lane] = a.t_coarse[rg * a.t_stride + lane];
-  }
-  __syncthreads();
-  float* buf = s_buf + lane * kBufPitch;
-  float* cdf = buf + F;
-  const float* tc = s_tc + lane * kTcPitch;
-  float T = 1.0f;
-  for (int i = 0; i < S; ++i) {
-    const float sigma = fmaxf(buf[i], 0.0f);
-    const float delta = (i < S - 1) ? __fsub_rn(tc[i + 1], tc[i]) : 1e10f;
-    const float alpha = alpha_of(sigma, delta);
-    const float w = __fmul_rn(T, alpha);
-    if (i >= 1 && i <= S - 2) cdf[i - 1] = __fadd_rn(w, 1e-5f);
-    T = __fmul_rn(T, fminf(fmaxf(__fsub_rn(1.0f, alpha), 1e-10f), 1.0f));
-  }
-  const float wsum = torch_sum62(cdf);
-  {
-    float run = 0.0f, prev = cdf[0];
-    cdf[0] = 0.0f;
-    for (int m = 1; m < NB; ++m) {
-      run = __fadd_rn(run, __fdiv_rn(prev, wsum));
-      prev = cdf[m];
-      cdf[m] = run;
-    }
-  }
-  __syncthreads();                                     // every lane has read its sigmas: slots [0,128) take the rays' u
-  for (int r = 0; r < kSampleThreads; ++r) {
-    long long rg = ray0 + r;
-    if (rg >= a.n_rays) rg = a.n_rays - 1;
-    s_buf[r * kBufPitch + lane] = a.u[rg * a.u_stride + lane];
-    s_buf[r * kBufPitch + 64 + lane] = a.u[rg * a.u_stride + 64 + lane];
-  }
-  __syncthreads();
-  const long long ray = ray0 + lane;
-  const bool ray_ok = ray < a.n_rays;
-  if (a.t_fine && ray_ok) {                            // in the caller's order: searchsorted(right) by bisection
-    for (int k = 0; k < F; ++k) {
-      const float u = buf[k];
-      int lo = 0, hi = NB;
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] <= u) lo = mid + 1; else hi = mid; }
-      a.t_fine[ray * F + k] = inv_cdf_at(cdf, tc, u, lo);
-    }
-  }
-  {
-    float r[F];
-#pragma clang loop unroll(full)
-    for (int k = 0; k < F; ++k) r[k] = buf[k];
-    sort128_ascending(r);
-#pragma clang loop unroll(full)
-    for (int k = 0; k < F; ++k) buf[k] = r[k];
-  }
-  int ind = 0;
-  for (int k = 0; k < F; ++k) {
-    const float u = buf[k];
-    while (ind < NB && cdf[ind] <= u) ++ind;
-    const float v = inv_cdf_at(cdf, tc, u, ind);
-    int j = k;
-    while (j > 0 && buf[j - 1] > v) { buf[j] = buf[j - 1]; --j; }
-    buf[j] = v;
-  }
-  {
-    int ic = S - 1, jf = F - 1;
-    for (int k = S + F - 1; k >= 0; --k) {
-      const bool take_f = (ic < 0) || (jf >= 0 && buf[jf] >= tc[ic]);
-      if (take_f) { buf[k] = buf[jf]; --jf; }
-      else { buf[k] = tc[ic]; --ic; }
-    }
-  }
-  __syncthreads();
-  for (int i = 0; i < S + F; ++i) {
-    const int e = lane + 64 * i, r = e / (S + F), k = e - r * (S + F);
-    const long long rg = ray0 + r;
-    if (rg < a.n_rays) a.t_sorted[rg * (S + F) + k] = s_buf[r * kBufPitch + k];
-  }
-}
-
-// nerf_sample_bwd_kernel with per-ray tables (strides as nerf_sample_fine_rays_kernel).  Each wave sorts its ray's u across
-// the wave first (bitonic, lane l holds elements l and l + 64): the merged-slot logic (k + ic with the running maximum, ties
-// coarse first) then holds as in the deterministic kernel.  LDS per 4-ray workgroup: 4 coarse rows, the cdf rows and the
-// float64 cdf adjoint rows, 4 352 B.
-__global__ __launch_bounds__(256)
-void nerf_sample_rays_bwd_kernel(const float* __restrict__ raw_c, const float* __restrict__ t_coarse, long long t_stride,
-                                 const float* __restrict__ u_in, long long u_stride, long long n_rays,
-                                 const float* __restrict__ g_tsorted, float* __restrict__ g_raw_c) {
-  constexpr int S = NERF_N_SAMPLES, F = NERF_N_IMPORTANCE, NB = S - 1;
-  static_assert(S == 64 && F == 128, "lane = coarse sample, two fine samples per lane");
-  __shared__ float s_tc[4][S];
-  __shared__ float s_cdf[4][S];
-  __shared__ double s_gcdf[4][S];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long ray_slot = (long long)blockIdx.x * 4 + wv;
-  const bool ray_ok = ray_slot < n_rays;
-  const long long ray = ray_ok ? ray_slot : n_rays - 1;
-  s_tc[wv][lane] = t_coarse[ray * t_stride + lane];
-  s_gcdf[wv][lane] = 0.0;
-  float us[2] = {u_in[ray * u_stride + lane], u_in[ray * u_stride + 64 + lane]};
-#pragma unroll
-  for (int k = 2; k <= F; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (j == 64) {                                   // k == 128: partners share the lane
-        const float x = us[0], y = us[1];
-        us[0] = fminf(x, y); us[1] = fmaxf(x, y);
-      } else {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int idx = lane + 64 * h;
-          const float p = __shfl_xor(us[h], j);
-          const bool up = (idx & k) == 0, low = (idx & j) == 0;
-          us[h] = (low == up) ? fminf(us[h], p) : fmaxf(us[h], p);
-        }
-      }
-    }
-  }
-  __syncthreads();
-  const float* tcw = s_tc[wv];
-  const int i = lane;
-  const float s_raw = raw_c[ray * (S * 4) + i * 4 + 3];
-  const float sigma = fmaxf(s_raw, 0.0f);
-  const float delta = (i < S - 1) ? __fsub_rn(tcw[i + 1], tcw[i]) : 1e10f;
-  const float e = expf(__fmul_rn(-sigma, delta));
-  const float alpha = __fsub_rn(1.0f, e);
-  const float om = __fsub_rn(1.0f, alpha);
-  const float q = fminf(fmaxf(om, 1e-10f), 1.0f);
-  float Ti = 1.0f;
-  {
-    float T = 1.0f;
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      if (lane == j) Ti = T;
-      T = __fmul_rn(T, lane_bcast(q, j));
-    }
-  }
-  const bool inner = i >= 1 && i <= S - 2;
-  const float we = __fadd_rn(__fmul_rn(Ti, alpha), 1e-5f);
-  const float wsum = torch_sum62_of([&](int k) { return lane_bcast(we, k + 1); });
-  const float pdf = __fdiv_rn(we, wsum);
-  float cdf_m = 0.0f;
-  {
-    float run = 0.0f;
-#pragma unroll
-    for (int m = 1; m < NB; ++m) {
-      run = __fadd_rn(run, lane_bcast(pdf, m));
-      if (lane == m) cdf_m = run;
-    }
-  }
-  s_cdf[wv][lane] = cdf_m;
-  __syncthreads();
-  const float* gts = g_tsorted + ray * (S + F);
-  float* cdf = s_cdf[wv];
-  double* gcdf = s_gcdf[wv];
-  int ic_carry = 0;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int k = lane + 64 * half;                   // rank of this fine sample among the ray's (sorted) fine samples
-    const float u = us[half];
-    int ind = 0;
-    for (int m = 0; m < NB; ++m) ind += cdf[m] <= u;
-    const int below = min(max(ind - 1, 0), S - 3), above = min(ind, S - 3);
-    const float cb = cdf[below], ca = cdf[above];
-    const float bb = __fmul_rn(0.5f, __fadd_rn(tcw[below + 1], tcw[below]));
-    const float ba = __fmul_rn(0.5f, __fadd_rn(tcw[above + 1], tcw[above]));
-    const float draw_ = __fsub_rn(ca, cb);
-    const bool live = !(draw_ < 1e-5f);
-    const float denom = live ? draw_ : 1.0f;
-    const float num = __fsub_rn(u, cb);
-    const float v = __fadd_rn(bb, __fmul_rn(__fdiv_rn(num, denom), __fsub_rn(ba, bb)));
-    int ic = 0;
-    for (int j = 0; j < S; ++j) ic += tcw[j] <= v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(ic, d);
-      if (lane >= d) ic = max(ic, o);
-    }
-    ic = max(ic, ic_carry);
-    ic_carry = __shfl(ic, 63);
-    const double g = (double)gts[k + ic];
-    const double g_frac = g * (double)__fsub_rn(ba, bb);
-    double g_cb = -g_frac / (double)denom, g_ca = 0.0;
-    if (live) { const double gden = -g_frac * (double)num / ((double)denom * (double)denom); g_ca += gden; g_cb -= gden; }
-    atomicAdd(&gcdf[below], g_cb);
-    atomicAdd(&gcdf[above], g_ca);
-  }
-  __syncthreads();
-  double sfx = lane < NB ? gcdf[lane] : 0.0;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_down(sfx, d);
-    if (lane + d < 64) sfx += o;
-  }
-  double gpdf_excl = __shfl_down(sfx, 1);
-  if (lane == 63) gpdf_excl = 0.0;
-  double gpdf_i = __shfl_up(gpdf_excl, 1);
-  if (!inner) gpdf_i = 0.0;
-  double dot = inner ? gpdf_i * (double)we : 0.0;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) dot += __shfl_xor(dot, d);
-  const double g_w = inner ? (gpdf_i / (double)wsum - dot / ((double)wsum * (double)wsum)) : 0.0;
-  double sf2 = g_w * (double)alpha * (double)Ti;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_down(sf2, d);
-    if (lane + d < 64) sf2 += o;
-  }
-  double suf = __shfl_down(sf2, 1);
-  if (lane == 63) suf = 0.0;
-  double g_alpha = g_w * (double)Ti;
-  if (om >= 1e-10f && om <= 1.0f) g_alpha -= suf / (double)q;
-  f32x4 go = {0.f, 0.f, 0.f, 0.f};
-  go.w = s_raw > 0.0f ? (float)(g_alpha * (double)delta * (double)e) : 0.0f;
-  if (ray_ok) reinterpret_cast<f32x4*>(g_raw_c)[ray * S + i] = go;
 }
 
 // ------------------------------------------------------------------------------------ training: live tiles of a backward pass
@@ -1787,12 +1579,12 @@ int32_t nerf_sample_fine(const float* raw_coarse, const float* t_coarse, const f
   if (n_rays == 0) return NERF_OK;
   if (!raw_coarse || !t_coarse || !u || !t_sorted) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine: null argument");
   SampleArgs a;
-  a.raw_c = raw_coarse; a.t_coarse = t_coarse; a.u_tab = u; a.n_rays = n_rays; a.t_sorted = t_sorted;
+  a.raw_c = raw_coarse; a.t_coarse = t_coarse; a.t_stride = 0; a.u = u; a.u_stride = 0; a.n_rays = n_rays; a.t_sorted = t_sorted;
   a.t_fine = t_fine; a.valid_sorted = valid_sorted; a.fast_sampling = valid_sorted != nullptr;
   a.weights_threshold = weights_threshold; a.ert_threshold = ert_threshold;
   const unsigned blocks = (unsigned)((n_rays + kSampleThreads - 1) / kSampleThreads);
-  hipLaunchKernelGGL(nerf_sample_fine_kernel, dim3(blocks), dim3(kSampleThreads), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_sample_fine_kernel");
+  hipLaunchKernelGGL(nerf_sample_fine_kernel<false>, dim3(blocks), dim3(kSampleThreads), 0, (hipStream_t)stream, a);
+  return check_launch("nerf_sample_fine_kernel<false>");
 }
 
 int32_t nerf_composite(const float* raw, const float* tvals, int64_t t_ray_stride, int64_t n_rays,
@@ -1938,9 +1730,9 @@ int32_t nerf_sample_fine_backward(const float* raw_coarse, const float* t_coarse
   if (n_rays == 0) return NERF_OK;
   if (!raw_coarse || !t_coarse || !u || !t_sorted || !g_t_sorted || !g_raw_coarse)
     return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_backward: null argument");
-  hipLaunchKernelGGL(nerf_sample_bwd_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0,
-                     (hipStream_t)stream, raw_coarse, t_coarse, u, (long long)n_rays, t_sorted, g_t_sorted, g_raw_coarse);
-  return check_launch("nerf_sample_bwd_kernel");
+  hipLaunchKernelGGL(nerf_sample_bwd_kernel<false>, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                     raw_coarse, t_coarse, 0LL, u, 0LL, (long long)n_rays, g_t_sorted, g_raw_coarse);
+  return check_launch("nerf_sample_bwd_kernel<false>");
 }
 
 int32_t nerf_stratified_samples(const float* t_linear, const float* jitter, int64_t n_rays, float* t_coarse, void* stream) {
@@ -1967,12 +1759,13 @@ int32_t nerf_sample_fine_rays(const float* raw_coarse, const float* t_coarse, in
   if (valid_sorted) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: fast_sampling needs the shared tables");
   if (n_rays == 0) return NERF_OK;
   if (!raw_coarse || !t_coarse || !u || !t_sorted) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: null argument");
-  SampleRaysArgs a;
+  SampleArgs a;
   a.raw_c = raw_coarse; a.t_coarse = t_coarse; a.t_stride = t_ray_stride; a.u = u; a.u_stride = u_ray_stride;
-  a.n_rays = n_rays; a.t_sorted = t_sorted; a.t_fine = t_fine;
+  a.n_rays = n_rays; a.t_sorted = t_sorted; a.t_fine = t_fine; a.valid_sorted = nullptr; a.fast_sampling = 0;
+  a.weights_threshold = a.ert_threshold = 0.0f;
   const unsigned blocks = (unsigned)((n_rays + kSampleThreads - 1) / kSampleThreads);
-  hipLaunchKernelGGL(nerf_sample_fine_rays_kernel, dim3(blocks), dim3(kSampleThreads), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_sample_fine_rays_kernel");
+  hipLaunchKernelGGL(nerf_sample_fine_kernel<true>, dim3(blocks), dim3(kSampleThreads), 0, (hipStream_t)stream, a);
+  return check_launch("nerf_sample_fine_kernel<true>");
 }
 
 int32_t nerf_sample_fine_rays_backward(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
@@ -1985,10 +1778,10 @@ int32_t nerf_sample_fine_rays_backward(const float* raw_coarse, const float* t_c
   if (n_rays == 0) return NERF_OK;
   if (!raw_coarse || !t_coarse || !u || !t_sorted || !g_t_sorted || !g_raw_coarse)
     return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays_backward: null argument");
-  hipLaunchKernelGGL(nerf_sample_rays_bwd_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(nerf_sample_bwd_kernel<true>, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                      raw_coarse, t_coarse, (long long)t_ray_stride, u, (long long)u_ray_stride, (long long)n_rays, g_t_sorted,
                      g_raw_coarse);
-  return check_launch("nerf_sample_rays_bwd_kernel");
+  return check_launch("nerf_sample_bwd_kernel<true>");
 }
 
 int32_t nerf_viewdirs_backward(const float* gsave, int64_t n_rays, int32_t n_samples, const float* w_views,

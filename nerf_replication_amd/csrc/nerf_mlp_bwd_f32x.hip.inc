@@ -35,29 +35,6 @@ __device__ __forceinline__ void xb_next_layer(XbScale& sc) {
   sc.mx = 0.0f;
 }
 
-// one in-feature tile of  g_in = W^T g_out : returns the fp32 tile (no bias)
-template <int KS>
-__device__ __forceinline__ f32x16 gemmxb_tile(XRing& r, int m, const h8* Bh, const h8* Bl) {
-  f32x16 ah, al;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { ah[i] = 0.0f; al[i] = 0.0f; }
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    const int fi = (m * KS + s) & (kXStepsPerChunk - 1);
-    xfrag_read(r, fi + kXPfDist, r.pfh[(fi + kXPfDist) % kXPf], r.pfl[(fi + kXPfDist) % kXPf]);
-    __builtin_amdgcn_sched_barrier(0x406);
-    const h8 wh = r.pfh[fi % kXPf], wl = r.pfl[fi % kXPf];
-    ah = mfma16(wh, Bh[s], ah);
-    al = mfma16(wh, Bl[s], al);
-    al = mfma16(wl, Bh[s], al);
-    xring_step(r, fi);
-  }
-  f32x16 out;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) out[i] = fmaf(al[i], kXLoInv, ah[i]);
-  return out;
-}
-
 // split a finished fp32 tile (times sc.adj) into the two packed B fragments (k-steps 2m, 2m+1) of the next GEMM
 __device__ __forceinline__ void splitx_tile(const f32x16& v, int m, h8* OUTh, h8* OUTl, XbScale& sc) {
   h8 h0, h1, l0, l1;
@@ -73,25 +50,19 @@ __device__ __forceinline__ void splitx_tile(const f32x16& v, int m, h8* OUTh, h8
   OUTl[2 * m] = l0; OUTl[2 * m + 1] = l1;
 }
 
-// Full layer: NM in-feature tiles of  g_in = W^T g_out, software-pipelined like the forward's layers (round 3: with one wave per
-// SIMD nothing else fills the matrix pipe while a finished tile is combined, masked, stored and split, so that epilogue is cut
-// into eight 2-value chunks issued behind the MFMAs of the NEXT tile; only a layer's last tile has its epilogue exposed).
+// Full layer: NM in-feature tiles of  g_in = W^T g_out  on the training layer skeleton (gemmx_layer_train in nerf_mlp_f32x.hip.inc:
+// a finished tile is combined, masked, stored and split in eight 2-value chunks behind the MFMAs of the NEXT tile).
 // EXTRA: + w_alpha * g_sigma (joins at z7).  MASK: ReLU mask from the sign bits the SAVE forward collected (TrainSave::off_bits:
 // ONE coalesced 16-byte load per lane and layer -- round 2 re-read the 1-KiB activation row of every point, 8.4 GB per step).
 // STORE: row-major g_z (times the inverse scale) for the weight-gradient kernels, through the per-wave LDS transpose (XRowStage in
 // nerf_mlp_f32x.hip.inc: full 128-byte lines per store instead of 64 scattered 16-byte pieces -- without its stores this kernel
 // was 48 % faster) -- UNCONDITIONAL: the lanes of a ragged last tile write their duplicate rows into the pad32 padding of the
 // TrainGrad regions, a wave without a tile never gets here.  `tile_rows`: wave-uniform address of the tile's (row 0, feature 0).
-#ifndef NERF_XB_ASM_BFE
-#define NERF_XB_ASM_BFE 1               // 0: the compiler's three-instruction mask (A/B: tools/ab_train.py)
-#endif
 #ifndef NERF_XB_HACK_NOSTORE
 #define NERF_XB_HACK_NOSTORE 0          // timing only: the chain without its g_z row stores
 #endif
-struct XbPending { f32x16 ah, al; h2 part_h[3], part_l[3]; };
-
 template <bool EXTRA, bool MASK, bool STORE, int MM, int Q>
-__device__ __forceinline__ void xb_epilogue_chunk(XbPending& t, h8* OUTh, h8* OUTl, const u32x4& mw, const XRowStage& st,
+__device__ __forceinline__ void xb_epilogue_chunk(XPending& t, h8* OUTh, h8* OUTl, const u32x4& mw, const XRowStage& st,
                                                   lds_cfloat* extra_w, float extra_g, float (&keep)[2], float sc_inv, float sc_adj, float& sc_mx) {
   // (scalar fp32 instructions on purpose: xsplit_pair in nerf_mlp_f32x.hip.inc)
   f32x2 v;
@@ -104,12 +75,8 @@ __device__ __forceinline__ void xb_epilogue_chunk(XbPending& t, h8* OUTh, h8* OU
     const int w = (int)mw[MM >> 1];
     // (v_bfe_i32 by asm: hipcc turns `x & sbfe(w, pos, 1)` into and + compare + select, three VALU per value instead of two)
     int m0, m1;
-    if constexpr (NERF_XB_ASM_BFE) {
-      asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m0) : "v"(w), "n"(16 * (MM & 1) + 2 * Q));
-      asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m1) : "v"(w), "n"(16 * (MM & 1) + 2 * Q + 1));
-    } else {
-      m0 = __builtin_amdgcn_sbfe(w, 16 * (MM & 1) + 2 * Q, 1); m1 = __builtin_amdgcn_sbfe(w, 16 * (MM & 1) + 2 * Q + 1, 1);
-    }
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m0) : "v"(w), "n"(16 * (MM & 1) + 2 * Q));
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m1) : "v"(w), "n"(16 * (MM & 1) + 2 * Q + 1));
     v.x = __int_as_float(__float_as_int(v.x) & m0);
     v.y = __int_as_float(__float_as_int(v.y) & m1);
   }
@@ -125,62 +92,24 @@ __device__ __forceinline__ void xb_epilogue_chunk(XbPending& t, h8* OUTh, h8* OU
   sc_mx = fmaxf(sc_mx, fmaxf(fabsf(a0), fabsf(a1)));
   h2 hi, lo;
   xsplit_pair(a0, a1, hi, lo);
-  constexpr int k = Q & 3;
-  if constexpr (k < 3) { t.part_h[k] = hi; t.part_l[k] = lo; }
-  else {
-    const h4 h01 = __builtin_shufflevector(t.part_h[0], t.part_h[1], 0, 1, 2, 3), h23 = __builtin_shufflevector(t.part_h[2], hi, 0, 1, 2, 3);
-    const h4 l01 = __builtin_shufflevector(t.part_l[0], t.part_l[1], 0, 1, 2, 3), l23 = __builtin_shufflevector(t.part_l[2], lo, 0, 1, 2, 3);
-    OUTh[2 * MM + (Q >> 2)] = __builtin_shufflevector(h01, h23, 0, 1, 2, 3, 4, 5, 6, 7);
-    OUTl[2 * MM + (Q >> 2)] = __builtin_shufflevector(l01, l23, 0, 1, 2, 3, 4, 5, 6, 7);
-  }
+  xpending_emit(t, MM, Q, hi, lo, OUTh, OUTl);
 }
 
 template <int KS, int NM, bool EXTRA, bool MASK, bool STORE>
 __device__ __forceinline__ void gemmxb_layer(XRing& r, const h8* Bh, const h8* Bl, h8* OUTh, h8* OUTl,
                                              const u32x4& mw, const XRowStage& st, float* tile_rows,
                                              lds_cfloat* extra_w, float extra_g, XbScale& sc) {
-  constexpr int kCps = (8 + KS - 1) / KS;                  // epilogue chunks issued per k-step
-  constexpr int kS7 = 7 / kCps;                            // k-step that issues chunk 7
-  constexpr bool kLate = kS7 + 2 < KS;                     // stage reads / stores spread over the k-steps behind chunk 7 (else: in place)
-  constexpr bool kStageIo = STORE && !NERF_XB_HACK_NOSTORE;
-  XStaged stg;
   const float sc_inv = sc.inv, sc_adj = sc.adj;            // (scalars: the struct, reached through the nested lambdas, ended up in
   float sc_mx = sc.mx;                                     //  LDS-promoted stack memory -- a ds_read + vmcnt(0) drain per chunk)
-  XbPending pend;
   float keep[2] = {0.0f, 0.0f};
-  static_for<NM>([&](auto M) {
-    constexpr int m = decltype(M)::value;
-    XbPending cur;
+  gemmx_layer_train<KS, 0, NM, 0, 1024, STORE && !NERF_XB_HACK_NOSTORE>(r, Bh, Bl, Bh, Bl, st, tile_rows,
+    [&](XPending& cur, auto) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { cur.ah[i] = 0.0f; cur.al[i] = 0.0f; }
-    static_for<KS>([&](auto S) {
-      constexpr int s = decltype(S)::value;
-      constexpr int fi = (m * KS + s) & (kXStepsPerChunk - 1);
-      xfrag_read(r, fi + kXPfDist, r.pfh[(fi + kXPfDist) % kXPf], r.pfl[(fi + kXPfDist) % kXPf]);
-      __builtin_amdgcn_sched_barrier(0x406);
-      const h8 wh = r.pfh[fi % kXPf], wl = r.pfl[fi % kXPf];
-      cur.ah = mfma16(wh, Bh[s], cur.ah);
-      cur.al = mfma16(wh, Bl[s], cur.al);
-      cur.al = mfma16(wl, Bh[s], cur.al);
-      if constexpr (m > 0) {
-        static_for<kCps>([&](auto C) {
-          constexpr int q = s * kCps + decltype(C)::value;
-          if constexpr (q < 8) xb_epilogue_chunk<EXTRA, MASK, STORE, m - 1, q>(pend, OUTh, OUTl, mw, st, extra_w, extra_g, keep, sc_inv, sc_adj, sc_mx);
-        });
-        if constexpr (kStageIo) {
-          if constexpr (kLate) {
-            if constexpr (s == kS7) xstage_get<0>(st, stg);
-            if constexpr (s == kS7 + 1) { xstage_store<1024, 0>(st, stg, tile_rows, m - 1); xstage_get<1>(st, stg); }
-            if constexpr (s == kS7 + 2) xstage_store<1024, 1>(st, stg, tile_rows, m - 1);
-          } else if constexpr (s == kS7) xstage_flush<1024>(st, tile_rows, m - 1);
-        }
-      }
-      xring_step(r, fi);
+      for (int i = 0; i < 16; ++i) { cur.ah[i] = 0.0f; cur.al[i] = 0.0f; }
+    },
+    [&](XPending& t, auto MM, auto Q) {
+      xb_epilogue_chunk<EXTRA, MASK, STORE, decltype(MM)::value, decltype(Q)::value>(t, OUTh, OUTl, mw, st, extra_w, extra_g, keep, sc_inv, sc_adj, sc_mx);
     });
-    pend = cur;
-  });
-  static_for<8>([&](auto Q) { xb_epilogue_chunk<EXTRA, MASK, STORE, NM - 1, decltype(Q)::value>(pend, OUTh, OUTl, mw, st, extra_w, extra_g, keep, sc_inv, sc_adj, sc_mx); });
-  if constexpr (kStageIo) xstage_flush<1024>(st, tile_rows, NM - 1);
   sc.mx = sc_mx;
   xb_next_layer(sc);
 }
@@ -372,7 +301,7 @@ void nerf_mlp_bwd_f32x_kernel(BwdArgs a) {
       if (h) gx[2] += inv * G1[14]; else { gx[0] += inv * G1[14]; gx[1] += inv * G1[15]; }
     };
     {
-      const f32x16 t0 = gemmxb_tile<16>(r, 0, Yh, Yl), t1 = gemmxb_tile<16>(r, 1, Yh, Yl);                              // W5[:, :63]^T g_z5
+      const f32x16 t0 = gemmx_tile<16, 0, 0, false>(r, Yh, Yl, Yh, Yl), t1 = gemmx_tile<16, 0, 0, false>(r, Yh, Yl, Yh, Yl);    // W5[:, :63]^T g_z5
       pe_contract(t0, t1, inv_z5);
     }
 #pragma unroll 1
@@ -381,7 +310,7 @@ void nerf_mlp_bwd_f32x_kernel(BwdArgs a) {
       gemmxb_layer<16, 8, false, true, true>(r, Yh, Yl, Xh, Xl, (it ? mk0 : mk2), st, srow(TrainGrad::off_gz(P, 2 - 2 * it), 256), nullptr, 0.f, sc);   // g_z2, g_z0
     }
     {
-      const f32x16 t0 = gemmxb_tile<16>(r, 0, Xh, Xl), t1 = gemmxb_tile<16>(r, 1, Xh, Xl);                              // W0^T g_z0
+      const f32x16 t0 = gemmx_tile<16, 0, 0, false>(r, Xh, Xl, Xh, Xl), t1 = gemmx_tile<16, 0, 0, false>(r, Xh, Xl, Xh, Xl);    // W0^T g_z0
       pe_contract(t0, t1, sc.inv);
     }
     if (PTS) {

@@ -29,10 +29,7 @@ constexpr float kXLoScale = 2048.0f, kXLoInv = 1.0f / 2048.0f;
 #define NERF_F32X_HACK_SAVE_NOSTORE 0   // training forward without its row stores
 #endif
 #ifndef NERF_F32X_STAGE
-#define NERF_F32X_STAGE 1               // 0: the training forwards store their rows directly (A/B: tools/ab_train.py)
-#endif
-#ifndef NERF_F32X_EPI_SCALAR
-#define NERF_F32X_EPI_SCALAR 1          // inference epilogue: scalar fp32 combine (and residual, except in the DSKIP instance); 0: packed (round 2)
+#define NERF_F32X_STAGE 1               // 0: the training forward's lanes store their own quads directly (A/B: tools/ab_train.py)
 #endif
 #ifndef NERF_F32X_HACK_NOEPI
 #define NERF_F32X_HACK_NOEPI 0      // only the first of the eight epilogue chunks of every tile
@@ -55,22 +52,19 @@ struct XRing {
 constexpr int kXChunkSigma = 2 * nerf::kF16FragSigma / nerf::kF16ChunkFrags;
 static_assert((2 * nerf::kF16FragSigma) % nerf::kF16ChunkFrags == 0 && 2 * (nerf::kF16FragFeat - nerf::kF16FragSigma) == nerf::kF16ChunkFrags,
               "the sigma head is one whole chunk");
-__device__ __forceinline__ int xring_next_chunk(const XRing& r, int n_chunks) {
+// the stream wraps after r.n_chunks (kXChunks forward, kXbChunks backward)
+__device__ __forceinline__ int xring_next_chunk(const XRing& r) {
   const int nc = r.next_chunk + 1;
-  return nc == (r.dens ? kXChunkSigma + 1 : n_chunks) ? r.first_chunk : nc;
+  return nc == (r.dens ? kXChunkSigma + 1 : r.n_chunks) ? r.first_chunk : nc;
 }
-
-// the stream wraps after n_chunks (kXChunks forward, kXbChunks backward)
-__device__ __forceinline__ void xring_issue_n(XRing& r, int n_chunks);
-__device__ __forceinline__ void xring_issue(XRing& r) { xring_issue_n(r, r.n_chunks); }
-__device__ __forceinline__ void xring_issue_n(XRing& r, int n_chunks) {
+__device__ __forceinline__ void xring_issue(XRing& r) {                       // this wave's 8 DMAs of the next chunk in one burst
   const char* src = r.gsrc + (long long)r.next_chunk * nerf::kF16ChunkBytes;
   lds_char* dst = r.ldst + r.next_slot * nerf::kF16ChunkBytes;
 #pragma unroll
   for (int i = 0; i < kXDmaPerWave; ++i)
     __builtin_amdgcn_global_load_lds((gbl_void*)((src + i * nerf::kF16FragBytes) + r.lane_off),
                                      (lds_void*)(dst + i * nerf::kF16FragBytes), 16, 0, 0);
-  r.next_chunk = xring_next_chunk(r, n_chunks);
+  r.next_chunk = xring_next_chunk(r);
   r.next_slot = (r.next_slot + 1) & (kF16RingSlots - 1);
 }
 __device__ __forceinline__ void xring_set_slots(XRing& r) {
@@ -87,7 +81,7 @@ __device__ __forceinline__ void xring_issue_part(XRing& r, int i) {           //
   lds_char* dst = r.ldst + r.next_slot * nerf::kF16ChunkBytes;
   __builtin_amdgcn_global_load_lds((gbl_void*)((src + i * nerf::kF16FragBytes) + r.lane_off), (lds_void*)(dst + i * nerf::kF16FragBytes), 16, 0, 0);
   if (i == kXDmaPerWave - 1) {
-    r.next_chunk = xring_next_chunk(r, r.n_chunks);
+    r.next_chunk = xring_next_chunk(r);
     r.next_slot = (r.next_slot + 1) & (kF16RingSlots - 1);
   }
 }
@@ -169,8 +163,9 @@ __device__ __forceinline__ void xbias_read_sync(lds_cfloat* p, XBias& b) {
                "s_waitcnt lgkmcnt(0)"
                : "=&v"(b.q0), "=&v"(b.q1), "=&v"(b.q2), "=&v"(b.q3) : "v"(a));
 }
-// the same, synchronously: reads and their wait in ONE asm statement, for places where the compiler copies registers right
-// behind the defining statement (in front of a join of branches): nothing can come between a read and its wait
+// prime the register prefetch on the first kXPfDist pairs of the chunk being consumed (kernel start, after a skipped colour branch),
+// asm reads -- synchronously: reads and their wait in ONE asm statement, for places where the compiler copies registers right
+// behind the defining statement (in front of a loop or a join of branches): nothing can come between a read and its wait
 __device__ __forceinline__ void xring_prime_sync(XRing& r) {
   static_assert(kXPfDist == 3, "operand list below");
   const unsigned base = (unsigned)(size_t)r.lcur;
@@ -179,33 +174,42 @@ __device__ __forceinline__ void xring_prime_sync(XRing& r) {
                "s_waitcnt lgkmcnt(0)"
                : "=&v"(r.pfh[0]), "=&v"(r.pfl[0]), "=&v"(r.pfh[1]), "=&v"(r.pfl[1]), "=&v"(r.pfh[2]), "=&v"(r.pfl[2]) : "v"(base));
 }
-// prime the register prefetch on the first kXPfDist pairs of the chunk being consumed (kernel start, after a skipped colour branch)
-__device__ __forceinline__ void xring_prime(XRing& r) {
-  static_for<kXPfDist>([&](auto I) { constexpr int i = decltype(I)::value; xfrag_read_asm<i>(r, r.pfh[i], r.pfl[i]); });
+
+// ---- the k-step: the (hi, lo) fragment pair of k-step fi of the chunk sits in ring registers fi % kXPf -----------------------------
+// request the pair kXPfDist steps ahead of FI.  ASM: by inline asm, to be waited for with a counted xwait_pair; else an ordinary
+// read the compiler schedules (and drains for: the training kernels, see XRowStage below)
+template <int FI, bool ASM>
+__device__ __forceinline__ void xfrag_prefetch(XRing& r) {
+  constexpr int p = FI + kXPfDist;
+  if constexpr (ASM) xfrag_read_asm<p>(r, r.pfh[p % kXPf], r.pfl[p % kXPf]);
+  else xfrag_read(r, p, r.pfh[p % kXPf], r.pfl[p % kXPf]);
+}
+// a w = a_h w_h + 2^-11 (a_h w_l + a_l w_h): the three MFMAs of a k-step, A fragments (wh, wl) from the ring, B fragments (bh, bl)
+// (operands by value: hipcc simplifies a helper on its own before it inlines it, and one that reaches the ring registers
+// through a reference comes out scheduled differently from the same lines written in place -- LAB_NOTEBOOK.md)
+__device__ __forceinline__ void xmfma3(f32x16& ah, f32x16& al, h8 wh, h8 wl, h8 bh, h8 bl) {
+  ah = mfma16(wh, bh, ah);
+  al = mfma16(wh, bl, al);
+  al = mfma16(wl, bh, al);
 }
 
-// one out-tile: returns  bias + sum_s W(m, s) . B[s]  in fp32 (hi and lo accumulators combined)
-template <int KS1, int KS2, int F0, bool WITH_BIAS>
-__device__ __forceinline__ f32x16 gemmx_tile(XRing& r, int m, const h8* B1h, const h8* B1l, const h8* B2h,
-                                             const h8* B2l, lds_cfloat* bias_lds_h) {
-  static_assert(!WITH_BIAS, "the heads add their bias at the output");
-  constexpr int KS = KS1 + KS2;
+// one out-tile without bias (the heads add theirs at the output, the backward chain has none): returns  sum_s W(s) . B[s]  in fp32
+// (hi and lo accumulators combined); F0: position of its first k-step in the chunk.  ASM: the inference kernel's asm reads with
+// counted waits; else the training kernels' compiler-scheduled reads.
+template <int KS1, int KS2, int F0, bool ASM>
+__device__ __forceinline__ f32x16 gemmx_tile(XRing& r, const h8* B1h, const h8* B1l, const h8* B2h, const h8* B2l) {
   f32x16 ah, al;
 #pragma unroll
   for (int i = 0; i < 16; ++i) { ah[i] = 0.0f; al[i] = 0.0f; }
-  static_for<KS>([&](auto S) {
+  static_for<KS1 + KS2>([&](auto S) {
     constexpr int s = decltype(S)::value;
-    constexpr int fi = (F0 + s) & (kXStepsPerChunk - 1);          // (heads: one out-tile, m = 0)
-    xfrag_read_asm<fi + kXPfDist>(r, r.pfh[(fi + kXPfDist) % kXPf], r.pfl[(fi + kXPfDist) % kXPf]);
-    xwait_pair<2 * kXPfDist>(r.pfh[fi % kXPf], r.pfl[fi % kXPf]);
-    const h8 wh = r.pfh[fi % kXPf], wl = r.pfl[fi % kXPf];
-    const h8 bh = s < KS1 ? B1h[s] : B2h[s - KS1], bl = s < KS1 ? B1l[s] : B2l[s - KS1];
-    ah = mfma16(wh, bh, ah);
-    al = mfma16(wh, bl, al);
-    al = mfma16(wl, bh, al);
+    constexpr int fi = (F0 + s) & (kXStepsPerChunk - 1);
+    xfrag_prefetch<fi, ASM>(r);
+    if constexpr (ASM) xwait_pair<2 * kXPfDist>(r.pfh[fi % kXPf], r.pfl[fi % kXPf]);
+    else __builtin_amdgcn_sched_barrier(0x406);
+    xmfma3(ah, al, r.pfh[fi % kXPf], r.pfl[fi % kXPf], s < KS1 ? B1h[s] : B2h[s - KS1], s < KS1 ? B1l[s] : B2l[s - KS1]);
     xring_step(r, fi);
   });
-  (void)m; (void)bias_lds_h;
   f32x16 out;
 #pragma unroll
   for (int i = 0; i < 16; ++i) out[i] = fmaf(al[i], kXLoInv, ah[i]);
@@ -222,7 +226,7 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 // (hi, lo) split of a pair, value by value with split16's roundings -- SCALAR fp32 instructions on purpose: beside MFMAs a packed
 // v_pk_{fma,add,mul}_f32 costs a lone wave ~17 cycles of issue against 2 x 4 for the two scalar ones (MI355X_MICROARCH.md, "price
-// of one filler beside MFMAs"); the residual is fma(-hi, 2^11, 2^11 x) = (x - hi) 2^11 exactly (both products are exact), which
+// of one filler beside MFMAs": -2.6 % on the fine launch for the combine alone, interleaved A/B); the residual is fma(-hi, 2^11, 2^11 x) = (x - hi) 2^11 exactly (both products are exact), which
 // the compiler turns into one v_fma_mix_f32 on the fp16 half instead of v_cvt_f32_f16 + v_sub + v_mul.
 // (2^11 is no inline constant and v_fma_mix_f32 takes no literal: handed over in an SGPR -- as a plain constant hipcc parks it in
 // a VGPR for the whole kernel and, under pressure, SPILLS it: a scratch reload with its vmcnt(0) drain in every layer)
@@ -238,34 +242,13 @@ __device__ __forceinline__ void xsplit_pair(float x0, float x1, h2& hi, h2& lo) 
   lo = __builtin_convertvector(f32x2{r0, r1}, h2);
 }
 
-struct XPending {            // a finished tile whose epilogue has not run yet (its bias is already inside ah)
+struct XPending {            // a finished tile whose epilogue has not run yet (forward: its bias is already inside ah)
   f32x16 ah, al;
   h2 part_h[3], part_l[3];   // fp16 pairs of the fragment being assembled (the fourth pair completes it)
 };
-
-// chunk q (0..7) of the epilogue of tile mm: values 2q, 2q+1 as one packed pair -- v_pk_fma_f32 (combine), 2 v_max, v_cvt_pk_f16_f32 (hi), 2 v_cvt_f32_f16, v_pk_add_f32 (residual, exact),
-// v_pk_mul_f32 (x 2^11), v_cvt_pk_f16_f32 (lo): same roundings as split16 value by value
-template <bool SRES>
-__device__ __forceinline__ void xepilogue_chunk(XPending& t, int mm, int q, h8* OUTh, h8* OUTl, bool relu,
-                                                float* __restrict__ save_row, int h, float (&keep)[2]) {
-  // Scalar fp32 instructions (a packed v_pk_{fma,add,mul}_f32 costs a lone wave ~17 issue cycles beside MFMAs against 2 x 4:
-  // -2.6 % on the fine launch for the combine alone, interleaved A/B; SRES: the residual too -- xsplit_pair, v_fma_mix_f32).
-  // With hipcc's default register allocation both together made the DSKIP instance spill its bias pointer; with the accumulators in
-  // VGPRs (this unit's XFLAGS) every instance takes both.  NERF_F32X_EPI_SCALAR=0: the round-2 packed form.
-  f32x2 x;
-  if constexpr (NERF_F32X_EPI_SCALAR) { x.x = fmaf(t.al[2 * q], kXLoInv, t.ah[2 * q]); x.y = fmaf(t.al[2 * q + 1], kXLoInv, t.ah[2 * q + 1]); }
-  else {
-    const f32x2 ah = {t.ah[2 * q], t.ah[2 * q + 1]}, al = {t.al[2 * q], t.al[2 * q + 1]};
-    x = __builtin_elementwise_fma(al, f32x2{kXLoInv, kXLoInv}, ah);
-  }
-  if (relu) x = __builtin_elementwise_max(x, f32x2{0.0f, 0.0f});
-  h2 hi, lo;
-  if constexpr (SRES && NERF_F32X_EPI_SCALAR) xsplit_pair(x.x, x.y, hi, lo);
-  else {
-    hi = __builtin_convertvector(x, h2);
-    const f32x2 res = (x - __builtin_convertvector(hi, f32x2)) * f32x2{kXLoScale, kXLoScale};
-    lo = __builtin_convertvector(res, h2);
-  }
+// the split pair of chunk q joins the B fragment being assembled; every fourth one completes it: k-step 2 mm + (q >> 2) of the
+// next GEMM
+__device__ __forceinline__ void xpending_emit(XPending& t, int mm, int q, h2 hi, h2 lo, h8* OUTh, h8* OUTl) {
   const int k = q & 3;
   if (k < 3) { t.part_h[k] = hi; t.part_l[k] = lo; }
   else {
@@ -274,29 +257,32 @@ __device__ __forceinline__ void xepilogue_chunk(XPending& t, int mm, int q, h8* 
     OUTh[2 * mm + (q >> 2)] = __builtin_shufflevector(h01, h23, 0, 1, 2, 3, 4, 5, 6, 7);
     OUTl[2 * mm + (q >> 2)] = __builtin_shufflevector(l01, l23, 0, 1, 2, 3, 4, 5, 6, 7);
   }
-  if (save_row != nullptr) {
-    if (q & 1) {
-      f32x4 o4; o4.x = keep[0]; o4.y = keep[1]; o4.z = x.x; o4.w = x.y;
-      *reinterpret_cast<f32x4*>(save_row + 32 * mm + 8 * (q >> 1) + 4 * h) = o4;
-    } else { keep[0] = x.x; keep[1] = x.y; }
-  }
 }
 
-// save_row (training forward): row-major fp32 activations of this lane's point, or nullptr
-// save_row (training forward): row-major fp32 activations of this lane's point, or nullptr.
+// chunk q (0..7) of the inference epilogue of tile mm: values 2q, 2q+1 -- combine (2 v_fma_f32), ReLU (2 v_max), split
+// (xsplit_pair: same roundings as split16 value by value)
+__device__ __forceinline__ void xepilogue_chunk(XPending& t, int mm, int q, h8* OUTh, h8* OUTl, bool relu) {
+  f32x2 x;                      // (scalar fp32 instructions on purpose: xsplit_pair)
+  x.x = fmaf(t.al[2 * q], kXLoInv, t.ah[2 * q]); x.y = fmaf(t.al[2 * q + 1], kXLoInv, t.ah[2 * q + 1]);
+  if (relu) x = __builtin_elementwise_max(x, f32x2{0.0f, 0.0f});
+  h2 hi, lo;
+  xsplit_pair(x.x, x.y, hi, lo);
+  xpending_emit(t, mm, q, hi, lo, OUTh, OUTl);
+}
+
+// The inference layer (asm reads with counted waits).
 // (Carrying a layer's last pending tile into the next layer's first tile was tried: +0.6 %, not kept.)
 // `nb` enters holding (in flight or landed) the bias of this layer's out-tile 0 and leaves holding that of the layer that follows
 // (next_layer_bias, with HAS_NEXT; without: nothing is fetched and nb is left dead).
-template <int KS1, int KS2, int NM, int F0, bool PIPE, bool HAS_NEXT, bool SRES>
+template <int KS1, int KS2, int NM, int F0, bool HAS_NEXT>
 __device__ __forceinline__ void gemmx_layer(XRing& r, XBias& nb, lds_cfloat* bias_lds_h, lds_cfloat* next_layer_bias,
                                             const h8* B1h, const h8* B1l, const h8* B2h, const h8* B2l, h8* OUTh, h8* OUTl,
-                                            bool relu, float* __restrict__ save_row = nullptr, int h = 0) {
+                                            bool relu) {
   constexpr int KS = KS1 + KS2;
-  constexpr int kCps = PIPE ? (8 + KS - 1) / KS : 0;      // epilogue chunks issued per k-step
+  constexpr int kCps = (8 + KS - 1) / KS;                 // epilogue chunks issued per k-step
   constexpr int kBiasAt = KS - 3;                         // k-step at which the NEXT tile's bias is requested (waited for one step later)
   static_assert(kBiasAt >= 1, "the current tile consumes nb at k-step 0");
   XPending pend;
-  float keep[2] = {0.0f, 0.0f};
   static_for<NM>([&](auto M) {
     constexpr int m = decltype(M)::value;
     XPending cur;
@@ -309,7 +295,7 @@ __device__ __forceinline__ void gemmx_layer(XRing& r, XBias& nb, lds_cfloat* bia
       // reads behind it (+ 4 at k-step kBiasAt itself); one step later the wait is tightened to "only the two newest pairs may be
       // outstanding", which covers the bias quads (tied there; the pair it additionally waits for was issued two steps ago).
       if constexpr (s == kBiasAt && fetch_next) xbias_read_asm(m + 1 < NM ? bias_lds_h + (m + 1) * 16 : next_layer_bias, nb);
-      xfrag_read_asm<fi + kXPfDist>(r, r.pfh[(fi + kXPfDist) % kXPf], r.pfl[(fi + kXPfDist) % kXPf]);
+      xfrag_prefetch<fi, true>(r);
       if constexpr (s == kBiasAt && fetch_next) xwait_pair<2 * kXPfDist + 4>(r.pfh[fi % kXPf], r.pfl[fi % kXPf]);
       else if constexpr (s == kBiasAt + 1 && fetch_next) xwait_pair_bias<4>(r.pfh[fi % kXPf], r.pfl[fi % kXPf], nb);
       else xwait_pair<2 * kXPfDist>(r.pfh[fi % kXPf], r.pfl[fi % kXPf]);
@@ -321,33 +307,23 @@ __device__ __forceinline__ void gemmx_layer(XRing& r, XBias& nb, lds_cfloat* bia
 #pragma unroll
         for (int i = 0; i < 16; ++i) cur.al[i] = 0.0f;
       }
-      const h8 wh = r.pfh[fi % kXPf], wl = r.pfl[fi % kXPf];
-      const h8 bh = s < KS1 ? B1h[s] : B2h[s - KS1], bl = s < KS1 ? B1l[s] : B2l[s - KS1];
-      cur.ah = mfma16(wh, bh, cur.ah);
-      cur.al = mfma16(wh, bl, cur.al);
-      cur.al = mfma16(wl, bh, cur.al);
-      if constexpr (PIPE && m > 0) {
+      xmfma3(cur.ah, cur.al, r.pfh[fi % kXPf], r.pfl[fi % kXPf], s < KS1 ? B1h[s] : B2h[s - KS1], s < KS1 ? B1l[s] : B2l[s - KS1]);
+      if constexpr (m > 0) {
 #pragma unroll
         for (int c = 0; c < kCps; ++c)
-          if (s * kCps + c < (NERF_F32X_HACK_NOEPI ? 1 : 8)) xepilogue_chunk<SRES>(pend, m - 1, s * kCps + c, OUTh, OUTl, relu, save_row, h, keep);
+          if (s * kCps + c < (NERF_F32X_HACK_NOEPI ? 1 : 8)) xepilogue_chunk(pend, m - 1, s * kCps + c, OUTh, OUTl, relu);
       }
       if (!NERF_F32X_HACK_NOADV) xring_step(r, fi);
     });
-    if constexpr (!PIPE) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) xepilogue_chunk<SRES>(cur, m, q, OUTh, OUTl, relu, save_row, h, keep);
-    }
     pend = cur;
   });
-  if (PIPE) {
 #pragma unroll
-    for (int q = 0; q < (NERF_F32X_HACK_NOEPI ? 1 : 8); ++q) xepilogue_chunk<SRES>(pend, NM - 1, q, OUTh, OUTl, relu, save_row, h, keep);
-  }
+  for (int q = 0; q < (NERF_F32X_HACK_NOEPI ? 1 : 8); ++q) xepilogue_chunk(pend, NM - 1, q, OUTh, OUTl, relu);
 }
 
-// ---- the training forward's layer (SAVE instances): compiler-scheduled LDS reads (every wait hipcc places is a full drain, see
-// above; with 256 + 256 registers in use it parks freshly "read" asm fragments in AGPRs before they have landed: 14 hazards in
-// tools/check_asm_stream.py), software-pipelined like the inference layer, bias as the accumulator's initial value.
+// ---- the training kernels' layer (SAVE forward here, backward chain in nerf_mlp_bwd_f32x.hip.inc): compiler-scheduled LDS reads
+// (every wait hipcc places is a full drain, see above; with 256 + 256 registers in use it parks freshly "read" asm fragments in
+// AGPRs before they have landed: 14 hazards in tools/check_asm_stream.py), software-pipelined like the inference layer.
 // Every store is UNCONDITIONAL: the lanes of a ragged last tile write their (duplicate) rows into the pad32 padding of the
 // TrainSave regions, and a wave without a 32-point tile never gets here (it lets the whole stream go by) -- round 2 predicated
 // each of the ~250 row stores of a tile with its own s_and_saveexec / s_cbranch_execz.
@@ -402,25 +378,65 @@ __device__ __forceinline__ void xstage_flush(const XRowStage& st, float* tile_ro
   xstage_get<1>(st, g); xstage_store<ROWB, 1>(st, g, tile_rows, m);
 }
 
-struct XPendingS {            // a finished tile whose epilogue has not run yet (its bias is already inside ah)
-  f32x16 ah, al;
-  h2 part_h[3], part_l[3];   // fp16 pairs of the fragment being assembled (the fourth pair completes it)
-};
+// The layer skeleton of both training kernels: NM out-tiles of KS1 + KS2 k-steps (B1 then B2 fragments; F0: position of the first
+// k-step in the chunk).  `init(cur, M)` starts tile M's accumulators, `chunk(pend, MM, Q)` is chunk Q (0..7) of the epilogue of
+// the finished tile MM (M, MM, Q: std::integral_constant) -- issued kCps per k-step behind the MFMAs of the NEXT tile, only the
+// layer's last tile has its epilogue exposed.  STAGE_IO: the chunks write the tile's quads to the LDS stage (xstage_put, every
+// second chunk one), the transposed halves come back in the two k-steps behind chunk 7 and are stored one k-step after their
+// read (`tile_rows`: wave-uniform address of (row 0, feature 0) of this wave's 32-point tile in the layer's row-major region with
+// ROWB-byte rows); where no k-step is left to spread that over, and for the last tile, the round trip runs in place.
+template <int KS1, int KS2, int NM, int F0, int ROWB, bool STAGE_IO, class Init, class Chunk>
+__device__ __forceinline__ void gemmx_layer_train(XRing& r, const h8* B1h, const h8* B1l, const h8* B2h, const h8* B2l,
+                                                  const XRowStage& st, float* tile_rows, Init&& init, Chunk&& chunk) {
+  constexpr int KS = KS1 + KS2;
+  constexpr int kCps = (8 + KS - 1) / KS;                 // epilogue chunks issued per k-step
+  constexpr int kS7 = 7 / kCps;                           // k-step that issues chunk 7
+  constexpr bool kLate = kS7 + 2 < KS;                    // stage reads / stores spread over the k-steps behind chunk 7 (else: in place)
+  XStaged stg;
+  XPending pend;
+  static_for<NM>([&](auto M) {
+    constexpr int m = decltype(M)::value;
+    XPending cur;
+    init(cur, M);
+    static_for<KS>([&](auto S) {
+      constexpr int s = decltype(S)::value;
+      constexpr int fi = (F0 + m * KS + s) & (kXStepsPerChunk - 1);
+      xfrag_prefetch<fi, false>(r);
+      __builtin_amdgcn_sched_barrier(0x406);
+      xmfma3(cur.ah, cur.al, r.pfh[fi % kXPf], r.pfl[fi % kXPf], s < KS1 ? B1h[s] : B2h[s - KS1], s < KS1 ? B1l[s] : B2l[s - KS1]);
+      if constexpr (m > 0) {
+        static_for<kCps>([&](auto C) {
+          constexpr int q = s * kCps + decltype(C)::value;
+          if constexpr (q < 8) chunk(pend, std::integral_constant<int, m - 1>{}, std::integral_constant<int, q>{});
+        });
+        if constexpr (STAGE_IO) {
+          if constexpr (kLate) {
+            if constexpr (s == kS7) xstage_get<0>(st, stg);
+            if constexpr (s == kS7 + 1) { xstage_store<ROWB, 0>(st, stg, tile_rows, m - 1); xstage_get<1>(st, stg); }
+            if constexpr (s == kS7 + 2) xstage_store<ROWB, 1>(st, stg, tile_rows, m - 1);
+          } else if constexpr (s == kS7) xstage_flush<ROWB>(st, tile_rows, m - 1);
+        }
+      }
+      xring_step(r, fi);
+    });
+    pend = cur;
+  });
+  static_for<8>([&](auto Q) { chunk(pend, std::integral_constant<int, NM - 1>{}, Q); });
+  if constexpr (STAGE_IO) xstage_flush<ROWB>(st, tile_rows, NM - 1);
+}
+
 struct XSaveBits { unsigned w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u; };      // (scalars: stay in registers)
 
-// chunk q (0..7) of the epilogue of tile mm: values 2q, 2q+1 as one packed pair -- v_pk_fma_f32 (combine), 2 v_max_i32 (ReLU on the
-// bit pattern), v_cvt_pk_f16_f32 (hi), 2 v_cvt_f32_f16, v_pk_add_f32 (residual, exact), v_pk_mul_f32 (x 2^11), v_cvt_pk_f16_f32
-// (lo): same roundings as split16 value by value.  BITS: the ReLU sign bits of this lane's values in the layout of the fp32 SAVE
-// forward (TrainSave::off_bits: bit 16 (mm & 1) + r of word mm >> 1 <-> accumulator register r of out-tile mm; the C/D layout of
-// the 32x32 MFMAs is dtype-independent): a rectified value is a non-negative integer, so "> 0" is min(bits, 1) -- v_min_u32 +
-// v_lshl_or_b32 per value.  `row`: this lane's row-major fp32 activation row (+ 4 h), every second chunk stores one 16-byte quad.
-template <bool RELU, bool BITS, bool STAGE, int MM, int Q>
-__device__ __forceinline__ void xepilogue_chunk_s(XPendingS& t, h8* OUTh, h8* OUTl, float* __restrict__ row, const XRowStage& st,
+// chunk Q (0..7) of the SAVE forward's epilogue of tile MM: values 2Q, 2Q+1 -- combine, ReLU on the bit pattern (2 v_max_i32), split
+// (xsplit_pair: same roundings as split16 value by value); every second chunk writes one 16-byte quad of this lane's row to the
+// LDS stage (NERF_F32X_STAGE=0: straight to `row`, this lane's row-major fp32 activation row + 4 h).  BITS: the ReLU sign bits of this lane's values in the layout of the fp32 SAVE forward (TrainSave::off_bits: bit
+// 16 (MM & 1) + r of word MM >> 1 <-> accumulator register r of out-tile MM; the C/D layout of the 32x32 MFMAs is
+// dtype-independent): a rectified value is a non-negative integer, so "> 0" is min(bits, 1) -- v_min_u32 + v_lshl_or_b32 per value.
+template <bool RELU, bool BITS, int MM, int Q>
+__device__ __forceinline__ void xepilogue_chunk_s(XPending& t, h8* OUTh, h8* OUTl, float* __restrict__ row, const XRowStage& st,
                                                   float (&keep)[2], XSaveBits& sb) {
-  constexpr int mm = MM, q = Q;
-  // (scalar fp32 instructions on purpose: xsplit_pair)
-  f32x2 x;
-  x.x = fmaf(t.al[2 * q], kXLoInv, t.ah[2 * q]); x.y = fmaf(t.al[2 * q + 1], kXLoInv, t.ah[2 * q + 1]);
+  f32x2 x;                      // (scalar fp32 instructions on purpose: xsplit_pair)
+  x.x = fmaf(t.al[2 * Q], kXLoInv, t.ah[2 * Q]); x.y = fmaf(t.al[2 * Q + 1], kXLoInv, t.ah[2 * Q + 1]);
   if constexpr (RELU) {
     const int i0 = max(__float_as_int(x.x), 0), i1 = max(__float_as_int(x.y), 0);
     x.x = __int_as_float(i0); x.y = __int_as_float(i1);
@@ -439,127 +455,44 @@ __device__ __forceinline__ void xepilogue_chunk_s(XPendingS& t, h8* OUTh, h8* OU
   }
   h2 hi, lo;
   xsplit_pair(x.x, x.y, hi, lo);
-  const int k = q & 3;
-  if (k < 3) { t.part_h[k] = hi; t.part_l[k] = lo; }
-  else {
-    const h4 h01 = __builtin_shufflevector(t.part_h[0], t.part_h[1], 0, 1, 2, 3), h23 = __builtin_shufflevector(t.part_h[2], hi, 0, 1, 2, 3);
-    const h4 l01 = __builtin_shufflevector(t.part_l[0], t.part_l[1], 0, 1, 2, 3), l23 = __builtin_shufflevector(t.part_l[2], lo, 0, 1, 2, 3);
-    OUTh[2 * mm + (q >> 2)] = __builtin_shufflevector(h01, h23, 0, 1, 2, 3, 4, 5, 6, 7);
-    OUTl[2 * mm + (q >> 2)] = __builtin_shufflevector(l01, l23, 0, 1, 2, 3, 4, 5, 6, 7);
-  }
-  if (q & 1) {
+  xpending_emit(t, MM, Q, hi, lo, OUTh, OUTl);
+  if (Q & 1) {
     f32x4 o4; o4.x = keep[0]; o4.y = keep[1]; o4.z = x.x; o4.w = x.y;
     if constexpr (NERF_F32X_HACK_SAVE_NOSTORE) {}
-    else if constexpr (STAGE) xstage_put<(Q >> 1)>(st, o4);
-    else *reinterpret_cast<f32x4*>(row + 32 * mm + 8 * (q >> 1)) = o4;
+    else if constexpr (NERF_F32X_STAGE) xstage_put<(Q >> 1)>(st, o4);
+    else *reinterpret_cast<f32x4*>(row + 32 * MM + 8 * (Q >> 1)) = o4;
   } else { keep[0] = x.x; keep[1] = x.y; }
 }
 
-// STAGE: the layer's rows go through the LDS transpose (`tile_rows`: wave-uniform address of (row 0, feature 0) of this wave's
-// 32-point tile in the layer's row-major region with ROWB-byte rows): a finished tile's quads are written to the stage with its
-// epilogue chunks, the transposed halves come back in the two k-steps behind chunk 7 and are stored one k-step after their read.
-// !STAGE: each lane stores its own quads straight to `row` (its row + 4 h).
-template <int KS1, int KS2, int NM, int F0, bool PIPE, bool RELU, bool BITS_, bool STAGE, int ROWB>
+// The SAVE forward's layer: the bias (16 floats per out-tile, accumulator-row order) is the hi accumulator's initial value; the
+// post-activation rows go through the LDS stage to `tile_rows` (NERF_F32X_STAGE=0: each lane's quads straight to `row`), the
+// sign-bit words of a rectified layer to `bits_dst`.
+template <int KS1, int KS2, int NM, int F0, bool RELU, bool BITS, int ROWB>
 __device__ __forceinline__ void gemmx_layer_s(XRing& r, lds_cfloat* bias_lds_h, const h8* B1h, const h8* B1l,
                                               const h8* B2h, const h8* B2l, h8* OUTh, h8* OUTl,
                                               float* __restrict__ row, const XRowStage& st, float* tile_rows,
                                               unsigned* __restrict__ bits_dst) {
-  constexpr bool BITS = BITS_;
   static_assert(!BITS || RELU, "sign bits belong to rectified layers");
-  static_assert(PIPE, "the training forward's layers are pipelined");
   XSaveBits sb;
-  constexpr int KS = KS1 + KS2;
-  constexpr int kCps = (8 + KS - 1) / KS;                 // epilogue chunks issued per k-step
-  constexpr int kS7 = 7 / kCps;                           // k-step that issues chunk 7
-  constexpr bool kLate = kS7 + 2 < KS;                    // stage reads / stores spread over the k-steps behind chunk 7 (else: in place)
-  constexpr bool kStageIo = STAGE && !NERF_F32X_HACK_SAVE_NOSTORE;
-  XStaged stg;
-  XPendingS pend;
   float keep[2] = {0.0f, 0.0f};
-  static_for<NM>([&](auto M) {
-    constexpr int m = decltype(M)::value;
-    XPendingS cur;
+  gemmx_layer_train<KS1, KS2, NM, F0, ROWB, NERF_F32X_STAGE && !NERF_F32X_HACK_SAVE_NOSTORE>(r, B1h, B1l, B2h, B2l, st, tile_rows,
+    [&](XPending& cur, auto M) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) cur.al[i] = 0.0f;
-    {
-      lds_cf32x4* b = reinterpret_cast<lds_cf32x4*>(bias_lds_h + m * 16);
+      for (int i = 0; i < 16; ++i) cur.al[i] = 0.0f;
+      lds_cf32x4* b = reinterpret_cast<lds_cf32x4*>(bias_lds_h + decltype(M)::value * 16);
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4) {
         const f32x4 bq = b[q4];
         cur.ah[4 * q4 + 0] = bq.x; cur.ah[4 * q4 + 1] = bq.y; cur.ah[4 * q4 + 2] = bq.z; cur.ah[4 * q4 + 3] = bq.w;
       }
-    }
-    static_for<KS>([&](auto S) {
-      constexpr int s = decltype(S)::value;
-      constexpr int fi = (F0 + m * KS + s) & (kXStepsPerChunk - 1);
-      xfrag_read(r, fi + kXPfDist, r.pfh[(fi + kXPfDist) % kXPf], r.pfl[(fi + kXPfDist) % kXPf]);
-      __builtin_amdgcn_sched_barrier(0x406);
-      const h8 wh = r.pfh[fi % kXPf], wl = r.pfl[fi % kXPf];
-      const h8 bh = s < KS1 ? B1h[s] : B2h[s - KS1], bl = s < KS1 ? B1l[s] : B2l[s - KS1];
-      cur.ah = mfma16(wh, bh, cur.ah);
-      cur.al = mfma16(wh, bl, cur.al);
-      cur.al = mfma16(wl, bh, cur.al);
-      if constexpr (m > 0) {
-        static_for<kCps>([&](auto C) {
-          constexpr int q = s * kCps + decltype(C)::value;
-          if constexpr (q < 8) xepilogue_chunk_s<RELU, BITS, STAGE, m - 1, q>(pend, OUTh, OUTl, row, st, keep, sb);
-        });
-        if constexpr (kStageIo) {
-          if constexpr (kLate) {
-            if constexpr (s == kS7) xstage_get<0>(st, stg);
-            if constexpr (s == kS7 + 1) { xstage_store<ROWB, 0>(st, stg, tile_rows, m - 1); xstage_get<1>(st, stg); }
-            if constexpr (s == kS7 + 2) xstage_store<ROWB, 1>(st, stg, tile_rows, m - 1);
-          } else if constexpr (s == kS7) xstage_flush<ROWB>(st, tile_rows, m - 1);
-        }
-      }
-      xring_step(r, fi);
+    },
+    [&](XPending& t, auto MM, auto Q) {
+      xepilogue_chunk_s<RELU, BITS, decltype(MM)::value, decltype(Q)::value>(t, OUTh, OUTl, row, st, keep, sb);
     });
-    pend = cur;
-  });
-  static_for<8>([&](auto Q) { xepilogue_chunk_s<RELU, BITS, STAGE, NM - 1, decltype(Q)::value>(pend, OUTh, OUTl, row, st, keep, sb); });
-  if constexpr (kStageIo) xstage_flush<ROWB>(st, tile_rows, NM - 1);
   if constexpr (BITS) {                                     // one coalesced 1-KiB block per wave and layer
     u32x4 w; w.x = sb.w0; w.y = sb.w1; w.z = sb.w2; w.w = sb.w3;
     *reinterpret_cast<u32x4*>(bits_dst) = w;
   }
-}
-
-// (compiler-scheduled form) one out-tile: returns  bias + sum_s W(m, s) . B[s]  in fp32 (hi and lo accumulators combined)
-template <int KS1, int KS2, int F0, bool WITH_BIAS>
-__device__ __forceinline__ f32x16 gemmx_tile_c(XRing& r, int m, const h8* B1h, const h8* B1l, const h8* B2h,
-                                             const h8* B2l, lds_cfloat* bias_lds_h) {
-  constexpr int KS = KS1 + KS2;
-  constexpr int kBiasAt = KS > 6 ? KS - 6 : 0;
-  f32x16 ah, al;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { ah[i] = 0.0f; al[i] = 0.0f; }
-  f32x4 bq0, bq1, bq2, bq3;
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    const int fi = (F0 + m * KS + s) & (kXStepsPerChunk - 1);
-    xfrag_read(r, fi + kXPfDist, r.pfh[(fi + kXPfDist) % kXPf], r.pfl[(fi + kXPfDist) % kXPf]);
-    if (WITH_BIAS && s == kBiasAt) {
-      lds_cf32x4* b = reinterpret_cast<lds_cf32x4*>(bias_lds_h + m * 16);
-      bq0 = b[0]; bq1 = b[1]; bq2 = b[2]; bq3 = b[3];
-    }
-    __builtin_amdgcn_sched_barrier(0x406);
-    const h8 wh = r.pfh[fi % kXPf], wl = r.pfl[fi % kXPf];
-    const h8 bh = s < KS1 ? B1h[s] : B2h[s - KS1], bl = s < KS1 ? B1l[s] : B2l[s - KS1];
-    ah = mfma16(wh, bh, ah);
-    al = mfma16(wh, bl, al);
-    al = mfma16(wl, bh, al);
-    xring_step(r, fi);
-  }
-  f32x16 out;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) out[i] = fmaf(al[i], kXLoInv, ah[i]);
-  if (WITH_BIAS) {
-    out[0] += bq0.x; out[1] += bq0.y; out[2] += bq0.z; out[3] += bq0.w;
-    out[4] += bq1.x; out[5] += bq1.y; out[6] += bq1.z; out[7] += bq1.w;
-    out[8] += bq2.x; out[9] += bq2.y; out[10] += bq2.z; out[11] += bq2.w;
-    out[12] += bq3.x; out[13] += bq3.y; out[14] += bq3.z; out[15] += bq3.w;
-  }
-  return out;
 }
 
 // DENS: stop after the sigma head (MlpArgs::density_only), raw = (0, 0, 0, sigma).  DSKIP (MlpArgs::skip_dead_colour): a wave whose 32
@@ -716,24 +649,24 @@ void nerf_mlp_f32x_kernel(MlpArgs a) {
     if constexpr (!SAVE) make_dpe();
 
     const long long P = a.n_points;
-    constexpr bool kPipe = true;
-    constexpr bool kSres = true;                   // (inference epilogue: xepilogue_chunk -- scalar residual in every instance)
-    // Every layer stores its rows through the LDS transpose (XRowStage, as the backward chain does; NERF_F32X_STAGE=0: each lane
-    // stores its own quads).  With the MFMA accumulators in VGPRs (this unit's XFLAGS) all instances fit the register file
-    // (12 bytes of scratch, touched at the tile boundaries); with hipcc's default allocation only the density-only instance did
-    // (LAB_NOTEBOOK.md A9, A10).
-    constexpr bool kStageTrunk = NERF_F32X_STAGE != 0, kStageColour = NERF_F32X_STAGE != 0;
+    // feature (8 chunks) + views and rgb (5 chunks): what a wave without density lets go by unread
+    constexpr int kColourChunks = 2 * (nerf::kF16Frags - nerf::kF16FragFeat) / nerf::kF16ChunkFrags;
+    static_assert(2 * (nerf::kF16Frags - nerf::kF16FragFeat) % nerf::kF16ChunkFrags == 0, "the colour branch is whole chunks");
     h8 Xh[16], Xl[16], Yh[16], Yl[16];
     f32x16 sig, col;
     bool dead_wave = false;                                                                    // (wave-uniform)
     if constexpr (SAVE) {
-      // training forward (gemmx_layer_s): every layer's post-activation output also goes to the row-major activation store, the
-      // ReLU sign bits of this wave's 32 points to block (tile * 4 + wave) of the TrainSave bit blocks
+      // training forward (gemmx_layer_s): every layer's post-activation output also goes to the row-major activation store through
+      // the LDS transpose (XRowStage, as in the backward chain; NERF_F32X_STAGE=0: each lane stores its own quads), the ReLU sign bits of this wave's 32 points to block
+      // (tile * 4 + wave) of the TrainSave bit blocks.  With the MFMA accumulators in VGPRs (this unit's XFLAGS) all instances fit
+      // the register file (12 bytes of scratch, touched at the tile boundaries); with hipcc's default allocation only the
+      // density-only instance did (LAB_NOTEBOOK.md A9, A10).
       const long long tile32 = tile * kXWaves + wave;
       // addresses as (wave-uniform 64-bit base) + (32-bit lane offset): the stores take the base from SGPRs
       const unsigned lrow = (unsigned)(wave * 32 + (lane & 31));          // this lane's row inside the 128-point tile
       // (the opaque redefinition of the lane offset keeps the compiler from computing all eleven row pointers at the top of the
       // tile and spilling them: each is built where its layer starts)
+      // this lane's row (+ 4 h) in a row-major region: what NERF_F32X_STAGE=0 stores to
       auto srow = [&](long long off, int width) -> float* {
         const char* base = reinterpret_cast<const char*>(a.save + off + tile * (long long)(kXTilePts * width));
         unsigned lo = lrow;
@@ -750,16 +683,16 @@ void nerf_mlp_f32x_kernel(MlpArgs a) {
         asm volatile("" : "+v"(lo));
         return reinterpret_cast<unsigned*>(const_cast<char*>(base) + lo * 16u);
       };
-      gemmx_layer_s<4, 0, 8, 0, kPipe, true, true, kStageTrunk, 1024>(r, bias_h, PEh, PEl, PEh, PEl, Xh, Xl, srow(TrainSave::off_h(P, 0), 256), st, trow(TrainSave::off_h(P, 0), 256), bdst(0));   // L0
+      gemmx_layer_s<4, 0, 8, 0, true, true, 1024>(r, bias_h, PEh, PEl, PEh, PEl, Xh, Xl, srow(TrainSave::off_h(P, 0), 256), st, trow(TrainSave::off_h(P, 0), 256), bdst(0));   // L0
 #pragma unroll 1
       for (int it = 0; it < 2; ++it) {                                                          // L1..L4
-        gemmx_layer_s<16, 0, 8, 0, kPipe, true, true, kStageTrunk, 1024>(r, bias_h + (1 + 2 * it) * 256, Xh, Xl, Xh, Xl, Yh, Yl, srow(TrainSave::off_h(P, 1 + 2 * it), 256), st, trow(TrainSave::off_h(P, 1 + 2 * it), 256), bdst(1 + 2 * it));
-        gemmx_layer_s<16, 0, 8, 0, kPipe, true, true, kStageTrunk, 1024>(r, bias_h + (2 + 2 * it) * 256, Yh, Yl, Yh, Yl, Xh, Xl, srow(TrainSave::off_h(P, 2 + 2 * it), 256), st, trow(TrainSave::off_h(P, 2 + 2 * it), 256), bdst(2 + 2 * it));
+        gemmx_layer_s<16, 0, 8, 0, true, true, 1024>(r, bias_h + (1 + 2 * it) * 256, Xh, Xl, Xh, Xl, Yh, Yl, srow(TrainSave::off_h(P, 1 + 2 * it), 256), st, trow(TrainSave::off_h(P, 1 + 2 * it), 256), bdst(1 + 2 * it));
+        gemmx_layer_s<16, 0, 8, 0, true, true, 1024>(r, bias_h + (2 + 2 * it) * 256, Yh, Yl, Yh, Yl, Xh, Xl, srow(TrainSave::off_h(P, 2 + 2 * it), 256), st, trow(TrainSave::off_h(P, 2 + 2 * it), 256), bdst(2 + 2 * it));
       }
-      gemmx_layer_s<4, 16, 8, 0, kPipe, true, true, kStageTrunk, 1024>(r, bias_h + 5 * 256, PEh, PEl, Xh, Xl, Yh, Yl, srow(TrainSave::off_h(P, 5), 256), st, trow(TrainSave::off_h(P, 5), 256), bdst(5));   // L5 = skip(PE) + hidden
-      gemmx_layer_s<16, 0, 8, 0, kPipe, true, true, kStageTrunk, 1024>(r, bias_h + 6 * 256, Yh, Yl, Yh, Yl, Xh, Xl, srow(TrainSave::off_h(P, 6), 256), st, trow(TrainSave::off_h(P, 6), 256), bdst(6));     // L6
-      gemmx_layer_s<16, 0, 8, 0, kPipe, true, true, kStageTrunk, 1024>(r, bias_h + 7 * 256, Xh, Xl, Xh, Xl, Yh, Yl, srow(TrainSave::off_h(P, 7), 256), st, trow(TrainSave::off_h(P, 7), 256), bdst(7));     // L7 -> Y = relu(h7)
-      sig = gemmx_tile_c<16, 0, 0, false>(r, 0, Yh, Yl, Yh, Yl, bias_h);                        // sigma head (ahead of the feature layer)
+      gemmx_layer_s<4, 16, 8, 0, true, true, 1024>(r, bias_h + 5 * 256, PEh, PEl, Xh, Xl, Yh, Yl, srow(TrainSave::off_h(P, 5), 256), st, trow(TrainSave::off_h(P, 5), 256), bdst(5));   // L5 = skip(PE) + hidden
+      gemmx_layer_s<16, 0, 8, 0, true, true, 1024>(r, bias_h + 6 * 256, Yh, Yl, Yh, Yl, Xh, Xl, srow(TrainSave::off_h(P, 6), 256), st, trow(TrainSave::off_h(P, 6), 256), bdst(6));     // L6
+      gemmx_layer_s<16, 0, 8, 0, true, true, 1024>(r, bias_h + 7 * 256, Xh, Xl, Xh, Xl, Yh, Yl, srow(TrainSave::off_h(P, 7), 256), st, trow(TrainSave::off_h(P, 7), 256), bdst(7));     // L7 -> Y = relu(h7)
+      sig = gemmx_tile<16, 0, 0, false>(r, Yh, Yl, Yh, Yl);                                     // sigma head (ahead of the feature layer)
       if constexpr (DSKIP)
         dead_wave = __builtin_amdgcn_readfirstlane((int)(__builtin_amdgcn_ballot_w64(
                         h == 0 && valid && sig[0] + hb_s > 0.0f) != 0ull)) == 0;
@@ -771,32 +704,31 @@ void nerf_mlp_f32x_kernel(MlpArgs a) {
       } else if (dead_wave) {
         // no density in this wave's 32 points: compositing's adjoint hands the tile a zero gradient, the backward works on live
         // tiles only -- feature / views rows and the views bits are not stored, the colour branch's 13 chunks go by unread
-        constexpr int kColourChunks = 2 * (nerf::kF16Frags - nerf::kF16FragFeat) / nerf::kF16ChunkFrags;
         skip_chunks(kColourChunks);
 #pragma unroll
         for (int i = 0; i < kXPfDist; ++i) xfrag_read(r, i, r.pfh[i], r.pfl[i]);
 #pragma unroll
         for (int i = 0; i < 16; ++i) col[i] = 0.0f;
       } else {
-        gemmx_layer_s<16, 0, 8, 0, kPipe, false, false, kStageColour, 1024>(r, bias_h + 8 * 256, Yh, Yl, Yh, Yl, Xh, Xl, srow(TrainSave::off_f(P), 256), st, trow(TrainSave::off_f(P), 256), nullptr);       // feature
+        gemmx_layer_s<16, 0, 8, 0, false, false, 1024>(r, bias_h + 8 * 256, Yh, Yl, Yh, Yl, Xh, Xl, srow(TrainSave::off_f(P), 256), st, trow(TrainSave::off_f(P), 256), nullptr);       // feature
         make_dpe();
         h8 Vh[8], Vl[8];
-        gemmx_layer_s<16, 2, 4, 0, kPipe, true, true, kStageColour, 512>(r, bias_views_h, Xh, Xl, DPEh, DPEl, Vh, Vl, srow(TrainSave::off_hv(P), 128), st, trow(TrainSave::off_hv(P), 128), bdst(8));       // views
-        col = gemmx_tile_c<8, 0, 8, false>(r, 0, Vh, Vl, Vh, Vl, bias_h);                         // rgb head
+        gemmx_layer_s<16, 2, 4, 0, true, true, 512>(r, bias_views_h, Xh, Xl, DPEh, DPEl, Vh, Vl, srow(TrainSave::off_hv(P), 128), st, trow(TrainSave::off_hv(P), 128), bdst(8));       // views
+        col = gemmx_tile<8, 0, 8, false>(r, Vh, Vl, Vh, Vl);                                      // rgb head
       }
     } else {
     // inference: LDS reads by inline asm with counted waits.  Entering a tile, every asm read issued so far has landed (the drains at
     // the end of the previous tile's branches / before the loop) and nb holds the bias of (L0, out-tile 0).
-    gemmx_layer<4, 0, 8, 0, kPipe, true, kSres>(r, nb, bias_h, bias_h + 256, PEh, PEl, PEh, PEl, Xh, Xl, true, nullptr, h);   // L0
+    gemmx_layer<4, 0, 8, 0, true>(r, nb, bias_h, bias_h + 256, PEh, PEl, PEh, PEl, Xh, Xl, true);   // L0
 #pragma unroll 1
     for (int it = 0; it < 2; ++it) {                                                          // L1..L4
-      gemmx_layer<16, 0, 8, 0, kPipe, true, kSres>(r, nb, bias_h + (1 + 2 * it) * 256, bias_h + (2 + 2 * it) * 256, Xh, Xl, Xh, Xl, Yh, Yl, true, nullptr, h);
-      gemmx_layer<16, 0, 8, 0, kPipe, true, kSres>(r, nb, bias_h + (2 + 2 * it) * 256, bias_h + (3 + 2 * it) * 256, Yh, Yl, Yh, Yl, Xh, Xl, true, nullptr, h);
+      gemmx_layer<16, 0, 8, 0, true>(r, nb, bias_h + (1 + 2 * it) * 256, bias_h + (2 + 2 * it) * 256, Xh, Xl, Xh, Xl, Yh, Yl, true);
+      gemmx_layer<16, 0, 8, 0, true>(r, nb, bias_h + (2 + 2 * it) * 256, bias_h + (3 + 2 * it) * 256, Yh, Yl, Yh, Yl, Xh, Xl, true);
     }
-    gemmx_layer<4, 16, 8, 0, kPipe, true, kSres>(r, nb, bias_h + 5 * 256, bias_h + 6 * 256, PEh, PEl, Xh, Xl, Yh, Yl, true, nullptr, h);   // L5 = skip(PE) + hidden
-    gemmx_layer<16, 0, 8, 0, kPipe, true, kSres>(r, nb, bias_h + 6 * 256, bias_h + 7 * 256, Yh, Yl, Yh, Yl, Xh, Xl, true, nullptr, h);     // L6
-    gemmx_layer<16, 0, 8, 0, kPipe, !DENS, kSres>(r, nb, bias_h + 7 * 256, bias_h + 8 * 256, Xh, Xl, Xh, Xl, Yh, Yl, true, nullptr, h);    // L7 -> Y = relu(h7); requests the feature layer's first bias
-    sig = gemmx_tile<16, 0, 0, false>(r, 0, Yh, Yl, Yh, Yl, bias_h);                           // sigma head (ahead of the feature layer)
+    gemmx_layer<4, 16, 8, 0, true>(r, nb, bias_h + 5 * 256, bias_h + 6 * 256, PEh, PEl, Xh, Xl, Yh, Yl, true);   // L5 = skip(PE) + hidden
+    gemmx_layer<16, 0, 8, 0, true>(r, nb, bias_h + 6 * 256, bias_h + 7 * 256, Yh, Yl, Yh, Yl, Xh, Xl, true);     // L6
+    gemmx_layer<16, 0, 8, 0, !DENS>(r, nb, bias_h + 7 * 256, bias_h + 8 * 256, Xh, Xl, Xh, Xl, Yh, Yl, true);    // L7 -> Y = relu(h7); requests the feature layer's first bias
+    sig = gemmx_tile<16, 0, 0, true>(r, Yh, Yl, Yh, Yl);                                       // sigma head (ahead of the feature layer)
     if constexpr (DSKIP) {
       // in front of the wave-uniform branch everything in flight lands (the three pairs the sigma head prefetched past its end, the
       // feature layer's first bias quad): the compiler copies registers on the edges into the two arms (one exposed LDS round
@@ -811,10 +743,8 @@ void nerf_mlp_f32x_kernel(MlpArgs a) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) col[i] = 0.0f;
     } else if (dead_wave) {
-      // no density in this wave's 32 points: feature (8 chunks) + views and rgb (5 chunks) go by unread (what the sigma head
-      // prefetched past its end has landed above and is simply dropped)
-      constexpr int kColourChunks = 2 * (nerf::kF16Frags - nerf::kF16FragFeat) / nerf::kF16ChunkFrags;
-      static_assert(2 * (nerf::kF16Frags - nerf::kF16FragFeat) % nerf::kF16ChunkFrags == 0, "the colour branch is whole chunks");
+      // no density in this wave's 32 points: the colour branch's chunks go by unread (what the sigma head prefetched past its
+      // end has landed above and is simply dropped)
 #pragma unroll 1
       for (int c = 0; c < kColourChunks; ++c) {
 #pragma unroll
@@ -825,10 +755,10 @@ void nerf_mlp_f32x_kernel(MlpArgs a) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) col[i] = 0.0f;
     } else {
-      gemmx_layer<16, 0, 8, 0, kPipe, true, kSres>(r, nb, bias_h + 8 * 256, bias_views_h, Yh, Yl, Yh, Yl, Xh, Xl, false, nullptr, h);       // feature
+      gemmx_layer<16, 0, 8, 0, true>(r, nb, bias_h + 8 * 256, bias_views_h, Yh, Yl, Yh, Yl, Xh, Xl, false);       // feature
       h8 Vh[8], Vl[8];
-      gemmx_layer<16, 2, 4, 0, kPipe, false, kSres>(r, nb, bias_views_h, bias_views_h, Xh, Xl, DPEh, DPEl, Vh, Vl, true, nullptr, h);      // views
-      col = gemmx_tile<8, 0, 8, false>(r, 0, Vh, Vl, Vh, Vl, bias_h);                             // rgb head
+      gemmx_layer<16, 2, 4, 0, false>(r, nb, bias_views_h, bias_views_h, Xh, Xl, DPEh, DPEl, Vh, Vl, true);      // views
+      col = gemmx_tile<8, 0, 8, true>(r, Vh, Vl, Vh, Vl);                                        // rgb head
     }
     // end of the tile on every path: request the bias of the next tile's (L0, out-tile 0) and let EVERYTHING in flight land -- the
     // pairs prefetched for the next tile's first steps stay valid in their registers, and no asm read is in flight across the

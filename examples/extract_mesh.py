@@ -1,0 +1,50 @@
+#!/usr/bin/env python3
+"""Checkpoint -> PLY: the density of the fine network on an N^3 grid and its iso-surface as a triangle mesh (what the
+reference's src/utils/mesh_utils.py extract_mesh is for).
+
+    python examples/extract_mesh.py --ckpt tests/golden/trained_ckpt.pth --n 256 --out mesh.ply
+    python examples/extract_mesh.py --level 32                 # the reference's cfg.level; default: picked from the grid
+    python examples/extract_mesh.py --precision f16            # fp16 density (PSNR-level accuracy)
+
+Needs an MI355X and the built library (python -c "import __graft_entry__ as g; g.build()")."""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import nerf_replication_amd as nerf  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ckpt", default=os.path.join(REPO, "tests", "golden", "trained_ckpt.pth"))
+    ap.add_argument("--n", type=int, default=256, help="grid points per axis (cfg.resolution of the reference)")
+    ap.add_argument("--level", type=float, default=None, help="iso level of the pre-ReLU density; default: midway between the "
+                    "grid's median and maximum")
+    ap.add_argument("--bbox", type=float, nargs=6, default=[-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], metavar="V", help="min xyz, max xyz")
+    ap.add_argument("--precision", default="f32", choices=["f32", "f16", "f32x"])
+    ap.add_argument("--out", default="mesh.ply")
+    args = ap.parse_args()
+
+    net = nerf.Network()
+    nerf.load_network(net, args.ckpt)
+    net = net.cuda().eval()
+    net.precision = args.precision
+    level = args.level
+    if level is None:
+        grid = nerf.density_grid(net, args.bbox, args.n)
+        level = 0.5 * (grid.median().item() + grid.max().item())
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    vertices, faces = nerf.extract_mesh(net, level, args.bbox, args.out, args.n)
+    torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    print("{}^3 grid, {}, level {:.4g}: {} vertices, {} triangles in {:.1f} ms (grid + surface + file)".format(
+        args.n, args.precision, level, vertices.shape[0], faces.shape[0], dt * 1e3))
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()

@@ -385,6 +385,33 @@ int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d,
                                        float weights_threshold, void* workspace, int64_t workspace_bytes,
                                        float* rgb, float* depth, void* stream);
 
+/* ---- iso-surface of a scalar grid (the reference's src/utils/mesh_utils.py:8-46, extract_mesh: density on a grid, then a
+ * triangle mesh of {f = level}; DESIGN section 2.8 lists where this departs from that function) -------------------------------
+ * The value of grid point (i, j, k) is field[((i*ny + j)*nz + k) * stride]: stride 1 for a dense [nx,ny,nz] grid, 4 to read
+ * sigma out of a `raw` [P,4] buffer (pass raw + 3).  Marching tetrahedra over the six-tetrahedra (Kuhn) split of every cell:
+ * tetrahedron q of cell c is {c, c + e_a, c + e_a + e_b, c + (1,1,1)} for the q-th permutation (a, b, c) of the axes in
+ * lexicographic order.  A point is inside iff f > level (NaN is not); an edge (p, p + e), e in {0,1}^3 \ 0, carries a vertex
+ * iff its endpoints differ, at x_p + tau (x_{p+e} - x_p) per axis with tau = (level - f_p) / (f_{p+e} - f_p) and
+ * x = fp32(origin + idx * step) (that in float64, rounded once); every other operation is separately rounded fp32.  Vertex ids
+ * ascend with (owner id p, edge type 4 e_x + 2 e_y + e_z), triangles with (cell id, tetrahedron, triangle); (v1 - v0) x (v2 - v0)
+ * points from inside to outside.  The mesh is indexed (one vertex per crossed edge), closed and consistently oriented wherever
+ * the level set stays off the grid boundary, and open where the boundary cuts it.  No atomics: two runs write the same bytes.
+ *
+ * Two phases, because the sizes depend on the data: nerf_isosurface_count fills `workspace`
+ * (nerf_isosurface_workspace_bytes: 4 bytes per point + 8 per 256 points) and writes counts[0] = V, counts[1] = T; the
+ * caller reads them, allocates vertices [V,3] and triangles [T,3] (or more rows: the rest is left untouched) and calls
+ * nerf_isosurface_emit with the same field, sizes, level and workspace.  Emit takes the topology from the workspace alone, so it
+ * writes inside those rows whatever the field holds by then.  A grid of more than 2^31 - 1 points is refused
+ * (NERF_ERR_INVALID_ARG; workspace_bytes returns -1); V or T beyond int32 cannot be known when the call is enqueued: counts is
+ * then (-1, -1) and emit must not follow.  Any dimension of 0 or 1 means no cells: success, counts = (0, 0), emit is a no-op.
+ * origin[3] and step[3] are HOST arrays. */
+int64_t nerf_isosurface_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int32_t nerf_isosurface_count(const float* field, int64_t stride, int32_t nx, int32_t ny, int32_t nz, float level,
+                              void* workspace, int32_t* counts, void* stream);
+int32_t nerf_isosurface_emit(const float* field, int64_t stride, int32_t nx, int32_t ny, int32_t nz, float level,
+                             const double origin[3], const double step[3], const void* workspace,
+                             float* vertices, int32_t* triangles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,10 +22,12 @@ _LAZY = {
     "generate_rays": ".rays",
     "Evaluator": ".evaluator",
     "load_network": ".checkpoint", "load_model": ".checkpoint", "save_model": ".checkpoint",
+    "density_grid": ".mesh", "isosurface": ".mesh", "write_ply": ".mesh", "extract_mesh": ".mesh",
 }
-_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist")
+_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh")
 
-__all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model"]
+__all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model",
+           "density_grid", "isosurface", "write_ply", "extract_mesh"]
 
 
 def __getattr__(name):

@@ -95,6 +95,11 @@ _PROTOS = {
     "nerf_mlp_backward_masked_workspace_bytes": (_c.c_int64, [_c.c_int64]),
     "nerf_mlp_backward_masked": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F, _F, _F,
                                               _c.POINTER(_c.c_void_p), _c.c_int32, _F, _c.c_void_p]),
+    # iso-surface of a scalar grid (mesh.py)
+    "nerf_isosurface_workspace_bytes": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32]),
+    "nerf_isosurface_count": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float, _F, _F, _c.c_void_p]),
+    "nerf_isosurface_emit": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float,
+                                          _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _F, _F, _F, _c.c_void_p]),
 }
 EXPORTS = tuple(_PROTOS)
 

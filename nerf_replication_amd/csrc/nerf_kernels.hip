@@ -2389,3 +2389,6 @@ int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d,
 }
 
 }  // extern "C"
+
+// ---- geometry out of a trained network: nerf_isosurface_* (kernels and entries)
+#include "nerf_isosurface.hip.inc"

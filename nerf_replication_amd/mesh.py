@@ -1,0 +1,242 @@
+"""Geometry out of a trained network: the density on a grid and its iso-surface as a triangle mesh, the role of the
+reference's src/utils/mesh_utils.py:8-46 (`extract_mesh(queryfn, level, bbox, output_path, N)`; cfg.level = 32.0,
+cfg.resolution = 256, src/config/config.py:10-12).
+
+The density comes from the fused MLP kernels (a grid line is a ray: nerf_mlp_forward_rays_density), the surface from the
+nerf_isosurface_* kernels (marching tetrahedra, include/nerf_mi355x.h); DESIGN.md section 2.8 has the definitions and where
+this departs from the reference's function, which is not runnable as written.  No CPU fallback: every number comes out of a
+HIP kernel, torch only moves tensors.
+"""
+import ctypes
+import numbers
+
+import numpy as np
+import torch
+
+from . import _lib
+from .network import Network, _reference_cfg
+
+DEFAULT_LEVEL = 32.0
+DEFAULT_RESOLUTION = 256
+CHUNK_POINTS = 1 << 22          # default bound on the points per MLP launch of density_grid: 64 MiB of [P,4] fp32 scratch
+QUERY_BATCH = 1 << 20           # points per call of a callable queryfn
+
+
+def _shape3(N):
+    dims = (N, N, N) if isinstance(N, numbers.Integral) and not isinstance(N, bool) else N
+    try:
+        dims = tuple(dims)
+    except TypeError:
+        raise ValueError(f"N must be an int or (nx, ny, nz), got {N!r}") from None
+    if len(dims) != 3 or not all(isinstance(n, numbers.Integral) and not isinstance(n, bool) and n >= 1 for n in dims):
+        raise ValueError(f"N must be an int or (nx, ny, nz) with every size >= 1, got {N!r}")
+    dims = tuple(int(n) for n in dims)
+    if dims[0] * dims[1] * dims[2] > 2 ** 31 - 1:
+        raise ValueError(f"a grid of {dims} has more than 2^31 - 1 points")
+    return dims
+
+
+def _bbox(bbox):
+    try:
+        b = np.asarray(bbox, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"bbox must hold 6 numbers (min xyz, max xyz), got {bbox!r}") from None
+    if b.shape != (6,) or not np.isfinite(b).all():
+        raise ValueError(f"bbox must hold 6 finite numbers (min xyz, max xyz), got {bbox!r}")
+    b = b.reshape(2, 3)
+    if (b[1] < b[0]).any():
+        raise ValueError(f"bbox max is below min: {bbox!r}")
+    return b
+
+
+def grid_axes(bbox, N):
+    """The float64 coordinates of the grid points per axis: min + i * (max - min) / (n - 1) (min alone for n == 1), and the
+    (origin, step) of the same grid."""
+    dims, b = _shape3(N), _bbox(bbox)
+    axes = [b[0, a] + np.arange(n, dtype=np.float64) * (b[1, a] - b[0, a]) / (n - 1) if n > 1 else np.array([b[0, a]])
+            for a, n in enumerate(dims)]
+    step = tuple(float((b[1, a] - b[0, a]) / (n - 1)) if n > 1 else 0.0 for a, n in enumerate(dims))
+    return axes, tuple(float(v) for v in b[0]), step
+
+
+def density_grid(net, bbox, N, model="fine", chunk_lines=None):
+    """Pre-ReLU sigma of `net`'s coarse ("") or fine model on a grid: device tensor [nx, ny, nz] fp32.
+
+    bbox: 6 numbers (min xyz, max xyz); N: an int or (nx, ny, nz), each >= 1.  Index i of an axis is at min + i (max - min) /
+    (n - 1), evaluated in float64 and rounded once to fp32.  The grid lines along z are rays, rays_o = (x_i, y_j, 0), rays_d =
+    (0, 0, 1), and the fp32 z coordinates are their shared depth table, so the kernels' o + d t is those coordinates exactly and
+    the whole grid runs at the density-only rate of nerf_mlp_forward_rays_density, in every precision of net.precision.
+    The nx * ny lines go through in chunks of `chunk_lines` (default: as many as keep a launch at 2^22 points, i.e. the [P,4]
+    fp32 scratch at 64 MiB); the grid does not depend on the chunking."""
+    if not isinstance(net, Network):
+        raise TypeError("density_grid needs a nerf_replication_amd Network")
+    if model not in ("", "fine"):
+        raise ValueError(f'model must be "" (coarse) or "fine", got {model!r}')
+    axes, _, _ = grid_axes(bbox, N)
+    nx, ny, nz = (len(a) for a in axes)
+    if chunk_lines is None:
+        chunk_lines = max(1, CHUNK_POINTS // nz)
+    if not isinstance(chunk_lines, numbers.Integral) or chunk_lines < 1:
+        raise ValueError(f"chunk_lines must be a positive int, got {chunk_lines!r}")
+    lib = _lib.load()
+    packed = net.packed(model)                     # raises for a network on the CPU
+    dev = packed.device
+    prec = _lib.PRECISIONS[net.precision]
+    x, y, z = (torch.from_numpy(a.astype(np.float32)) for a in axes)
+    lines = nx * ny
+    rays_o = torch.zeros((lines, 3), dtype=torch.float32)
+    rays_o[:, 0] = x[:, None].expand(nx, ny).reshape(-1)
+    rays_o[:, 1] = y[None, :].expand(nx, ny).reshape(-1)
+    rays_d = torch.zeros((lines, 3), dtype=torch.float32)
+    rays_d[:, 2] = 1.0
+    rays_o, rays_d, t = rays_o.to(dev), rays_d.to(dev), z.to(dev)
+    grid = torch.empty((lines, nz), dtype=torch.float32, device=dev)
+    raw = torch.empty((min(lines, int(chunk_lines)), nz, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = _lib.stream_of(dev)
+        for l0 in range(0, lines, int(chunk_lines)):
+            l1 = min(lines, l0 + int(chunk_lines))
+            _lib.check(lib.nerf_mlp_forward_rays_density(_lib.ptr(rays_o[l0:l1]), _lib.ptr(rays_d[l0:l1]), _lib.ptr(t), 0, l1 - l0,
+                                                         nz, packed.data_ptr(), _lib.ptr(raw), prec, st),
+                       "nerf_mlp_forward_rays_density")
+            grid[l0:l1].copy_(raw[:l1 - l0, :, 3])
+    return grid.view(nx, ny, nz)
+
+
+def _field_layout(field):
+    """(tensor whose first element is grid point (0,0,0), element stride, shape) of a dense [nx,ny,nz] grid or a [...,4] raw view."""
+    if not isinstance(field, torch.Tensor):
+        raise TypeError("field must be a torch tensor")
+    if field.dtype != torch.float32:
+        raise ValueError("field must be float32")
+    if field.dim() == 4 and field.shape[3] == 4:              # raw [nx,ny,nz,4]: sigma is channel 3
+        field = field[..., 3]
+    if field.dim() != 3:
+        raise ValueError("field must be [nx, ny, nz], or a raw buffer [nx, ny, nz, 4]")
+    nx, ny, nz = (int(n) for n in field.shape)
+    _shape3((max(nx, 1), max(ny, 1), max(nz, 1)))
+    s = 1
+    if min(nx, ny, nz) >= 2:                                    # (smaller grids have no cells: nothing is read)
+        s = field.stride(2)
+        if s < 1 or field.stride() != (ny * nz * s, nz * s, s):
+            raise ValueError("field must be a dense grid or a channel of a contiguous [...,4] buffer (k fastest)")
+    return field, int(s), (nx, ny, nz)
+
+
+def _vec3(v, name):
+    try:
+        out = tuple(float(x) for x in v)
+    except TypeError:
+        raise ValueError(f"{name} must hold 3 numbers, got {v!r}") from None
+    if len(out) != 3 or not all(np.isfinite(out)):
+        raise ValueError(f"{name} must hold 3 finite numbers, got {v!r}")
+    return out
+
+
+def isosurface(field, level, origin, step):
+    """Iso-surface {field = level} of a scalar grid as an indexed triangle mesh on the device:
+    (vertices [V,3] float32, faces [T,3] int32).
+
+    field: device tensor [nx,ny,nz] fp32 (point (i,j,k) at origin + (i,j,k) * step), or a raw buffer [nx,ny,nz,4] / any view of
+    one of its channels (read in place with a stride of 4).  Marching tetrahedra on the Kuhn split of every cell; inside is
+    field > level, faces wind so that their normal points from inside to outside; closed and manifold wherever the surface stays
+    off the grid boundary, open where the boundary cuts it; repeatable to the byte (include/nerf_mi355x.h, nerf_isosurface_*).
+    One host synchronisation: the two counts are read between the counting and the emitting pass."""
+    field, stride, (nx, ny, nz) = _field_layout(field)
+    level = float(level)
+    origin, step = _vec3(origin, "origin"), _vec3(step, "step")
+    lib = _lib.load()
+    if not field.is_cuda:
+        raise _lib.NerfLibraryError("isosurface needs the field on a GPU (cuda) device; there is no CPU fallback")
+    dev = field.device
+    vertices = torch.empty((0, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((0, 3), dtype=torch.int32, device=dev)
+    if min(nx, ny, nz) < 2:
+        return vertices, faces
+    nbytes = int(lib.nerf_isosurface_workspace_bytes(nx, ny, nz))
+    if nbytes < 0:
+        raise _lib.NerfLibraryError(f"nerf_isosurface_workspace_bytes refused a grid of {nx} x {ny} x {nz} points")
+    with torch.cuda.device(dev):
+        st = _lib.stream_of(dev)
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        _lib.check(lib.nerf_isosurface_count(field.data_ptr(), stride, nx, ny, nz, level, workspace.data_ptr(), counts.data_ptr(),
+                                             st), "nerf_isosurface_count")
+        n_v, n_t = (int(c) for c in counts.cpu())
+        if n_v < 0 or n_t < 0:
+            raise _lib.NerfLibraryError("isosurface: more than 2^31 - 1 vertices or triangles")
+        if n_t == 0:
+            return vertices, faces
+        vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+        c3 = ctypes.c_double * 3
+        _lib.check(lib.nerf_isosurface_emit(field.data_ptr(), stride, nx, ny, nz, level, c3(*origin), c3(*step), workspace.data_ptr(),
+                                            vertices.data_ptr(), faces.data_ptr(), st), "nerf_isosurface_emit")
+    return vertices, faces
+
+
+def write_ply(path, vertices, faces):
+    """Binary little-endian PLY: `float` x y z per vertex, `uchar int` index lists per face."""
+    v = np.ascontiguousarray(torch.as_tensor(vertices).detach().cpu().numpy(), dtype="<f4")
+    f = np.ascontiguousarray(torch.as_tensor(faces).detach().cpu().numpy(), dtype="<i4")
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError("write_ply needs vertices [V,3] and faces [T,3]")
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
+    rec = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    rec["n"], rec["i"] = 3, f
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+        out.write(rec.tobytes())
+
+
+def _query_grid(queryfn, axes, device):
+    """The reference's protocol: queryfn(xyz [n,3] on the GPU) -> [..., 0] is the density; explicit grid points in batches."""
+    nx, ny, nz = (len(a) for a in axes)
+    x, y, z = (torch.from_numpy(a.astype(np.float32)).to(device) for a in axes)
+    grid = torch.empty(nx * ny * nz, dtype=torch.float32, device=device)
+    per = max(1, QUERY_BATCH // (ny * nz))                      # whole x-slabs per call
+    with torch.no_grad():
+        for i0 in range(0, nx, per):
+            i1 = min(nx, i0 + per)
+            pts = torch.stack(torch.meshgrid(x[i0:i1], y, z, indexing="ij"), dim=-1).reshape(-1, 3)
+            out = queryfn(pts)
+            sigma = out[..., 0].reshape(-1).to(torch.float32)
+            if sigma.numel() != pts.shape[0]:
+                raise ValueError(f"queryfn returned {sigma.numel()} densities for {pts.shape[0]} points")
+            grid[i0 * ny * nz:i1 * ny * nz] = sigma
+    return grid.view(nx, ny, nz)
+
+
+def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None):
+    """The reference's extract_mesh (src/utils/mesh_utils.py:8-46), same argument order: density on an N^3 grid over `bbox`, the
+    iso-surface at `level`, written to `output_path` as a PLY; returns (vertices, faces) on the device.
+
+    queryfn: a Network (the fast path: density_grid on its fine model), or a callable taking xyz [n,3] on the GPU whose
+    result's [..., 0] is the density (the reference's protocol; evaluated on explicit grid points in batches).  level and N
+    default to cfg.level / cfg.resolution inside the reference, else 32.0 / 256.  Arguments are checked before any GPU work."""
+    cfg = _reference_cfg()
+    if level is None:
+        level = getattr(cfg, "level", DEFAULT_LEVEL) if cfg is not None else DEFAULT_LEVEL
+    if N is None:
+        N = getattr(cfg, "resolution", DEFAULT_RESOLUTION) if cfg is not None else DEFAULT_RESOLUTION
+    if not isinstance(queryfn, Network) and not callable(queryfn):
+        raise TypeError("queryfn must be a Network or a callable xyz [n,3] -> [..., 0] density")
+    if isinstance(level, bool) or not isinstance(level, numbers.Real) or not np.isfinite(level):
+        raise ValueError(f"level must be a finite number, got {level!r}")
+    if bbox is None:
+        raise ValueError("bbox is required: 6 numbers (min xyz, max xyz)")
+    if not isinstance(output_path, (str, bytes)) and not hasattr(output_path, "__fspath__"):
+        raise TypeError(f"output_path must be a path, got {output_path!r}")
+    axes, origin, step = grid_axes(bbox, N)
+    if isinstance(queryfn, Network):
+        grid = density_grid(queryfn, bbox, N, model="fine")
+    else:
+        if not torch.cuda.is_available():
+            raise _lib.NerfLibraryError("extract_mesh needs a GPU; there is no CPU fallback")
+        grid = _query_grid(queryfn, axes, torch.device("cuda", torch.cuda.current_device()))
+    vertices, faces = isosurface(grid, level, origin, step)
+    write_ply(output_path, vertices, faces)
+    return vertices, faces

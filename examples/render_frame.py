@@ -4,6 +4,7 @@ per test view: rays from the camera pose, Renderer.render, evaluator image dump)
 
     python examples/render_frame.py --ckpt tests/golden/synthetic_ckpt.pth --angle 40 --res 400 --out /tmp/nerf_out
     python examples/render_frame.py --precision f16      # BASELINE config 5 arithmetic
+    python examples/render_frame.py --occupancy 128      # skip empty space: occupancy grid of 128^3 points on [-2,2]^3
 
 Needs an MI355X and the built library (python -c "import __graft_entry__ as g; g.build()")."""
 import argparse
@@ -37,6 +38,8 @@ def main():
     ap.add_argument("--angle", type=float, default=40.0)
     ap.add_argument("--res", type=int, default=800)
     ap.add_argument("--precision", default="f32", choices=["f32", "f16", "f32x"])
+    ap.add_argument("--occupancy", type=int, default=0, metavar="N",
+                    help="cull empty space with an occupancy grid of N^3 points on [-2,2]^3, dilate 1 (f32 / f32x; 0: off)")
     ap.add_argument("--out", default="nerf_out")
     args = ap.parse_args()
 
@@ -45,6 +48,11 @@ def main():
     net = net.cuda().eval()
     net.precision = args.precision
     renderer = nerf.Renderer(net)
+    if args.occupancy:
+        renderer.occupancy = nerf.OccupancyGrid.from_network(net, [-2, -2, -2, 2, 2, 2], args.occupancy, dilate=1)
+        renderer.occupancy_stats = []
+        print("occupancy grid {0}^3: {1:.1%} of the coarse and {2:.1%} of the fine cells occupied".format(
+            args.occupancy, renderer.occupancy.occupied_fraction(""), renderer.occupancy.occupied_fraction("fine")))
     rays_o, rays_d = nerf.generate_rays(camera_pose(args.angle), args.res, args.res, 0.6911112070083618, "cuda")
     with torch.no_grad():
         renderer.render({"rays_o": rays_o[None, :1024], "rays_d": rays_d[None, :1024]})       # warm-up (weight packing)
@@ -52,6 +60,9 @@ def main():
         rgb, depth = renderer.render({"rays_o": rays_o[None], "rays_d": rays_d[None]})
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
     print("{}x{} frame, {}: {:.1f} ms, {:.0f} rays/s".format(args.res, args.res, args.precision, dt * 1e3, rays_o.shape[0] / dt))
+    if args.occupancy:
+        evaluated, total = renderer.occupancy_stats[-1]
+        print("evaluated {:.1%} of the coarse and {:.1%} of the fine points".format(evaluated[0].item() / total[0], evaluated[1].item() / total[1]))
     ev = nerf.Evaluator(result_dir=args.out)                    # writes <out>/images/view000_{pred,gt}.png
     ev.evaluate((rgb, depth), {"colors": rgb[None], "H": torch.tensor(args.res), "W": torch.tensor(args.res), "id": torch.tensor(0)})
     print("wrote", os.path.join(args.out, "images", "view000_pred.png"))

@@ -412,6 +412,50 @@ int32_t nerf_isosurface_emit(const float* field, int64_t stride, int32_t nx, int
                              const double origin[3], const double step[3], const void* workspace,
                              float* vertices, int32_t* triangles, void* stream);
 
+/* ---- occupancy grid: skip the samples of a render that lie in empty space ------------------------------
+ * Grid: nx x ny x nz points (every size >= 2, at most 2^31 - 1 points), values laid out as for nerf_isosurface_* (stride 1, or 4
+ * for the sigma column of a `raw` buffer).  Cell (i, j, k) lies between the points i..i+1, j..j+1, k..k+1; its id is
+ * (i*(ny-1) + j)*(nz-1) + k.  A cell is OCCUPIED iff some grid point in [i-r, i+1+r] x [j-r, j+1+r] x [k-r, k+1+r] (clipped to the
+ * grid, r = dilate >= 0) has f > level or is NaN (NaN counts as occupied, the conservative side; nerf_isosurface_*'s "inside"
+ * goes the other way).  Bitfield: bit (id & 31) of the 32-bit word (id >> 5); nerf_occupancy_words gives the number of words,
+ * rounded up to an even number (-1 for a refused size); the unused tail bits are 0.  No atomics: two builds write the same bytes.
+ *
+ * Lookup of a sample (ray r, depth t): x = fadd(o, fmul(d, t)) -- the forward kernels' two roundings -- and per axis
+ * c = floorf(fmul(fsub(x, box_min), inv_step)), with box_min = fp32(min) and inv_step = fp32((n - 1) / (max - min)) computed in
+ * float64 by the caller and rounded once.  The sample is KEPT if any c is outside [0, n-2] (outside the box counts as occupied),
+ * if anything is NaN, or if the cell's bit is set.  nerf_occupancy_mark writes
+ *     valid[r, s] = (and_with_existing ? valid[r, s] != 0 : 1) & keep(sample)
+ * for t = tvals[r * t_ray_stride + s] (stride 0: one shared table); n_rays * n_samples <= 2^31 - 1.  dims, box_min and inv_step
+ * are HOST arrays. */
+int64_t nerf_occupancy_words(int32_t nx, int32_t ny, int32_t nz);
+int32_t nerf_occupancy_build(const float* field, int64_t stride, int32_t nx, int32_t ny, int32_t nz, float level,
+                             int32_t dilate, uint32_t* bits, void* stream);
+int32_t nerf_occupancy_mark(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
+                            int64_t n_rays, int32_t n_samples, const uint32_t* bits, const int32_t dims[3],
+                            const float box_min[3], const float inv_step[3], int32_t and_with_existing, uint8_t* valid,
+                            void* stream);
+
+/* nerf_render_forward with occupancy culling.  occ_coarse / occ_fine (each nullable) are the bitfields looked up for the 64
+ * coarse depths / the 192 merged depths (normally built from the coarse / the fine model's density; occ_fine is ignored when
+ * n_importance is 0).  A pass with a bitfield evaluates the kept samples only (device-side compaction, as fast_sampling does) and
+ * leaves raw = 0 at the others; nerf_sample_fine and nerf_composite both apply relu(sigma), so rgb and depth are bit-equal to
+ * nerf_render_forward's wherever every culled sample has a true sigma <= 0.  With fast_sampling the fine list is the sampler's
+ * mask AND the lookup.  With both bitfields NULL it launches what nerf_render_forward launches (dims, box_min, inv_step are then
+ * not read).  `evaluated`: nullable DEVICE int64[2], zeroed by the call, receives the numbers of coarse and of fine points
+ * evaluated, summed over the ray blocks (one single-thread launch per pass and block).  NERF_PREC_F32 / NERF_PREC_F32X only
+ * (NERF_ERR_UNSUPPORTED otherwise: the fp16 far-plane guard is not defined on a culled list); n_rays * 192 <= 2^31 - 1
+ * (NERF_ERR_INVALID_ARG).  workspace: nerf_render_occupancy_workspace_bytes (nerf_render_workspace_bytes with the fine mask and
+ * list whatever fast_sampling is, plus the coarse mask [n,64] and its list). */
+int64_t nerf_render_occupancy_workspace_bytes(int64_t n_rays, int32_t n_importance, int32_t fast_sampling);
+int32_t nerf_render_forward_occupancy(const float* rays_o, const float* rays_d, int64_t n_rays,
+                                      const void* packed_coarse, const void* packed_fine,
+                                      const float* t_coarse, const float* u, int32_t n_importance,
+                                      int32_t white_bkgd, int32_t precision, int32_t fast_sampling,
+                                      float weights_threshold, const uint32_t* occ_coarse, const uint32_t* occ_fine,
+                                      const int32_t dims[3], const float box_min[3], const float inv_step[3],
+                                      int64_t* evaluated, void* workspace, int64_t workspace_bytes,
+                                      float* rgb, float* depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,11 +23,12 @@ _LAZY = {
     "Evaluator": ".evaluator",
     "load_network": ".checkpoint", "load_model": ".checkpoint", "save_model": ".checkpoint",
     "density_grid": ".mesh", "isosurface": ".mesh", "write_ply": ".mesh", "extract_mesh": ".mesh",
+    "OccupancyGrid": ".occupancy",
 }
-_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh")
+_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy")
 
 __all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model",
-           "density_grid", "isosurface", "write_ply", "extract_mesh"]
+           "density_grid", "isosurface", "write_ply", "extract_mesh", "OccupancyGrid"]
 
 
 def __getattr__(name):

@@ -100,6 +100,15 @@ _PROTOS = {
     "nerf_isosurface_count": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float, _F, _F, _c.c_void_p]),
     "nerf_isosurface_emit": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float,
                                           _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _F, _F, _F, _c.c_void_p]),
+    # occupancy grid (occupancy.py)
+    "nerf_occupancy_words": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32]),
+    "nerf_occupancy_build": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float, _c.c_int32, _F, _c.c_void_p]),
+    "nerf_occupancy_mark": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _c.POINTER(_c.c_int32),
+                                         _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _c.c_int32, _F, _c.c_void_p]),
+    "nerf_render_occupancy_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int32, _c.c_int32]),
+    "nerf_render_forward_occupancy": (_c.c_int32, [_F, _F, _c.c_int64, _F, _F, _F, _F, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                                   _c.c_float, _F, _F, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_float),
+                                                   _c.POINTER(_c.c_float), _F, _F, _c.c_int64, _F, _F, _c.c_void_p]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -2234,11 +2234,13 @@ static int64_t render_block_rays() {
 
 // The workspace of one block of `n_rays` rays, carved in this order, every piece 256-byte aligned.  index / count: with fast_sampling
 // the compacted ids of the valid merged samples and their number, otherwise the last-sample ids of the fp16 far-plane guard and
-// their number.  t_jit: the jittered coarse depths [n,64] of a stochastic render.
+// their number.  t_jit: the jittered coarse depths [n,64] of a stochastic render.  occupancy (nerf_render_forward_occupancy): the
+// fine pass may be listed without fast_sampling too, and the coarse pass gets a mask [n,64] and an id list of its own behind.
 struct RenderWorkspace {
   float* raw_c; float* t_sorted = nullptr; float* raw_f = nullptr; uint8_t* valid = nullptr; int* index; int* count; float* t_jit = nullptr;
+  uint8_t* valid_c = nullptr; int* index_c = nullptr;
   int64_t bytes;
-  RenderWorkspace(void* base, int64_t n_rays, int32_t n_importance, int32_t fast_sampling, bool stochastic) {
+  RenderWorkspace(void* base, int64_t n_rays, int32_t n_importance, int32_t fast_sampling, bool stochastic, bool occupancy = false) {
     uintptr_t p = (uintptr_t)base;
     auto take = [&p](int64_t n) { void* q = (void*)p; p += (uintptr_t)align256(n); return q; };
     const int64_t S = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
@@ -2247,7 +2249,7 @@ struct RenderWorkspace {
       t_sorted = (float*)take(n_rays * S * (int64_t)sizeof(float));
       raw_f = (float*)take(n_rays * S * 4 * (int64_t)sizeof(float));
     }
-    if (n_importance && fast_sampling) {
+    if (n_importance && (fast_sampling || occupancy)) {
       valid = (uint8_t*)take(n_rays * S);
       index = (int*)take(n_rays * S * (int64_t)sizeof(int));
     } else {
@@ -2255,14 +2257,29 @@ struct RenderWorkspace {
     }
     count = (int*)take(sizeof(int));
     if (stochastic) t_jit = (float*)take(n_rays * NERF_N_SAMPLES * (int64_t)sizeof(float));
+    if (occupancy) {
+      valid_c = (uint8_t*)take(n_rays * NERF_N_SAMPLES);
+      index_c = (int*)take(n_rays * NERF_N_SAMPLES * (int64_t)sizeof(int));
+    }
     bytes = (int64_t)(p - (uintptr_t)base);
   }
 };
-static int64_t render_workspace_bytes(int64_t n_rays_frame, int32_t n_importance, int32_t fast_sampling, bool stochastic) {
+static int64_t render_workspace_bytes(int64_t n_rays_frame, int32_t n_importance, int32_t fast_sampling, bool stochastic,
+                                      bool occupancy = false) {
   if (n_rays_frame < 0) return -1;
   const int64_t n_rays = n_rays_frame < render_block_rays() ? n_rays_frame : render_block_rays();
-  return RenderWorkspace(nullptr, n_rays, n_importance, fast_sampling, stochastic).bytes;
+  return RenderWorkspace(nullptr, n_rays, n_importance, fast_sampling, stochastic, occupancy).bytes;
 }
+
+// Occupancy culling of a frame (nerf_render_forward_occupancy, csrc/nerf_occupancy.hip.inc): the bitfields of the coarse and the fine
+// pass (each nullable: that pass runs on every sample), the lookup frame, and the DEVICE int64[2] that takes the numbers of coarse /
+// fine points evaluated (nullable).
+struct RenderOccupancy {
+  const uint32_t* coarse; const uint32_t* fine;
+  int32_t dims[3]; float box_min[3], inv_step[3];
+  long long* evaluated;
+};
+static int occupancy_tally(const int* count, long long all, long long* evaluated, hipStream_t st);
 int64_t nerf_render_workspace_bytes(int64_t n_rays_frame, int32_t n_importance, int32_t fast_sampling) {
   return render_workspace_bytes(n_rays_frame, n_importance, fast_sampling, false);
 }
@@ -2276,7 +2293,8 @@ int64_t nerf_render_stochastic_workspace_bytes(int64_t n_rays_frame, int32_t n_i
 static int32_t render_frame(const char* entry, const float* rays_o, const float* rays_d, int64_t n_rays, const void* packed_coarse,
                             const void* packed_fine, const float* t_coarse, const float* u, const float* jitter, const float* u_rays,
                             bool stochastic, int32_t n_importance, int32_t white_bkgd, int32_t precision, int32_t fast_sampling,
-                            float weights_threshold, void* workspace, int64_t workspace_bytes, float* rgb, float* depth, void* stream) {
+                            float weights_threshold, void* workspace, int64_t workspace_bytes, float* rgb, float* depth, void* stream,
+                            const RenderOccupancy* occ = nullptr) {
   if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s: bad size", entry);
   if (n_importance != 0 && n_importance != NERF_N_IMPORTANCE)
     return fail(NERF_ERR_INVALID_ARG, "%s: n_importance must be 0 or 128", entry);
@@ -2284,7 +2302,7 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
   if (!rays_o || !rays_d || !packed_coarse || !t_coarse || !rgb || !depth || !workspace ||
       (n_importance && (!packed_fine || !u)))
     return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
-  if (workspace_bytes < render_workspace_bytes(n_rays, n_importance, fast_sampling, stochastic))
+  if (workspace_bytes < render_workspace_bytes(n_rays, n_importance, fast_sampling, stochastic, occ != nullptr))
     return fail(NERF_ERR_WORKSPACE, "%s: workspace too small", entry);
   // the masked fine pass addresses (ray, sample) pairs by 32-bit ids (nerf_compact_kernel, MlpArgs::index)
   const int64_t S = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
@@ -2299,7 +2317,20 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
     const float* d = rays_d + 3 * r0;
     float* rgb_b = rgb + 3 * r0;
     float* depth_b = depth + r0;
-    const RenderWorkspace w(workspace, nb, n_importance, fast_sampling, stochastic);
+    const RenderWorkspace w(workspace, nb, n_importance, fast_sampling, stochastic, occ != nullptr);
+    // A pass on a list: the ids with valid != 0 compacted (unordered: `raw` is written by id), `raw` zero-filled -- an unlisted
+    // sample keeps raw = 0, and compositing and the sampler both apply relu(sigma), so that is exact wherever its true sigma <= 0
+    auto list_pass = [&](const uint8_t* valid, long long np, int* index, float* raw) -> int {
+      if (hipMemsetAsync(w.count, 0, sizeof(int), st) != hipSuccess ||
+          hipMemsetAsync(raw, 0, (size_t)(np * 4 * (int64_t)sizeof(float)), st) != hipSuccess)
+        return fail(NERF_ERR_HIP, "%s: memset failed", entry);
+      hipLaunchKernelGGL(nerf_compact_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, valid, np, index, w.count);
+      return check_launch("nerf_compact_kernel");
+    };
+    // (occupancy) the points a pass evaluated: the length of its list, or all of them
+    auto tally = [&](int pass, bool listed, long long all) -> int {
+      return occ && occ->evaluated ? occupancy_tally(listed ? w.count : nullptr, all, occ->evaluated + pass, st) : NERF_OK;
+    };
     const float* tc = t_coarse;
     int64_t tcs = 0;
     int rc;
@@ -2311,7 +2342,17 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
     // hierarchical render: the coarse network only places the fine samples -- nothing but its sigma is read
     // (volume_renderer.py:335; the returned rgb/depth come from the fine outputs, :414-437), so the coarse pass stops after
     // the sigma head.  With n_importance == 0 the coarse outputs ARE the frame and the full network runs.
-    rc = forward_rays(entry, o, d, tc, tcs, nb, NERF_N_SAMPLES, packed_coarse, w.raw_c, false, nullptr, n_importance != 0, false, precision, stream);
+    const bool cull_c = occ && occ->coarse;
+    if (cull_c) {
+      rc = nerf_occupancy_mark(o, d, tc, tcs, nb, NERF_N_SAMPLES, occ->coarse, occ->dims, occ->box_min, occ->inv_step, 0, w.valid_c, stream);
+      if (rc) return rc;
+      rc = list_pass(w.valid_c, nb * NERF_N_SAMPLES, w.index_c, w.raw_c);
+      if (rc) return rc;
+    }
+    rc = forward_rays(entry, o, d, tc, tcs, nb, NERF_N_SAMPLES, packed_coarse, w.raw_c, false, nullptr, n_importance != 0, false, precision, stream,
+                      cull_c ? w.index_c : nullptr, cull_c ? w.count : nullptr);
+    if (rc) return rc;
+    rc = tally(0, cull_c, nb * NERF_N_SAMPLES);
     if (rc) return rc;
     // fp16 far-plane guard.  The last sample of a ray has delta = 1e10 (volume_renderer.py:85-86): ANY sigma > 0 there makes alpha = 1, so
     // an fp16 rounding that flips the sign of a sigma within 1e-2 of zero turns a background ray into a full far-plane hit (round 2:
@@ -2337,9 +2378,16 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
     }
     // fast_sampling, ESS/ERT (volume_renderer.py:359-369, network.py:207-253): the sampler also marks the valid merged samples
     rc = nerf_sample_fine_rays(w.raw_c, tc, tcs, u_rays ? u_rays + NERF_N_IMPORTANCE * r0 : u, u_rays ? NERF_N_IMPORTANCE : 0, nb, w.t_sorted,
-                               nullptr, w.valid, fast_sampling ? weights_threshold : 0.f, fast_sampling ? 0.45f : 0.f, stream);
+                               nullptr, fast_sampling ? w.valid : nullptr, fast_sampling ? weights_threshold : 0.f, fast_sampling ? 0.45f : 0.f,
+                               stream);
     if (rc) return rc;
-    if (!fast_sampling) {
+    const bool cull_f = occ && occ->fine;
+    if (cull_f) {
+      rc = nerf_occupancy_mark(o, d, w.t_sorted, S, nb, (int32_t)S, occ->fine, occ->dims, occ->box_min, occ->inv_step, fast_sampling != 0, w.valid,
+                               stream);
+      if (rc) return rc;
+    }
+    if (!fast_sampling && !cull_f) {
       rc = forward_rays(entry, o, d, w.t_sorted, S, nb, (int32_t)S, packed_fine, w.raw_f, false, nullptr, false, true, precision, stream);
       if (rc) return rc;
       if (guard) {
@@ -2348,17 +2396,14 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
       }
     } else {
       // only the valid merged samples go through the fine network; the others keep raw = 0 (sigma 0 -> weight 0)
-      if (hipMemsetAsync(w.count, 0, sizeof(int), st) != hipSuccess ||
-          hipMemsetAsync(w.raw_f, 0, (size_t)(nb * S * 4 * (int64_t)sizeof(float)), st) != hipSuccess)
-        return fail(NERF_ERR_HIP, "%s: memset failed", entry);
-      const long long np = nb * S;
-      hipLaunchKernelGGL(nerf_compact_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, w.valid, np, w.index, w.count);
-      rc = check_launch("nerf_compact_kernel");
+      rc = list_pass(w.valid, nb * S, w.index, w.raw_f);
       if (rc) return rc;
       rc = forward_rays(entry, o, d, w.t_sorted, S, nb, (int32_t)S, packed_fine, w.raw_f, false, nullptr, false, true, precision, stream,
                         w.index, w.count);
       if (rc) return rc;
     }
+    rc = tally(1, fast_sampling || cull_f, nb * S);
+    if (rc) return rc;
     rc = nerf_composite(w.raw_f, w.t_sorted, S, nb, (int32_t)S, white_bkgd, rgb_b, depth_b, nullptr, stream);
     if (rc) return rc;
   }
@@ -2392,3 +2437,5 @@ int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d,
 
 // ---- geometry out of a trained network: nerf_isosurface_* (kernels and entries)
 #include "nerf_isosurface.hip.inc"
+// ---- occupancy grid: nerf_occupancy_* and nerf_render_forward_occupancy
+#include "nerf_occupancy.hip.inc"

@@ -55,6 +55,10 @@ class Renderer:
         self.device = None
         self._tables = {}
         self._workspace = None
+        # occupancy culling (occupancy.py): an OccupancyGrid, or None = every sample is evaluated.  occupancy_stats: set it
+        # to a list to receive (evaluated [2] int64 device tensor, (64 n, 192 n)) per culled render() call, without a host sync
+        self.occupancy = None
+        self.occupancy_stats = None
         if self.N_samples != _lib.N_SAMPLES or self.N_importance not in (0, _lib.N_IMPORTANCE):
             raise ValueError("HIP renderer is built for N_samples=64 and N_importance in {0,128}")
 
@@ -89,6 +93,29 @@ class Renderer:
             ws = self._workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         return ws
 
+    def _check_occupancy(self, dev, rays_grad, stochastic):
+        """What a render with self.occupancy set refuses, before anything is launched."""
+        grid = self.occupancy
+        if not isinstance(grid, _sibling("occupancy").OccupancyGrid):
+            raise TypeError("Renderer.occupancy must be an OccupancyGrid or None")
+        if rays_grad or (torch.is_grad_enabled() and getattr(self.net, "training", False) and
+                         any(p.requires_grad for p in self.net.parameters())):
+            raise NotImplementedError("occupancy culling is an inference feature: no training step and no ray gradients with "
+                                      "Renderer.occupancy set")
+        if stochastic:
+            raise NotImplementedError(f"occupancy culling is not built for stochastic sampling (task={self.task!r}, "
+                                      f"perturb={bool(self.perturb)})")
+        prec_name = getattr(self.net, "precision", "f32")
+        if _lib.PRECISIONS[prec_name] not in (_lib.PREC_F32, _lib.PREC_F32X):
+            raise NotImplementedError(f"occupancy culling runs in precision 'f32' or 'f32x', not {prec_name!r}: the fp16 far-plane "
+                                      "guard is not defined on a culled list")
+        if grid.device != dev:
+            raise ValueError(f"the occupancy grid is on {grid.device}, the rays on {dev}")
+        for model in ("", "fine") if self.N_importance > 0 else ("",):
+            if grid.stale(self.net, model):
+                raise RuntimeError("the network's parameters changed since the occupancy grid was built from them: rebuild the "
+                                   "grid (OccupancyGrid.from_network), or set Renderer.occupancy = None")
+
     def render(self, batch):
         rays_o, rays_d = batch["rays_o"], batch["rays_d"]
         self.device = dev = rays_o.device
@@ -107,6 +134,8 @@ class Renderer:
             # refused before any launch: never a detached result for rays that require grad
             _sibling("training").check_differentiable(self, True)
         stochastic = bool(self.perturb) or self.task == "train"
+        if self.occupancy is not None:
+            self._check_occupancy(dev, rays_grad, stochastic)          # refused before any launch
         if stochastic:
             prec_name = getattr(self.net, "precision", "f32")
             if _lib.PRECISIONS[prec_name] not in (_lib.PREC_F32, _lib.PREC_F32X):
@@ -145,9 +174,26 @@ class Renderer:
                     _lib.ptr(rgb), _lib.ptr(depth), _lib.stream_of(dev)), "nerf_render_forward_stochastic")
             return rgb, depth
         fast = int(bool(self.fast_sampling) and self.N_importance > 0)
+        prec = _lib.PRECISIONS[getattr(self.net, "precision", "f32")]
+        if self.occupancy is not None:
+            grid = self.occupancy
+            occ_c, occ_f = grid.bits[""], grid.bits["fine"] if self.N_importance > 0 else None
+            dims, box_min, inv_step = grid.lookup_args()
+            ws = self._get_workspace(int(lib.nerf_render_occupancy_workspace_bytes(n, self.N_importance, fast)), dev)
+            evaluated = torch.empty(2, dtype=torch.int64, device=dev) if self.occupancy_stats is not None else None
+            with torch.cuda.device(dev):
+                _lib.check(lib.nerf_render_forward_occupancy(
+                    _lib.ptr(o), _lib.ptr(d), n, pk_c.data_ptr(), pk_f.data_ptr() if pk_f is not None else None,
+                    _lib.ptr(t_c), _lib.ptr(u),
+                    int(self.N_importance), int(bool(self.white_bkgd)), prec, fast, float(self.weights_threshold),
+                    _lib.ptr(occ_c, torch.int32), _lib.ptr(occ_f, torch.int32), dims, box_min, inv_step,
+                    evaluated.data_ptr() if evaluated is not None else None, ws.data_ptr(), ws.numel(),
+                    _lib.ptr(rgb), _lib.ptr(depth), _lib.stream_of(dev)), "nerf_render_forward_occupancy")
+            if evaluated is not None:
+                self.occupancy_stats.append((evaluated.clone(), (_lib.N_SAMPLES * n, (_lib.N_SAMPLES + _lib.N_IMPORTANCE) * n)))
+            return rgb, depth
         nbytes = int(lib.nerf_render_workspace_bytes(n, self.N_importance, fast))
         ws = self._get_workspace(nbytes, dev)
-        prec = _lib.PRECISIONS[getattr(self.net, "precision", "f32")]
         with torch.cuda.device(dev):
             _lib.check(lib.nerf_render_forward(
                 _lib.ptr(o), _lib.ptr(d), n, pk_c.data_ptr(), pk_f.data_ptr() if pk_f is not None else None,

@@ -13,6 +13,20 @@
  * default stream); calls only enqueue work (no host sync, graph-capturable); the return value is 0
  * on success or a negative nerf_status, never an exception; nerf_last_error() gives the message of
  * the calling thread's last failure.  n_rays == 0 is a successful no-op everywhere.
+ *
+ * Library-owned memory: an fp32 forward launch that evaluates colours (everything but the density-only
+ * entries) enqueues one extra small kernel in front of the MLP kernel -- it folds feature_linear into
+ * the views layer for the weights of that launch -- and uses about 150 KB of device memory that the
+ * library owns: one buffer per (device, stream), allocated on the stream's first such launch (the
+ * only call that may allocate and wait; never during a capture: make one eager call on a stream
+ * before capturing on it), kept until the process ends, at most 64 per process.  Stream order
+ * protects the buffer, so: (1) a graph captured from these calls holds its capture stream's buffer --
+ * replay it where its replays are ordered with that stream's other fp32 launches and with each
+ * other (two graphs captured on one stream must not replay concurrently); (2) host threads may share
+ * a stream (the fold and the MLP kernel are enqueued under one lock), but a handle that names a
+ * different stream in every thread (hipStreamPerThread) is not supported: pass real stream handles;
+ * (3) that first, allocating call must not run while another thread captures in global mode
+ * (hipMalloc would invalidate that capture).
  */
 #ifndef NERF_MI355X_H
 #define NERF_MI355X_H

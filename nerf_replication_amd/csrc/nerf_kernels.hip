@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <math.h>
+#include <mutex>
 
 #include "../../include/nerf_mi355x.h"
 #include "nerf_layout.h"
@@ -121,6 +122,64 @@ __global__ void nerf_pack_kernel(PackArgs a) {
   else if (i < kOffHeadBias) v = pack_w_rgb_value(a.p[P_WR], (int)(i - kOffWRgb));
   else v = pack_head_bias_value(a, (int)(i - kOffHeadBias));
   a.out[i] = v;
+}
+
+// ------------------------------------------------------------------------------------ fold (nerf_layout.h kFold*)
+// feature_linear folded into the views layer, from the PACKED fp32 stream (so it sees exactly the weights the MLP kernel of the
+// same launch sees): Wvf = Wv[:, :256] . Wf and bvf = Wv[:, :256] . bf + bv, every element accumulated in float64 (products of
+// two floats are exact there) in one fixed order and rounded once to fp32.  Blocks of 256 threads = 64 outputs x 4 quarters of
+// the 256-term sum (partial sums meet in LDS, combined as (0 + 1) + (2 + 3)):
+//   blocks 0..127    one 1-KiB block (g, j) of Wvf each: thread (lane, part) -> float4 of lane
+//   blocks 128, 129  64 values of bvf each
+//   blocks 130..133  copy of the views layer's direction-part blocks
+// Element m of the inner dimension is feature act_feat(t, r, h) with  t = m >> 5, h = (m >> 2) & 1, r = (m & 3) + 4 ((m & 31) >> 3).
+constexpr int kFoldBlocks = 128 + 2 + 4;
+__global__ __launch_bounds__(256) void nerf_fold_f32_kernel(const float* __restrict__ pk, float* __restrict__ fold) {
+  using namespace nerf;
+  __shared__ double part_sum[4][64][4];
+  const int lane = threadIdx.x & 63, part = threadIdx.x >> 6, b = blockIdx.x;
+  if (b >= 130) {                                   // direction part: 16 blocks of 1 KiB, unchanged
+    const int i = (b - 130) * 256 + threadIdx.x;    // float4 index, < 1024
+    reinterpret_cast<f32x4*>(fold + kFoldOffDir)[i] = reinterpret_cast<const f32x4*>(pk + kOffViewsDir)[i];
+    return;
+  }
+  const bool bias = b >= 128;
+  // the row of Wv this thread's output belongs to: out-tile j, row (lane & 31) of it
+  int j, row, g = 0, h = 0;
+  if (!bias) { j = b & 3; g = b >> 2; h = lane >> 5; row = lane & 31; }
+  else {
+    const int rel = (b - 128) * 64 + lane, o = act_feat((rel & 63) >> 4, rel & 15, rel >> 6);     // [h][t*16 + r] as kOffBiasViews
+    j = o >> 5; row = o & 31;
+  }
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 8
+  for (int mm = 0; mm < 64; ++mm) {
+    const int m = part * 64 + mm;
+    const int mt = m >> 5, mh = (m >> 2) & 1, mg = 4 * mt + ((m & 31) >> 3), mq = m & 3;          // Wv[o][m]: block (mg, j), lane (row, mh), component mq
+    const double wv = (double)pk[kOffViews + (((long long)(mg * 4 + j) * 64 + row + 32 * mh) << 2) + mq];
+    if (!bias) {
+      // Wf[m][k], k = the four features this lane's float4 holds in block (g, .): block (g, m >> 5), lane (m & 31, h)
+      const f32x4 wf = *reinterpret_cast<const f32x4*>(pk + kOffFeat + (((long long)(g * 8 + mt) * 64 + (m & 31) + 32 * h) << 2));
+      acc[0] += wv * (double)wf.x; acc[1] += wv * (double)wf.y; acc[2] += wv * (double)wf.z; acc[3] += wv * (double)wf.w;
+    } else {
+      const int mr = (m & 3) + 4 * ((m & 31) >> 3);
+      acc[0] += wv * (double)pk[kOffBias + 8 * 256 + mh * 128 + mt * 16 + mr];                       // bf[m]
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) part_sum[part][lane][q] = acc[q];
+  __syncthreads();
+  if (part != 0) return;
+  double r[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) r[q] = (part_sum[0][lane][q] + part_sum[1][lane][q]) + (part_sum[2][lane][q] + part_sum[3][lane][q]);
+  if (!bias) {
+    f32x4 v; v.x = (float)r[0]; v.y = (float)r[1]; v.z = (float)r[2]; v.w = (float)r[3];
+    reinterpret_cast<f32x4*>(fold + kFoldOffWvf)[b * 64 + lane] = v;
+  } else {
+    const int rel = (b - 128) * 64 + lane;
+    fold[kFoldOffBias + rel] = (float)(r[0] + (double)pk[kOffBiasViews + rel]);
+  }
 }
 
 // transposed stream for the backward chain (nerf_layout.h kBwd*)
@@ -1431,16 +1490,67 @@ static unsigned persistent_blocks(long long n_points, int wg_pts) {
   return (unsigned)(n_tiles < num_cus() ? n_tiles : num_cus());
 }
 
+// Fold buffers (nerf_layout.h kFold*, 156 672 bytes each): library-owned device memory, one per (device, stream) that has ever
+// made an fp32 forward launch with a colour branch.  A buffer is allocated on that stream's first such launch and kept until the
+// process ends (the runtime releases it; nothing is freed from a static destructor, where the runtime may already be gone).
+// In steady state a launch takes the lock, finds its buffer and enqueues: no allocation, no free, no host wait.  Stream order
+// alone protects a buffer: the fold kernel of launch n + 1 is enqueued behind the MLP kernel of launch n on the same stream,
+// and two streams never share one.  Nothing is cached across launches, so an in-place weight update or a packed buffer
+// re-used at the same address cannot meet a stale fold.  The lock is held across the fold launch AND the MLP launch, so two host
+// threads that launch on one stream cannot interleave as fold A, fold B, MLP A, MLP B.  (A handle that names a different stream
+// per thread -- hipStreamPerThread -- maps those streams onto one buffer: not supported, include/nerf_mi355x.h.)  Bound: kFoldPoolSlots buffers (10 MB) per process; a launch on a
+// further stream fails with NERF_ERR_UNSUPPORTED.  While a stream is capturing nothing is allocated: a capture on a stream
+// without a buffer fails, so a caller makes one eager call on that stream first.
+constexpr int kFoldPoolSlots = 64;
+struct FoldSlot { int device; hipStream_t stream; float* buf; };
+static FoldSlot g_fold_pool[kFoldPoolSlots];
+static int g_fold_pool_used = 0;
+static std::mutex g_fold_pool_lock;
+static int fold_buffer(hipStream_t st, const char* entry, float** out) {      // (the caller holds g_fold_pool_lock)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return fail(NERF_ERR_HIP, "%s: hipGetDevice failed", entry);
+  for (int i = 0; i < g_fold_pool_used; ++i)
+    if (g_fold_pool[i].device == dev && g_fold_pool[i].stream == st) { *out = g_fold_pool[i].buf; return NERF_OK; }
+  if (g_fold_pool_used == kFoldPoolSlots)
+    return fail(NERF_ERR_UNSUPPORTED, "%s: fp32 forward launches on more than 64 (device, stream) pairs in one process", entry);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return fail(NERF_ERR_HIP, "%s: hipStreamIsCapturing failed", entry); }
+  if (cap != hipStreamCaptureStatusNone)
+    return fail(NERF_ERR_UNSUPPORTED, "%s: first fp32 forward launch on a capturing stream: make one eager call on this stream before the capture", entry);
+  float* buf = nullptr;
+  // (the padding behind bvf and the ring slack are zeroed once, in this stream's own order: no arithmetic ever consumes them)
+  if (hipMalloc((void**)&buf, nerf::kFoldFloats * sizeof(float)) != hipSuccess || hipMemsetAsync(buf, 0, nerf::kFoldFloats * sizeof(float), st) != hipSuccess) {
+    (void)hipGetLastError();
+    if (buf) (void)hipFree(buf);
+    return fail(NERF_ERR_HIP, "%s: allocating the fold buffer failed", entry);
+  }
+  g_fold_pool[g_fold_pool_used++] = FoldSlot{dev, st, buf};
+  *out = buf;
+  return NERF_OK;
+}
+
 // every MLP forward launch: the family from (precision, save), the instance from (ray_mode, density_only, skip_dead_colour).
 // `entry`: the public function that was called (error texts)
-static int launch_mlp(const MlpArgs& a, bool ray_mode, bool save, int precision, hipStream_t st, const char* entry) {
+static int launch_mlp(const MlpArgs& a_in, bool ray_mode, bool save, int precision, hipStream_t st, const char* entry) {
   if (!mlp_family(precision, false)) return fail(NERF_ERR_UNSUPPORTED, "%s: precision not built", entry);
-  if (a.n_points <= 0) return NERF_OK;
+  if (a_in.n_points <= 0) return NERF_OK;
+  MlpArgs a = a_in;
   if (a.index && a.n_points > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s: index mode: point ids are int32", entry);
   const MlpFamily* f = mlp_family(precision, save);
   if (!f) return fail(NERF_ERR_UNSUPPORTED, "%s: f32 or f32x only", entry);
   // density_only (ray mode): every precision has an instance that stops after the sigma head
   const MlpKernel k = f->inst[!ray_mode ? 3 : a.density_only ? 0 : a.skip_dead_colour ? 1 : 2];
+  std::unique_lock<std::mutex> hold(g_fold_pool_lock, std::defer_lock);
+  if (precision == NERF_PREC_F32 && !(ray_mode && a.density_only)) {
+    // fp32 with a colour branch: fold feature_linear into the views layer for THIS launch's weights, on this launch's stream;
+    // the pool lock is kept until the MLP kernel is enqueued behind it
+    hold.lock();
+    float* fold = nullptr;
+    if (const int rc = fold_buffer(st, entry, &fold)) return rc;
+    hipLaunchKernelGGL(nerf_fold_f32_kernel, dim3(kFoldBlocks), dim3(256), 0, st, a.packed, fold);
+    if (const int rc = check_launch("nerf_fold_f32_kernel")) return rc;
+    a.fold = fold;
+  }
   if (f->persistent) {
     hipLaunchKernelGGL(k, dim3(persistent_blocks(a.n_points, f->wg_pts)), dim3(f->threads), 0, st, a);
   } else {

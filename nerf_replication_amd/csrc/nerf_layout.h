@@ -72,6 +72,19 @@ constexpr int64_t kOffWRgb = kOffWAlpha + 256;                 // [3][2][64]
 constexpr int64_t kOffHeadBias = kOffWRgb + 384;               // b_rgb[3], b_alpha
 constexpr int64_t kPackedFloats = kOffHeadBias + 4;
 
+// ---- fold buffer (nerf_fold_f32_kernel, library-owned: NOT part of the packed model) ------------
+// feature_linear has no activation behind it (network.py:62), so the views layer's feature part folds into it:
+//   Wvf = Wv[:, :256] . Wf   (128 x 256),   bvf = Wv[:, :256] . bf + bv,
+// both accumulated in float64 from the packed stream and rounded once to fp32.  One linear weight stream covers the whole
+// colour branch of the fp32 kernels: the 32 x 4 blocks of Wvf in the block order of the views layer's feature part, a copy
+// of its 4 x 4 direction-part blocks, then bvf in the [2][64] layout of kOffBiasViews (padded to one 1-KiB LDS-DMA block).
+constexpr int64_t kFoldOffWvf = 0;
+constexpr int64_t kFoldOffDir = kFoldOffWvf + wsize(128, 4);
+constexpr int64_t kFoldOffBias = kFoldOffDir + wsize(16, 4);
+constexpr int64_t kFoldFloats = kFoldOffBias + 256 + 8 * 256;  // + what a compiler-scheduled ring (kPF blocks ahead) reads past the
+                                                               // direction part: 156 672 bytes
+constexpr int64_t kOffViewsDir = kOffViews + wsize(128, 4);    // the direction-part blocks inside the packed stream
+
 // ---- fp16-activation path (nerf_mlp_f16.hip.inc): v_mfma_f32_32x32x16_f16 ---------------------
 // Same idea, K-step = 16 features: after bias+ReLU the 16 accumulator registers of out-tile m are
 // converted pairwise to fp16 and registers 8*s2 .. 8*s2+7 become, unchanged, the 8-element B

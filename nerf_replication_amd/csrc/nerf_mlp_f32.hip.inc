@@ -17,7 +17,8 @@
 // with all of them removed the same MFMA stream runs at 150 TFLOP/s.
 //   registers: 128 (X) + 128 (Y) + 32 (xyz PE, kept for the skip) + 16 (dir PE) + prefetch
 //   -> 1 wave per SIMD with the full 512-entry VGPR+AGPR file; MFMA-bound by construction:
-//   9280 MFMAs x 64 cycles per tile vs ~1.5k VALU instructions.
+//   8256 MFMAs x 64 cycles per tile vs ~1.5k VALU instructions (9280 before feature_linear was folded into the views
+//   layer, nerf_layout.h kFold*; the training forward still issues 9280: it keeps the feature GEMM for the backward pass).
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -75,6 +76,8 @@ struct MlpArgs {
   int skip_dead_colour;    // ray mode, fp32 inference kernel: tiles without a single sigma > 0 stop after the sigma head (DSKIP)
   int density_only;        // ray mode, fp32 kernel: stop after the sigma head (raw = (0,0,0,sigma)): the coarse pass of a
                            // hierarchical render / training step, whose colour is never read (volume_renderer.py:335 / SURVEY F6)
+  const float* fold;       // fp32 kernel with a colour branch: the fold buffer of `packed` (nerf_layout.h kFold*), filled by
+                           // nerf_fold_f32_kernel on the same stream right before this launch (launch_mlp)
 };
 
 // Training forward keeps what the backward pass needs, row-major per point (the layout the weight-
@@ -356,11 +359,13 @@ __device__ __forceinline__ void gemm_tiles(f32x16 (&acc)[NT], const f32x16 (&X)[
 #ifndef NERF_F32_ASM_OVERRUN
 #define NERF_F32_ASM_OVERRUN 0      // 1 re-creates the prefetch past the stream end (a known hazard: self-test of tools/check_asm_stream.py)
 #endif
-    if constexpr (NT == 8 && !LAST && !TAP::kIsTap) {      // (GEMMs with a storing tap: the spread form measured 2.8 % SLOWER)
+    if constexpr (NT == 8 && !TAP::kIsTap && !(LAST && NERF_F32_ASM_OVERRUN)) {      // (GEMMs with a storing tap: the spread form measured 2.8 % SLOWER)
       // Spread form (the 8-out-tile GEMMs = 90 % of the MFMAs): the eight loads of the NEXT group are not issued back to
       // back at the group start -- 8 x ~16 cycles of vector-memory issue during which this wave, alone on its SIMD,
       // feeds the matrix pipe nothing -- but two behind each of the first four MFMAs, where a 64-cycle MFMA covers them.
-      // The group's own blocks were the last loads issued (during the previous group): the wait is vmcnt(0).
+      // The group's own blocks were the last loads issued (during the previous group): the wait is vmcnt(0) -- also in the
+      // LAST GEMM of a stream, whose final group simply issues nothing (layer 7 of the inference instances).
+      const bool kMore = !LAST || g * NT + kPF < kBlocks;      // (g is a constant once the loop is unrolled)
       astream_wait<NT, 0>(as, (g * NT) % kRing);
       __builtin_amdgcn_sched_barrier(0);
       const int t = g >> 2, r0 = (g & 3) * 4;
@@ -371,7 +376,7 @@ __device__ __forceinline__ void gemm_tiles(f32x16 (&acc)[NT], const f32x16 (&X)[
         for (int j = 0; j < NT; ++j) {
           const f32x4 a = as.ring[(g * NT + j) % kRing];
           acc[j] = mfma32(a[q], X[t][r0 + q], acc[j]);
-          if (q == 0 && j < 4) {
+          if (q == 0 && j < 4 && kMore) {
             __builtin_amdgcn_sched_barrier(0);
             if (j == 0) { astream_load_one<0>(as, g * NT + kPF, (g * NT + kPF) % kRing); astream_load_one<1>(as, g * NT + kPF, (g * NT + kPF) % kRing); }
             if (j == 1) { astream_load_one<2>(as, g * NT + kPF, (g * NT + kPF) % kRing); astream_load_one<3>(as, g * NT + kPF, (g * NT + kPF) % kRing); }
@@ -476,15 +481,20 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   const long long ray = pc / a.n_samples;
   const int s = (int)(pc - ray * a.n_samples);
 
-  __shared__ __attribute__((aligned(16))) float tail_smem[NERF_F32_WG_WAVES * kTailFloats];      // 12 KiB per wave of the workgroup
+  // 12 KiB per wave of the workgroup, + 1 KiB behind it for the folded views bias (instances with a colour branch)
+  constexpr int kTailLds = kTailFloats + (DENS ? 0 : 256);
+  __shared__ __attribute__((aligned(16))) float tail_smem[NERF_F32_WG_WAVES * kTailLds];
   typedef __attribute__((address_space(3))) char tail_lds_char;
-  tail_lds_char* const tail_w = (tail_lds_char*)tail_smem + wave * (kTailFloats * 4);
+  tail_lds_char* const tail_w = (tail_lds_char*)tail_smem + wave * (kTailLds * 4);
   {
     const char* src = reinterpret_cast<const char*>(a.packed + kOffBias) + lane * 16;
 #pragma unroll
     for (int i = 0; i < kTailFloats * 4 / 1024; ++i)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024),
                                        (__attribute__((address_space(3))) void*)(tail_w + i * 1024), 16, 0, 0);
+    if constexpr (!DENS)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(a.fold + kFoldOffBias) + lane * 16),
+                                       (__attribute__((address_space(3))) void*)(tail_w + kTailFloats * 4), 16, 0, 0);
   }
   tail_float* const tail = reinterpret_cast<tail_float*>(tail_w);
 
@@ -604,10 +614,10 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   relu8(X, 0);
 
   float sigma = 0.0f;
-  constexpr int kPairs = (DENS || DSKIP) ? 3 : 4;     // density only / dead-colour skip: layer 7 is peeled off below
+  constexpr int kPairs = 3;                           // layer 7 is peeled off below: every instance ends or restarts its stream there
 #pragma unroll 1
   for (int pr = 0; pr < kPairs; ++pr) {
-    // X -> Y : L1, L3, L5, L7   (consumes h0, h2, h4, h6)
+    // X -> Y : L1, L3, L5   (consumes h0, h2, h4)
     load_bias<8>(Y, bias + (1 + 2 * pr) * 256);
     if (pr == 2) {                                     // skip connection: cat([pts63, h]) (network.py:58)
       gemm_tiles<2, 8>(Y, PE, ws);
@@ -615,27 +625,11 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
     gemm_tiles<8, 8, false>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 2 * pr), &sb));
     tap_bits_done(2 * pr);
     relu8(Y, 1 + 2 * pr);
-    if (pr == 3) {                                     // sigma head on relu(h7) (network.py:61)
-      stream_drain(ws);
-      tail_f32x4* wa = reinterpret_cast<tail_f32x4*>(tail + (kOffWAlpha - kOffBias) + h * 128);
-      float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
-#pragma unroll
-      for (int t = 0; t < 8; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 w4 = wa[t * 4 + q];
-          acc0 = fmaf(w4.x, Y[t][4 * q + 0], acc0);
-          acc1 = fmaf(w4.y, Y[t][4 * q + 1], acc1);
-          acc2 = fmaf(w4.z, Y[t][4 * q + 2], acc2);
-          acc3 = fmaf(w4.w, Y[t][4 * q + 3], acc3);
-        }
-      sigma = (acc0 + acc1) + (acc2 + acc3);
-    }
-    // Y -> X : L2, L4, L6, feature (no ReLU on feature, network.py:62)   (consumes h1, h3, h5, h7)
+    // Y -> X : L2, L4, L6   (consumes h1, h3, h5)
     load_bias<8>(X, bias + (2 + 2 * pr) * 256);
     gemm_tiles<8, 8, false>(X, Y, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 1 + 2 * pr), &sb));
     tap_bits_done(1 + 2 * pr);
-    if (pr != 3) relu8(X, 2 + 2 * pr);                  // (no ReLU on the feature vector, network.py:62)
+    relu8(X, 2 + 2 * pr);
   }
 
   if constexpr (DENS) {
@@ -675,30 +669,33 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
     return;
   }
 
+  // Layer 7, peeled off the pair loop, and the sigma head on relu(h7) (network.py:61) on a drained ring.  The packed stream
+  // ends here for the inference instances: the colour branch reads the FOLD buffer (nerf_layout.h kFold*), so this GEMM is
+  // the last of its stream and must not prefetch past it (the compiler reuses ring registers it believes dead, as in DENS).
+  // The training forward still runs the feature layer from the packed stream -- the backward pass needs its row -- so
+  // there layer 7 keeps prefetching and the feature GEMM is the last of the stream.
+  load_bias<8>(Y, bias + 7 * 256);
+  gemm_tiles<8, 8, !SAVE>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 6), &sb));
+  tap_bits_done(6);
+  relu8(Y, 7);
+  stream_drain(ws);
+  {
+    tail_f32x4* wa = reinterpret_cast<tail_f32x4*>(tail + (kOffWAlpha - kOffBias) + h * 128);
+    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 w4 = wa[t * 4 + q];
+        acc0 = fmaf(w4.x, Y[t][4 * q + 0], acc0);
+        acc1 = fmaf(w4.y, Y[t][4 * q + 1], acc1);
+        acc2 = fmaf(w4.z, Y[t][4 * q + 2], acc2);
+        acc3 = fmaf(w4.w, Y[t][4 * q + 3], acc3);
+      }
+    sigma = (acc0 + acc1) + (acc2 + acc3);
+  }
   bool live_tile = true;
   if constexpr (DSKIP) {
-    // the fourth layer pair, peeled: layer 7 (its GEMM keeps prefetching: the feature weights follow in the stream), the
-    // sigma head on the drained ring exactly as in the loop above, then the exit test, then the feature layer
-    load_bias<8>(Y, bias + 7 * 256);
-    gemm_tiles<8, 8, false>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 6), &sb));
-    tap_bits_done(6);
-    relu8(Y, 7);
-    stream_drain(ws);
-    {
-      tail_f32x4* wa = reinterpret_cast<tail_f32x4*>(tail + (kOffWAlpha - kOffBias) + h * 128);
-      float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
-#pragma unroll
-      for (int t = 0; t < 8; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 w4 = wa[t * 4 + q];
-          acc0 = fmaf(w4.x, Y[t][4 * q + 0], acc0);
-          acc1 = fmaf(w4.y, Y[t][4 * q + 1], acc1);
-          acc2 = fmaf(w4.z, Y[t][4 * q + 2], acc2);
-          acc3 = fmaf(w4.w, Y[t][4 * q + 3], acc3);
-        }
-      sigma = (acc0 + acc1) + (acc2 + acc3);
-    }
     // (wave-uniform) does any point of this tile have sigma > 0?  If none, the colour branch below is skipped as a whole:
     // structured as ONE scalar branch around it that rejoins at the output store -- an early `return` here made the
     // compiler merge the exits behind a divergent store and carry the stream base in VGPRs (not an "s" operand any more)
@@ -708,18 +705,28 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
 
   float rgb[3] = {0.0f, 0.0f, 0.0f};
   if (!DSKIP || live_tile) {
-  if constexpr (DSKIP) {
+  if constexpr (SAVE) {
+    // feature layer (no ReLU, network.py:62): the forward result no longer needs it, the backward pass does (it differentiates
+    // the unfolded chain, the same function).  Last GEMM of the packed stream; its row is stored explicitly, as the views row is.
     load_bias<8>(X, bias + 8 * 256);
-    gemm_tiles<8, 8, false>(X, Y, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 7), &sb));   // feature (no ReLU, network.py:62)
+    gemm_tiles<8, 8, true>(X, Y, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 7), &sb));
     tap_bits_done(7);
+    StoreTap<false> ftap{srow + TrainSave::off_f(a.n_points), nullptr};
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ftap(t, q, X[t]);
   }
-  // views layer: cat([feature256, dirs27]) -> 128, ReLU (network.py:63-67)   (consumes the feature vector)
+  // views layer on the folded weights: relu(Wvf . relu(h7) + Wv[:, 256:] . dirs27 + bvf)  ==  network.py:62-67 with
+  // feature_linear folded in (nerf_layout.h kFold*).  Every instance, inference or training forward, issues exactly this
+  // sequence, so the render under autograd stays bit-equal to the no-grad render.
   f32x16 V[4];
-  if (!SAVE || 0) { stream_drain(ws); encode_dir(); }
-  load_bias<4>(V, tail + (kOffBiasViews - kOffBias) + h * 64);
-  gemm_tiles<8, 4, false>(V, X, ws, save_tap<SAVE, false>(srow + TrainSave::off_f(a.n_points), nullptr));
+  if (!SAVE) encode_dir();
+  wstream_start(ws, reinterpret_cast<const f32x4*>(a.fold + kFoldOffWvf), lane);
+  load_bias<4>(V, tail + kTailFloats + h * 64);
+  gemm_tiles<8, 4, false>(V, Y, ws);
   gemm_tiles<1, 4, true>(V, DPE, ws);    // last call of the tile (the compiler-scheduled form runs kPF blocks past the
-                                         // stream end: still inside the packed buffer; the asm form stops at the end)
+                                         // stream end: still inside the fold buffer; the asm form stops at the end)
   if constexpr (SAVE) {                  // nothing consumes the views row through a GEMM: stored here, as the tile ends
     const u32x4 b = relu_bits_tiles<4>(V);
     if (!NERF_F32_HACK_NOSAVE) bits_out[8 * 64] = b;

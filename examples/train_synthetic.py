@@ -4,6 +4,7 @@ training step (trainers/nerf.py:27-33 + trainer.py:53-60: 4096 random rays, MSE 
 Adam 5e-4, exponential decay) on the HIP training path, with periodic checkpoints in the reference's layout.
 
     python examples/train_synthetic.py --steps 600 --precision f32x --out /tmp/nerf_train
+    python examples/train_synthetic.py --steps 600 --occupancy 64          # cull the fine pass with an occupancy grid
 
 There is no dataset offline, so the "photos" are renders of tests/golden/synthetic_ckpt.pth from random poses."""
 import argparse
@@ -39,9 +40,17 @@ def main():
                          "back-propagates the valid merged samples only; deterministic sampling (not with --perturb)")
     ap.add_argument("--weights-threshold", type=float, default=0.25,
                     help="ESS threshold on the coarse weights with --fast-sampling (reference default 0.25; 0.02 keeps far more fine samples)")
+    ap.add_argument("--occupancy", type=int, default=0, metavar="N",
+                    help="cull the fine pass of the training step with an occupancy grid of N^3 points on [-2,2]^3 (Renderer.train_occupancy), "
+                         "rebuilt from the network as it trains; works with --perturb and with --fast-sampling")
+    ap.add_argument("--occupancy-every", type=int, default=16, metavar="K", help="one grid build serves K steps (train_occupancy_every)")
+    ap.add_argument("--occupancy-hold", type=int, default=1, metavar="H",
+                    help="a grid point stays occupied for H refreshes after it was last above the level (OccupancyGrid.hold)")
     args = ap.parse_args()
     if args.fast_sampling and args.perturb:
         ap.error("--fast-sampling trains with deterministic sampling: leave --perturb out")
+    if args.occupancy and args.occupancy < 2:
+        ap.error("--occupancy needs at least 2 grid points per axis")
     dev = "cuda"
 
     teacher = nerf.Network(); nerf.load_network(teacher, args.teacher); teacher = teacher.cuda().eval()
@@ -67,6 +76,20 @@ def main():
     if args.fast_sampling:
         train_ren = nerf.Renderer(net)
         train_ren.fast_sampling, train_ren.weights_threshold = True, args.weights_threshold
+    refreshes = [0]
+    if args.occupancy:
+        if train_ren is ren:
+            train_ren = nerf.Renderer(net)
+        grid = nerf.OccupancyGrid.from_network(net, [-2.0, -2.0, -2.0, 2.0, 2.0, 2.0], args.occupancy, dilate=1, models=("fine",))
+        grid.hold = args.occupancy_hold
+        refresh = grid.refresh
+
+        def counted(*a, **k):
+            refreshes[0] += 1
+            return refresh(*a, **k)
+        grid.refresh = counted
+        train_ren.train_occupancy, train_ren.train_occupancy_every = grid, args.occupancy_every
+        train_ren.masked_stats = []
     opt = FusedAdam(net.parameters(), lr=5e-4, eps=1e-8, clip_value=40.0)
     lr0, gen = 5e-4, torch.Generator(device=dev).manual_seed(1)
 
@@ -90,6 +113,11 @@ def main():
         ids = torch.randint(0, O.shape[0], (4096,), device=dev, generator=gen)
         opt.lr = FusedAdam.exponential_lr(lr0, epoch=step / 50.0)          # ExponentialLR, one "epoch" = 50 iterations here
         loss = train_step(train_ren, opt, O[ids].contiguous(), D[ids].contiguous(), C[ids].contiguous())
+    if args.occupancy and train_ren.masked_stats:
+        evaluated = sum(int(m.item()) for m, _ in train_ren.masked_stats)
+        capacity = sum(cap for _, cap in train_ren.masked_stats)
+        print("occupancy grid {0}^3, every {1}, hold {2}: the fine network evaluated {3:.3f} of the merged samples; {4} refreshes in {5} steps"
+              .format(args.occupancy, args.occupancy_every, args.occupancy_hold, evaluated / capacity, refreshes[0], args.steps))
     nerf.save_model(net, opt, None, None, args.out, epoch=args.steps // 50, last=True)
     print("saved", os.path.join(args.out, "latest.pth"))
 

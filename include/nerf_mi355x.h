@@ -449,6 +449,19 @@ int32_t nerf_occupancy_mark(const float* rays_o, const float* rays_d, const floa
                             const float box_min[3], const float inv_step[3], int32_t and_with_existing, uint8_t* valid,
                             void* stream);
 
+/* The grid's memory across refreshes (training with a grid): near sigma = 0 the sign of a grid point flickers
+ * from one evaluation to the next, so every point carries an age, the number of refreshes since it was last above the level:
+ *     hit(p) = field[p*stride] > level || isnan(field[p*stride])
+ *     age[p] = hit ? 0 : (age[p] == 255 ? 255 : age[p] + 1)
+ *     on[p]  = age[p] < hold ? 1.0f : -1.0f                      (dense, stride 1)
+ * build(on, 1, nx, ny, nz, 0.0f, dilate, bits) then gives the bitfield of the points hit within the last `hold` refreshes: with hold
+ * = 1 the bytes of a direct build from the field, with hold = 2 (dilation being a union over points) the bytewise OR of the last two
+ * direct builds.  The caller fills `age` (one byte per point) with 255 before the first call.  hold in [1, 255]; 0 <= n_points <=
+ * 2^31 - 1, n_points == 0 is a no-op; `on` may be `field` itself when stride == 1.  Size and range checks come before any pointer is
+ * looked at (NERF_ERR_INVALID_ARG), as for nerf_occupancy_build.  One thread per point, no atomics. */
+int32_t nerf_occupancy_age(const float* field, int64_t stride, int64_t n_points, float level, int32_t hold,
+                           uint8_t* age, float* on, void* stream);
+
 /* nerf_render_forward with occupancy culling.  occ_coarse / occ_fine (each nullable) are the bitfields looked up for the 64
  * coarse depths / the 192 merged depths (normally built from the coarse / the fine model's density; occ_fine is ignored when
  * n_importance is 0).  A pass with a bitfield evaluates the kept samples only (device-side compaction, as fast_sampling does) and

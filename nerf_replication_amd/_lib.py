@@ -105,6 +105,7 @@ _PROTOS = {
     "nerf_occupancy_build": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float, _c.c_int32, _F, _c.c_void_p]),
     "nerf_occupancy_mark": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _c.POINTER(_c.c_int32),
                                          _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _c.c_int32, _F, _c.c_void_p]),
+    "nerf_occupancy_age": (_c.c_int32, [_F, _c.c_int64, _c.c_int64, _c.c_float, _c.c_int32, _F, _F, _c.c_void_p]),
     "nerf_render_occupancy_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int32, _c.c_int32]),
     "nerf_render_forward_occupancy": (_c.c_int32, [_F, _F, _c.c_int64, _F, _F, _F, _F, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
                                                    _c.c_float, _F, _F, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_float),

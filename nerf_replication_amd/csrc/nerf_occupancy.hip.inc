@@ -48,6 +48,21 @@ void nerf_occupancy_build_kernel(const float* __restrict__ field, long long stri
   }
 }
 
+// The grid's memory across refreshes: one thread per grid point.  age counts the refreshes since the point was last above the level
+// (0: now; saturates at 255), `on` is > 0 while that is fewer than `hold` refreshes ago.  `on` may be `field` itself (stride 1): each
+// thread reads its own point before it writes it, so neither pointer is __restrict__.
+__global__ __launch_bounds__(kOccBlock)
+void nerf_occupancy_age_kernel(const float* field, long long stride, long long n_points, float level, int hold,
+                               unsigned char* __restrict__ age, float* on) {
+  const long long p = (long long)blockIdx.x * kOccBlock + threadIdx.x;
+  if (p >= n_points) return;
+  const float f = field[p * stride];
+  const bool hit = !(f <= level);                          // f > level, or NaN
+  const int a = hit ? 0 : min((int)age[p] + 1, 255);
+  age[p] = (unsigned char)a;
+  on[p] = a < hold ? 1.0f : -1.0f;
+}
+
 struct OccLookup {
   int cx, cy, cz;
   float min[3], inv[3];
@@ -141,6 +156,17 @@ int32_t nerf_occupancy_build(const float* field, int64_t stride, int32_t nx, int
   hipLaunchKernelGGL(nerf_occupancy_build_kernel, dim3((unsigned)blocks), dim3(kOccBlock), 0, (hipStream_t)stream, field, (long long)stride,
                      G, level, dilate < reach ? dilate : reach, n_words64, bits);
   return check_launch("nerf_occupancy_build_kernel");
+}
+
+int32_t nerf_occupancy_age(const float* field, int64_t stride, int64_t n_points, float level, int32_t hold, uint8_t* age, float* on,
+                           void* stream) {
+  if (n_points < 0 || n_points > (int64_t)0x7fffffff) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_occupancy_age: n_points must be in [0, 2^31 - 1]");
+  if (stride < 1 || hold < 1 || hold > 255) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_occupancy_age: stride must be >= 1 and hold in [1, 255]");
+  if (n_points == 0) return NERF_OK;
+  if (!field || !age || !on) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_occupancy_age: null argument");
+  hipLaunchKernelGGL(nerf_occupancy_age_kernel, dim3((unsigned)((n_points + kOccBlock - 1) / kOccBlock)), dim3(kOccBlock), 0, (hipStream_t)stream,
+                     field, (long long)stride, (long long)n_points, level, hold, age, on);
+  return check_launch("nerf_occupancy_age_kernel");
 }
 
 int32_t nerf_occupancy_mark(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride, int64_t n_rays,

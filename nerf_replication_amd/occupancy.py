@@ -6,6 +6,10 @@ sampler both apply relu(sigma), so the image is bit-equal to the plain render wh
 exact wherever the grid is right, and the grid is made conservative by dilation.  The density comes from density_grid (the
 fused MLP kernels), the bitfield and the lookup from the nerf_occupancy_* kernels (include/nerf_mi355x.h has the definitions);
 torch only moves tensors.  No CPU fallback.
+
+Training: `Renderer.train_occupancy = grid` culls the fine pass of the training step with the fine bitfield
+(the coarse one is ignored there), and OccupancyGrid.refresh rebuilds a bitfield in place from the network as it is now; `hold`
+keeps a grid point occupied for that many refreshes after it was last above the level (nerf_occupancy_age).
 """
 import ctypes
 import numbers
@@ -49,6 +53,12 @@ def lookup_frame(bbox, dims):
     return b[0].astype(np.float32), inv.astype(np.float32)
 
 
+def _hold(hold):
+    if isinstance(hold, bool) or not isinstance(hold, numbers.Integral) or hold < 1 or hold > 255:
+        raise ValueError(f"hold must be an int in [1, 255] (refreshes), got {hold!r}")
+    return int(hold)
+
+
 def _params_key(net, model):
     sub = net.model_fine if model == "fine" else net.model
     return tuple((p.data_ptr(), p._version) for p in sub.ordered_params())
@@ -59,10 +69,18 @@ class OccupancyGrid:
 
     The coarse bitfield culls the 64 coarse samples, the fine one the 192 merged samples (with N_importance = 0 the coarse
     network draws the frame and only the coarse bitfield is used).  A missing bitfield means that pass runs on every sample.
-    Build with from_network or from_fields."""
+    Build with from_network or from_fields.
 
-    def __init__(self, bbox, dims, level, dilate, bits, keys):
+    refresh(net) rebuilds bitfields in place from `net` as it is now.  `hold` (int in [1, 255], default 1, read by refresh): a grid
+    point counts as occupied if it was above the level in one of the last `hold` refreshes.  It looks back over refreshes only: the
+    build that created the grid is not remembered.  `uses` counts the training steps served since the last refresh
+    (Renderer.train_occupancy)."""
+
+    def __init__(self, bbox, dims, level, dilate, bits, keys, chunk_lines=None):
         self.bbox, self.dims, self.level, self.dilate = bbox, dims, level, dilate
+        self.chunk_lines = chunk_lines        # density_grid's chunking, as from_network was given it
+        self.hold, self.uses = 1, 0
+        self._age = {}                        # model -> uint8 [nx*ny*nz]: refreshes since the point was last above the level
         self.bits = bits                      # model -> int32 [words] device tensor, or None
         self.keys = keys                      # model -> parameter key at build time; None: built from fields, never stale
         self.box_min, self.inv_step = lookup_frame(bbox, dims)
@@ -88,7 +106,7 @@ class OccupancyGrid:
         for m in models:
             keys[m] = _params_key(net, m)
             bits[m] = _build(density_grid(net, b.reshape(-1), dims, model=m, chunk_lines=chunk_lines), level, dilate)
-        return cls(b, dims, level, dilate, bits, keys)
+        return cls(b, dims, level, dilate, bits, keys, chunk_lines)
 
     @classmethod
     def from_fields(cls, bbox, coarse=None, fine=None, level=0.0, dilate=1):
@@ -131,6 +149,51 @@ class OccupancyGrid:
     def stale(self, net, model):
         """True iff the grid was built from a network whose `model` parameters have since changed (or from another network)."""
         return self.keys is not None and model in self.keys and self.keys[model] != _params_key(net, model)
+
+    def refresh(self, net, models=None):
+        """Rebuild the bitfields of `models` (default: those the grid has) IN PLACE from `net` as it is now, in its current
+        precision and under no_grad: density_grid on the grid's bbox and dims, nerf_occupancy_age with self.hold, nerf_occupancy_build
+        into the existing words (same data_ptr, same word count).  Afterwards the key of each model is the network's current one
+        (stale() is False) and uses = 0.  The age state, one uint8 per grid point and model, is created (255 everywhere) at a model's
+        first refresh, so `hold` looks back over refreshes only, not to the build that created the grid.  A grid from from_fields can be
+        refreshed too; it then carries a key."""
+        hold = _hold(self.hold)
+        if not isinstance(net, Network):
+            raise TypeError("OccupancyGrid.refresh needs a nerf_replication_amd Network")
+        if models is None:
+            models = tuple(m for m in MODELS if self.bits[m] is not None)
+        try:
+            models = tuple(models)
+        except TypeError:
+            raise ValueError(f'models must be a sequence out of ("", "fine"), got {models!r}') from None
+        if not models or len(set(models)) != len(models):
+            raise ValueError(f'models must be a non-empty sequence out of ("", "fine") without repeats, got {models!r}')
+        for m in models:
+            self._bits(m)
+        lib = _lib.load()
+        nx, ny, nz = self.dims
+        with torch.no_grad():
+            for m in models:
+                bits, key = self.bits[m], _params_key(net, m)
+                field = density_grid(net, self.bbox.reshape(-1), self.dims, model=m, chunk_lines=self.chunk_lines)
+                if field.device != self.device:
+                    raise ValueError(f"the occupancy grid is on {self.device}, the network on {field.device}")
+                if int(lib.nerf_occupancy_words(nx, ny, nz)) != bits.numel():
+                    raise _lib.NerfLibraryError(f"the bitfield of model {m!r} does not have the words of a {self.dims} grid")
+                age = self._age.get(m)
+                if age is None:
+                    age = self._age[m] = torch.full((field.numel(),), 255, dtype=torch.uint8, device=self.device)
+                with torch.cuda.device(self.device):
+                    st = _lib.stream_of(self.device)
+                    # `on` overwrites the field: it is not needed again
+                    _lib.check(lib.nerf_occupancy_age(_lib.ptr(field), 1, field.numel(), self.level, hold, _lib.ptr(age, torch.uint8),
+                                                      _lib.ptr(field), st), "nerf_occupancy_age")
+                    _lib.check(lib.nerf_occupancy_build(_lib.ptr(field), 1, nx, ny, nz, 0.0, self.dilate, bits.data_ptr(), st),
+                               "nerf_occupancy_build")
+                if self.keys is None:
+                    self.keys = {}
+                self.keys[m] = key
+        self.uses = 0
 
     def lookup_args(self):
         """(dims, box_min, inv_step) as the HOST arrays of nerf_occupancy_mark / nerf_render_forward_occupancy."""

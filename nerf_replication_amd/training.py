@@ -20,6 +20,11 @@ Two more modes train, with deterministic sampling and parameter gradients: fast_
 ESS / ERT mask, volume_renderer.py:132-244 / :359-369 / network.py:207-253 -- the fine network, its activation store and its
 backward run on the valid merged samples only, compacted on the device) and N_importance == 0 (CoarseRenderFunction: the coarse
 network alone, composited over its 64 samples).  The unmasked step above issues exactly the launches it issued before.
+
+With Renderer.train_occupancy set (CulledRenderFunction) the fine pass runs on the merged samples the grid's fine
+bitfield keeps, deterministic or stochastic, through the same masked entries; with fast_sampling the list is the sampler's mask AND
+the lookup.  Compositing's adjoint is exactly zero wherever sigma <= 0, so the step has the plain step's gradients wherever the
+grid is right.
 """
 import ctypes
 
@@ -92,6 +97,14 @@ class _Step:
                                                   _lib.ptr(t_sorted), None, _lib.ptr(valid, torch.uint8), *thresholds, self.st),
                    "nerf_sample_fine_rays")
         return t_sorted, valid
+
+    def mark(self, grid, tvals, S, valid=None):
+        """The grid's fine bitfield looked up at the S depths of every ray -> valid [n,S] uint8; ANDed into `valid` if given."""
+        out = self.empty(self.n, S, dtype=torch.uint8) if valid is None else valid
+        _lib.check(self.lib.nerf_occupancy_mark(_lib.ptr(self.rays_o), _lib.ptr(self.rays_d), _lib.ptr(tvals), S, self.n, S,
+                                                _lib.ptr(grid.bits["fine"], torch.int32), *grid.lookup_args(), int(valid is not None),
+                                                _lib.ptr(out, torch.uint8), self.st), "nerf_occupancy_mark")
+        return out
 
     def compact(self, valid):
         """-> (ids of the valid samples, their number), both on the device."""
@@ -247,6 +260,48 @@ class RenderFunction(torch.autograd.Function):
         return (None,) + g_rays + (None,) + s.param_grads()
 
 
+def _masked_forward(ctx, renderer, rays_o, rays_d, draws, grid, params):
+    """The forward of a step whose fine pass runs on a compact list: the sampler's mask (fast_sampling), the lookup of `grid`'s fine
+    bitfield at the merged depths, or both ANDed.  The coarse pass is the plain step's, on the shared or the drawn depths."""
+    s = _Step(renderer, rays_o, rays_d)
+    pk_c, pk_f = renderer.net.packed(""), renderer.net.packed("fine")
+    raw_f = torch.zeros((s.n, s.S_f, 4), dtype=torch.float32, device=s.dev)           # unlisted samples keep raw = 0
+    with torch.cuda.device(s.dev):
+        ctx.stochastic = s.use_draws(*draws) if draws is not None else None
+        raw_c, save_c = s.forward_save(pk_c, s.t_c, s.t_cs, s.S_c, density_only=True)
+        t_sorted, valid = s.sample_fine(raw_c, fast_sampling=grid is None or bool(renderer.fast_sampling))
+        if grid is not None:
+            valid = s.mark(grid, t_sorted, s.S_f, valid)
+        index, count = s.compact(valid)
+        raw_f, save_f = s.forward_save(pk_f, t_sorted, s.S_f, s.S_f, masked=(index, count), raw=raw_f)
+        rgb, depth = s.composite(raw_f, t_sorted, s.S_f, s.S_f)
+    stats = getattr(renderer, "masked_stats", None)
+    if stats is not None:         # (points the fine network evaluated as a 1-element device tensor, capacity): no host sync here
+        stats.append((count.clone(), s.n * s.S_f))
+    cap = getattr(renderer, "capture_adjoints", None)
+    if cap is not None:
+        cap["valid_sorted"] = valid.clone()
+    ctx.renderer, ctx.prec, ctx.params = renderer, s.prec, params
+    ctx.save_for_backward(rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f, index, count)
+    return rgb, depth
+
+
+def _masked_backward(ctx, g_rgb, g_depth, n_inputs):
+    """The backward of such a step; the parameters are the inputs from `n_inputs` on."""
+    rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f, index, count = ctx.saved_tensors
+    s = _Step(ctx.renderer, rays_o, rays_d, ctx.prec, ctx.stochastic)
+    s.begin_backward(ctx, g_rgb, g_depth, n_inputs)
+    if s.grads is None:
+        return (None,) * (n_inputs + len(s.params))
+    with torch.cuda.device(s.dev):
+        # fine pass: image -> raw_fine and depths (all 192 samples; g_raw is exactly zero at the masked ones: sigma = 0)
+        g_raw_f, g_t = s.composite_backward(raw_f, t_sorted, s.S_f, s.S_f)
+        g_t.add_(s.mlp_backward_masked(s.params[24:], s.grads[24:], t_sorted, s.S_f, (index, count), g_raw_f, save_f))
+        # coarse pass, as in the unmasked step
+        s.coarse_backward(raw_c, save_c, t_sorted, g_t, s.live_count(s.S_f))
+    return (None,) * n_inputs + s.param_grads()
+
+
 class MaskedRenderFunction(torch.autograd.Function):
     """The step with fast_sampling: the sampler also yields the validity of the 192 merged samples (coarse samples always valid,
     fine ones unless ESS / ERT / the empty-ray test drop them); the fine network runs on the M valid samples, raw_fine is exactly 0
@@ -255,39 +310,27 @@ class MaskedRenderFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, renderer, rays_o, rays_d, *params):
-        s = _Step(renderer, rays_o, rays_d)
-        pk_c, pk_f = renderer.net.packed(""), renderer.net.packed("fine")
-        raw_f = torch.zeros((s.n, s.S_f, 4), dtype=torch.float32, device=s.dev)           # masked samples keep raw = 0
-        with torch.cuda.device(s.dev):
-            raw_c, save_c = s.forward_save(pk_c, s.t_c, 0, s.S_c, density_only=True)
-            t_sorted, valid = s.sample_fine(raw_c, fast_sampling=True)
-            index, count = s.compact(valid)
-            raw_f, save_f = s.forward_save(pk_f, t_sorted, s.S_f, s.S_f, masked=(index, count), raw=raw_f)
-            rgb, depth = s.composite(raw_f, t_sorted, s.S_f, s.S_f)
-        stats = getattr(renderer, "masked_stats", None)
-        if stats is not None:         # (points the fine network evaluated as a 1-element device tensor, capacity): no host sync here
-            stats.append((count.clone(), s.n * s.S_f))
-        cap = getattr(renderer, "capture_adjoints", None)
-        if cap is not None:
-            cap["valid_sorted"] = valid.clone()
-        ctx.renderer, ctx.prec, ctx.params = renderer, s.prec, params
-        ctx.save_for_backward(rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f, index, count)
-        return rgb, depth
+        return _masked_forward(ctx, renderer, rays_o, rays_d, None, None, params)
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth):
-        rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f, index, count = ctx.saved_tensors
-        s = _Step(ctx.renderer, rays_o, rays_d, ctx.prec)
-        s.begin_backward(ctx, g_rgb, g_depth, 3)
-        if s.grads is None:
-            return (None,) * (3 + len(s.params))
-        with torch.cuda.device(s.dev):
-            # fine pass: image -> raw_fine and depths (all 192 samples; g_raw is exactly zero at the masked ones: sigma = 0)
-            g_raw_f, g_t = s.composite_backward(raw_f, t_sorted, s.S_f, s.S_f)
-            g_t.add_(s.mlp_backward_masked(s.params[24:], s.grads[24:], t_sorted, s.S_f, (index, count), g_raw_f, save_f))
-            # coarse pass, as in the unmasked step
-            s.coarse_backward(raw_c, save_c, t_sorted, g_t, s.live_count(s.S_f))
-        return (None, None, None) + s.param_grads()
+        return _masked_backward(ctx, g_rgb, g_depth, 3)
+
+
+class CulledRenderFunction(torch.autograd.Function):
+    """The step with Renderer.train_occupancy: the coarse pass as in the plain step (unculled, shared or jittered depths), then the
+    grid's fine bitfield looked up at the 192 merged depths (nerf_occupancy_mark; ANDed into the sampler's mask with fast_sampling)
+    and the fine network on the kept samples only, raw_fine = 0 at the others.  The lookup is made of comparisons, a constant for
+    autograd, so the backward is the masked step's, with the stochastic strides when draws are given.  A culled sample with a true
+    sigma <= 0 has an exactly zero g_raw row in the plain step too: wherever the grid is right the gradients are the plain step's."""
+
+    @staticmethod
+    def forward(ctx, renderer, rays_o, rays_d, draws, grid, *params):
+        return _masked_forward(ctx, renderer, rays_o, rays_d, draws, grid, params)
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth):
+        return _masked_backward(ctx, g_rgb, g_depth, 5)
 
 
 class CoarseRenderFunction(torch.autograd.Function):
@@ -333,15 +376,21 @@ def check_differentiable(renderer, rays_grad=False):
         raise NotImplementedError("gradients with respect to the rays are built for N_importance=128 without fast_sampling")
 
 
-def render_with_grad(renderer, rays_o, rays_d, jitter=None, u=None):
+def render_with_grad(renderer, rays_o, rays_d, jitter=None, u=None, occupancy=None):
     """rays [n,3] (contiguous fp32, on the GPU) -> (rgb [n,3], depth [n]) attached to the autograd graph of
     the 48 network parameters (coarse sub-model first, then fine, state_dict order) and of the rays, each where it
     requires grad.  `jitter` [n,64] / `u` [n,128]: the reference's training-mode draws (Renderer._draws); None keeps the
-    shared deterministic table."""
+    shared deterministic table.  `occupancy`: an OccupancyGrid whose fine bitfield culls the fine pass (Renderer._train_grid has
+    checked it); parameter gradients only, N_importance = 128."""
     net = renderer.net
     rays_grad = rays_o.requires_grad or rays_d.requires_grad
     check_differentiable(renderer, rays_grad)
     draws = (jitter, u) if (jitter is not None or u is not None) else None
+    if occupancy is not None:
+        if rays_grad or renderer.N_importance != _lib.N_IMPORTANCE or (draws is not None and renderer.fast_sampling):
+            raise NotImplementedError("the culled step trains parameters with N_importance=128; fast_sampling with deterministic sampling only")
+        params = tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
+        return CulledRenderFunction.apply(renderer, rays_o, rays_d, draws, occupancy, *params)
     if renderer.N_importance == 0 or renderer.fast_sampling:
         if draws is not None:
             raise NotImplementedError("stochastic sampling trains with N_importance=128 without fast_sampling only")

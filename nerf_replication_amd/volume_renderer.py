@@ -59,6 +59,11 @@ class Renderer:
         # to a list to receive (evaluated [2] int64 device tensor, (64 n, 192 n)) per culled render() call, without a host sync
         self.occupancy = None
         self.occupancy_stats = None
+        # training with a grid: an OccupancyGrid whose FINE bitfield culls the fine pass of the training step (its coarse
+        # bitfield is ignored), refreshed from the network every train_occupancy_every steps once the parameters moved.  Read at render()
+        # time; acts on the autograd path only (inference culling is `occupancy`)
+        self.train_occupancy = None
+        self.train_occupancy_every = 16
         if self.N_samples != _lib.N_SAMPLES or self.N_importance not in (0, _lib.N_IMPORTANCE):
             raise ValueError("HIP renderer is built for N_samples=64 and N_importance in {0,128}")
 
@@ -116,6 +121,28 @@ class Renderer:
                 raise RuntimeError("the network's parameters changed since the occupancy grid was built from them: rebuild the "
                                    "grid (OccupancyGrid.from_network), or set Renderer.occupancy = None")
 
+    def _train_grid(self, dev, rays_grad):
+        """The grid of a training call with self.train_occupancy set: what that call refuses, before anything is launched, then the
+        refresh schedule -- one build serves train_occupancy_every steps, and a grid whose network did not move is never rebuilt."""
+        _sibling("training").check_differentiable(self, rays_grad)
+        grid, every = self.train_occupancy, self.train_occupancy_every
+        if not isinstance(grid, _sibling("occupancy").OccupancyGrid):
+            raise TypeError("Renderer.train_occupancy must be an OccupancyGrid or None")
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError(f"Renderer.train_occupancy_every must be an int >= 1 (steps), got {every!r}")
+        if grid.bits["fine"] is None:
+            raise ValueError("Renderer.train_occupancy needs a grid with a fine bitfield: the training step culls the fine pass only")
+        if grid.device != dev:
+            raise ValueError(f"the occupancy grid is on {grid.device}, the rays on {dev}")
+        if rays_grad:
+            raise NotImplementedError("no ray gradients with Renderer.train_occupancy set: the masked backward forms no point gradients")
+        if self.N_importance == 0:
+            raise NotImplementedError("Renderer.train_occupancy culls the fine pass: there is none with N_importance = 0")
+        if grid.stale(self.net, "fine") and grid.uses >= every:
+            grid.refresh(self.net, models=("fine",))
+        grid.uses += 1
+        return grid
+
     def render(self, batch):
         rays_o, rays_d = batch["rays_o"], batch["rays_d"]
         self.device = dev = rays_o.device
@@ -144,17 +171,21 @@ class Renderer:
             if self.fast_sampling:
                 raise NotImplementedError(f"stochastic sampling (task={self.task!r}, perturb={bool(self.perturb)}) is not "
                                           "built with fast_sampling")
+        with_grad = rays_grad or (torch.is_grad_enabled() and getattr(self.net, "training", False) and
+                                  any(p.requires_grad for p in self.net.parameters()))
+        train_grid = self._train_grid(dev, rays_grad) if with_grad and self.train_occupancy is not None else None
+        if stochastic:
             jitter, u_rays = self._draws(n, dev)
-        if rays_grad or (torch.is_grad_enabled() and getattr(self.net, "training", False) and
-                         any(p.requires_grad for p in self.net.parameters())):
+        if with_grad:
             # training call (trainers/nerf.py:27 under trainer.py:53-60), or rays that require grad: forward with activation
             # save, backward through the adjoint HIP kernels (training.py)
             render_with_grad = _sibling("training").render_with_grad
             if n == 0:
                 return torch.empty((0, 3), device=dev), torch.empty((0,), device=dev)
+            kw = {} if train_grid is None else {"occupancy": train_grid}
             if stochastic:
-                return render_with_grad(self, o, d, jitter, u_rays)
-            return render_with_grad(self, o, d)
+                return render_with_grad(self, o, d, jitter, u_rays, **kw)
+            return render_with_grad(self, o, d, **kw)
         t_c, u = self._get_tables(dev)
         pk_c = self.net.packed("")
         pk_f = self.net.packed("fine") if self.N_importance > 0 else None

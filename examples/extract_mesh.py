@@ -5,6 +5,7 @@ reference's src/utils/mesh_utils.py extract_mesh is for).
     python examples/extract_mesh.py --ckpt tests/golden/trained_ckpt.pth --n 256 --out mesh.ply
     python examples/extract_mesh.py --level 32                 # the reference's cfg.level; default: picked from the grid
     python examples/extract_mesh.py --precision f16            # fp16 density (PSNR-level accuracy)
+    python examples/extract_mesh.py --normals                  # vertex normals (nx ny nz) from the density gradient: smooth shading
 
 Needs an MI355X and the built library (python -c "import __graft_entry__ as g; g.build()")."""
 import argparse
@@ -27,6 +28,8 @@ def main():
                     "grid's median and maximum")
     ap.add_argument("--bbox", type=float, nargs=6, default=[-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], metavar="V", help="min xyz, max xyz")
     ap.add_argument("--precision", default="f32", choices=["f32", "f16", "f32x"])
+    ap.add_argument("--normals", action="store_true",
+                    help="write unit vertex normals -grad sigma / |grad sigma| (nerf.vertex_normals; f32 / f32x)")
     ap.add_argument("--out", default="mesh.ply")
     args = ap.parse_args()
 
@@ -39,10 +42,10 @@ def main():
         grid = nerf.density_grid(net, args.bbox, args.n)
         level = 0.5 * (grid.median().item() + grid.max().item())
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    vertices, faces = nerf.extract_mesh(net, level, args.bbox, args.out, args.n)
+    vertices, faces = nerf.extract_mesh(net, level, args.bbox, args.out, args.n, normals=True if args.normals else None)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
-    print("{}^3 grid, {}, level {:.4g}: {} vertices, {} triangles in {:.1f} ms (grid + surface + file)".format(
-        args.n, args.precision, level, vertices.shape[0], faces.shape[0], dt * 1e3))
+    print("{}^3 grid, {}, level {:.4g}: {} vertices, {} triangles in {:.1f} ms (grid + surface{} + file)".format(
+        args.n, args.precision, level, vertices.shape[0], faces.shape[0], dt * 1e3, " + vertex normals" if args.normals else ""))
     print("wrote", args.out)
 
 

@@ -5,6 +5,7 @@ per test view: rays from the camera pose, Renderer.render, evaluator image dump)
     python examples/render_frame.py --ckpt tests/golden/synthetic_ckpt.pth --angle 40 --res 400 --out /tmp/nerf_out
     python examples/render_frame.py --precision f16      # BASELINE config 5 arithmetic
     python examples/render_frame.py --occupancy 128      # skip empty space: occupancy grid of 128^3 points on [-2,2]^3
+    python examples/render_frame.py --geometry           # also normal.png (surface normals) and acc.png (opacity)
 
 Needs an MI355X and the built library (python -c "import __graft_entry__ as g; g.build()")."""
 import argparse
@@ -40,6 +41,10 @@ def main():
     ap.add_argument("--precision", default="f32", choices=["f32", "f16", "f32x"])
     ap.add_argument("--occupancy", type=int, default=0, metavar="N",
                     help="cull empty space with an occupancy grid of N^3 points on [-2,2]^3, dilate 1 (f32 / f32x; 0: off)")
+    ap.add_argument("--geometry", action="store_true",
+                    help="also write images/normal.png and images/acc.png (Renderer.render_geometry; f32 / f32x, no --occupancy)")
+    ap.add_argument("--geometry-block-rays", type=int, default=4096, metavar="R",
+                    help="rays per block of the geometry pass: about 3.9 MB of scratch per ray (default 4096, 16 GB)")
     ap.add_argument("--out", default="nerf_out")
     args = ap.parse_args()
 
@@ -66,6 +71,22 @@ def main():
     ev = nerf.Evaluator(result_dir=args.out)                    # writes <out>/images/view000_{pred,gt}.png
     ev.evaluate((rgb, depth), {"colors": rgb[None], "H": torch.tensor(args.res), "W": torch.tensor(args.res), "id": torch.tensor(0)})
     print("wrote", os.path.join(args.out, "images", "view000_pred.png"))
+    if args.geometry:
+        from nerf_replication_amd.evaluator import write_png
+        renderer.geometry_block_rays = args.geometry_block_rays
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        geo = renderer.render_geometry({"rays_o": rays_o[None], "rays_d": rays_d[None]})
+        torch.cuda.synchronize(); dt = time.perf_counter() - t0
+        assert torch.equal(geo["rgb"], rgb) and torch.equal(geo["depth"], depth)
+        print("geometry pass (rgb, depth, acc, normal): {:.1f} ms, {:.0f} rays/s".format(dt * 1e3, rays_o.shape[0] / dt))
+        normal, acc = geo["normal"], geo["acc"]
+        # 0.5 + 0.5 n / max(|n|, 1e-6), white where the ray is mostly empty
+        shown = 0.5 + 0.5 * normal / normal.norm(dim=-1, keepdim=True).clamp_min(1e-6)
+        shown = torch.where(acc[:, None] < 0.5, torch.ones_like(shown), shown)
+        to_u8 = lambda x: (x.clamp(0, 1) * 255).to(torch.uint8).reshape(args.res, args.res, 3)
+        for name, img in (("normal.png", shown), ("acc.png", acc[:, None].expand(-1, 3))):
+            write_png(os.path.join(args.out, "images", name), to_u8(img))
+            print("wrote", os.path.join(args.out, "images", name))
 
 
 if __name__ == "__main__":

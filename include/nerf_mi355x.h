@@ -483,6 +483,44 @@ int32_t nerf_render_forward_occupancy(const float* rays_o, const float* rays_d, 
                                       int64_t* evaluated, void* workspace, int64_t workspace_bytes,
                                       float* rgb, float* depth, void* stream);
 
+/* ---- geometry outputs: density gradient, surface normal and opacity ---------------------------------------
+ * Definitions.  For sample i of a ray, with raw sigma_i the pre-activation density of the network that is composited (the fine one;
+ * the coarse one when n_importance == 0) at x_i = fadd(o, fmul(d, t_i)):
+ *     g_i = grad_x raw sigma(x_i): the data-gradient chain's g_x for an incoming gradient of 1 on sigma and 0 on rgb -- back through
+ *           alpha_linear, the eight trunk layers with the skip, and the positional encoding's derivative; no view branch;
+ *     n_i = -g_i / |g_i| if raw sigma_i > 0 and g_i . g_i > 0, else the zero vector; separately rounded fp32:
+ *           gg = fadd(fadd(fmul(gx, gx), fmul(gy, gy)), fmul(gz, gz)), r = sqrt(gg), n = -g / r, square root and division both
+ *           correctly rounded (the instruction sequences are written down in csrc/nerf_normals.hip.inc), no reciprocal shortcut;
+ *     w_i = nerf_composite's weights (volume_renderer.py:67-96), from the same device function: bit-equal to its `weights` output;
+ *     acc = sum_i w_i,  normal = sum_i w_i n_i, both summed left to right over the samples as nerf_composite sums (acc is the sum
+ *           nerf_composite subtracts from 1 for the white background).  The normal is NOT renormalised: |normal| <= acc; callers
+ *           normalise for display.
+ *
+ * nerf_density_gradient: sigma [P] (nullable) = raw sigma and grad [P,3] = g at the P = n_rays * n_samples points o + d t (t of
+ * (ray i, sample s) at tvals[i*t_ray_stride + s], stride 0: one shared table).  With n_samples = 1 and t = 0 this is a plain point
+ * list: fadd(o, fmul(d, 0)) = o for finite d.  sigma is bit for bit column 3 of nerf_mlp_forward_rays_density.
+ * positive_only != 0: grad is exactly zero wherever raw sigma <= 0, and 32-point tiles without any density are dropped from the chain
+ * (dead-tile skipping, above); elsewhere the values are those of positive_only == 0.
+ * The points are cut into blocks of whole rays; per block: nerf_mlp_forward_rays_save_density, one small kernel that turns raw into
+ * the chain's incoming gradient (0, 0, 0, seed) and copies sigma out, and nerf_mlp_backward_rays_x(density_only = 1, grads = NULL) --
+ * all ordered on `stream`, no host sync.  The result does not depend on the blocking.  `workspace` holds one block: its TrainSave,
+ * TrainGrad, raw and incoming gradient.  A block of r rays fits if
+ *     workspace_bytes >= nerf_density_gradient_point_bytes() * r * n_samples      (r * n_samples rounded up to a multiple of 32),
+ * and the entry takes the largest r <= floor(workspace_bytes / point_bytes / n_samples) whose layout fits: the caller bounds the
+ * memory, not the frame.  NERF_ERR_WORKSPACE if that is no ray at all.  n_samples <= 192 (NERF_ERR_INVALID_ARG).  `packed` /
+ * `packed_bwd`: nerf_pack_model / nerf_pack_model_bwd of `precision`; NERF_PREC_F32 and NERF_PREC_F32X only (NERF_ERR_UNSUPPORTED). */
+int64_t nerf_density_gradient_point_bytes(void);
+int32_t nerf_density_gradient(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride, int64_t n_rays,
+                              int32_t n_samples, const void* packed, const void* packed_bwd, int32_t positive_only, float* sigma,
+                              float* grad, int32_t precision, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* raw [n,S,4], t as for nerf_composite, grad [n,S,3] (g of the definitions) -> normal [n,3], acc [n].  S <= 192
+ * (NERF_ERR_INVALID_ARG).  One wave per ray; lane l prepares samples l, l + 64, l + 128, then every lane walks the samples in order
+ * (csrc/nerf_normals.hip.inc): no reduction tree, no atomics, two runs write the same bytes.  rgb is not read, white_bkgd plays no
+ * part.  grad rows of samples with raw sigma <= 0 are read but never used (they may hold anything, NaN included). */
+int32_t nerf_composite_normals(const float* raw, const float* tvals, int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
+                               const float* grad, float* normal, float* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

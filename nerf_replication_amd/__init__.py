@@ -23,12 +23,14 @@ _LAZY = {
     "Evaluator": ".evaluator",
     "load_network": ".checkpoint", "load_model": ".checkpoint", "save_model": ".checkpoint",
     "density_grid": ".mesh", "isosurface": ".mesh", "write_ply": ".mesh", "extract_mesh": ".mesh",
+    "density_gradient": ".mesh", "vertex_normals": ".mesh",
     "OccupancyGrid": ".occupancy",
 }
 _SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy")
 
 __all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model",
-           "density_grid", "isosurface", "write_ply", "extract_mesh", "OccupancyGrid"]
+           "density_grid", "isosurface", "write_ply", "extract_mesh", "density_gradient", "vertex_normals",
+           "OccupancyGrid"]
 
 
 def __getattr__(name):

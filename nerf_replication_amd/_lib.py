@@ -110,6 +110,11 @@ _PROTOS = {
     "nerf_render_forward_occupancy": (_c.c_int32, [_F, _F, _c.c_int64, _F, _F, _F, _F, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
                                                    _c.c_float, _F, _F, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_float),
                                                    _c.POINTER(_c.c_float), _F, _F, _c.c_int64, _F, _F, _c.c_void_p]),
+    # geometry outputs: density gradient, composited normal and opacity (Renderer.render_geometry, mesh.vertex_normals)
+    "nerf_density_gradient_point_bytes": (_c.c_int64, []),
+    "nerf_density_gradient": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _c.c_int32, _F, _F, _c.c_int32,
+                                           _F, _c.c_int64, _c.c_void_p]),
+    "nerf_composite_normals": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_void_p]),
 }
 EXPORTS = tuple(_PROTOS)
 

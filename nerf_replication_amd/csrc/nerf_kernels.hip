@@ -641,12 +641,26 @@ __device__ __forceinline__ float sigmoid_rn(float x) { return __fdiv_rn(1.0f, __
 
 // Running state of one ray and the per-sample step of volume_renderer.py:67-96, :414-432; the rounding sequence of `add` and
 // `store` is what both forward kernels (and every stored result) agree on bit for bit.
+// The weight of one sample (volume_renderer.py:67-96): alpha of relu(sigma) over delta and the factor q the transmittance takes on
+// behind the sample; step() gives w_k = T alpha and moves T on.  The one definition of the weights: nerf_composite's kernels take
+// both halves at once, nerf_composite_normals computes `of` lane-parallel and walks step() over the lanes in sample order.
+struct CompositeWeight {
+  float alpha, q;
+  static __device__ __forceinline__ CompositeWeight of(float sigma_raw, float delta) {
+    const float alpha = alpha_of(fmaxf(sigma_raw, 0.0f), delta);
+    return {alpha, fminf(fmaxf(__fsub_rn(1.0f, alpha), 1e-10f), 1.0f)};
+  }
+  __device__ __forceinline__ float step(float& T) const {
+    const float wk = __fmul_rn(T, alpha);
+    T = __fmul_rn(T, q);
+    return wk;
+  }
+};
+
 struct CompositeAcc {
   float T = 1.0f, r = 0.f, g = 0.f, b = 0.f, d = 0.f, w = 0.f;
   __device__ __forceinline__ float add(f32x4 v, float t_cur, float delta) {      // returns the sample's weight
-    const float alpha = alpha_of(fmaxf(v.w, 0.0f), delta);
-    const float wk = __fmul_rn(T, alpha);
-    T = __fmul_rn(T, fminf(fmaxf(__fsub_rn(1.0f, alpha), 1e-10f), 1.0f));
+    const float wk = CompositeWeight::of(v.w, delta).step(T);
     const float cr = sigmoid_rn(v.x), cg = sigmoid_rn(v.y), cb = sigmoid_rn(v.z);
     r = __fadd_rn(r, __fmul_rn(wk, cr));
     g = __fadd_rn(g, __fmul_rn(wk, cg));
@@ -2549,3 +2563,5 @@ int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d,
 #include "nerf_isosurface.hip.inc"
 // ---- occupancy grid: nerf_occupancy_* and nerf_render_forward_occupancy
 #include "nerf_occupancy.hip.inc"
+// ---- geometry outputs: nerf_density_gradient and nerf_composite_normals
+#include "nerf_normals.hip.inc"

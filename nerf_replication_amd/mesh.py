@@ -4,8 +4,9 @@ cfg.resolution = 256, src/config/config.py:10-12).
 
 The density comes from the fused MLP kernels (a grid line is a ray: nerf_mlp_forward_rays_density), the surface from the
 nerf_isosurface_* kernels (marching tetrahedra, include/nerf_mi355x.h); DESIGN.md section 2.8 has the definitions and where
-this departs from the reference's function, which is not runnable as written.  No CPU fallback: every number comes out of a
-HIP kernel, torch only moves tensors.
+this departs from the reference's function, which is not runnable as written.  Vertex normals are the density gradient of the
+fused data-gradient chain at the vertices (nerf_density_gradient).  No CPU fallback: every number comes
+out of a HIP kernel, torch only moves tensors (and normalises the [V,3] gradient of vertex_normals).
 """
 import ctypes
 import numbers
@@ -20,6 +21,7 @@ DEFAULT_LEVEL = 32.0
 DEFAULT_RESOLUTION = 256
 CHUNK_POINTS = 1 << 22          # default bound on the points per MLP launch of density_grid: 64 MiB of [P,4] fp32 scratch
 QUERY_BATCH = 1 << 20           # points per call of a callable queryfn
+GRADIENT_BLOCK_POINTS = 1 << 16 # default bound on the points per block of density_gradient: 1.3 GB of saved / gradient rows
 
 
 def _shape3(N):
@@ -175,14 +177,72 @@ def isosurface(field, level, origin, step):
     return vertices, faces
 
 
-def write_ply(path, vertices, faces):
-    """Binary little-endian PLY: `float` x y z per vertex, `uchar int` index lists per face."""
+def density_gradient(net, points, model="fine", positive_only=False, block_points=None):
+    """(sigma [P], grad [P,3]) of `net`'s coarse ("") or fine model at explicit points [P,3] on the device: the pre-ReLU density and
+    its spatial gradient, through nerf_density_gradient (include/nerf_mi355x.h, "geometry outputs"; net.precision 'f32' / 'f32x').
+    Every point is a ray of one sample, rays_o = the point, rays_d = (0, 0, 1), t = 0, so the kernels' o + d t is the point itself.
+    positive_only: grad is exactly zero wherever sigma <= 0.  The entry works in blocks of `block_points` points (default 2^16, about
+    1.3 GB of scratch); the result does not depend on the blocking."""
+    if not isinstance(net, Network):
+        raise TypeError("density_gradient needs a nerf_replication_amd Network")
+    if model not in ("", "fine"):
+        raise ValueError(f'model must be "" (coarse) or "fine", got {model!r}')
+    if block_points is None:
+        block_points = GRADIENT_BLOCK_POINTS
+    if isinstance(block_points, bool) or not isinstance(block_points, numbers.Integral) or block_points < 1:
+        raise ValueError(f"block_points must be a positive int, got {block_points!r}")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be a tensor [P,3]")
+    lib = _lib.load()
+    packed = net.packed(model)                     # raises for a network on the CPU
+    packed_bwd = net.packed_bwd(model)             # raises for an fp16 precision
+    dev = packed.device
+    pts = points.detach().to(device=dev, dtype=torch.float32).contiguous()
+    P = pts.shape[0]
+    sigma = torch.empty((P,), dtype=torch.float32, device=dev)
+    grad = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    if P == 0:
+        return sigma, grad
+    rays_d = torch.zeros((P, 3), dtype=torch.float32, device=dev)
+    rays_d[:, 2] = 1.0
+    t = torch.zeros(1, dtype=torch.float32, device=dev)
+    rows = (min(int(block_points), P) + 31) // 32 * 32
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(lib.nerf_density_gradient_point_bytes()) * rows, dtype=torch.uint8, device=dev)
+        _lib.check(lib.nerf_density_gradient(_lib.ptr(pts), _lib.ptr(rays_d), _lib.ptr(t), 0, P, 1, packed.data_ptr(),
+                                             packed_bwd.data_ptr(), int(bool(positive_only)), _lib.ptr(sigma), _lib.ptr(grad),
+                                             _lib.PRECISIONS[net.precision], ws.data_ptr(), ws.numel(), _lib.stream_of(dev)),
+                   "nerf_density_gradient")
+    return sigma, grad
+
+
+def vertex_normals(net, vertices, model="fine"):
+    """Unit outward normals [V,3] of an iso-surface of `net`'s density at its vertices [V,3]: -grad sigma / |grad sigma| (density
+    falls towards the outside), the gradient from density_gradient (every point, whatever the sign of sigma).  A vertex with a zero
+    (or non-finite) gradient gets the zero vector.  The gradient comes out of the HIP chain; the normalisation of the [V,3] result
+    is three torch operations."""
+    _, g = density_gradient(net, vertices, model=model, positive_only=False)
+    nrm = g.norm(dim=-1, keepdim=True)
+    ok = torch.isfinite(nrm) & (nrm > 0)
+    return torch.where(ok, -g / torch.where(ok, nrm, torch.ones_like(nrm)), torch.zeros_like(g))
+
+
+def write_ply(path, vertices, faces, normals=None):
+    """Binary little-endian PLY: `float` x y z per vertex (followed by `float` nx ny nz when `normals` [V,3] is given), `uchar int`
+    index lists per face."""
     v = np.ascontiguousarray(torch.as_tensor(vertices).detach().cpu().numpy(), dtype="<f4")
     f = np.ascontiguousarray(torch.as_tensor(faces).detach().cpu().numpy(), dtype="<i4")
     if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
         raise ValueError("write_ply needs vertices [V,3] and faces [T,3]")
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        nv = np.ascontiguousarray(torch.as_tensor(normals).detach().cpu().numpy(), dtype="<f4")
+        if nv.shape != v.shape:
+            raise ValueError(f"write_ply needs normals of the vertices' shape {v.shape}, got {nv.shape}")
+        v = np.ascontiguousarray(np.concatenate([v, nv], axis=1))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {len(v)}\n" + props +
               f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
     rec = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
     rec["n"], rec["i"] = 3, f
@@ -210,9 +270,11 @@ def _query_grid(queryfn, axes, device):
     return grid.view(nx, ny, nz)
 
 
-def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None):
+def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None, normals=None):
     """The reference's extract_mesh (src/utils/mesh_utils.py:8-46), same argument order: density on an N^3 grid over `bbox`, the
     iso-surface at `level`, written to `output_path` as a PLY; returns (vertices, faces) on the device.
+    normals: None -- positions and faces only (the bytes are what they always were); True -- vertex_normals of the fine model are
+    written with the vertices (queryfn must be a Network); an array [V,3] is passed through to write_ply as it is.
 
     queryfn: a Network (the fast path: density_grid on its fine model), or a callable taking xyz [n,3] on the GPU whose
     result's [..., 0] is the density (the reference's protocol; evaluated on explicit grid points in batches).  level and N
@@ -230,6 +292,10 @@ def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None)
         raise ValueError("bbox is required: 6 numbers (min xyz, max xyz)")
     if not isinstance(output_path, (str, bytes)) and not hasattr(output_path, "__fspath__"):
         raise TypeError(f"output_path must be a path, got {output_path!r}")
+    if normals is True and not isinstance(queryfn, Network):
+        raise TypeError("normals=True needs a Network as queryfn (vertex_normals); pass an array [V,3] otherwise")
+    if normals is False:
+        normals = None
     axes, origin, step = grid_axes(bbox, N)
     if isinstance(queryfn, Network):
         grid = density_grid(queryfn, bbox, N, model="fine")
@@ -238,5 +304,7 @@ def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None)
             raise _lib.NerfLibraryError("extract_mesh needs a GPU; there is no CPU fallback")
         grid = _query_grid(queryfn, axes, torch.device("cuda", torch.cuda.current_device()))
     vertices, faces = isosurface(grid, level, origin, step)
-    write_ply(output_path, vertices, faces)
+    if normals is True:
+        normals = vertex_normals(queryfn, vertices, model="fine")
+    write_ply(output_path, vertices, faces, normals)
     return vertices, faces

@@ -122,6 +122,31 @@ class Network(nn.Module):
         self._packed[tag] = (key, out)
         return out
 
+    def packed_bwd(self, model=""):
+        """The transposed weight stream of the data-gradient chain (nerf_pack_model_bwd) for self.precision ("f32" / "f32x"), cached
+        and refreshed like packed(): what a frozen network's point gradients read (render_geometry, mesh.vertex_normals)."""
+        tag = "fine" if model == "fine" else ""
+        params = (self.model_fine if tag == "fine" else self.model).ordered_params()
+        dev = params[0].device
+        if dev.type != "cuda":
+            raise _lib.NerfLibraryError("Network parameters are on the CPU: call .cuda() first; the render path is "
+                                        "HIP-only (no CPU fallback)")
+        prec = _lib.PRECISIONS[self.precision]
+        lib = _lib.load()
+        nbytes = int(lib.nerf_packed_bwd_bytes(prec))
+        if nbytes <= 0:
+            raise NotImplementedError(f"the data-gradient chain runs in precision 'f32' or 'f32x', not {self.precision!r}")
+        key = (prec,) + tuple((p.data_ptr(), p._version) for p in params)
+        hit = self._packed.get("bwd" + tag)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        arr = _lib.ptr_array([p.detach().contiguous() for p in params], torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_pack_model_bwd(arr, out.data_ptr(), prec, _lib.stream_of(dev)), "nerf_pack_model_bwd")
+        self._packed["bwd" + tag] = (key, out)
+        return out
+
     def forward(self, inputs, viewdirs, valid_mask, model=""):
         """inputs [n,s,3], viewdirs [n,3], valid_mask BoolTensor[n,s] | None, model "" | "fine"
         -> raw [n,s,4] = (r,g,b,sigma) pre-activation (network.py:199-258).

@@ -64,6 +64,9 @@ class Renderer:
         # time; acts on the autograd path only (inference culling is `occupancy`)
         self.train_occupancy = None
         self.train_occupancy_every = 16
+        # render_geometry works ray block by ray block: a block's scratch is ~3.9 MB per ray (the saved rows and gradient
+        # rows of its 192 points), so 4096 rays -- a training step's batch -- are about 16 GB
+        self.geometry_block_rays = 4096
         if self.N_samples != _lib.N_SAMPLES or self.N_importance not in (0, _lib.N_IMPORTANCE):
             raise ValueError("HIP renderer is built for N_samples=64 and N_importance in {0,128}")
 
@@ -233,3 +236,85 @@ class Renderer:
                 ws.data_ptr(), ws.numel(),
                 _lib.ptr(rgb), _lib.ptr(depth), _lib.stream_of(dev)), "nerf_render_forward")
         return rgb, depth
+
+    def render_geometry(self, batch):
+        """rgb [n,3] and depth [n] as render(batch) returns them (bit-equal), plus the two other geometry outputs of the composited
+        network (fine; coarse when N_importance == 0): acc [n] = sum_i w_i, the accumulated opacity, and normal [n,3] = sum_i w_i n_i
+        with n_i = -grad sigma / |grad sigma| at sample i where sigma_i > 0, else 0 (include/nerf_mi355x.h, "geometry outputs").  The
+        normal is not renormalised: |normal| <= acc.  white_bkgd does not enter acc or normal.
+
+        Inference only: no autograd path (detached tensors under any grad mode; rays that require grad are refused).  The rays go
+        through in blocks of self.geometry_block_rays; the result does not depend on the blocking.  Per block: the staged calls
+        nerf_render_forward is made of, then nerf_density_gradient(positive_only) at the composited depths and
+        nerf_composite_normals.  Deterministic sampling in precision 'f32' / 'f32x'; see DESIGN section 6 for what is refused."""
+        rays_o, rays_d = batch["rays_o"], batch["rays_d"]
+        self.device = dev = rays_o.device
+        if dev.type != "cuda":
+            raise _lib.NerfLibraryError("Renderer.render_geometry needs rays on a GPU: the render path is HIP-only")
+        # refused before any launch, each with the mode's name
+        if rays_o.requires_grad or rays_d.requires_grad:
+            raise NotImplementedError("render_geometry has no autograd path: rays that require grad are refused (detach them; "
+                                      "render() is the differentiable call)")
+        prec_name = getattr(self.net, "precision", "f32")
+        if _lib.PRECISIONS[prec_name] not in (_lib.PREC_F32, _lib.PREC_F32X):
+            raise NotImplementedError(f"render_geometry runs in precision 'f32' or 'f32x', not {prec_name!r}: the gradient chain "
+                                      "has no fp16 form")
+        if self.fast_sampling:
+            raise NotImplementedError("render_geometry is not built with fast_sampling")
+        if self.occupancy is not None:
+            raise NotImplementedError("render_geometry is not built with occupancy culling: set Renderer.occupancy = None")
+        if bool(self.perturb) or self.task == "train":
+            raise NotImplementedError(f"render_geometry is not built for stochastic sampling (task={self.task!r}, "
+                                      f"perturb={bool(self.perturb)})")
+        block = self.geometry_block_rays
+        if isinstance(block, bool) or not isinstance(block, int) or block < 1:
+            raise ValueError(f"Renderer.geometry_block_rays must be an int >= 1 (rays), got {block!r}")
+        lib = _lib.load()
+        B, N, _ = rays_o.shape
+        n = B * N
+        o = rays_o.detach().reshape(n, 3).to(torch.float32).contiguous()
+        d = rays_d.detach().reshape(n, 3).to(torch.float32).contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out = {"rgb": new(n, 3), "depth": new(n), "acc": new(n), "normal": new(n, 3)}
+        if n == 0:
+            return out
+        prec = _lib.PRECISIONS[prec_name]
+        t_c, u = self._get_tables(dev)
+        fine = self.N_importance > 0
+        model = "fine" if fine else ""
+        pk_c = self.net.packed("")
+        pk = self.net.packed(model)                      # the composited network, and its transposed stream for the chain
+        pk_b = self.net.packed_bwd(model)
+        S_c, S = _lib.N_SAMPLES, _lib.N_SAMPLES + (_lib.N_IMPORTANCE if fine else 0)
+        nb_max = min(block, n)
+        raw_c = new(nb_max, S_c, 4)
+        t_sorted, raw_f = (new(nb_max, S), new(nb_max, S, 4)) if fine else (None, None)
+        grad = new(nb_max, S, 3)
+        ws = torch.empty(int(lib.nerf_density_gradient_point_bytes()) * ((nb_max * S + 31) // 32 * 32), dtype=torch.uint8, device=dev)
+        white = int(bool(self.white_bkgd))
+        with torch.cuda.device(dev):
+            st = _lib.stream_of(dev)
+            for r0 in range(0, n, block):
+                nb = min(block, n - r0)
+                ob, db = _lib.ptr(o[r0:r0 + nb]), _lib.ptr(d[r0:r0 + nb])
+                if fine:
+                    _lib.check(lib.nerf_mlp_forward_rays_density(ob, db, _lib.ptr(t_c), 0, nb, S_c, pk_c.data_ptr(), _lib.ptr(raw_c),
+                                                                 prec, st), "nerf_mlp_forward_rays_density")
+                    _lib.check(lib.nerf_sample_fine(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), nb, _lib.ptr(t_sorted), None, None,
+                                                    0.0, 0.0, st), "nerf_sample_fine")
+                    _lib.check(lib.nerf_mlp_forward_rays_for_compositing(ob, db, _lib.ptr(t_sorted), S, nb, S, pk.data_ptr(),
+                                                                         _lib.ptr(raw_f), prec, st),
+                               "nerf_mlp_forward_rays_for_compositing")
+                    raw, tv, stride = raw_f, t_sorted, S
+                else:
+                    _lib.check(lib.nerf_mlp_forward_rays(ob, db, _lib.ptr(t_c), 0, nb, S_c, pk_c.data_ptr(), _lib.ptr(raw_c), prec, st),
+                               "nerf_mlp_forward_rays")
+                    raw, tv, stride = raw_c, t_c, 0
+                _lib.check(lib.nerf_composite(_lib.ptr(raw), _lib.ptr(tv), stride, nb, S, white, _lib.ptr(out["rgb"][r0:r0 + nb]),
+                                              _lib.ptr(out["depth"][r0:r0 + nb]), None, st), "nerf_composite")
+                _lib.check(lib.nerf_density_gradient(ob, db, _lib.ptr(tv), stride, nb, S, pk.data_ptr(), pk_b.data_ptr(), 1, None,
+                                                     _lib.ptr(grad), prec, ws.data_ptr(), ws.numel(), st), "nerf_density_gradient")
+                _lib.check(lib.nerf_composite_normals(_lib.ptr(raw), _lib.ptr(tv), stride, nb, S, _lib.ptr(grad),
+                                                      _lib.ptr(out["normal"][r0:r0 + nb]), _lib.ptr(out["acc"][r0:r0 + nb]), st),
+                           "nerf_composite_normals")
+        return out

@@ -6,6 +6,8 @@ reference's src/utils/mesh_utils.py extract_mesh is for).
     python examples/extract_mesh.py --level 32                 # the reference's cfg.level; default: picked from the grid
     python examples/extract_mesh.py --precision f16            # fp16 density (PSNR-level accuracy)
     python examples/extract_mesh.py --normals                  # vertex normals (nx ny nz) from the density gradient: smooth shading
+    python examples/extract_mesh.py --keep-largest 1 --colors  # the object alone, without floaters, coloured by the network
+    python examples/extract_mesh.py --min-triangles 100        # everything bigger than a crumb
 
 Needs an MI355X and the built library (python -c "import __graft_entry__ as g; g.build()")."""
 import argparse
@@ -30,6 +32,11 @@ def main():
     ap.add_argument("--precision", default="f32", choices=["f32", "f16", "f32x"])
     ap.add_argument("--normals", action="store_true",
                     help="write unit vertex normals -grad sigma / |grad sigma| (nerf.vertex_normals; f32 / f32x)")
+    ap.add_argument("--keep-largest", type=int, default=None, metavar="K",
+                    help="keep the K connected components with the most triangles (nerf.filter_components)")
+    ap.add_argument("--min-triangles", type=int, default=None, metavar="M", help="keep the connected components with at least M triangles")
+    ap.add_argument("--colors", action="store_true",
+                    help="write vertex colours (red green blue): the network's colour seen head-on from outside (nerf.vertex_colors; f32 / f32x)")
     ap.add_argument("--out", default="mesh.ply")
     args = ap.parse_args()
 
@@ -42,10 +49,14 @@ def main():
         grid = nerf.density_grid(net, args.bbox, args.n)
         level = 0.5 * (grid.median().item() + grid.max().item())
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    vertices, faces = nerf.extract_mesh(net, level, args.bbox, args.out, args.n, normals=True if args.normals else None)
+    vertices, faces = nerf.extract_mesh(net, level, args.bbox, args.out, args.n, normals=True if args.normals else None,
+                                        min_triangles=args.min_triangles, keep_largest=args.keep_largest,
+                                        colors=True if args.colors else None)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
-    print("{}^3 grid, {}, level {:.4g}: {} vertices, {} triangles in {:.1f} ms (grid + surface{} + file)".format(
-        args.n, args.precision, level, vertices.shape[0], faces.shape[0], dt * 1e3, " + vertex normals" if args.normals else ""))
+    print("{}^3 grid, {}, level {:.4g}: {} vertices, {} triangles in {:.1f} ms (grid + surface{}{}{} + file)".format(
+        args.n, args.precision, level, vertices.shape[0], faces.shape[0], dt * 1e3,
+        " + component filter" if args.keep_largest is not None or args.min_triangles is not None else "",
+        " + vertex normals" if args.normals else "", " + vertex colours" if args.colors else ""))
     print("wrote", args.out)
 
 

@@ -521,6 +521,37 @@ int32_t nerf_density_gradient(const float* rays_o, const float* rays_d, const fl
 int32_t nerf_composite_normals(const float* raw, const float* tvals, int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                                const float* grad, float* normal, float* acc, void* stream);
 
+/* ---- mesh clean-up: connected components of an indexed triangle mesh, and the filter that keeps whole components (DESIGN section
+ * 2.11; what users of the reference's src/utils/mesh_utils.py:45 get from trimesh's split) ---------------------------------------
+ * faces [T,3] int32 over the vertex ids 0..V-1.  Two vertices are connected when a face names both; components are the transitive
+ * closure.  vertex_label[v] = the SMALLEST vertex id of v's component; a vertex that no face names is a component of its own with 0
+ * faces.  face_label[t] = vertex_label of the face's first vertex.  A face with any index outside [0, V) joins nothing, has the label
+ * -1, belongs to no component and is never read through (a guard against writing outside the buffers, not an error).  Duplicate and
+ * degenerate faces (v0 == v1) are faces like any other.
+ * Table: one row per component, ascending label: comp_label[c], comp_faces[c] (faces with that label), comp_vertices[c]; the caller
+ * gives room for V rows (every vertex may be alone), the first C = *n_components (DEVICE int) are written, the rest is left untouched.
+ * Lock-free union-find that always links the larger root under the smaller one: the root of a tree is its minimum whatever the
+ * arrival order, the counts are integer atomic adds and the table is ordered by a scan, so two runs write the same bytes.
+ * V = 0: C = 0 and every face label is -1.  T = 0: every vertex is its own component.  V or T above 2^31 - 1: NERF_ERR_INVALID_ARG
+ * before any launch or pointer is looked at (workspace_bytes returns -1).  workspace: nerf_mesh_components_workspace_bytes(V, T),
+ * which covers both nerf_mesh_components and nerf_mesh_filter_* (they use it one after the other).
+ *
+ * Filter: component `l` is kept iff keep[l] != 0 (keep: V bytes, indexed by LABEL, i.e. by the component's smallest vertex id).  The
+ * kept vertices and faces come out in their original order, the faces re-indexed; vertex_index[i] is the old id of new vertex i (to
+ * gather normals, colours, ...).  Faces with label -1 are dropped.  Two phases as for nerf_isosurface_*: nerf_mesh_filter_count
+ * fills `workspace` and writes counts[0] = V', counts[1] = T'; the caller reads them, allocates out_vertices [V',3], out_faces [T',3]
+ * and vertex_index [V'] (or more rows: the rest is left untouched) and calls nerf_mesh_filter_emit with the same sizes and
+ * workspace.  Emit takes where it writes from the workspace alone.  No atomics. */
+int64_t nerf_mesh_components_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int32_t nerf_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_vertices, void* workspace,
+                             int32_t* vertex_label, int32_t* face_label, int32_t* comp_label, int32_t* comp_faces,
+                             int32_t* comp_vertices, int32_t* n_components, void* stream);
+int32_t nerf_mesh_filter_count(const int32_t* vertex_label, const int32_t* face_label, const uint8_t* keep,
+                               int64_t n_vertices, int64_t n_faces, void* workspace, int32_t* counts, void* stream);
+int32_t nerf_mesh_filter_emit(const float* vertices, const int32_t* faces, int64_t n_vertices, int64_t n_faces,
+                              const void* workspace, float* out_vertices, int32_t* out_faces, int32_t* vertex_index,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

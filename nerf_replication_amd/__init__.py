@@ -24,13 +24,14 @@ _LAZY = {
     "load_network": ".checkpoint", "load_model": ".checkpoint", "save_model": ".checkpoint",
     "density_grid": ".mesh", "isosurface": ".mesh", "write_ply": ".mesh", "extract_mesh": ".mesh",
     "density_gradient": ".mesh", "vertex_normals": ".mesh",
+    "mesh_components": ".mesh", "filter_components": ".mesh", "vertex_colors": ".mesh", "write_ply_colors": ".mesh",
     "OccupancyGrid": ".occupancy",
 }
 _SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy")
 
 __all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model",
            "density_grid", "isosurface", "write_ply", "extract_mesh", "density_gradient", "vertex_normals",
-           "OccupancyGrid"]
+           "mesh_components", "filter_components", "vertex_colors", "write_ply_colors", "OccupancyGrid"]
 
 
 def __getattr__(name):

@@ -115,6 +115,11 @@ _PROTOS = {
     "nerf_density_gradient": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _c.c_int32, _F, _F, _c.c_int32,
                                            _F, _c.c_int64, _c.c_void_p]),
     "nerf_composite_normals": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_void_p]),
+    # mesh clean-up: connected components and the component filter (mesh.py)
+    "nerf_mesh_components_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int64]),
+    "nerf_mesh_components": (_c.c_int32, [_F, _c.c_int64, _c.c_int64, _F, _F, _F, _F, _F, _F, _F, _c.c_void_p]),
+    "nerf_mesh_filter_count": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _F, _F, _c.c_void_p]),
+    "nerf_mesh_filter_emit": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int64, _F, _F, _F, _F, _c.c_void_p]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -2565,3 +2565,5 @@ int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d,
 #include "nerf_occupancy.hip.inc"
 // ---- geometry outputs: nerf_density_gradient and nerf_composite_normals
 #include "nerf_normals.hip.inc"
+// ---- mesh clean-up: nerf_mesh_components and nerf_mesh_filter_*
+#include "nerf_mesh_components.hip.inc"

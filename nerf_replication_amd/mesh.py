@@ -5,9 +5,13 @@ cfg.resolution = 256, src/config/config.py:10-12).
 The density comes from the fused MLP kernels (a grid line is a ray: nerf_mlp_forward_rays_density), the surface from the
 nerf_isosurface_* kernels (marching tetrahedra, include/nerf_mi355x.h); DESIGN.md section 2.8 has the definitions and where
 this departs from the reference's function, which is not runnable as written.  Vertex normals are the density gradient of the
-fused data-gradient chain at the vertices (nerf_density_gradient).  No CPU fallback: every number comes
-out of a HIP kernel, torch only moves tensors (and normalises the [V,3] gradient of vertex_normals).
+fused data-gradient chain at the vertices (nerf_density_gradient).  Clean-up: the connected components of
+the mesh and the filter that keeps whole components (nerf_mesh_components, nerf_mesh_filter_*), the role of
+trimesh's split behind the reference's mesh_utils.py:45, and vertex colours from the network itself.  No CPU fallback: every number
+comes out of a HIP kernel, torch only moves tensors (and normalises the [V,3] gradient of vertex_normals, takes the sigmoid of the
+[V,3] colours, and picks rows of the per-component table).
 """
+import collections
 import ctypes
 import numbers
 
@@ -227,13 +231,180 @@ def vertex_normals(net, vertices, model="fine"):
     return torch.where(ok, -g / torch.where(ok, nrm, torch.ones_like(nrm)), torch.zeros_like(g))
 
 
+ComponentTable = collections.namedtuple("ComponentTable", ["label", "faces", "vertices"])
+ComponentTable.__doc__ = """One row per connected component, ascending label: its label (smallest vertex id), face count and vertex
+count; three device tensors [C] int32."""
+
+
+def _count(x, name):
+    if x is None:
+        return None
+    if isinstance(x, bool) or not isinstance(x, numbers.Integral) or x < 0:
+        raise ValueError(f"{name} must be a non-negative int, got {x!r}")
+    return int(x)
+
+
+def _mesh_arrays(vertices, faces):
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError("faces must be an integer tensor [T,3]")
+    if vertices is not None and (not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or
+                                 not vertices.is_floating_point()):
+        raise ValueError("vertices must be a floating-point tensor [V,3]")
+
+
+class _Components:
+    """The labels and the table of one mesh, with the workspace they share with the filter."""
+
+    def __init__(self, faces, n_vertices):
+        lib = _lib.load()
+        if not faces.is_cuda:
+            raise _lib.NerfLibraryError("mesh_components needs the faces on a GPU (cuda) device; there is no CPU fallback")
+        dev = faces.device
+        self.faces = faces.detach().to(torch.int32).contiguous()
+        self.V, self.T = V, T = int(n_vertices), int(faces.shape[0])
+        nbytes = int(lib.nerf_mesh_components_workspace_bytes(V, T))
+        if nbytes < 0:
+            raise _lib.NerfLibraryError(f"nerf_mesh_components_workspace_bytes refused {V} vertices and {T} faces")
+        with torch.cuda.device(dev):
+            self.workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            self.vertex_label = torch.empty(V, dtype=torch.int32, device=dev)
+            self.face_label = torch.empty(T, dtype=torch.int32, device=dev)
+            rows = torch.empty((3, V), dtype=torch.int32, device=dev)
+            n_comp = torch.empty(1, dtype=torch.int32, device=dev)
+            _lib.check(lib.nerf_mesh_components(self.faces.data_ptr(), T, V, self.workspace.data_ptr(), self.vertex_label.data_ptr(),
+                                                self.face_label.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(),
+                                                n_comp.data_ptr(), _lib.stream_of(dev)), "nerf_mesh_components")
+            C = int(n_comp.item())
+        self.table = ComponentTable(rows[0, :C], rows[1, :C], rows[2, :C])
+
+    def select(self, min_triangles, keep_largest):
+        """keep [V] uint8, indexed by label: the rows of the table (C rows, C << V) that pass, as a few torch operations."""
+        label, n_faces, _ = self.table
+        ok = torch.ones_like(label, dtype=torch.bool)
+        if min_triangles is not None:
+            ok &= n_faces >= min_triangles
+        if keep_largest is not None:
+            order = torch.sort(-n_faces.to(torch.int64), stable=True).indices        # most faces first, ties by the smaller label
+            top = torch.zeros_like(ok)
+            top[order[:keep_largest]] = True
+            ok &= top
+        keep = torch.zeros(self.V, dtype=torch.uint8, device=label.device)
+        keep[label[ok].to(torch.int64)] = 1
+        return keep
+
+    def filter(self, vertices, keep):
+        lib = _lib.load()
+        dev = self.faces.device
+        V, T = self.V, self.T
+        with torch.cuda.device(dev):
+            st = _lib.stream_of(dev)
+            counts = torch.empty(2, dtype=torch.int32, device=dev)
+            _lib.check(lib.nerf_mesh_filter_count(self.vertex_label.data_ptr(), self.face_label.data_ptr(), _lib.ptr(keep, torch.uint8), V, T,
+                                                  self.workspace.data_ptr(), counts.data_ptr(), st), "nerf_mesh_filter_count")
+            n_v, n_t = (int(c) for c in counts.cpu())
+            out_v = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+            out_f = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+            index = torch.empty(n_v, dtype=torch.int32, device=dev)
+            if n_v > 0:
+                _lib.check(lib.nerf_mesh_filter_emit(_lib.ptr(vertices), self.faces.data_ptr(), V, T, self.workspace.data_ptr(),
+                                                     out_v.data_ptr(), out_f.data_ptr(), index.data_ptr(), st), "nerf_mesh_filter_emit")
+        return out_v, out_f, index
+
+
+def mesh_components(faces, n_vertices):
+    """Connected components of an indexed triangle mesh on the device: (vertex_label [V] int32, face_label [T] int32, table).
+
+    faces: device tensor [T,3] of vertex ids below n_vertices.  Two vertices are connected when a face names both; the label of a
+    vertex is the smallest vertex id of its component, the label of a face that of its first vertex; a face with an index outside
+    [0, V) joins nothing and has the label -1.  table: ComponentTable(label, faces, vertices), three [C] tensors, ascending label; a
+    vertex no face names is a component with 0 faces.  Lock-free union-find in HIP (nerf_mesh_components, include/nerf_mi355x.h);
+    repeatable to the byte.  One host synchronisation: the number of components."""
+    _mesh_arrays(None, faces)
+    if isinstance(n_vertices, bool) or not isinstance(n_vertices, numbers.Integral) or not 0 <= n_vertices <= 2 ** 31 - 1:
+        raise ValueError(f"n_vertices must be an int in [0, 2^31 - 1], got {n_vertices!r}")
+    if faces.shape[0] > 2 ** 31 - 1:
+        raise ValueError("more than 2^31 - 1 faces")
+    c = _Components(faces, n_vertices)
+    return c.vertex_label, c.face_label, c.table
+
+
+def _filter_arguments(min_triangles, keep_largest, required):
+    min_triangles, keep_largest = _count(min_triangles, "min_triangles"), _count(keep_largest, "keep_largest")
+    if required and min_triangles is None and keep_largest is None:
+        raise ValueError("filter_components needs min_triangles, keep_largest or both")
+    return min_triangles, keep_largest
+
+
+def filter_components(vertices, faces, min_triangles=None, keep_largest=None):
+    """Drop whole connected components of a mesh: (vertices' [V',3] float32, faces' [T',3] int32, vertex_index [V'] int32).
+
+    min_triangles=m keeps the components with at least m faces; keep_largest=k keeps the k components with the most faces, ties
+    going to the smaller label (the smaller lowest vertex id); with both, a component must pass both.  The kept vertices and faces
+    stay in their original order, faces re-indexed; vertex_index holds the old id of every new vertex (vertices' is
+    vertices[vertex_index]; gather normals or colours with it).  Faces with an index outside [0, V) are dropped.  The components,
+    the counting and the copying are HIP (nerf_mesh_components, nerf_mesh_filter_*); choosing rows of the per-component table is a
+    few torch operations.  Two host synchronisations: the number of components, and the two counts."""
+    min_triangles, keep_largest = _filter_arguments(min_triangles, keep_largest, True)
+    _mesh_arrays(vertices, faces)
+    if vertices.shape[0] > 2 ** 31 - 1 or faces.shape[0] > 2 ** 31 - 1:
+        raise ValueError("more than 2^31 - 1 vertices or faces")
+    if not vertices.is_cuda or vertices.device != faces.device:
+        raise _lib.NerfLibraryError("filter_components needs vertices and faces on one GPU (cuda) device; there is no CPU fallback")
+    comps = _Components(faces, vertices.shape[0])
+    return comps.filter(vertices.detach().to(torch.float32).contiguous(), comps.select(min_triangles, keep_largest))
+
+
+def _head_on(normals):
+    """The direction of travel of a ray that meets the surface head-on from outside: -normal, (0, 0, 1) where the normal is zero."""
+    ahead = torch.tensor([0.0, 0.0, 1.0], dtype=normals.dtype, device=normals.device)
+    return torch.where((normals == 0).all(dim=-1, keepdim=True), ahead, -normals)
+
+
+def vertex_colors(net, vertices, viewdirs=None, model="fine"):
+    """Colours [V,3] fp32 in [0,1] of `net`'s coarse ("") or fine model at the vertices [V,3]: sigmoid(raw[:, :3]) of Network.forward
+    (inputs [V,1,3], viewdirs [V,3], inference path, every precision of net.precision).  viewdirs=None looks at every vertex head-on
+    from outside: the direction of travel is -vertex_normals(net, vertices, model) ((0, 0, 1) where the normal is the zero vector;
+    the normals need net.precision 'f32' / 'f32x').  The raw values come out of the fused MLP kernel; the sigmoid of the [V,3] result
+    is one torch operation."""
+    if not isinstance(net, Network):
+        raise TypeError("vertex_colors needs a nerf_replication_amd Network")
+    if model not in ("", "fine"):
+        raise ValueError(f'model must be "" (coarse) or "fine", got {model!r}')
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be a tensor [V,3]")
+    if viewdirs is not None and (not isinstance(viewdirs, torch.Tensor) or viewdirs.shape != vertices.shape):
+        raise ValueError(f"viewdirs must be a tensor of the vertices' shape {tuple(vertices.shape)}")
+    dev = net.packed(model).device                 # raises for a network on the CPU
+    pts = vertices.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if pts.shape[0] == 0:
+        return torch.empty((0, 3), dtype=torch.float32, device=dev)
+    if viewdirs is None:
+        viewdirs = _head_on(vertex_normals(net, pts, model=model))
+    dirs = viewdirs.detach().to(device=dev, dtype=torch.float32).contiguous()
+    with torch.no_grad():
+        raw = net.forward(pts[:, None, :], dirs, None, model=model)
+    return torch.sigmoid(raw[:, 0, :3])
+
+
 def write_ply(path, vertices, faces, normals=None):
     """Binary little-endian PLY: `float` x y z per vertex (followed by `float` nx ny nz when `normals` [V,3] is given), `uchar int`
-    index lists per face."""
+    index lists per face.  write_ply_colors writes colours as well."""
+    _write_ply(path, vertices, faces, normals, None)
+
+
+def write_ply_colors(path, vertices, faces, normals=None, colors=None):
+    """write_ply with vertex colours: `uchar` red green blue per vertex, behind nx ny nz when both are given.  colors [V,3] are floats
+    in [0,1], written as floor(clip(c, 0, 1) * 255 + 0.5), exactly (evaluated in float64; NaN gives 0).  With colors=None the bytes are
+    write_ply's.  (A function of its own: write_ply's parameter list is part of the tested surface and stays as it is.)"""
+    _write_ply(path, vertices, faces, normals, colors)
+
+
+def _write_ply(path, vertices, faces, normals, colors):
     v = np.ascontiguousarray(torch.as_tensor(vertices).detach().cpu().numpy(), dtype="<f4")
     f = np.ascontiguousarray(torch.as_tensor(faces).detach().cpu().numpy(), dtype="<i4")
     if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
         raise ValueError("write_ply needs vertices [V,3] and faces [T,3]")
+    n_v = len(v)
     props = "property float x\nproperty float y\nproperty float z\n"
     if normals is not None:
         nv = np.ascontiguousarray(torch.as_tensor(normals).detach().cpu().numpy(), dtype="<f4")
@@ -241,8 +412,16 @@ def write_ply(path, vertices, faces, normals=None):
             raise ValueError(f"write_ply needs normals of the vertices' shape {v.shape}, got {nv.shape}")
         v = np.ascontiguousarray(np.concatenate([v, nv], axis=1))
         props += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        c = np.asarray(torch.as_tensor(colors).detach().cpu().numpy(), dtype=np.float64)
+        if c.shape != (n_v, 3):
+            raise ValueError(f"write_ply_colors needs colors of the vertices' shape {(n_v, 3)}, got {c.shape}")
+        vrec = np.empty(n_v, dtype=np.dtype([("f", "<f4", (v.shape[1],)), ("c", "u1", (3,))]))      # packed: no padding
+        vrec["f"], vrec["c"] = v, np.floor(np.clip(np.nan_to_num(c, nan=0.0), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+        v = vrec
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {len(v)}\n" + props +
+              f"element vertex {n_v}\n" + props +
               f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
     rec = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
     rec["n"], rec["i"] = 3, f
@@ -270,11 +449,17 @@ def _query_grid(queryfn, axes, device):
     return grid.view(nx, ny, nz)
 
 
-def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None, normals=None):
+def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None, normals=None, min_triangles=None, keep_largest=None,
+                 colors=None):
     """The reference's extract_mesh (src/utils/mesh_utils.py:8-46), same argument order: density on an N^3 grid over `bbox`, the
     iso-surface at `level`, written to `output_path` as a PLY; returns (vertices, faces) on the device.
     normals: None -- positions and faces only (the bytes are what they always were); True -- vertex_normals of the fine model are
     written with the vertices (queryfn must be a Network); an array [V,3] is passed through to write_ply as it is.
+    min_triangles / keep_largest: filter_components between the surface and the normals / colours (floaters are dropped before
+    anything is evaluated at them); the filtered (vertices, faces) are written and returned.  colors: None -- no colours; True --
+    vertex_colors of the fine model, each vertex seen head-on from outside (queryfn must be a Network); an array [V,3] in [0,1] is
+    passed through to write_ply_colors.  Arrays must match the vertices that are written.  With the defaults the result and the file are what
+    they always were.
 
     queryfn: a Network (the fast path: density_grid on its fine model), or a callable taking xyz [n,3] on the GPU whose
     result's [..., 0] is the density (the reference's protocol; evaluated on explicit grid points in batches).  level and N
@@ -296,6 +481,11 @@ def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None,
         raise TypeError("normals=True needs a Network as queryfn (vertex_normals); pass an array [V,3] otherwise")
     if normals is False:
         normals = None
+    if colors is True and not isinstance(queryfn, Network):
+        raise TypeError("colors=True needs a Network as queryfn (vertex_colors); pass an array [V,3] otherwise")
+    if colors is False:
+        colors = None
+    min_triangles, keep_largest = _filter_arguments(min_triangles, keep_largest, False)
     axes, origin, step = grid_axes(bbox, N)
     if isinstance(queryfn, Network):
         grid = density_grid(queryfn, bbox, N, model="fine")
@@ -304,7 +494,12 @@ def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None,
             raise _lib.NerfLibraryError("extract_mesh needs a GPU; there is no CPU fallback")
         grid = _query_grid(queryfn, axes, torch.device("cuda", torch.cuda.current_device()))
     vertices, faces = isosurface(grid, level, origin, step)
-    if normals is True:
+    if min_triangles is not None or keep_largest is not None:
+        vertices, faces, _ = filter_components(vertices, faces, min_triangles, keep_largest)
+    made_normals = normals is True
+    if made_normals:
         normals = vertex_normals(queryfn, vertices, model="fine")
-    write_ply(output_path, vertices, faces, normals)
+    if colors is True:                             # (the normals just computed are the ones vertex_colors would compute again)
+        colors = vertex_colors(queryfn, vertices, _head_on(normals) if made_normals else None, model="fine")
+    _write_ply(output_path, vertices, faces, normals, colors)
     return vertices, faces

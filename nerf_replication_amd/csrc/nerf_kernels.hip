@@ -21,19 +21,7 @@
 #define NERF_X_INST extern template
 #include "nerf_kernels_x.inst.inc"
 
-// Timing-only switches (tools/ab_bench.py) change the NUMERICS of the kernels they are compiled into.  A library
-// built with any of them set must say so: it only compiles with -DNERF_TIMING_BUILD, and then reports it through
-// nerf_build_flags(), which the Python loader (and any other binder) checks -- so a stray -D can no longer produce a
-// library that passes nerf_abi_version() and computes garbage.
-#define NERF_ANY_TIMING_HACK (NERF_F32_HACK_NOLOAD || NERF_F32_HACK_NOBIAS || NERF_F32_HACK_NORELU || NERF_F32_HACK_NOPE || \
-                              NERF_F32_ASM_OVERRUN || NERF_F32_HACK_NOSAVE || NERF_BWD_HACK_NOMASK || NERF_F16_HACK_NOADV || \
-                              NERF_F16_HACK_NOBARRIER || NERF_WG_HACK_NOATOMIC || NERF_F16_HACK_NOEPI || NERF_F16_HACK_NORELU || \
-                              NERF_F32X_HACK_NOADV || NERF_F32X_HACK_NOPE || NERF_F32X_HACK_NOEPI || NERF_F32X_HACK_SAVE_NOSTORE || \
-                              NERF_XB_HACK_NOSTORE)
-// (a structural knob of the SAVE forward also breaks results when switched off: no rows stored)
-#if (NERF_ANY_TIMING_HACK || NERF_SAVE_TAPS == 0) && !defined(NERF_TIMING_BUILD)
-#error "a NERF_*_HACK_* / NERF_F32_ASM_OVERRUN timing switch is set: such a library computes wrong results; build it with -DNERF_TIMING_BUILD (tools/ab_bench.py does) so that nerf_build_flags() reports it"
-#endif
+#include "nerf_timing_guard.h"         // after the kernel includes: refuses a build with a stray timing switch
 
 namespace {
 
@@ -1450,8 +1438,7 @@ void nerf_rays_bwd_kernel(long long n_rays, const float* __restrict__ t_c, long 
 bool dead_tile_list_available(long long P, int precision) {
   const char* env = getenv("NERF_DEAD_TILE_SKIP");
   const bool want = !(env && env[0] == '0');
-  return want && (precision == NERF_PREC_F32 || precision == NERF_PREC_F32X) && NERF_WGRAD_ASM && NERF_WGVEC_ASM &&
-         P % 32 == 0 && P / 32 <= 0x7fffffffLL;
+  return want && (precision == NERF_PREC_F32 || precision == NERF_PREC_F32X) && P % 32 == 0 && P / 32 <= 0x7fffffffLL;
 }
 __global__ void nerf_check_stamp_kernel(const float* __restrict__ stamp, float* __restrict__ poison) {
   if (threadIdx.x == 0 && __float_as_int(stamp[0]) != 0) poison[0] = __int_as_float(0x7fc00000);
@@ -1778,7 +1765,7 @@ static int32_t wgrad_impl(const float* dz, int64_t ldz, int32_t zc0, int32_t n_o
   hipStream_t st = (hipStream_t)stream;
   const bool aligned = ldz % 4 == 0 && ldh % 4 == 0 && zc0 % 4 == 0 && hc0 % 4 == 0 &&
                        (uintptr_t)dz % 16 == 0 && (uintptr_t)hin % 16 == 0;
-  if (n_out == 256 && n_in == 256 && aligned && NERF_WGRAD_ASM && n_points % 16 == 0 && n_points / 16 >= blocks &&
+  if (n_out == 256 && n_in == 256 && aligned && n_points % 16 == 0 && n_points / 16 >= blocks &&
       ldz * 8 < (1ll << 31) && ldh * 8 < (1ll << 31)) {
     a.osplit = 2; a.isplit = 2;        // whole groups of 8 k-steps per workgroup: the clamp-free asm-load form
     WgradBatch wb;
@@ -1787,7 +1774,7 @@ static int32_t wgrad_impl(const float* dz, int64_t ldz, int32_t zc0, int32_t n_o
     else hipLaunchKernelGGL(nerf_wgrad256_f32_asm_kernel<false>, grid, blk, 0, st, wb);
   } else if (live) {
     // list mode needs the asm-ring form of the small-layer kernels (whole 32-point tiles)
-    if (!(NERF_WGVEC_ASM && n_points % 32 == 0 && ldz < (1ll << 28) && ldh < (1ll << 28)))
+    if (!(n_points % 32 == 0 && ldz < (1ll << 28) && ldh < (1ll << 28)))
       return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_wgrad: live-tile list on a shape without an asm-ring kernel");
     const dim3 lgrid((unsigned)num_cus());
 #define VECL(AV, BV, OS, IS) do { a.osplit = OS; a.isplit = IS; \
@@ -1808,13 +1795,13 @@ static int32_t wgrad_impl(const float* dz, int64_t ldz, int32_t zc0, int32_t n_o
   // point range splits into whole groups of PF k-steps per workgroup (every training shape does: P is a multiple of 64)
 #define VEC(AV, BV, PF, OS, IS) do { \
     a.osplit = OS; a.isplit = IS; \
-    if (NERF_WGVEC_ASM && n_points % (2 * PF) == 0 && n_points / (2 * PF) >= 1 && ldz < (1ll << 28) && ldh < (1ll << 28)) { \
+    if (n_points % (2 * PF) == 0 && n_points / (2 * PF) >= 1 && ldz < (1ll << 28) && ldh < (1ll << 28)) { \
       long long g = n_points / (2 * PF); \
       if (g > num_cus()) g = num_cus(); \
       hipLaunchKernelGGL((nerf_wgrad_vec_f32_asm_kernel<AV, BV, PF>), dim3((unsigned)g), blk, 0, st, a); \
     } else hipLaunchKernelGGL((nerf_wgrad_vec_f32_kernel<AV, BV>), grid, blk, 0, st, a); \
   } while (0)
-  else if (n_out == 256 && n_in <= 64 && aligned) VEC(4, 1, NERF_WGVEC_PF41, 2, 2);         // PE -> 256 (layers 0 and 5)
+  else if (n_out == 256 && n_in <= 64 && aligned) VEC(4, 1, 16, 2, 2);         // PE -> 256 (layers 0 and 5)
   else if (n_out == 128 && n_in == 256 && aligned) VEC(4, 2, 16, 1, 4);        // views_linears.0, feature part
   else if (n_out == 128 && n_in <= 32) VEC(1, 1, 16, 4, 1);                    // views_linears.0, direction part
   else if (n_out <= 32 && n_in == 256 && ldh % 2 == 0 && hc0 % 2 == 0 && (uintptr_t)hin % 8 == 0)
@@ -2125,7 +2112,7 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
     hipLaunchKernelGGL(nerf_wgrad256_bf16x3_kernel, dim3((unsigned)(slices * n_jobs)), dim3(256), 0, (hipStream_t)stream, w);
     rc = check_launch("nerf_wgrad256_bf16x3_kernel");
     if (rc) return rc;
-  } else if (NERF_WGRAD_ASM && P % 16 == 0 && P / 16 >= num_cus() / 8) {
+  } else if (P % 16 == 0 && P / 16 >= num_cus() / 8) {
     // fp32 MFMA, in one launch of the asm-load kernel
     WgradBatch wb;
     wb.n_jobs = n_jobs;
@@ -2295,7 +2282,7 @@ int32_t nerf_mlp_backward_masked(const float* rays_o, const float* rays_d, const
   if (precision != NERF_PREC_F32 && precision != NERF_PREC_F32X) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_mlp_backward_masked: f32 or f32x only");
   const long long P = n_rays * (int64_t)n_samples;
   // compact rows past the count are kept out by the live-tile list alone: the list-mode kernels must exist (whole 32-point tiles)
-  if (!(NERF_WGRAD_ASM && NERF_WGVEC_ASM) || P % 32 != 0)
+  if (P % 32 != 0)
     return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_mlp_backward_masked: needs the live-tile kernels and a point count that is a multiple of 32");
   hipStream_t st = (hipStream_t)stream;
   float* draw_c = (float*)workspace;

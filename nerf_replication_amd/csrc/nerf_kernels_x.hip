@@ -24,3 +24,4 @@
 #include "nerf_mlp_bwd_f32.hip.inc"    // BwdArgs, TrainGrad
 #include "nerf_mlp_bwd_f32x.hip.inc"
 #include "nerf_kernels_x.inst.inc"
+#include "nerf_timing_guard.h"         // after the kernel includes: refuses a build with a stray timing switch

@@ -88,7 +88,7 @@ void nerf_mlp_bwd_f32_kernel(BwdArgs a) {
   const float* __restrict__ pk = a.packed_bwd;
   // the weight ring in asm-load form like the forward kernels: possible since the chain no longer spills (the ReLU
   // masks come as sign bits, the rows go out through the taps); tools/check_asm_stream.py covers these instances too
-  typename nerf_select<(NERF_F32_ASM_LOADS != 0), AStream, WStream>::type ws;
+  AStream ws;
   const bool dens = a.density_only != 0;                             // (uniform)
   wstream_start(ws, reinterpret_cast<const f32x4*>(pk + (dens ? kBwdOffW7T : 0)), lane);
 

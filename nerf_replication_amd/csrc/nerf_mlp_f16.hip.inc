@@ -40,13 +40,7 @@ __device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
 typedef __attribute__((address_space(3))) char lds_char;
 typedef const __attribute__((address_space(3))) float lds_cfloat;
 
-// tuning knobs (tools/ab_bench.py builds variants with -D...)
-#ifndef NERF_F16_PF_RING
-#define NERF_F16_PF_RING 4
-#endif
-#ifndef NERF_F16_PF_DIST
-#define NERF_F16_PF_DIST 3
-#endif
+// timing-only switches (tools/ab_bench.py builds variants with -D...)
 #ifndef NERF_F16_HACK_NOADV
 #define NERF_F16_HACK_NOADV 0       // timing-only: never advance the LDS ring (wrong results)
 #endif
@@ -59,8 +53,8 @@ typedef const __attribute__((address_space(3))) float lds_cfloat;
 #ifndef NERF_F16_HACK_NOEPI
 #define NERF_F16_HACK_NOEPI 0       // timing-only: no bias / fp16 pack / ReLU after an out-tile (wrong results)
 #endif
-constexpr int kPfRing = NERF_F16_PF_RING;   // A-fragment prefetch ring in registers (4 VGPRs per slot)
-constexpr int kPfDist = NERF_F16_PF_DIST;   // fragments in flight ahead of the consumer (may reach into the next chunk)
+// A-fragment prefetch ring in registers (4 VGPRs per slot); fragments in flight ahead of the consumer (may reach into the next chunk)
+constexpr int kPfRing = 4, kPfDist = 3;
 
 struct FragRing {
   const char* gsrc;        // (wave-uniform) byte address of (chunk 0, this wave's first fragment): stays in SGPRs

@@ -145,15 +145,6 @@ __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
 // asynchronous LDS-DMAs issued before the positional encoding is computed, so the 32 bias reads at every layer boundary
 // and the head-weight reads are ds_read_b128 with ~100 cycles of latency instead of global loads with > 1000 -- with one
 // wave per SIMD that latency was exposed ten times per tile (round 1 measured the boundary bias loads at 1.7 %).
-#ifndef NERF_F32_UNROLL_PAIRS        // 1: let the compiler unroll the (X->Y, Y->X) layer-pair loop (it unrolls by two: no register
-                                    // shuffles at the back edge, but twice the code): 2.5 % SLOWER (instruction cache), A/B.  Off.
-#define NERF_F32_UNROLL_PAIRS 0
-#endif
-#ifndef NERF_F32_FAST_SINCOS         // 1: Cody-Waite sincos (1e-7 abs, as the f32x / backward kernels) instead of ocml's sincosf in the forward encodings:
-                                    // +0.57 % (A/B), but raw moves by up to 1.1e-4 and a different ray of the white-noise parity scene flips (PSNR 65 -> 49 dB
-                                    // on that fixture): not worth leaving the <= 2 ulp agreement with the reference's sin / cos.  Off.
-#define NERF_F32_FAST_SINCOS 0
-#endif
 constexpr int kTailFloats = 3072;                      // [kOffBias, kOffBias + 3072): everything but the 4 head biases
 static_assert(nerf::kOffHeadBias - nerf::kOffBias == kTailFloats, "LDS tail = biases + views bias + head weights");
 typedef const __attribute__((address_space(3))) float tail_float;
@@ -176,20 +167,6 @@ __device__ __forceinline__ void load_bias(f32x16 (&acc)[NT], tail_float* bias_h)
 // layer boundaries without ever draining (every layer has a multiple of kRing steps).
 constexpr int kRing = 16;   // ring slots (4 VGPRs each)
 constexpr int kPF = 8;       // blocks in flight ahead of the consumer
-template <bool C, class A, class B> struct nerf_select { typedef A type; };
-template <class A, class B> struct nerf_select<false, A, B> { typedef B type; };
-struct WStream;
-__device__ __forceinline__ void stream_drain(WStream&) {}       // compiler-scheduled loads need no drain
-struct WStream {
-  const f32x4* p;          // this lane's float4 of the NEXT block to consume
-  f32x4 ring[kRing];
-};
-__device__ __forceinline__ void wstream_start(WStream& ws, const f32x4* p_lane0, int lane) {
-  const f32x4* p = p_lane0 + lane;
-  ws.p = p;
-#pragma unroll
-  for (int i = 0; i < kPF; ++i) ws.ring[i] = p[i * 64];
-}
 
 // A "tap" is called once per 4-k-step group of a GEMM with the (tile, quad) of the INPUT registers that group consumes,
 // X[t][4q .. 4q+3] = features 32t + 8q + 4h + (0..3) of the lane's point.  The training kernels use it to store an
@@ -197,20 +174,15 @@ __device__ __forceinline__ void wstream_start(WStream& ws, const f32x4* p_lane0,
 // layer -- instead of 32 stores back to back after the producing layer: every s_waitcnt vmcnt(N) of the weight ring
 // also waits for older stores (one in-order counter), so a burst of stores exposed their full write latency once per
 // layer (measured: 1.64 ms of an 8.2 ms SAVE forward, 1.0 ms of the backward chain, tools/ab_train.py).
-#ifndef NERF_TAP_VMCNT_SLACK
-#define NERF_TAP_VMCNT_SLACK 0    // 1: ring waits leave the newest tap store in flight (vmcnt(9)); 0: vmcnt(8) also waits for it.
-                                  // Measured (tools/ab_train.py): 1 is 5 % SLOWER on the SAVE forward -- store latency is not what the taps cost
-#endif
 #ifndef NERF_SAVE_TAPS
 #define NERF_SAVE_TAPS 1
 #endif
-struct NoTap { static constexpr int kStores = 0; static constexpr bool kIsTap = false; __device__ __forceinline__ void operator()(int, int, const f32x16&) const {} };
+struct NoTap { static constexpr bool kIsTap = false; __device__ __forceinline__ void operator()(int, int, const f32x16&) const {} };
 // store the quad to its row-major [point][feature] row
 struct SignBits { unsigned w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u; };     // bit 16*(t&1) + 4q + e of word t>>1 (scalars: stays in registers)
 template <bool GRAD, bool BITS = false>   // GRAD: a gradient row of the backward chain (only the timing switches differ)
 struct StoreTap {
   static constexpr bool kIsTap = true;
-  static constexpr int kStores = 0;   // vector-memory operations it issues per group that a ring wait may leave in flight
   float* row;              // this lane's row + 4h
   SignBits* sb;            // BITS: collects the sign bits of the row on the way (compile-time switch: no branch, no array)
   __device__ __forceinline__ void operator()(int t, int q, const f32x16& Xt) const {
@@ -243,44 +215,11 @@ __device__ __forceinline__ auto save_tap(float* row, SignBits* sb) {
   else return NoTap{};
 }
 
-// acc[j] += W(j, :) . X   over KT input tiles (16 k-steps each).
-// Interleaved form: the NT blocks of a 4-k-step group are consumed component by component, so
-// consecutive MFMAs always hit different accumulators (no back-to-back dependent MFMAs); the ring
-// (2 x 8 blocks) holds the current group(s) while the next 8 blocks of the stream are in flight.
-template <int KT, int NT, bool LAST = false, class TAP = NoTap>      // (LAST only matters to the asm-load form below)
-__device__ __forceinline__ void gemm_tiles(f32x16 (&acc)[NT], const f32x16 (&X)[KT], WStream& ws, TAP tap = TAP()) {
-  static_assert(kRing == 16 && kPF == 8, "interleaved form: ring 16, 8 blocks in flight");
-  static_assert((KT * 4 * NT) % kRing == 0, "layer steps must be a multiple of the ring");
-#pragma unroll
-  for (int g = 0; g < KT * 4; ++g) {
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int i = g * NT + j;
-      ws.ring[(i + kPF) % kRing] = ws.p[(i + kPF) * 64];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const int t = g >> 2, r0 = (g & 3) * 4;
-    tap(t, g & 3, X[t]);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const f32x4 a = ws.ring[(g * NT + j) % kRing];
-        acc[j] = mfma32(a[q], X[t][r0 + q], acc[j]);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  ws.p += KT * 4 * NT * 64;
-}
-
-// The same stream consumed through inline-asm loads (inference instance).  What it buys: (1) the loads use the
-// scalar-base form `global_load_dwordx4 v, v_laneoff, s[base] offset:imm` (no per-load 64-bit VALU address);
-// (2) ONE `s_waitcnt vmcnt(kPF)` per k-group instead of the eight the compiler places in front of the first row's
-// MFMAs -- with one wave per SIMD every instruction issued between MFMAs is time off the matrix pipe.
-#ifndef NERF_F32_ASM_LOADS
-#define NERF_F32_ASM_LOADS 1
-#endif
+// The stream is consumed through inline-asm loads (every instance, training and backward included).  What that buys
+// over loads the compiler schedules: (1) the loads use the scalar-base form
+// `global_load_dwordx4 v, v_laneoff, s[base] offset:imm` (no per-load 64-bit VALU address); (2) ONE
+// `s_waitcnt vmcnt(kPF)` per k-group instead of the eight the compiler places in front of the first row's MFMAs --
+// with one wave per SIMD every instruction issued between MFMAs is time off the matrix pipe.
 struct AStream {
   const char* base;        // (uniform) byte address of block 0 of the NEXT block to consume
   unsigned voff;           // this lane's byte offset inside a block (lane * 16)
@@ -333,7 +272,6 @@ __device__ __forceinline__ void stream_drain(AStream& as) {
 }
 // after a wave-uniform early exit the compiler's divergence analysis no longer proves the stream base uniform (it would
 // feed a VGPR pair to the "s" operand of the asm loads): re-assert it, two v_readfirstlane
-__device__ __forceinline__ void stream_reassert_uniform(WStream&) {}
 __device__ __forceinline__ void stream_reassert_uniform(AStream& as) {
   const unsigned long long b = reinterpret_cast<unsigned long long>(as.base);
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
@@ -344,10 +282,14 @@ __device__ __forceinline__ void wstream_start(AStream& as, const f32x4* p_lane0,
   as.voff = (unsigned)lane * 16u;
   astream_load<8>(as, 0, 0);
 }
-// LAST: the stream of this tile ends with this call.  Unlike the compiler-scheduled form, the asm form must not
-// prefetch past the end: the compiler sees those ring registers as dead and reuses them while the loads are still in
-// flight (found by scanning the ISA: the rgb-head temporaries landed in v[0:3] of the ring).  So the last groups issue
-// no loads and wait for correspondingly fewer outstanding ones.
+// acc[j] += W(j, :) . X   over KT input tiles (16 k-steps each).
+// Interleaved form: the NT blocks of a 4-k-step group are consumed component by component, so
+// consecutive MFMAs always hit different accumulators (no back-to-back dependent MFMAs); the ring
+// (2 x 8 blocks) holds the current group(s) while the next 8 blocks of the stream are in flight.
+// LAST: the stream of this tile ends with this call.  The asm loads must not prefetch past the end: the compiler sees
+// those ring registers as dead and reuses them while the loads are still in flight (found by scanning the ISA: the
+// rgb-head temporaries landed in v[0:3] of the ring).  So the last groups issue no loads and wait for
+// correspondingly fewer outstanding ones.
 template <int KT, int NT, bool LAST = false, class TAP = NoTap>
 __device__ __forceinline__ void gemm_tiles(f32x16 (&acc)[NT], const f32x16 (&X)[KT], AStream& as, TAP tap = TAP()) {
   static_assert(kRing == 16 && kPF == 8, "interleaved form: ring 16, 8 blocks in flight");
@@ -390,10 +332,12 @@ __device__ __forceinline__ void gemm_tiles(f32x16 (&acc)[NT], const f32x16 (&X)[
       continue;
     } else if constexpr (!LAST || NERF_F32_ASM_OVERRUN) {
       astream_load<NT>(as, g * NT + kPF, (g * NT + kPF) % kRing);
-      // everything but the kPF newest loads has landed: this group's blocks (a storing tap's row store of the previous group is
-      // waited for with them: letting it stay in flight measured 5 % slower)
+      // everything but the kPF newest loads has landed: this group's blocks.  A storing tap's row store of the previous
+      // group is older than those loads, so vmcnt(kPF) waits for it too; vmcnt(kPF + 1), which leaves it in flight,
+      // measured 5 % SLOWER on the SAVE forward (store latency is not what the taps cost).  Both calls wait for vmcnt(kPF);
+      // they stay two call sites because merging them changes the schedule the compiler emits for the SAVE instances
       if (g == 0) astream_wait<NT>(as, (g * NT) % kRing);            // (first group of a call: no tap store issued yet)
-      else astream_wait<NT, kPF + TAP::kStores>(as, (g * NT) % kRing);
+      else astream_wait<NT, kPF>(as, (g * NT) % kRing);
     } else {
       // tail of the tile's stream: nothing is issued past its end, and the wait allows only the loads that really are
       // younger than this group's blocks (g is a constant once the loop is unrolled: the switch folds to one case)
@@ -523,6 +467,8 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   }
 
   // ---- positional encoding straight into B-operand layout (nerf_layout.h pe_*_feat) -------
+  // ocml's sincosf stays: the Cody-Waite sincos of the f32x / backward kernels (1e-7 abs) measured +0.57 % here, but raw
+  // moves by up to 1.1e-4 and a different ray of the white-noise parity scene flips (PSNR 65 -> 49 dB on that fixture)
   f32x16 PE[2], DPE[1];
   {
     const float hs = h ? 32.0f : 1.0f;                 // lane-half 1 evaluates octaves 5..9
@@ -579,12 +525,10 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   }
 
   const float* __restrict__ pk = a.packed;
-  // running weight stream in asm-load form.  The asm loads are asynchronous behind the compiler's back: were it to
-  // spill or copy a ring register between a load and the group's s_waitcnt it would move stale data (seen in the
-  // backward kernel, which spills 37 VGPRs: wrong gradients; it keeps compiler-scheduled loads).  Every instance that
-  // uses the asm form is proven hazard-free on its ISA by tools/check_asm_stream.py (CPU test suite) and checked bit
-  // for bit against the compiler-scheduled form (tools/ab_bench.py).
-  typename nerf_select<(NERF_F32_ASM_LOADS != 0), AStream, WStream>::type ws;
+  // running weight stream.  The asm loads are asynchronous behind the compiler's back: were it to spill or copy a ring
+  // register between a load and the group's s_waitcnt it would move stale data (wrong results, or a fault).  So every
+  // instance is proven hazard-free on its ISA by tools/check_asm_stream.py (every build, and the CPU test suite).
+  AStream ws;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // the tail DMAs (issued before the encodings) have landed
   wstream_start(ws, reinterpret_cast<const f32x4*>(pk), lane);
   tail_float* bias = tail + h * 128;                                 // + 256 per layer
@@ -615,6 +559,8 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
 
   float sigma = 0.0f;
   constexpr int kPairs = 3;                           // layer 7 is peeled off below: every instance ends or restarts its stream there
+  // not unrolled: unrolled by two the compiler saves the register shuffles at the back edge, but twice the code measured
+  // 2.5 % SLOWER (instruction cache)
 #pragma unroll 1
   for (int pr = 0; pr < kPairs; ++pr) {
     // X -> Y : L1, L3, L5   (consumes h0, h2, h4)
@@ -725,8 +671,7 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   wstream_start(ws, reinterpret_cast<const f32x4*>(a.fold + kFoldOffWvf), lane);
   load_bias<4>(V, tail + kTailFloats + h * 64);
   gemm_tiles<8, 4, false>(V, Y, ws);
-  gemm_tiles<1, 4, true>(V, DPE, ws);    // last call of the tile (the compiler-scheduled form runs kPF blocks past the
-                                         // stream end: still inside the fold buffer; the asm form stops at the end)
+  gemm_tiles<1, 4, true>(V, DPE, ws);    // last call of the tile: the ring stops at the stream end
   if constexpr (SAVE) {                  // nothing consumes the views row through a GEMM: stored here, as the tile ends
     const u32x4 b = relu_bits_tiles<4>(V);
     if (!NERF_F32_HACK_NOSAVE) bits_out[8 * 64] = b;

@@ -28,9 +28,6 @@ constexpr float kXLoScale = 2048.0f, kXLoInv = 1.0f / 2048.0f;
 #ifndef NERF_F32X_HACK_SAVE_NOSTORE
 #define NERF_F32X_HACK_SAVE_NOSTORE 0   // training forward without its row stores
 #endif
-#ifndef NERF_F32X_STAGE
-#define NERF_F32X_STAGE 1               // 0: the training forward's lanes store their own quads directly (A/B: tools/ab_train.py)
-#endif
 #ifndef NERF_F32X_HACK_NOEPI
 #define NERF_F32X_HACK_NOEPI 0      // only the first of the eight epilogue chunks of every tile
 #endif
@@ -429,12 +426,11 @@ struct XSaveBits { unsigned w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u; };      // (scal
 
 // chunk Q (0..7) of the SAVE forward's epilogue of tile MM: values 2Q, 2Q+1 -- combine, ReLU on the bit pattern (2 v_max_i32), split
 // (xsplit_pair: same roundings as split16 value by value); every second chunk writes one 16-byte quad of this lane's row to the
-// LDS stage (NERF_F32X_STAGE=0: straight to `row`, this lane's row-major fp32 activation row + 4 h).  BITS: the ReLU sign bits of this lane's values in the layout of the fp32 SAVE forward (TrainSave::off_bits: bit
+// LDS stage.  BITS: the ReLU sign bits of this lane's values in the layout of the fp32 SAVE forward (TrainSave::off_bits: bit
 // 16 (MM & 1) + r of word MM >> 1 <-> accumulator register r of out-tile MM; the C/D layout of the 32x32 MFMAs is
 // dtype-independent): a rectified value is a non-negative integer, so "> 0" is min(bits, 1) -- v_min_u32 + v_lshl_or_b32 per value.
 template <bool RELU, bool BITS, int MM, int Q>
-__device__ __forceinline__ void xepilogue_chunk_s(XPending& t, h8* OUTh, h8* OUTl, float* __restrict__ row, const XRowStage& st,
-                                                  float (&keep)[2], XSaveBits& sb) {
+__device__ __forceinline__ void xepilogue_chunk_s(XPending& t, h8* OUTh, h8* OUTl, const XRowStage& st, float (&keep)[2], XSaveBits& sb) {
   f32x2 x;                      // (scalar fp32 instructions on purpose: xsplit_pair)
   x.x = fmaf(t.al[2 * Q], kXLoInv, t.ah[2 * Q]); x.y = fmaf(t.al[2 * Q + 1], kXLoInv, t.ah[2 * Q + 1]);
   if constexpr (RELU) {
@@ -458,24 +454,22 @@ __device__ __forceinline__ void xepilogue_chunk_s(XPending& t, h8* OUTh, h8* OUT
   xpending_emit(t, MM, Q, hi, lo, OUTh, OUTl);
   if (Q & 1) {
     f32x4 o4; o4.x = keep[0]; o4.y = keep[1]; o4.z = x.x; o4.w = x.y;
-    if constexpr (NERF_F32X_HACK_SAVE_NOSTORE) {}
-    else if constexpr (NERF_F32X_STAGE) xstage_put<(Q >> 1)>(st, o4);
-    else *reinterpret_cast<f32x4*>(row + 32 * MM + 8 * (Q >> 1)) = o4;
+    if constexpr (!NERF_F32X_HACK_SAVE_NOSTORE) xstage_put<(Q >> 1)>(st, o4);
   } else { keep[0] = x.x; keep[1] = x.y; }
 }
 
 // The SAVE forward's layer: the bias (16 floats per out-tile, accumulator-row order) is the hi accumulator's initial value; the
-// post-activation rows go through the LDS stage to `tile_rows` (NERF_F32X_STAGE=0: each lane's quads straight to `row`), the
-// sign-bit words of a rectified layer to `bits_dst`.
+// post-activation rows go through the LDS stage to `tile_rows`, the sign-bit words of a rectified layer to `bits_dst`.  (The
+// unnamed pointer is this lane's own row, which nothing stores to any more: the caller says why it is still computed.)
 template <int KS1, int KS2, int NM, int F0, bool RELU, bool BITS, int ROWB>
 __device__ __forceinline__ void gemmx_layer_s(XRing& r, lds_cfloat* bias_lds_h, const h8* B1h, const h8* B1l,
                                               const h8* B2h, const h8* B2l, h8* OUTh, h8* OUTl,
-                                              float* __restrict__ row, const XRowStage& st, float* tile_rows,
+                                              float* __restrict__ /*row*/, const XRowStage& st, float* tile_rows,
                                               unsigned* __restrict__ bits_dst) {
   static_assert(!BITS || RELU, "sign bits belong to rectified layers");
   XSaveBits sb;
   float keep[2] = {0.0f, 0.0f};
-  gemmx_layer_train<KS1, KS2, NM, F0, ROWB, NERF_F32X_STAGE && !NERF_F32X_HACK_SAVE_NOSTORE>(r, B1h, B1l, B2h, B2l, st, tile_rows,
+  gemmx_layer_train<KS1, KS2, NM, F0, ROWB, !NERF_F32X_HACK_SAVE_NOSTORE>(r, B1h, B1l, B2h, B2l, st, tile_rows,
     [&](XPending& cur, auto M) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) cur.al[i] = 0.0f;
@@ -487,7 +481,7 @@ __device__ __forceinline__ void gemmx_layer_s(XRing& r, lds_cfloat* bias_lds_h, 
       }
     },
     [&](XPending& t, auto MM, auto Q) {
-      xepilogue_chunk_s<RELU, BITS, decltype(MM)::value, decltype(Q)::value>(t, OUTh, OUTl, row, st, keep, sb);
+      xepilogue_chunk_s<RELU, BITS, decltype(MM)::value, decltype(Q)::value>(t, OUTh, OUTl, st, keep, sb);
     });
   if constexpr (BITS) {                                     // one coalesced 1-KiB block per wave and layer
     u32x4 w; w.x = sb.w0; w.y = sb.w1; w.z = sb.w2; w.w = sb.w3;
@@ -657,16 +651,15 @@ void nerf_mlp_f32x_kernel(MlpArgs a) {
     bool dead_wave = false;                                                                    // (wave-uniform)
     if constexpr (SAVE) {
       // training forward (gemmx_layer_s): every layer's post-activation output also goes to the row-major activation store through
-      // the LDS transpose (XRowStage, as in the backward chain; NERF_F32X_STAGE=0: each lane stores its own quads), the ReLU sign bits of this wave's 32 points to block
+      // the LDS transpose (XRowStage, as in the backward chain), the ReLU sign bits of this wave's 32 points to block
       // (tile * 4 + wave) of the TrainSave bit blocks.  With the MFMA accumulators in VGPRs (this unit's XFLAGS) all instances fit
       // the register file (12 bytes of scratch, touched at the tile boundaries); with hipcc's default allocation only the
       // density-only instance did (LAB_NOTEBOOK.md A9, A10).
       const long long tile32 = tile * kXWaves + wave;
-      // addresses as (wave-uniform 64-bit base) + (32-bit lane offset): the stores take the base from SGPRs
+      // this lane's row (+ 4 h) in a row-major region, as (wave-uniform 64-bit base) + (32-bit lane offset).  Nothing stores through
+      // it since every row goes through the LDS stage, but the opaque redefinition of its lane offset still shapes the register
+      // allocation of the four SAVE instances: taking it out changes their code, so that is a performance change to be measured.
       const unsigned lrow = (unsigned)(wave * 32 + (lane & 31));          // this lane's row inside the 128-point tile
-      // (the opaque redefinition of the lane offset keeps the compiler from computing all eleven row pointers at the top of the
-      // tile and spilling them: each is built where its layer starts)
-      // this lane's row (+ 4 h) in a row-major region: what NERF_F32X_STAGE=0 stores to
       auto srow = [&](long long off, int width) -> float* {
         const char* base = reinterpret_cast<const char*>(a.save + off + tile * (long long)(kXTilePts * width));
         unsigned lo = lrow;
@@ -677,6 +670,9 @@ void nerf_mlp_f32x_kernel(MlpArgs a) {
       auto trow = [&](long long off, int width) -> float* {
         return a.save + off + (tile * (long long)kXTilePts + wave * 32) * width;
       };
+      // the bit blocks as (wave-uniform 64-bit base) + (32-bit lane offset): the stores take the base from SGPRs.  (The opaque
+      // redefinition of the lane offset keeps the compiler from computing all nine pointers at the top of the tile and spilling them:
+      // each is built where its layer starts)
       auto bdst = [&](int which) -> unsigned* {
         const char* base = reinterpret_cast<const char*>(a.save + TrainSave::off_bits(P) + TrainSave::bits_block(tile32, which));
         unsigned lo = (unsigned)lane;

@@ -181,9 +181,6 @@ void nerf_wgrad256_f32_kernel(WgradArgs a) {
 // whole groups of 8 k-steps (16 points) per workgroup, so no row is ever out of range.  The asm loads complete behind
 // the compiler's back (see nerf_mlp_f32.hip.inc): the consumed slot is refilled only after the 16 MFMAs that read it
 // have been issued, and tools/check_asm_stream.py covers this kernel too.
-#ifndef NERF_WGRAD_ASM
-#define NERF_WGRAD_ASM 1
-#endif
 // Several layers can share one launch ("jobs": blockIdx % n_jobs picks the layer, as in nerf_wgrad_bf16x3.hip.inc):
 // a workgroup then integrates n_jobs times more points before its 65 536 atomic adds, and workgroups that finish
 // together add to different matrices.
@@ -370,12 +367,6 @@ void nerf_wgrad_vec_f32_kernel(WgradArgs a) {
 // Host contract: n_points % (2 PF) == 0 and at least one group per workgroup, so no row is ever out of range; lanes
 // whose columns do not exist read column 0 of their operand (finite or not: an MFMA row/column only ever reaches its
 // own outputs, and those are never written).  tools/check_asm_stream.py covers every instance.
-#ifndef NERF_WGVEC_ASM
-#define NERF_WGVEC_ASM 1
-#endif
-#ifndef NERF_WGVEC_PF41             // k-steps in flight per wave, per shape <floats per lane of dZ, of the input>
-#define NERF_WGVEC_PF41 16          // PE -> 256: 4 MFMAs per k-step
-#endif
 template <int N> struct WgAsmLd;
 template <> struct WgAsmLd<1> {
   static __device__ __forceinline__ void ld(float& d, unsigned voff, const char* base) {

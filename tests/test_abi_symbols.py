@@ -70,9 +70,10 @@ def test_product_never_imports_oracle():
 
 
 def test_inline_asm_weight_stream_has_no_register_hazard():
-    """The fp32 inference kernel fills its weight ring with inline-asm loads that complete behind the compiler's
-    back; tools/check_asm_stream.py compiles the kernel to ISA and proves that no instruction touches a ring
-    register between its load and the s_waitcnt that covers it (a spill, copy or reuse there would move stale data)."""
+    """The fp32 MLP kernels (and others) fill a register ring with inline-asm loads that complete behind the compiler's
+    back; tools/check_asm_stream.py compiles both units to ISA and proves, for every kernel with such a load, that no
+    instruction touches a ring register between its load and the wait that covers it (a spill, copy or reuse there
+    would move stale data)."""
     import shutil
     import subprocess
     import sys
@@ -96,7 +97,14 @@ def test_inline_asm_weight_stream_has_no_register_hazard():
     if not proven:
         r = subprocess.run(tool, capture_output=True, text=True)
         assert r.returncode == 0, r.stdout + r.stderr
-        assert r.stdout.count(" 0 hazards") == 28 and "no asm loads found" not in r.stdout    # 12 fp32 + 8 small-layer + 8 split-fp16 instances
+        # the checker finds its kernels by content (an inline-asm load): every instance of every template that has one
+        import collections
+        import re
+        found = collections.Counter(m.group(1) for m in re.finditer(r"^_Z\d+(nerf_\w+?_kernel)\S*: [1-9]\d* asm loads, 0 hazards$", r.stdout, re.M))
+        assert found == {"nerf_mlp_f32_kernel": 8, "nerf_mlp_bwd_f32_kernel": 2, "nerf_wgrad256_f32_asm_kernel": 2,
+                         "nerf_wgrad_vec_f32_asm_kernel": 8, "nerf_wgrad256_bf16x3_kernel": 1,
+                         "nerf_mlp_f32x_kernel": 4}, r.stdout        # (f32x: the inference instances; the SAVE instances have none by design)
+        assert r.stdout.count(" hazards") == 25, r.stdout
     # the checker itself: re-creating the prefetch past the stream end (whose registers the compiler reuses) must be caught
     bad = subprocess.run(tool, capture_output=True, text=True, env=dict(os.environ, NERF_CHECK_EXTRA_FLAGS="-DNERF_F32_ASM_OVERRUN=1 -DNERF_TIMING_BUILD"))
     assert bad.returncode == 1 and "touched before its wait" in bad.stdout
@@ -117,4 +125,11 @@ def test_stray_timing_switch_does_not_build():
         r = subprocess.run(base + [flag], capture_output=True, text=True)
         assert r.returncode != 0 and "timing switch is set" in r.stderr, (flag, r.stderr[-400:])
     ok = subprocess.run(base, capture_output=True, text=True)
+    assert ok.returncode == 0, ok.stderr[-400:]
+    # the split-fp16 unit has the same guard: a switch that acts only there must not build either
+    srcx = os.path.join(REPO, "nerf_replication_amd", "csrc", "nerf_kernels_x.hip")
+    basex = [hipcc, "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fsyntax-only", srcx]
+    r = subprocess.run(basex + ["-DNERF_F32X_HACK_NOPE=1"], capture_output=True, text=True)
+    assert r.returncode != 0 and "timing switch is set" in r.stderr, r.stderr[-400:]
+    ok = subprocess.run(basex, capture_output=True, text=True)
     assert ok.returncode == 0, ok.stderr[-400:]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved in-process A/B timing of kernel build variants (cdna_hip_programming.md rule 24).
 
-    python tools/ab_bench.py f16 "base:" "ring8:-DNERF_F16_PF_RING=8 -DNERF_F16_PF_DIST=6" ...
+    python tools/ab_bench.py f16 "base:" "noadv:-DNERF_F16_HACK_NOADV=1" "noepi:-DNERF_F16_HACK_NOEPI=1" ...
 
 Builds one libnerf variant per spec into nerf_replication_amd/csrc/variants/, then times
 nerf_mlp_forward_rays (fine model, 192 samples/ray) for each, round-robin, HIP events, and prints

@@ -2,7 +2,7 @@
 """Interleaved in-process A/B timing of build variants of the SMALL-LAYER weight-gradient kernels (companion of
 tools/ab_bench.py / ab_train.py).
 
-    python tools/ab_wgrad.py "base:" "c++:-DNERF_WGVEC_ASM=0" "pf32:-DNERF_WGVEC_PF41=32" ...
+    python tools/ab_wgrad.py "base:" "noatomic:-DNERF_WG_HACK_NOATOMIC=1" ...
 
 Per variant and round: nerf_wgrad on the six small shapes of a training step's fine pass (AB_POINTS points, default
 4096 x 192), each between its own pair of HIP events, in the layouts mlp_backward_impl uses.  Developer tool."""

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Static check of the kernels that fill a register ring with inline-asm loads: nerf_mlp_f32_kernel<*, false> (the
-inference instances), nerf_wgrad256_f32_asm_kernel and every nerf_wgrad_vec_f32_asm_kernel instance.
+"""Static check of every kernel that fills registers with inline-asm loads (the fp32 MLP kernels' weight ring, the
+weight-gradient kernels' operand rings, the split-fp16 inference kernels' LDS reads, ...).  The kernels are found by
+what they contain, in both translation units: a new kernel or instance with such a load is checked without being named.
 
 The asm `global_load_dwordx4` loads are asynchronous behind the compiler's back: between a load and the asm
 `s_waitcnt vmcnt(N)` that covers it, NO instruction may read or write the destination registers (the compiler could
@@ -22,20 +23,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # of the library being built; the default below mirrors csrc/Makefile for stand-alone runs
 FLAGS = "-O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize --offload-arch=gfx950"
 HIPCC = "/opt/rocm/bin/hipcc"
-KERNELS = ["_Z19nerf_mlp_f32_kernelILb1ELb0ELb0ELb0EEv7MlpArgs", "_Z19nerf_mlp_f32_kernelILb0ELb0ELb0ELb0EEv7MlpArgs",
-           "_Z19nerf_mlp_f32_kernelILb1ELb1ELb0ELb0EEv7MlpArgs", "_Z19nerf_mlp_f32_kernelILb0ELb1ELb0ELb0EEv7MlpArgs",
-           "_Z19nerf_mlp_f32_kernelILb1ELb1ELb1ELb0EEv7MlpArgs", "_Z19nerf_mlp_f32_kernelILb1ELb0ELb1ELb0EEv7MlpArgs",
-           "_Z19nerf_mlp_f32_kernelILb1ELb0ELb0ELb1EEv7MlpArgs", "_Z19nerf_mlp_f32_kernelILb1ELb1ELb0ELb1EEv7MlpArgs",
-           "_Z23nerf_mlp_bwd_f32_kernelILb0EEv7BwdArgs", "_Z23nerf_mlp_bwd_f32_kernelILb1EEv7BwdArgs",
-           "_Z28nerf_wgrad256_f32_asm_kernelILb0EEv10WgradBatch", "_Z28nerf_wgrad256_f32_asm_kernelILb1EEv10WgradBatch"]
-# every instance of these templates found in the ISA is checked too (their ring depth is part of the mangled name)
-KERNEL_PREFIXES = ["_Z29nerf_wgrad_vec_f32_asm_kernelI", "_Z20nerf_mlp_f32x_kernelI"]
 # The library is two translation units (csrc/Makefile): the split-fp16 kernels are compiled with XFLAGS on top of the common
 # flags (nerf_kernels_x.hip says why); each unit is checked on the flags IT is built with.
 XFLAGS = "-mllvm -amdgpu-mfma-vgpr-form=1"
 CSRC = os.path.join(REPO, "nerf_replication_amd", "csrc")
-UNITS = [{"src": os.path.join(CSRC, "nerf_kernels.hip"), "x": False, "kernels": KERNELS, "prefixes": ["_Z29nerf_wgrad_vec_f32_asm_kernelI"]},
-         {"src": os.path.join(CSRC, "nerf_kernels_x.hip"), "x": True, "kernels": [], "prefixes": ["_Z20nerf_mlp_f32x_kernelI"]}]
+UNITS = [{"src": os.path.join(CSRC, "nerf_kernels.hip"), "x": False}, {"src": os.path.join(CSRC, "nerf_kernels_x.hip"), "x": True}]
 
 
 def vregs(text):
@@ -47,10 +39,23 @@ def vregs(text):
     return out
 
 
-def check(lines, name):
-    a = next(i for i, l in enumerate(lines) if l.startswith(name + ":"))
-    b = next(i for i, l in enumerate(lines) if i > a and ".amdhsa_kernel " + name in l)
-    K = lines[a:b]
+def kernels(lines):
+    """(name, code lines) of every kernel of a unit's ISA: from its label to its .amdhsa_kernel descriptor."""
+    label = {}
+    for i, l in enumerate(lines):
+        m = re.match(r"^([A-Za-z_$][\w$.]*):", l)
+        if m:
+            label.setdefault(m.group(1), i)
+    out = []
+    for i, l in enumerate(lines):
+        m = re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", l)
+        if m:
+            out.append((m.group(1), lines[label[m.group(1)]:i]))
+    return sorted(out)
+
+
+def check(K):
+    """K: the code lines of one kernel.  -> (number of inline-asm loads, hazards)"""
     ins, label_at = [], {}
     for i, l in enumerate(K):
         t = l.strip()
@@ -135,21 +140,19 @@ def main():
             if pr.wait() != 0:
                 raise SystemExit(f"compiling {u['src']} failed")
             lines = open(out).read().split("\n")
-            found = sorted({m.group(1) for l in lines for m in [re.match(r"^(_Z\w+):", l)] if m and m.group(1).startswith(tuple(u["prefixes"]))})
-            for pre in u["prefixes"]:
-                if not any(k.startswith(pre) for k in found):
-                    print("    (no instance of", pre, "found)")
-                    bad += 1
-            for k in u["kernels"] + found:
-                n, hz = check(lines, k)
+            checked = 0
+            for k, K in kernels(lines):
+                n, hz = check(K)
+                if n == 0:
+                    continue                                   # no inline-asm load: nothing the compiler cannot see
+                checked += 1
                 print(f"{k}: {n} asm loads, {len(hz)} hazards")
                 for kind, ld, use in hz[:10]:
                     print("   ", kind, "|", ld, "|", use)
                 bad += len(hz)
-                if n == 0:
-                    # the training (SAVE) instances of nerf_mlp_f32x_kernel read LDS with compiler-scheduled loads on purpose
-                    save_f32x = k.startswith("_Z20nerf_mlp_f32x_kernelI") and re.match(r"_Z20nerf_mlp_f32x_kernelILb[01]ELb1E", k)
-                    print("    (compiler-scheduled instance: nothing to check)" if save_f32x else "    (no asm loads found: NERF_F32_ASM_LOADS off?)")
+            if checked == 0:                                   # both units have such kernels: their loads were not recognised
+                print(f"    (no kernel with an inline-asm load found in {os.path.basename(u['src'])})")
+                bad += 1
     return 1 if bad else 0
 
 

@@ -1,5 +1,5 @@
 // Iso-surface extraction: marching tetrahedra over the six-tetrahedra (Kuhn) split of every grid cell (DESIGN.md section 2.8).
-// Included at the end of nerf_kernels.hip (uses its fail / check_launch / align256).
+// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH / Carver).
 //
 // Grid point (i, j, k) has the linear id g = (i*ny + j)*nz + k and the value field[g * stride]; a cell is named by its lowest
 // corner.  Every edge of the split runs from a point p to p + e, e in {0,1}^3 \ 0: seven edge types t = 4 ex + 2 ey + ez, owned
@@ -13,10 +13,11 @@
 // rows whatever the field holds by then.  Vertex ids ascend with (owner id, edge type), triangles with (cell id, tetrahedron,
 // triangle); nothing is atomic, so two runs write the same bytes.
 #include "nerf_isosurface_table.inc"
+#include "nerf_scan.hip.inc"
 
 namespace {
 
-constexpr int kIsoBlock = 256;
+constexpr int kIsoBlock = kRankBlock;          // iso_block_exclusive (nerf_scan.hip.inc)
 
 struct IsoGrid {
   int nx, ny, nz;
@@ -32,28 +33,6 @@ __device__ __forceinline__ void iso_ijk(const IsoGrid& G, long long g, int& i, i
 }
 __device__ __forceinline__ long long iso_corner_offset(const IsoGrid& G, int o) {
   return (long long)((o >> 2) & 1) * G.ny * G.nz + (long long)((o >> 1) & 1) * G.nz + (o & 1);
-}
-
-// exclusive rank of `v` among the block's threads (v < 2^16 per thread; two 16-bit fields are scanned as one int by the caller)
-__device__ __forceinline__ int iso_block_exclusive(int v, int* s_wave, int& block_total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += u;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  int before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kIsoBlock / 64; ++w) {
-    const int c = s_wave[w];
-    if (w < wave) before += c;
-    total += c;
-  }
-  block_total = total;
-  return before + inc - v;
 }
 
 __global__ __launch_bounds__(kIsoBlock)
@@ -91,32 +70,20 @@ void nerf_isosurface_count_kernel(const float* __restrict__ field, IsoGrid G, fl
 
 // block totals -> exclusive offsets in place, counts = (vertices, triangles); one workgroup, as nerf_compact_scan_kernel.  The
 // sums are 64-bit: totals beyond int32 give counts = (-1, -1) (and meaningless offsets: nerf_isosurface_emit must not follow).
-__global__ __launch_bounds__(1024)
+struct IsoSums {                              // (vertices, triangles)
+  long long v, t;
+  __device__ IsoSums operator+(const IsoSums& o) const { return {v + o.v, t + o.t}; }
+  __device__ IsoSums operator-(const IsoSums& o) const { return {v - o.v, t - o.t}; }
+};
+__global__ __launch_bounds__(kScanThreads)
 void nerf_isosurface_scan_kernel(int* __restrict__ block_v, int* __restrict__ block_t, long long n_blocks, int* __restrict__ counts) {
-  __shared__ long long s_v[1024], s_t[1024];
-  const int tid = threadIdx.x;
-  const long long per = (n_blocks + 1023) / 1024;
-  const long long b0 = tid * per < n_blocks ? tid * per : n_blocks, b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
-  long long cv = 0, ct = 0;
-  for (long long b = b0; b < b1; ++b) { cv += block_v[b]; ct += block_t[b]; }
-  s_v[tid] = cv; s_t[tid] = ct;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {                 // inclusive Hillis-Steele scan
-    const long long v = tid >= d ? s_v[tid - d] : 0, t = tid >= d ? s_t[tid - d] : 0;
-    __syncthreads();
-    s_v[tid] += v; s_t[tid] += t;
-    __syncthreads();
-  }
-  long long pv = s_v[tid] - cv, pt = s_t[tid] - ct;
-  for (long long b = b0; b < b1; ++b) {
-    const int v = block_v[b], t = block_t[b];
-    block_v[b] = (int)pv; block_t[b] = (int)pt;
-    pv += v; pt += t;
-  }
-  if (tid == 1023) {
-    const bool fits = s_v[1023] <= 0x7fffffffLL && s_t[1023] <= 0x7fffffffLL;
-    counts[0] = fits ? (int)s_v[1023] : -1;
-    counts[1] = fits ? (int)s_t[1023] : -1;
+  __shared__ IsoSums s_sum[kScanThreads];
+  const IsoSums total = workgroup_scan(n_blocks, s_sum, [&](long long b) { return IsoSums{block_v[b], block_t[b]}; },
+                                       [&](long long b, IsoSums pos) { block_v[b] = (int)pos.v; block_t[b] = (int)pos.t; });
+  if (threadIdx.x == 0) {
+    const bool fits = total.v <= 0x7fffffffLL && total.t <= 0x7fffffffLL;
+    counts[0] = fits ? (int)total.v : -1;
+    counts[1] = fits ? (int)total.t : -1;
   }
 }
 
@@ -193,7 +160,20 @@ int iso_sizes(const char* entry, int32_t nx, int32_t ny, int32_t nz, int64_t str
   return NERF_OK;
 }
 inline bool iso_no_cells(const IsoGrid& G) { return G.nx < 2 || G.ny < 2 || G.nz < 2; }
-inline long long iso_blocks(const IsoGrid& G) { return (G.n + kIsoBlock - 1) / kIsoBlock; }
+
+// The workspace: one word per grid point, then the vertex and the triangle totals of every 256-point block
+struct IsoWorkspace {
+  long long n_blocks;
+  unsigned* words; int* block_v; int* block_t;
+  int64_t bytes;
+  IsoWorkspace(const void* base, const IsoGrid& G) : n_blocks((G.n + kIsoBlock - 1) / kIsoBlock) {
+    Carver c(base);
+    words = c.take<unsigned>(G.n);
+    block_v = c.take<int>(n_blocks);
+    block_t = c.take<int>(n_blocks);
+    bytes = c.bytes();
+  }
+};
 
 }  // namespace
 
@@ -202,7 +182,7 @@ extern "C" {
 int64_t nerf_isosurface_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
   IsoGrid G;
   if (iso_sizes("nerf_isosurface_workspace_bytes", nx, ny, nz, 1, G)) return -1;
-  return align256(G.n * (int64_t)sizeof(unsigned)) + 2 * align256(iso_blocks(G) * (int64_t)sizeof(int));
+  return IsoWorkspace(nullptr, G).bytes;
 }
 
 int32_t nerf_isosurface_count(const float* field, int64_t stride, int32_t nx, int32_t ny, int32_t nz, float level, void* workspace,
@@ -217,15 +197,11 @@ int32_t nerf_isosurface_count(const float* field, int64_t stride, int32_t nx, in
     return NERF_OK;
   }
   if (!field || !workspace) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_isosurface_count: null argument");
-  const long long n_blocks = iso_blocks(G);
-  unsigned* words = (unsigned*)workspace;
-  int* block_v = (int*)((char*)workspace + align256(G.n * (int64_t)sizeof(unsigned)));
-  int* block_t = (int*)((char*)block_v + align256(n_blocks * (int64_t)sizeof(int)));
-  hipLaunchKernelGGL(nerf_isosurface_count_kernel, dim3((unsigned)n_blocks), dim3(kIsoBlock), 0, st, field, G, level, words, block_v, block_t);
-  rc = check_launch("nerf_isosurface_count_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL(nerf_isosurface_scan_kernel, dim3(1), dim3(1024), 0, st, block_v, block_t, n_blocks, counts);
-  return check_launch("nerf_isosurface_scan_kernel");
+  const IsoWorkspace w(workspace, G);
+  if ((rc = NERF_LAUNCH(nerf_isosurface_count_kernel, dim3((unsigned)w.n_blocks), dim3(kIsoBlock), st, field, G, level, w.words,
+                        w.block_v, w.block_t)))
+    return rc;
+  return NERF_LAUNCH(nerf_isosurface_scan_kernel, dim3(1), dim3(kScanThreads), st, w.block_v, w.block_t, w.n_blocks, counts);
 }
 
 int32_t nerf_isosurface_emit(const float* field, int64_t stride, int32_t nx, int32_t ny, int32_t nz, float level, const double origin[3],
@@ -236,15 +212,11 @@ int32_t nerf_isosurface_emit(const float* field, int64_t stride, int32_t nx, int
   if (iso_no_cells(G)) return NERF_OK;
   if (!field || !origin || !step || !workspace || !vertices || !triangles)
     return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_isosurface_emit: null argument");
-  const long long n_blocks = iso_blocks(G);
-  const unsigned* words = (const unsigned*)workspace;
-  const int* block_v = (const int*)((const char*)workspace + align256(G.n * (int64_t)sizeof(unsigned)));
-  const int* block_t = (const int*)((const char*)block_v + align256(n_blocks * (int64_t)sizeof(int)));
+  const IsoWorkspace w(workspace, G);
   IsoFrame F;
   for (int a = 0; a < 3; ++a) { F.origin[a] = origin[a]; F.step[a] = step[a]; }
-  hipLaunchKernelGGL(nerf_isosurface_emit_kernel, dim3((unsigned)n_blocks), dim3(kIsoBlock), 0, (hipStream_t)stream, field, G, level, F, words,
-                     block_v, block_t, vertices, triangles);
-  return check_launch("nerf_isosurface_emit_kernel");
+  return NERF_LAUNCH(nerf_isosurface_emit_kernel, dim3((unsigned)w.n_blocks), dim3(kIsoBlock), (hipStream_t)stream, field, G, level, F,
+                     w.words, w.block_v, w.block_t, vertices, triangles);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 
 #include "../../include/nerf_mi355x.h"
 #include "nerf_layout.h"
+#include "nerf_scan.hip.inc"
 #include "nerf_mlp_f32.hip.inc"
 #include "nerf_mlp_f16.hip.inc"
 #include "nerf_mlp_f16s.hip.inc"
@@ -31,14 +32,18 @@ int fail(int code, const char* fmt, const char* what) {
   snprintf(g_err, sizeof(g_err), fmt, what);
   return code;
 }
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return NERF_ERR_HIP;
-  }
-  return NERF_OK;
+// Every kernel launch: NERF_OK, or NERF_ERR_HIP with "<kernel>: <hip error>" in nerf_last_error().  NERF_LAUNCH names the kernel
+// expression as it is written at the call (a template instance with a comma in its arguments is written, and reported, in
+// parentheses).
+template <class K, class... Args>
+int launch(const char* name, K kernel, dim3 grid, dim3 block, hipStream_t st, const Args&... args) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return NERF_OK;
+  snprintf(g_err, sizeof(g_err), "%s: %s", name, hipGetErrorString(e));
+  return NERF_ERR_HIP;
 }
+#define NERF_LAUNCH(kernel, grid, block, stream, ...) launch(#kernel, kernel, grid, block, stream, __VA_ARGS__)
 
 // ------------------------------------------------------------------------------------ pack
 struct PackArgs {
@@ -1036,26 +1041,12 @@ void nerf_tile_flags_kernel(const f32x4* __restrict__ draw, long long P, int den
   if ((lane & 31) == 0 && (p & ~31LL) < P) flags[tile] = (lane ? (b >> 32) : (b & 0xffffffffull)) != 0ull;
 }
 // flags -> ascending list of live tiles + count; one workgroup (the list is a few thousand entries per pass)
-__global__ __launch_bounds__(1024)
+__global__ __launch_bounds__(kScanThreads)
 void nerf_tile_scan_kernel(const int* __restrict__ flags, int n_tiles, int* __restrict__ live, int* __restrict__ count) {
-  __shared__ int s_cnt[1024];
-  const int tid = threadIdx.x;
-  const int per = (n_tiles + 1023) / 1024;
-  const int t0 = tid * per, t1 = min(t0 + per, n_tiles);
-  int c = 0;
-  for (int t = t0; t < t1; ++t) c += flags[t] != 0;
-  s_cnt[tid] = c;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {                 // inclusive Hillis-Steele scan
-    const int v = tid >= d ? s_cnt[tid - d] : 0;
-    __syncthreads();
-    s_cnt[tid] += v;
-    __syncthreads();
-  }
-  int pos = s_cnt[tid] - c;
-  for (int t = t0; t < t1; ++t)
-    if (flags[t] != 0) live[pos++] = t;
-  if (tid == 1023) *count = s_cnt[1023];
+  __shared__ int s_cnt[kScanThreads];
+  const int total = workgroup_scan(n_tiles, s_cnt, [&](long long t) { return (int)(flags[t] != 0); },
+                                   [&](long long t, int pos) { if (flags[t] != 0) live[pos] = (int)t; });
+  if (threadIdx.x == 0) *count = total;
 }
 
 // ------------------------------------------------------------------------------------ training: the masked (fast_sampling) fine pass
@@ -1064,22 +1055,7 @@ void nerf_tile_scan_kernel(const int* __restrict__ flags, int n_tiles, int* __re
 // the order here is fixed, because the training forward stores the activations of index[j] at row j of the save buffer: a
 // repeatable layout gives repeatable tiles, live-tile lists and gradient sums.  Three launches: per-block counts (256 ids per
 // block), one-workgroup exclusive scan of the block counts, ordered scatter.  No atomics.
-constexpr int kCompactBlock = 256;
-__device__ __forceinline__ int compact_block_rank(bool v, int* s_wave, int& block_total) {
-  const unsigned long long m = __builtin_amdgcn_ballot_w64(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_wave[wave] = (int)__popcll(m);
-  __syncthreads();
-  int before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kCompactBlock / 64; ++w) {
-    const int c = s_wave[w];
-    if (w < wave) before += c;
-    total += c;
-  }
-  block_total = total;
-  return before + (int)__popcll(m & ((1ull << lane) - 1ull));
-}
+constexpr int kCompactBlock = kRankBlock;       // compact_block_rank (nerf_scan.hip.inc)
 __global__ __launch_bounds__(kCompactBlock)
 void nerf_compact_count_kernel(const unsigned char* __restrict__ valid, long long n, int* __restrict__ block_count) {
   __shared__ int s_wave[kCompactBlock / 64];
@@ -1089,29 +1065,12 @@ void nerf_compact_count_kernel(const unsigned char* __restrict__ valid, long lon
   if (threadIdx.x == 0) block_count[blockIdx.x] = total;
 }
 // block counts -> exclusive offsets in place, *count = their sum; one workgroup (3072 blocks for a 4096-ray step)
-__global__ __launch_bounds__(1024)
+__global__ __launch_bounds__(kScanThreads)
 void nerf_compact_scan_kernel(int* __restrict__ block_count, long long n_blocks, int* __restrict__ count) {
-  __shared__ int s_cnt[1024];
-  const int tid = threadIdx.x;
-  const long long per = (n_blocks + 1023) / 1024;
-  const long long b0 = tid * per, b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
-  int c = 0;
-  for (long long b = b0; b < b1; ++b) c += block_count[b];
-  s_cnt[tid] = c;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {                 // inclusive Hillis-Steele scan
-    const int v = tid >= d ? s_cnt[tid - d] : 0;
-    __syncthreads();
-    s_cnt[tid] += v;
-    __syncthreads();
-  }
-  int pos = s_cnt[tid] - c;
-  for (long long b = b0; b < b1; ++b) {
-    const int cb = block_count[b];
-    block_count[b] = pos;
-    pos += cb;
-  }
-  if (tid == 1023) *count = s_cnt[1023];
+  __shared__ int s_cnt[kScanThreads];
+  const int total = workgroup_scan(n_blocks, s_cnt, [&](long long b) { return block_count[b]; },
+                                   [&](long long b, int pos) { block_count[b] = pos; });
+  if (threadIdx.x == 0) *count = total;
 }
 __global__ __launch_bounds__(kCompactBlock)
 void nerf_compact_scatter_kernel(const unsigned char* __restrict__ valid, long long n, const int* __restrict__ block_offset,
@@ -1458,6 +1417,19 @@ int num_cus() {
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
+// Every workspace is ONE layout struct that takes its pieces from a Carver, in order, each 256-byte aligned: built on the
+// caller's pointer it holds the pieces, built on a null base its bytes() is what the *_workspace_bytes entry reports.
+struct Carver {
+  uintptr_t base, p;
+  explicit Carver(const void* b) : base((uintptr_t)b), p((uintptr_t)b) {}
+  template <class T> T* take(int64_t count) {
+    T* q = (T*)p;
+    p += (uintptr_t)align256(count * (int64_t)sizeof(T));
+    return q;
+  }
+  int64_t bytes() const { return (int64_t)(p - base); }
+};
+
 }  // namespace
 
 // ===================================================================================== C ABI
@@ -1471,8 +1443,6 @@ struct MlpFamily {
   bool persistent;           // one workgroup per CU walks the tiles; otherwise one workgroup per tile
   MlpKernel inst[4];         // rays, density only | rays, dead-colour skip | rays | points
 };
-// hipcc emits the instances in the order of their first use, and the library's device code is kept byte for byte: the inference
-// families stand here, the SAVE families behind mlp_backward_impl (their place before there was a table)
 #define NERF_MLP_INFERENCE_3(K) {K<true, true>, K<true, false, true>, K<true>, K<false>}
 #define NERF_MLP_INFERENCE_4(K) {K<true, false, true>, K<true, false, false, true>, K<true>, K<false>}
 #define NERF_MLP_SAVE(K) {K<true, true, true>, K<true, true, false, true>, K<true, true>, K<false, true>}
@@ -1483,7 +1453,18 @@ static const MlpFamily kMlpF16 = {"nerf_mlp_f16_kernel", kF16TilePts, kF16Thread
 // barrier-free: workgroups of NERF_F32_WG_WAVES one-tile waves (nerf_mlp_f32.hip.inc says why one)
 static const MlpFamily kMlpF32 = {"nerf_mlp_f32_kernel", nerf::kTilePts * NERF_F32_WG_WAVES, 64 * NERF_F32_WG_WAVES, false,
                            NERF_MLP_INFERENCE_4(nerf_mlp_f32_kernel)};
-static const MlpFamily* mlp_family(int precision, bool save);
+// the SAVE families (training forward): one-wave workgroups for f32
+static const MlpFamily kMlpSaveF32x = {"nerf_mlp_f32x_kernel", kXTilePts, kXThreads, true, NERF_MLP_SAVE(nerf_mlp_f32x_kernel)};
+static const MlpFamily kMlpSaveF32 = {"nerf_mlp_f32_kernel", nerf::kTilePts, 64, false, NERF_MLP_SAVE(nerf_mlp_f32_kernel)};
+static const MlpFamily* mlp_family(int precision, bool save) {
+  switch (precision) {
+    case NERF_PREC_F32: return save ? &kMlpSaveF32 : &kMlpF32;
+    case NERF_PREC_F32X: return save ? &kMlpSaveF32x : &kMlpF32x;
+    case NERF_PREC_F16: return save ? nullptr : &kMlpF16;
+    case NERF_PREC_F16S: return save ? nullptr : &kMlpF16s;
+  }
+  return nullptr;
+}
 
 // persistent kernels: one workgroup per CU, fewer when there are fewer tiles
 static unsigned persistent_blocks(long long n_points, int wg_pts) {
@@ -1548,18 +1529,13 @@ static int launch_mlp(const MlpArgs& a_in, bool ray_mode, bool save, int precisi
     hold.lock();
     float* fold = nullptr;
     if (const int rc = fold_buffer(st, entry, &fold)) return rc;
-    hipLaunchKernelGGL(nerf_fold_f32_kernel, dim3(kFoldBlocks), dim3(256), 0, st, a.packed, fold);
-    if (const int rc = check_launch("nerf_fold_f32_kernel")) return rc;
+    if (const int rc = NERF_LAUNCH(nerf_fold_f32_kernel, dim3(kFoldBlocks), dim3(256), st, a.packed, fold)) return rc;
     a.fold = fold;
   }
-  if (f->persistent) {
-    hipLaunchKernelGGL(k, dim3(persistent_blocks(a.n_points, f->wg_pts)), dim3(f->threads), 0, st, a);
-  } else {
-    const long long blocks = (a.n_points + f->wg_pts - 1) / f->wg_pts;
-    if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s: too many points for one launch", entry);
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(f->threads), 0, st, a);
-  }
-  return check_launch(f->name);
+  if (f->persistent) return launch(f->name, k, dim3(persistent_blocks(a.n_points, f->wg_pts)), dim3(f->threads), st, a);
+  const long long blocks = (a.n_points + f->wg_pts - 1) / f->wg_pts;
+  if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s: too many points for one launch", entry);
+  return launch(f->name, k, dim3((unsigned)blocks), dim3(f->threads), st, a);
 }
 
 // The ray-mode forward entries.  for_compositing: `raw` only ever reaches nerf_composite, where the colours of zero-density
@@ -1626,20 +1602,18 @@ int32_t nerf_pack_model(const float* const params[24], void* packed, int32_t pre
   if (precision == NERF_PREC_F16 || precision == NERF_PREC_F32X || precision == NERF_PREC_F16S) {
     const long long n = nerf::kF16ConstBytes / 4 + (long long)nerf::kF16Frags * 512;
     const dim3 grid((unsigned)((n + threads - 1) / threads));
-    if (precision == NERF_PREC_F16S) hipLaunchKernelGGL(nerf_pack_f16s_kernel, grid, dim3(threads), 0, (hipStream_t)stream, a);
-    else if (precision == NERF_PREC_F16) hipLaunchKernelGGL(nerf_pack_f16_kernel<false>, grid, dim3(threads), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(nerf_pack_f16_kernel<true>, grid, dim3(threads), 0, (hipStream_t)stream, a);
-    if (precision != NERF_PREC_F32X) {          // + the f32x stream behind the fp16 one
-      PackArgs ax = a;
-      ax.out = reinterpret_cast<float*>(reinterpret_cast<char*>(packed) + nerf::kF16PackedBytes);
-      hipLaunchKernelGGL(nerf_pack_f16_kernel<true>, grid, dim3(threads), 0, (hipStream_t)stream, ax);
-    }
-    return check_launch("nerf_pack_f16_kernel");
+    hipStream_t st = (hipStream_t)stream;
+    if (precision == NERF_PREC_F32X) return NERF_LAUNCH(nerf_pack_f16_kernel<true>, grid, dim3(threads), st, a);
+    if (const int rc = precision == NERF_PREC_F16S ? NERF_LAUNCH(nerf_pack_f16s_kernel, grid, dim3(threads), st, a)
+                                                   : NERF_LAUNCH(nerf_pack_f16_kernel<false>, grid, dim3(threads), st, a))
+      return rc;
+    PackArgs ax = a;                            // + the f32x stream behind the fp16 one
+    ax.out = reinterpret_cast<float*>(reinterpret_cast<char*>(packed) + nerf::kF16PackedBytes);
+    return NERF_LAUNCH(nerf_pack_f16_kernel<true>, grid, dim3(threads), st, ax);
   }
   if (precision != NERF_PREC_F32) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_pack_model: unknown precision");
   const unsigned blocks = (unsigned)((nerf::kPackedFloats + threads - 1) / threads);
-  hipLaunchKernelGGL(nerf_pack_kernel, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_pack_kernel");
+  return NERF_LAUNCH(nerf_pack_kernel, dim3(blocks), dim3(threads), (hipStream_t)stream, a);
 }
 
 int32_t nerf_positional_encoding(const float* x, int64_t n, int32_t n_freqs, float* out, void* stream) {
@@ -1647,8 +1621,7 @@ int32_t nerf_positional_encoding(const float* x, int64_t n, int32_t n_freqs, flo
   if (n == 0) return NERF_OK;
   if (!x || !out) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_positional_encoding: null argument");
   const unsigned blocks = (unsigned)((n * 3 + 255) / 256);
-  hipLaunchKernelGGL(nerf_pe_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (long long)n, n_freqs, out);
-  return check_launch("nerf_pe_kernel");
+  return NERF_LAUNCH(nerf_pe_kernel, dim3(blocks), dim3(256), (hipStream_t)stream, x, (long long)n, n_freqs, out);
 }
 
 int32_t nerf_mlp_forward(const float* pts, const float* viewdirs, int64_t n_rays, int32_t n_samples,
@@ -1683,19 +1656,40 @@ int32_t nerf_mlp_forward_rays_density(const float* rays_o, const float* rays_d, 
                       nullptr, true, false, precision, stream);
 }
 
+static bool bad_strides(int64_t t_ray_stride, int64_t u_ray_stride) {
+  return (t_ray_stride != 0 && t_ray_stride != NERF_N_SAMPLES) || (u_ray_stride != 0 && u_ray_stride != NERF_N_IMPORTANCE);
+}
+// nerf_sample_fine (shared tables: both strides 0) and nerf_sample_fine_rays behind their own size checks.  Shared tables take
+// the <false> instance, a table per ray of either kind the <true> one.
+static int32_t sample_fine(const char* entry, const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                           int64_t u_ray_stride, int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
+                           float weights_threshold, float ert_threshold, void* stream) {
+  const bool per_ray = t_ray_stride != 0 || u_ray_stride != 0;
+  if (per_ray && valid_sorted) return fail(NERF_ERR_INVALID_ARG, "%s: fast_sampling needs the shared tables", entry);
+  if (n_rays == 0) return NERF_OK;
+  if (!raw_coarse || !t_coarse || !u || !t_sorted) return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
+  SampleArgs a;
+  a.raw_c = raw_coarse; a.t_coarse = t_coarse; a.t_stride = t_ray_stride; a.u = u; a.u_stride = u_ray_stride; a.n_rays = n_rays;
+  a.t_sorted = t_sorted; a.t_fine = t_fine; a.valid_sorted = valid_sorted; a.fast_sampling = valid_sorted != nullptr;
+  a.weights_threshold = per_ray ? 0.0f : weights_threshold; a.ert_threshold = per_ray ? 0.0f : ert_threshold;
+  const dim3 blocks((unsigned)((n_rays + kSampleThreads - 1) / kSampleThreads));
+  return per_ray ? NERF_LAUNCH(nerf_sample_fine_kernel<true>, blocks, dim3(kSampleThreads), (hipStream_t)stream, a)
+                 : NERF_LAUNCH(nerf_sample_fine_kernel<false>, blocks, dim3(kSampleThreads), (hipStream_t)stream, a);
+}
 int32_t nerf_sample_fine(const float* raw_coarse, const float* t_coarse, const float* u,
                          int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
                          float weights_threshold, float ert_threshold, void* stream) {
   if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine: bad size");
-  if (n_rays == 0) return NERF_OK;
-  if (!raw_coarse || !t_coarse || !u || !t_sorted) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine: null argument");
-  SampleArgs a;
-  a.raw_c = raw_coarse; a.t_coarse = t_coarse; a.t_stride = 0; a.u = u; a.u_stride = 0; a.n_rays = n_rays; a.t_sorted = t_sorted;
-  a.t_fine = t_fine; a.valid_sorted = valid_sorted; a.fast_sampling = valid_sorted != nullptr;
-  a.weights_threshold = weights_threshold; a.ert_threshold = ert_threshold;
-  const unsigned blocks = (unsigned)((n_rays + kSampleThreads - 1) / kSampleThreads);
-  hipLaunchKernelGGL(nerf_sample_fine_kernel<false>, dim3(blocks), dim3(kSampleThreads), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_sample_fine_kernel<false>");
+  return sample_fine("nerf_sample_fine", raw_coarse, t_coarse, 0, u, 0, n_rays, t_sorted, t_fine, valid_sorted, weights_threshold,
+                     ert_threshold, stream);
+}
+int32_t nerf_sample_fine_rays(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                              int64_t u_ray_stride, int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
+                              float weights_threshold, float ert_threshold, void* stream) {
+  if (n_rays < 0 || bad_strides(t_ray_stride, u_ray_stride))
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: bad size or stride (t: 0 or 64, u: 0 or 128)");
+  return sample_fine("nerf_sample_fine_rays", raw_coarse, t_coarse, t_ray_stride, u, u_ray_stride, n_rays, t_sorted, t_fine, valid_sorted,
+                     weights_threshold, ert_threshold, stream);
 }
 
 int32_t nerf_composite(const float* raw, const float* tvals, int64_t t_ray_stride, int64_t n_rays,
@@ -1705,14 +1699,12 @@ int32_t nerf_composite(const float* raw, const float* tvals, int64_t t_ray_strid
   if (n_rays == 0) return NERF_OK;
   if (!raw || !tvals || !rgb || !depth) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_composite: null argument");
   if (n_samples % kCompChunk == 0 && (t_ray_stride % 4 == 0) && ((uintptr_t)tvals % 16 == 0)) {
-    hipLaunchKernelGGL(nerf_composite_staged_kernel, dim3((unsigned)((n_rays + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
-                       raw, tvals, (long long)t_ray_stride, (long long)n_rays, n_samples, white_bkgd, rgb, depth, weights);
-    return check_launch("nerf_composite_staged_kernel");
+    return NERF_LAUNCH(nerf_composite_staged_kernel, dim3((unsigned)((n_rays + 63) / 64)), dim3(64), (hipStream_t)stream, raw, tvals,
+                       (long long)t_ray_stride, (long long)n_rays, n_samples, white_bkgd, rgb, depth, weights);
   }
   const unsigned blocks = (unsigned)((n_rays + 255) / 256);
-  hipLaunchKernelGGL(nerf_composite_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, raw, tvals,
-                     (long long)t_ray_stride, (long long)n_rays, n_samples, white_bkgd, rgb, depth, weights);
-  return check_launch("nerf_composite_kernel");
+  return NERF_LAUNCH(nerf_composite_kernel, dim3(blocks), dim3(256), (hipStream_t)stream, raw, tvals, (long long)t_ray_stride,
+                     (long long)n_rays, n_samples, white_bkgd, rgb, depth, weights);
 }
 
 int32_t nerf_generate_rays(const double c2w[12], int32_t H, int32_t W, double focal, int64_t pixel_begin,
@@ -1726,8 +1718,7 @@ int32_t nerf_generate_rays(const double c2w[12], int32_t H, int32_t W, double fo
   for (int i = 0; i < 12; ++i) a.c2w[i] = c2w[i];
   a.focal = focal; a.cx = W / 2.0; a.cy = H / 2.0; a.pixel_begin = pixel_begin; a.n_pixels = n_pixels; a.W = W;
   a.pixel_ids = (const long long*)pixel_ids; a.rays_o = rays_o; a.rays_d = rays_d;
-  hipLaunchKernelGGL(nerf_generate_rays_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_generate_rays_kernel");
+  return NERF_LAUNCH(nerf_generate_rays_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), (hipStream_t)stream, a);
 }
 
 int32_t nerf_image_metrics(const float* pred, const float* gt, int64_t n_values, double* sums2, void* stream) {
@@ -1739,9 +1730,8 @@ int32_t nerf_image_metrics(const float* pred, const float* gt, int64_t n_values,
   if (!pred || !gt) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_image_metrics: null argument");
   long long blocks = (n_values + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(nerf_image_metrics_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pred, gt,
-                     (long long)n_values, sums2);
-  return check_launch("nerf_image_metrics_kernel");
+  return NERF_LAUNCH(nerf_image_metrics_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, pred, gt, (long long)n_values,
+                     sums2);
 }
 
 // live / n_live: the live-tile list of a backward pass (device pointers) or nullptr for the whole point range; with a list,
@@ -1770,51 +1760,46 @@ static int32_t wgrad_impl(const float* dz, int64_t ldz, int32_t zc0, int32_t n_o
     a.osplit = 2; a.isplit = 2;        // whole groups of 8 k-steps per workgroup: the clamp-free asm-load form
     WgradBatch wb;
     wb.job[0] = a; wb.n_jobs = 1;
-    if (live) hipLaunchKernelGGL(nerf_wgrad256_f32_asm_kernel<true>, grid, blk, 0, st, wb);
-    else hipLaunchKernelGGL(nerf_wgrad256_f32_asm_kernel<false>, grid, blk, 0, st, wb);
-  } else if (live) {
-    // list mode needs the asm-ring form of the small-layer kernels (whole 32-point tiles)
-    if (!(n_points % 32 == 0 && ldz < (1ll << 28) && ldh < (1ll << 28)))
-      return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_wgrad: live-tile list on a shape without an asm-ring kernel");
-    const dim3 lgrid((unsigned)num_cus());
-#define VECL(AV, BV, OS, IS) do { a.osplit = OS; a.isplit = IS; \
-      hipLaunchKernelGGL((nerf_wgrad_vec_f32_asm_kernel<AV, BV, 16, true>), lgrid, blk, 0, st, a); } while (0)
-    if (n_out == 256 && n_in <= 64 && aligned) VECL(4, 1, 2, 2);
-    else if (n_out == 128 && n_in == 256 && aligned) VECL(4, 2, 1, 4);
-    else if (n_out == 128 && n_in <= 32) VECL(1, 1, 4, 1);
-    else if (n_out <= 32 && n_in == 256 && ldh % 2 == 0 && hc0 % 2 == 0 && (uintptr_t)hin % 8 == 0) VECL(1, 2, 1, 4);
-    else if (n_out <= 32 && n_in <= 128) VECL(1, 1, 1, 4);
-    else return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_wgrad: live-tile list on a shape without an asm-ring kernel");
-#undef VECL
-  } else if (n_out == 256 && n_in == 256 && aligned) {
+    return live ? NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<true>, grid, blk, st, wb)
+                : NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<false>, grid, blk, st, wb);
+  }
+  // the asm-ring form of the small-layer kernels: the point range splits into whole groups of 16 k-steps (32 points) per
+  // workgroup (every training shape does: P is a multiple of 64).  List mode needs it (whole 32-point tiles)
+  const bool ring = n_points % 32 == 0 && ldz < (1ll << 28) && ldh < (1ll << 28);
+  const char* no_list_kernel = "nerf_wgrad: live-tile list on a shape without an asm-ring kernel";
+  if (live && !ring) return fail(NERF_ERR_INVALID_ARG, "%s", no_list_kernel);
+  if (!live && n_out == 256 && n_in == 256 && aligned) {
     a.osplit = 2; a.isplit = 2;
-    hipLaunchKernelGGL(nerf_wgrad256_f32_kernel, grid, blk, 0, st, a);
+    return NERF_LAUNCH(nerf_wgrad256_f32_kernel, grid, blk, st, a);
   }
   // small layers on the vector-load kernel: (floats per lane, wave split) chosen so that 32*AV*osplit covers n_out
-  // and 32*BV*isplit covers n_in; operands must be aligned to their vector width.  VEC picks the asm-ring form when the
-  // point range splits into whole groups of PF k-steps per workgroup (every training shape does: P is a multiple of 64)
-#define VEC(AV, BV, PF, OS, IS) do { \
+  // and 32*BV*isplit covers n_in; operands must be aligned to their vector width.  With a list every CU's workgroup reads
+  // *n_live itself; without one the ring form takes one workgroup per group of 16 k-steps, at most one per CU
+  const long long groups = n_points / 32;
+#define VEC(AV, BV, OS, IS) do { \
     a.osplit = OS; a.isplit = IS; \
-    if (n_points % (2 * PF) == 0 && n_points / (2 * PF) >= 1 && ldz < (1ll << 28) && ldh < (1ll << 28)) { \
-      long long g = n_points / (2 * PF); \
-      if (g > num_cus()) g = num_cus(); \
-      hipLaunchKernelGGL((nerf_wgrad_vec_f32_asm_kernel<AV, BV, PF>), dim3((unsigned)g), blk, 0, st, a); \
-    } else hipLaunchKernelGGL((nerf_wgrad_vec_f32_kernel<AV, BV>), grid, blk, 0, st, a); \
+    if (live) return NERF_LAUNCH((nerf_wgrad_vec_f32_asm_kernel<AV, BV, 16, true>), dim3((unsigned)num_cus()), blk, st, a); \
+    if (ring) return NERF_LAUNCH((nerf_wgrad_vec_f32_asm_kernel<AV, BV, 16>), dim3((unsigned)(groups < num_cus() ? groups : num_cus())), blk, st, a); \
+    return NERF_LAUNCH((nerf_wgrad_vec_f32_kernel<AV, BV>), grid, blk, st, a); \
   } while (0)
-  else if (n_out == 256 && n_in <= 64 && aligned) VEC(4, 1, 16, 2, 2);         // PE -> 256 (layers 0 and 5)
-  else if (n_out == 128 && n_in == 256 && aligned) VEC(4, 2, 16, 1, 4);        // views_linears.0, feature part
-  else if (n_out == 128 && n_in <= 32) VEC(1, 1, 16, 4, 1);                    // views_linears.0, direction part
-  else if (n_out <= 32 && n_in == 256 && ldh % 2 == 0 && hc0 % 2 == 0 && (uintptr_t)hin % 8 == 0)
-    VEC(1, 2, 16, 1, 4);                                                       // alpha_linear
-  else if (n_out <= 32 && n_in <= 128) VEC(1, 1, 16, 1, 4);                    // rgb_linear
+  if (n_out == 256 && n_in <= 64 && aligned) VEC(4, 1, 2, 2);                  // PE -> 256 (layers 0 and 5)
+  if (n_out == 128 && n_in == 256 && aligned) VEC(4, 2, 1, 4);                 // views_linears.0, feature part
+  if (n_out == 128 && n_in <= 32) VEC(1, 1, 4, 1);                             // views_linears.0, direction part
+  if (n_out <= 32 && n_in == 256 && ldh % 2 == 0 && hc0 % 2 == 0 && (uintptr_t)hin % 8 == 0) VEC(1, 2, 1, 4);     // alpha_linear
+  if (n_out <= 32 && n_in <= 128) VEC(1, 1, 1, 4);                             // rgb_linear
 #undef VEC
-  else if (to > 4 && ti > 4) { a.osplit = 2; a.isplit = 2; hipLaunchKernelGGL((nerf_wgrad_f32_kernel<4, 4>), grid, blk, 0, st, a); }
-  else if (to > 4)           { a.osplit = 2; a.isplit = 2; hipLaunchKernelGGL((nerf_wgrad_f32_kernel<4, 1>), grid, blk, 0, st, a); }
-  else if (to > 1 && ti > 4) { a.osplit = 2; a.isplit = 2; hipLaunchKernelGGL((nerf_wgrad_f32_kernel<2, 4>), grid, blk, 0, st, a); }
-  else if (to > 1)           { a.osplit = 4; a.isplit = 1; hipLaunchKernelGGL((nerf_wgrad_f32_kernel<1, 1>), grid, blk, 0, st, a); }
-  else if (ti > 4)           { a.osplit = 1; a.isplit = 4; hipLaunchKernelGGL((nerf_wgrad_f32_kernel<1, 2>), grid, blk, 0, st, a); }
-  else                       { a.osplit = 1; a.isplit = 4; hipLaunchKernelGGL((nerf_wgrad_f32_kernel<1, 1>), grid, blk, 0, st, a); }
-  return check_launch("nerf_wgrad_f32_kernel");
+  if (live) return fail(NERF_ERR_INVALID_ARG, "%s", no_list_kernel);
+#define GEN(TO, TI, OS, IS) do { \
+    a.osplit = OS; a.isplit = IS; \
+    return NERF_LAUNCH((nerf_wgrad_f32_kernel<TO, TI>), grid, blk, st, a); \
+  } while (0)
+  if (to > 4 && ti > 4) GEN(4, 4, 2, 2);
+  if (to > 4) GEN(4, 1, 2, 2);
+  if (to > 1 && ti > 4) GEN(2, 4, 2, 2);
+  if (to > 1) GEN(1, 1, 4, 1);
+  if (ti > 4) GEN(1, 2, 1, 4);
+  GEN(1, 1, 1, 4);
+#undef GEN
 }
 
 int32_t nerf_wgrad(const float* dz, int64_t ldz, int32_t zc0, int32_t n_out, const float* hin, int64_t ldh,
@@ -1830,20 +1815,36 @@ int32_t nerf_composite_backward(const float* raw, const float* tvals, int64_t t_
   if (n_rays == 0) return NERF_OK;
   if (!raw || !tvals || !g_rgb || !g_raw) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_composite_backward: null argument");
   if (n_samples > kCbMaxSamples) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_composite_backward: at most 192 samples per ray");
-  hipLaunchKernelGGL(nerf_composite_bwd_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, raw, tvals,
+  return NERF_LAUNCH(nerf_composite_bwd_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), (hipStream_t)stream, raw, tvals,
                      (long long)t_ray_stride, (long long)n_rays, n_samples, white_bkgd, g_rgb, g_depth, g_raw, g_t);
-  return check_launch("nerf_composite_bwd_kernel");
 }
 
+// the same pair for the backward: nerf_sample_fine_backward and nerf_sample_fine_rays_backward
+static int32_t sample_fine_backward(const char* entry, const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride,
+                                    const float* u, int64_t u_ray_stride, int64_t n_rays, const float* t_sorted,
+                                    const float* g_t_sorted, float* g_raw_coarse, void* stream) {
+  if (n_rays == 0) return NERF_OK;
+  if (!raw_coarse || !t_coarse || !u || !t_sorted || !g_t_sorted || !g_raw_coarse) return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
+  const dim3 blocks((unsigned)((n_rays + 3) / 4));
+  const long long ts = t_ray_stride, us = u_ray_stride, n = n_rays;
+  return ts != 0 || us != 0
+             ? NERF_LAUNCH(nerf_sample_bwd_kernel<true>, blocks, dim3(256), (hipStream_t)stream, raw_coarse, t_coarse, ts, u, us, n,
+                           g_t_sorted, g_raw_coarse)
+             : NERF_LAUNCH(nerf_sample_bwd_kernel<false>, blocks, dim3(256), (hipStream_t)stream, raw_coarse, t_coarse, ts, u, us, n,
+                           g_t_sorted, g_raw_coarse);
+}
 int32_t nerf_sample_fine_backward(const float* raw_coarse, const float* t_coarse, const float* u, int64_t n_rays,
                                   const float* t_sorted, const float* g_t_sorted, float* g_raw_coarse, void* stream) {
   if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_backward: bad size");
-  if (n_rays == 0) return NERF_OK;
-  if (!raw_coarse || !t_coarse || !u || !t_sorted || !g_t_sorted || !g_raw_coarse)
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_backward: null argument");
-  hipLaunchKernelGGL(nerf_sample_bwd_kernel<false>, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                     raw_coarse, t_coarse, 0LL, u, 0LL, (long long)n_rays, g_t_sorted, g_raw_coarse);
-  return check_launch("nerf_sample_bwd_kernel<false>");
+  return sample_fine_backward("nerf_sample_fine_backward", raw_coarse, t_coarse, 0, u, 0, n_rays, t_sorted, g_t_sorted, g_raw_coarse, stream);
+}
+int32_t nerf_sample_fine_rays_backward(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                                       int64_t u_ray_stride, int64_t n_rays, const float* t_sorted, const float* g_t_sorted,
+                                       float* g_raw_coarse, void* stream) {
+  if (n_rays < 0 || bad_strides(t_ray_stride, u_ray_stride))
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays_backward: bad size or stride (t: 0 or 64, u: 0 or 128)");
+  return sample_fine_backward("nerf_sample_fine_rays_backward", raw_coarse, t_coarse, t_ray_stride, u, u_ray_stride, n_rays, t_sorted,
+                              g_t_sorted, g_raw_coarse, stream);
 }
 
 int32_t nerf_stratified_samples(const float* t_linear, const float* jitter, int64_t n_rays, float* t_coarse, void* stream) {
@@ -1851,48 +1852,8 @@ int32_t nerf_stratified_samples(const float* t_linear, const float* jitter, int6
   if (n_rays == 0) return NERF_OK;
   if (!t_linear || !jitter || !t_coarse) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_stratified_samples: null argument");
   const long long ne = (long long)n_rays * NERF_N_SAMPLES;
-  hipLaunchKernelGGL(nerf_stratified_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     t_linear, jitter, (long long)n_rays, t_coarse);
-  return check_launch("nerf_stratified_kernel");
-}
-
-static bool bad_strides(int64_t t_ray_stride, int64_t u_ray_stride) {
-  return (t_ray_stride != 0 && t_ray_stride != NERF_N_SAMPLES) || (u_ray_stride != 0 && u_ray_stride != NERF_N_IMPORTANCE);
-}
-
-int32_t nerf_sample_fine_rays(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
-                              int64_t u_ray_stride, int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
-                              float weights_threshold, float ert_threshold, void* stream) {
-  if (n_rays < 0 || bad_strides(t_ray_stride, u_ray_stride))
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: bad size or stride (t: 0 or 64, u: 0 or 128)");
-  if (t_ray_stride == 0 && u_ray_stride == 0)
-    return nerf_sample_fine(raw_coarse, t_coarse, u, n_rays, t_sorted, t_fine, valid_sorted, weights_threshold, ert_threshold, stream);
-  if (valid_sorted) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: fast_sampling needs the shared tables");
-  if (n_rays == 0) return NERF_OK;
-  if (!raw_coarse || !t_coarse || !u || !t_sorted) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: null argument");
-  SampleArgs a;
-  a.raw_c = raw_coarse; a.t_coarse = t_coarse; a.t_stride = t_ray_stride; a.u = u; a.u_stride = u_ray_stride;
-  a.n_rays = n_rays; a.t_sorted = t_sorted; a.t_fine = t_fine; a.valid_sorted = nullptr; a.fast_sampling = 0;
-  a.weights_threshold = a.ert_threshold = 0.0f;
-  const unsigned blocks = (unsigned)((n_rays + kSampleThreads - 1) / kSampleThreads);
-  hipLaunchKernelGGL(nerf_sample_fine_kernel<true>, dim3(blocks), dim3(kSampleThreads), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_sample_fine_kernel<true>");
-}
-
-int32_t nerf_sample_fine_rays_backward(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
-                                       int64_t u_ray_stride, int64_t n_rays, const float* t_sorted, const float* g_t_sorted,
-                                       float* g_raw_coarse, void* stream) {
-  if (n_rays < 0 || bad_strides(t_ray_stride, u_ray_stride))
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays_backward: bad size or stride (t: 0 or 64, u: 0 or 128)");
-  if (t_ray_stride == 0 && u_ray_stride == 0)
-    return nerf_sample_fine_backward(raw_coarse, t_coarse, u, n_rays, t_sorted, g_t_sorted, g_raw_coarse, stream);
-  if (n_rays == 0) return NERF_OK;
-  if (!raw_coarse || !t_coarse || !u || !t_sorted || !g_t_sorted || !g_raw_coarse)
-    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays_backward: null argument");
-  hipLaunchKernelGGL(nerf_sample_bwd_kernel<true>, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                     raw_coarse, t_coarse, (long long)t_ray_stride, u, (long long)u_ray_stride, (long long)n_rays, g_t_sorted,
-                     g_raw_coarse);
-  return check_launch("nerf_sample_bwd_kernel<true>");
+  return NERF_LAUNCH(nerf_stratified_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), (hipStream_t)stream, t_linear, jitter,
+                     (long long)n_rays, t_coarse);
 }
 
 int32_t nerf_viewdirs_backward(const float* gsave, int64_t n_rays, int32_t n_samples, const float* w_views,
@@ -1901,9 +1862,8 @@ int32_t nerf_viewdirs_backward(const float* gsave, int64_t n_rays, int32_t n_sam
   if (n_rays == 0) return NERF_OK;
   if (!gsave || !w_views || !viewdirs || !g_viewdirs) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_viewdirs_backward: null argument");
   if (n_rays > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_viewdirs_backward: too many rays for one launch");
-  hipLaunchKernelGGL(nerf_viewdirs_bwd_kernel, dim3((unsigned)n_rays), dim3(128), 0, (hipStream_t)stream,
+  return NERF_LAUNCH(nerf_viewdirs_bwd_kernel, dim3((unsigned)n_rays), dim3(128), (hipStream_t)stream,
                      gsave + TrainGrad::off_gzv(n_rays * n_samples), (long long)n_rays, n_samples, w_views, viewdirs, g_viewdirs);
-  return check_launch("nerf_viewdirs_bwd_kernel");
 }
 
 int32_t nerf_rays_viewdirs_backward(const float* rays_d, int64_t n_rays, int32_t n_samples, const float* gsave,
@@ -1913,10 +1873,9 @@ int32_t nerf_rays_viewdirs_backward(const float* rays_d, int64_t n_rays, int32_t
   if (!rays_d || !gsave || !w_views || !g_rays_d_view) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_viewdirs_backward: null argument");
   if (n_rays > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_viewdirs_backward: too many rays for one launch");
   const long long P = n_rays * n_samples;
-  hipLaunchKernelGGL(nerf_rays_viewdirs_bwd_kernel, dim3((unsigned)n_rays), dim3(128), 0, (hipStream_t)stream,
+  return NERF_LAUNCH(nerf_rays_viewdirs_bwd_kernel, dim3((unsigned)n_rays), dim3(128), (hipStream_t)stream,
                      gsave + TrainGrad::off_gzv(P), reinterpret_cast<const int*>(gsave + TrainGrad::off_flags(P)),
                      reinterpret_cast<const int*>(gsave + TrainGrad::off_count(P)), n_samples, w_views, rays_d, g_rays_d_view);
-  return check_launch("nerf_rays_viewdirs_bwd_kernel");
 }
 
 int32_t nerf_rays_backward(int64_t n_rays, const float* t_coarse, int64_t t_ray_stride, const float* g_x_coarse,
@@ -1929,9 +1888,8 @@ int32_t nerf_rays_backward(int64_t n_rays, const float* t_coarse, int64_t t_ray_
     return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_backward: null argument");
   const long long blocks = (n_rays + 3) / 4;
   if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_rays_backward: too many rays for one launch");
-  hipLaunchKernelGGL(nerf_rays_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long long)n_rays,
-                     t_coarse, (long long)t_ray_stride, g_x_coarse, t_sorted, g_x_fine, g_rays_d_view, g_rays_o, g_rays_d);
-  return check_launch("nerf_rays_bwd_kernel");
+  return NERF_LAUNCH(nerf_rays_bwd_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, (long long)n_rays, t_coarse,
+                     (long long)t_ray_stride, g_x_coarse, t_sorted, g_x_fine, g_rays_d_view, g_rays_o, g_rays_d);
 }
 
 int32_t nerf_adam_step(int32_t n_tensors, float* const params[], const float* const grads[], float* const exp_avg[],
@@ -1952,8 +1910,7 @@ int32_t nerf_adam_step(int32_t n_tensors, float* const params[], const float* co
   a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   long long blocks = (run + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(nerf_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_adam_kernel");
+  return NERF_LAUNCH(nerf_adam_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, a);
 }
 
 int64_t nerf_train_grad_floats(int64_t n_points) { return n_points < 0 ? -1 : TrainGrad::floats(n_points); }
@@ -1969,12 +1926,10 @@ int32_t nerf_pack_model_bwd(const float* const params[24], void* packed_bwd_v, i
   if (const int rc = fill_pack_args("nerf_pack_model_bwd", params, packed_bwd_v, a)) return rc;
   if (precision == NERF_PREC_F32X) {
     const long long n = nerf::kF16ConstBytes / 4 + (long long)nerf::kXbSteps * 512;
-    hipLaunchKernelGGL(nerf_pack_bwd_f32x_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return check_launch("nerf_pack_bwd_f32x_kernel");
+    return NERF_LAUNCH(nerf_pack_bwd_f32x_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, a);
   }
   if (precision != NERF_PREC_F32) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_pack_model_bwd: f32 or f32x only");
-  hipLaunchKernelGGL(nerf_pack_bwd_kernel, dim3((unsigned)((nerf::kBwdPackedFloats + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("nerf_pack_bwd_kernel");
+  return NERF_LAUNCH(nerf_pack_bwd_kernel, dim3((unsigned)((nerf::kBwdPackedFloats + 255) / 256)), dim3(256), (hipStream_t)stream, a);
 }
 
 // grads[24]: device pointers in state_dict order (nn.Linear layouts), accumulated into (caller zeroes them); nullptr: the
@@ -1998,6 +1953,7 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
   const bool dens = a.density_only != 0;
   const long long P = a.n_points;
   const float* draw = a.draw; const float* save = a.save; float* gsave = a.gsave;
+  hipStream_t st = (hipStream_t)stream;
   int rc;
   // live tiles: tiles whose incoming gradient is zero throughout are dropped from the chain launch and from every
   // weight-gradient launch -- see nerf_tile_flags_kernel.  Needs the asm-ring weight-gradient kernels (whole 32-point tiles).
@@ -2009,19 +1965,12 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
       int* flags = reinterpret_cast<int*>(gsave + TrainGrad::off_flags(P));
       int* lv = reinterpret_cast<int*>(gsave + TrainGrad::off_live(P));
       int* cnt = reinterpret_cast<int*>(gsave + TrainGrad::off_count(P));
-      if (by_gradient) {
-        hipLaunchKernelGGL(nerf_tile_flags_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const f32x4*>(draw), P, a.density_only, flags);
-        rc = check_launch("nerf_tile_flags_kernel");
-      } else {
-        hipLaunchKernelGGL(nerf_tile_occupied_kernel, dim3((unsigned)((P / 32 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           occupied, P / 32, flags);
-        rc = check_launch("nerf_tile_occupied_kernel");
-      }
+      rc = by_gradient ? NERF_LAUNCH(nerf_tile_flags_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), st,
+                                     reinterpret_cast<const f32x4*>(draw), P, a.density_only, flags)
+                       : NERF_LAUNCH(nerf_tile_occupied_kernel, dim3((unsigned)((P / 32 + 255) / 256)), dim3(256), st, occupied, P / 32,
+                                     flags);
       if (rc) return rc;
-      hipLaunchKernelGGL(nerf_tile_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, flags, (int)(P / 32), lv, cnt);
-      rc = check_launch("nerf_tile_scan_kernel");
-      if (rc) return rc;
+      if ((rc = NERF_LAUNCH(nerf_tile_scan_kernel, dim3(1), dim3(kScanThreads), st, flags, (int)(P / 32), lv, cnt))) return rc;
       // dead tiles have no workgroup: their g_t / g_x is the zero written here
       if (!pts_mode && !ray_x && g_t_out && hipMemsetAsync(g_t_out, 0, (size_t)P * sizeof(float), (hipStream_t)stream) != hipSuccess)
         return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward: memset failed");
@@ -2039,34 +1988,27 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
         return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward: memset failed");
       // a dense backward needs every row of `save`: refuse (NaN in the alpha-bias gradient) a buffer whose forward skipped rows
       // (chain only: the skipped tiles' incoming gradient is zero by the forward's contract, so is all the chain makes of them)
-      if (grads) {
-        hipLaunchKernelGGL(nerf_check_stamp_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, save + TrainSave::off_stamp(P), grads[nerf::P_BA]);
-        rc = check_launch("nerf_check_stamp_kernel");
-        if (rc) return rc;
-      }
+      if (grads && (rc = NERF_LAUNCH(nerf_check_stamp_kernel, dim3(1), dim3(64), st, save + TrainSave::off_stamp(P),
+                                     grads[nerf::P_BA]))) return rc;
     }
   }
   if (precision == NERF_PREC_F32X) {
-    const unsigned blocks = persistent_blocks(P, kXTilePts);
-    if (pts_mode) hipLaunchKernelGGL(nerf_mlp_bwd_f32x_kernel<true>, dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
-    else if (dens) hipLaunchKernelGGL((nerf_mlp_bwd_f32x_kernel<false, true>), dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(nerf_mlp_bwd_f32x_kernel<false>, dim3(blocks), dim3(kXThreads), 0, (hipStream_t)stream, a);
-    rc = check_launch("nerf_mlp_bwd_f32x_kernel");
+    const dim3 blocks(persistent_blocks(P, kXTilePts)), threads(kXThreads);
+    rc = pts_mode ? NERF_LAUNCH(nerf_mlp_bwd_f32x_kernel<true>, blocks, threads, st, a)
+         : dens   ? NERF_LAUNCH((nerf_mlp_bwd_f32x_kernel<false, true>), blocks, threads, st, a)
+                  : NERF_LAUNCH(nerf_mlp_bwd_f32x_kernel<false>, blocks, threads, st, a);
   } else if (precision == NERF_PREC_F32) {
     const long long tiles = (P + nerf::kTilePts - 1) / nerf::kTilePts;
     if (tiles > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mlp_backward: too many points for one launch");
     // barrier-free: one-wave workgroups (with a live list: one slot per tile, slots >= *n_live exit at once)
-    if (pts_mode) hipLaunchKernelGGL(nerf_mlp_bwd_f32_kernel<true>, dim3((unsigned)tiles), dim3(64), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(nerf_mlp_bwd_f32_kernel<false>, dim3((unsigned)tiles), dim3(64), 0, (hipStream_t)stream, a);
-    rc = check_launch("nerf_mlp_bwd_f32_kernel");
+    rc = pts_mode ? NERF_LAUNCH(nerf_mlp_bwd_f32_kernel<true>, dim3((unsigned)tiles), dim3(64), st, a)
+                  : NERF_LAUNCH(nerf_mlp_bwd_f32_kernel<false>, dim3((unsigned)tiles), dim3(64), st, a);
   } else return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_mlp_backward: f32 or f32x only");
   if (rc) return rc;
-  if (ray_x && g_t_out) {
-    hipLaunchKernelGGL(nerf_gt_of_gx_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g_x_out, a.rays_d,
-                       a.n_samples, P, g_t_out);
-    rc = check_launch("nerf_gt_of_gx_kernel");
-    if (rc) return rc;
-  }
+  if (ray_x && g_t_out &&
+      (rc = NERF_LAUNCH(nerf_gt_of_gx_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), st, g_x_out, a.rays_d, a.n_samples, P,
+                        g_t_out)))
+    return rc;
   if (!grads) return NERF_OK;                       // chain only
   // weight / bias gradients: grad_W = g_z^T @ input, grad_b = sum g_z   (network.py:22-47 layers)
   const float* pe = save + TrainSave::off_pe(P);
@@ -2109,9 +2051,7 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
     long long slices = num_cus() / n_jobs;
     if (slices > steps) slices = steps;
     if (slices < 1) slices = 1;
-    hipLaunchKernelGGL(nerf_wgrad256_bf16x3_kernel, dim3((unsigned)(slices * n_jobs)), dim3(256), 0, (hipStream_t)stream, w);
-    rc = check_launch("nerf_wgrad256_bf16x3_kernel");
-    if (rc) return rc;
+    return NERF_LAUNCH(nerf_wgrad256_bf16x3_kernel, dim3((unsigned)(slices * n_jobs)), dim3(256), st, w);
   } else if (P % 16 == 0 && P / 16 >= num_cus() / 8) {
     // fp32 MFMA, in one launch of the asm-load kernel
     WgradBatch wb;
@@ -2124,28 +2064,14 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
     }
     long long slices = num_cus() / n_jobs;
     if (slices < 1) slices = 1;                       // a device with fewer CUs than jobs still gets a non-empty grid
-    if (live) hipLaunchKernelGGL(nerf_wgrad256_f32_asm_kernel<true>, dim3((unsigned)(slices * n_jobs)), dim3(256), 0, (hipStream_t)stream, wb);
-    else hipLaunchKernelGGL(nerf_wgrad256_f32_asm_kernel<false>, dim3((unsigned)(slices * n_jobs)), dim3(256), 0, (hipStream_t)stream, wb);
-    rc = check_launch("nerf_wgrad256_f32_asm_kernel");
-    if (rc) return rc;
+    const dim3 grid((unsigned)(slices * n_jobs));
+    return live ? NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<true>, grid, dim3(256), st, wb)
+                : NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<false>, grid, dim3(256), st, wb);
   } else {
     for (int i = 0; i < n_jobs; ++i) WG(job[i].dz, 256, 0, 256, job[i].hin, 256, 0, 256, job[i].dw, job[i].ldw, job[i].wc0, job[i].db);
   }
 #undef WG
   return NERF_OK;
-}
-
-// the SAVE families (see kMlpF32 for their place): one-wave workgroups for f32
-static const MlpFamily kMlpSaveF32x = {"nerf_mlp_f32x_kernel", kXTilePts, kXThreads, true, NERF_MLP_SAVE(nerf_mlp_f32x_kernel)};
-static const MlpFamily kMlpSaveF32 = {"nerf_mlp_f32_kernel", nerf::kTilePts, 64, false, NERF_MLP_SAVE(nerf_mlp_f32_kernel)};
-static const MlpFamily* mlp_family(int precision, bool save) {
-  switch (precision) {
-    case NERF_PREC_F32: return save ? &kMlpSaveF32 : &kMlpF32;
-    case NERF_PREC_F32X: return save ? &kMlpSaveF32x : &kMlpF32x;
-    case NERF_PREC_F16: return save ? nullptr : &kMlpF16;
-    case NERF_PREC_F16S: return save ? nullptr : &kMlpF16s;
-  }
-  return nullptr;
 }
 
 // the ray-mode backward entries (grads == nullptr where `grads_optional`: the chain alone)
@@ -2244,14 +2170,11 @@ int32_t nerf_compact_valid(const uint8_t* valid, int64_t n_points, int32_t* inde
   if (!valid || !index || !workspace) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_compact_valid: null argument");
   const long long n_blocks = (n_points + kCompactBlock - 1) / kCompactBlock;
   int* block = (int*)workspace;
-  hipLaunchKernelGGL(nerf_compact_count_kernel, dim3((unsigned)n_blocks), dim3(kCompactBlock), 0, st, valid, (long long)n_points, block);
-  int rc = check_launch("nerf_compact_count_kernel");
+  int rc = NERF_LAUNCH(nerf_compact_count_kernel, dim3((unsigned)n_blocks), dim3(kCompactBlock), st, valid, (long long)n_points, block);
   if (rc) return rc;
-  hipLaunchKernelGGL(nerf_compact_scan_kernel, dim3(1), dim3(1024), 0, st, block, n_blocks, count);
-  rc = check_launch("nerf_compact_scan_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL(nerf_compact_scatter_kernel, dim3((unsigned)n_blocks), dim3(kCompactBlock), 0, st, valid, (long long)n_points, block, index);
-  return check_launch("nerf_compact_scatter_kernel");
+  if ((rc = NERF_LAUNCH(nerf_compact_scan_kernel, dim3(1), dim3(kScanThreads), st, block, n_blocks, count))) return rc;
+  return NERF_LAUNCH(nerf_compact_scatter_kernel, dim3((unsigned)n_blocks), dim3(kCompactBlock), st, valid, (long long)n_points, block,
+                     index);
 }
 
 int32_t nerf_mlp_forward_rays_save_masked(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
@@ -2266,9 +2189,21 @@ int32_t nerf_mlp_forward_rays_save_masked(const float* rays_o, const float* rays
                       save, false, true, precision, stream, index, count);
 }
 
+// The workspace of nerf_mlp_backward_masked: the compact rows the chain works on (incoming gradient, points) and its g_x rows
+struct MaskedBackwardWorkspace {
+  float* draw_c; float* pts_c; float* gx_c;
+  int64_t bytes;
+  MaskedBackwardWorkspace(const void* base, int64_t P) {
+    Carver c(base);
+    draw_c = c.take<float>(P * 4);
+    pts_c = c.take<float>(P * 3);
+    gx_c = c.take<float>(P * 3);
+    bytes = c.bytes();
+  }
+};
 int64_t nerf_mlp_backward_masked_workspace_bytes(int64_t n_points) {
   if (n_points < 0 || n_points > 0x7fffffffLL) return -1;
-  return align256(n_points * 4 * (int64_t)sizeof(float)) + 2 * align256(n_points * 3 * (int64_t)sizeof(float));
+  return MaskedBackwardWorkspace(nullptr, n_points).bytes;
 }
 int32_t nerf_mlp_backward_masked(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride,
                                  int64_t n_rays, int32_t n_samples, const int32_t* index, const int32_t* count,
@@ -2285,23 +2220,19 @@ int32_t nerf_mlp_backward_masked(const float* rays_o, const float* rays_d, const
   if (P % 32 != 0)
     return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_mlp_backward_masked: needs the live-tile kernels and a point count that is a multiple of 32");
   hipStream_t st = (hipStream_t)stream;
-  float* draw_c = (float*)workspace;
-  float* pts_c = (float*)((char*)draw_c + align256(P * 4 * (int64_t)sizeof(float)));
-  float* gx_c = (float*)((char*)pts_c + align256(P * 3 * (int64_t)sizeof(float)));
+  const MaskedBackwardWorkspace w(workspace, P);
   const unsigned blocks = (unsigned)((P + 255) / 256);
-  hipLaunchKernelGGL(nerf_masked_gather_kernel, dim3(blocks), dim3(256), 0, st, index, count, P, reinterpret_cast<const f32x4*>(draw),
-                     rays_o, rays_d, tvals, (long long)t_ray_stride, n_samples, reinterpret_cast<f32x4*>(draw_c), pts_c);
-  int rc = check_launch("nerf_masked_gather_kernel");
+  int rc = NERF_LAUNCH(nerf_masked_gather_kernel, dim3(blocks), dim3(256), st, index, count, P, reinterpret_cast<const f32x4*>(draw),
+                       rays_o, rays_d, tvals, (long long)t_ray_stride, n_samples, reinterpret_cast<f32x4*>(w.draw_c), w.pts_c);
   if (rc) return rc;
   // the chain and the weight-gradient kernels in point mode over the compact rows (live tiles only)
   BwdArgs a{};
-  a.pts = pts_c; a.g_x = g_t ? gx_c : nullptr; a.n_points = P; a.n_samples = n_samples;
-  a.packed_bwd = (const float*)packed_bwd_v; a.draw = draw_c; a.save = save; a.gsave = gsave;
+  a.pts = w.pts_c; a.g_x = g_t ? w.gx_c : nullptr; a.n_points = P; a.n_samples = n_samples;
+  a.packed_bwd = (const float*)packed_bwd_v; a.draw = w.draw_c; a.save = save; a.gsave = gsave;
   rc = mlp_backward_impl(a, true, grads, precision, stream, count);
   if (rc || !g_t) return rc;
   if (hipMemsetAsync(g_t, 0, (size_t)P * sizeof(float), st) != hipSuccess) return fail(NERF_ERR_HIP, "%s", "nerf_mlp_backward_masked: memset failed");
-  hipLaunchKernelGGL(nerf_masked_gt_scatter_kernel, dim3(blocks), dim3(256), 0, st, index, count, P, gx_c, rays_d, n_samples, g_t);
-  return check_launch("nerf_masked_gt_scatter_kernel");
+  return NERF_LAUNCH(nerf_masked_gt_scatter_kernel, dim3(blocks), dim3(256), st, index, count, P, w.gx_c, rays_d, n_samples, g_t);
 }
 
 int32_t nerf_mlp_forward_points_save(const float* pts, const float* viewdirs, int64_t n_rays, int32_t n_samples,
@@ -2324,8 +2255,7 @@ int32_t nerf_image_ssim(const float* pred, const float* gt, int32_t H, int32_t W
     return fail(NERF_ERR_HIP, "%s", "nerf_image_ssim: memset failed");
   long long blocks = ((long long)(H - 6) * (W - 6) * 3 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(nerf_ssim_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pred, gt, H, W, sum1);
-  return check_launch("nerf_ssim_kernel");
+  return NERF_LAUNCH(nerf_ssim_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, pred, gt, H, W, sum1);
 }
 
 // Ray blocks.  nerf_render_forward walks a frame in blocks of kRenderBlockRays rays (the four stages per block, same stream): the
@@ -2352,27 +2282,26 @@ struct RenderWorkspace {
   uint8_t* valid_c = nullptr; int* index_c = nullptr;
   int64_t bytes;
   RenderWorkspace(void* base, int64_t n_rays, int32_t n_importance, int32_t fast_sampling, bool stochastic, bool occupancy = false) {
-    uintptr_t p = (uintptr_t)base;
-    auto take = [&p](int64_t n) { void* q = (void*)p; p += (uintptr_t)align256(n); return q; };
+    Carver c(base);
     const int64_t S = NERF_N_SAMPLES + NERF_N_IMPORTANCE;
-    raw_c = (float*)take(n_rays * NERF_N_SAMPLES * 4 * (int64_t)sizeof(float));
+    raw_c = c.take<float>(n_rays * NERF_N_SAMPLES * 4);
     if (n_importance) {
-      t_sorted = (float*)take(n_rays * S * (int64_t)sizeof(float));
-      raw_f = (float*)take(n_rays * S * 4 * (int64_t)sizeof(float));
+      t_sorted = c.take<float>(n_rays * S);
+      raw_f = c.take<float>(n_rays * S * 4);
     }
     if (n_importance && (fast_sampling || occupancy)) {
-      valid = (uint8_t*)take(n_rays * S);
-      index = (int*)take(n_rays * S * (int64_t)sizeof(int));
+      valid = c.take<uint8_t>(n_rays * S);
+      index = c.take<int>(n_rays * S);
     } else {
-      index = (int*)take(n_rays * (int64_t)sizeof(int));
+      index = c.take<int>(n_rays);
     }
-    count = (int*)take(sizeof(int));
-    if (stochastic) t_jit = (float*)take(n_rays * NERF_N_SAMPLES * (int64_t)sizeof(float));
+    count = c.take<int>(1);
+    if (stochastic) t_jit = c.take<float>(n_rays * NERF_N_SAMPLES);
     if (occupancy) {
-      valid_c = (uint8_t*)take(n_rays * NERF_N_SAMPLES);
-      index_c = (int*)take(n_rays * NERF_N_SAMPLES * (int64_t)sizeof(int));
+      valid_c = c.take<uint8_t>(n_rays * NERF_N_SAMPLES);
+      index_c = c.take<int>(n_rays * NERF_N_SAMPLES);
     }
-    bytes = (int64_t)(p - (uintptr_t)base);
+    bytes = c.bytes();
   }
 };
 static int64_t render_workspace_bytes(int64_t n_rays_frame, int32_t n_importance, int32_t fast_sampling, bool stochastic,
@@ -2435,8 +2364,7 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
       if (hipMemsetAsync(w.count, 0, sizeof(int), st) != hipSuccess ||
           hipMemsetAsync(raw, 0, (size_t)(np * 4 * (int64_t)sizeof(float)), st) != hipSuccess)
         return fail(NERF_ERR_HIP, "%s: memset failed", entry);
-      hipLaunchKernelGGL(nerf_compact_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, valid, np, index, w.count);
-      return check_launch("nerf_compact_kernel");
+      return NERF_LAUNCH(nerf_compact_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), st, valid, np, index, w.count);
     };
     // (occupancy) the points a pass evaluated: the length of its list, or all of them
     auto tally = [&](int pass, bool listed, long long all) -> int {
@@ -2472,9 +2400,8 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
     // split-fp16 stream that rides behind their packed model: fp32-accurate sigma and colour where it matters, ~1.5 % of the frame.
     const bool guard = (precision == NERF_PREC_F16 || precision == NERF_PREC_F16S) && nb <= (int64_t)0x7fffffff / S;
     auto far_plane_guard = [&](const float* tvals, int64_t stride, int32_t S_, const void* packed_f16, float* raw) -> int {
-      hipLaunchKernelGGL(nerf_last_sample_index_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, w.index, w.count, (long long)nb, S_);
-      const int r2 = check_launch("nerf_last_sample_index_kernel");
-      if (r2) return r2;
+      if (const int r2 = NERF_LAUNCH(nerf_last_sample_index_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), st, w.index, w.count,
+                                     (long long)nb, S_)) return r2;
       return forward_rays(entry, o, d, tvals, stride, nb, S_, (const char*)packed_f16 + nerf::kF16PackedBytes, raw, false, nullptr, false,
                           false, NERF_PREC_F32X, stream, w.index, w.count);
     };

@@ -1,6 +1,6 @@
 // Connected components of an indexed triangle mesh and the filter that keeps whole components (DESIGN.md section 2.11).
-// Included at the end of nerf_kernels.hip (uses its fail / check_launch / align256 and the ordered compaction's
-// compact_block_rank / nerf_compact_scan_kernel).
+// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH / Carver and the ordered compaction's
+// nerf_compact_scan_kernel; compact_block_rank comes from nerf_scan.hip.inc).
 //
 // Union-find over parent[V] (int32), lock-free.  A root is always linked under a SMALLER root, so parent[x] <= x holds at every
 // moment, every chain strictly descends, and the root a tree ends up with is the smallest id in it whatever the order in which the
@@ -16,9 +16,11 @@
 //     under (< x) and the union goes on from there: a + b strictly falls with every failed CAS.  No loop waits for another thread.
 //   * labels are read only in later launches than the unions (the kernel boundary is the synchronisation).
 
+#include "nerf_scan.hip.inc"
+
 namespace {
 
-constexpr int kMcBlock = kCompactBlock;      // 256: compact_block_rank's block
+constexpr int kMcBlock = kRankBlock;         // compact_block_rank's block
 
 __device__ __forceinline__ int mc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -174,10 +176,6 @@ void nerf_mesh_filter_emit_kernel(const float* __restrict__ vertices, const int*
   }
 }
 
-struct McLayout {
-  long long nbv, nbf;                 // 256-blocks of the vertices / faces
-  int64_t a, b, c, d, total;          // byte offsets of the second..fourth array and of the end
-};
 inline long long mc_blocks(int64_t n) { return (n + kMcBlock - 1) / kMcBlock; }
 
 int mc_sizes(const char* entry, int64_t n_vertices, int64_t n_faces) {
@@ -186,26 +184,34 @@ int mc_sizes(const char* entry, int64_t n_vertices, int64_t n_faces) {
     return fail(NERF_ERR_INVALID_ARG, "%s: more than 2^31 - 1 vertices or faces", entry);
   return NERF_OK;
 }
-// components: parent[V] | cnt_f[V] | cnt_v[V] | block[nbv]
-McLayout mc_components_layout(int64_t V) {
-  McLayout L;
-  L.nbv = mc_blocks(V); L.nbf = 0;
-  L.a = align256(V * (int64_t)sizeof(int));
-  L.b = 2 * L.a;
-  L.c = 3 * L.a;
-  L.d = L.total = L.c + align256(L.nbv * (int64_t)sizeof(int));
-  return L;
-}
-// filter: rank_v[V] | rank_f[T] | off_v[nbv] | off_f[nbf]
-McLayout mc_filter_layout(int64_t V, int64_t T) {
-  McLayout L;
-  L.nbv = mc_blocks(V); L.nbf = mc_blocks(T);
-  L.a = align256(V * (int64_t)sizeof(int));
-  L.b = L.a + align256(T * (int64_t)sizeof(int));
-  L.c = L.b + align256(L.nbv * (int64_t)sizeof(int));
-  L.d = L.total = L.c + align256(L.nbf * (int64_t)sizeof(int));
-  return L;
-}
+// The two workspaces (one buffer serves both: nerf_mesh_components_workspace_bytes is the larger).  nbv / nbf: 256-blocks of the
+// vertices / faces
+struct McComponentsWorkspace {
+  long long nbv;
+  int* parent; int* cnt_f; int* cnt_v; int* block;
+  int64_t bytes;
+  McComponentsWorkspace(const void* base, int64_t V) : nbv(mc_blocks(V)) {
+    Carver c(base);
+    parent = c.take<int>(V);
+    cnt_f = c.take<int>(V);
+    cnt_v = c.take<int>(V);
+    block = c.take<int>(nbv);
+    bytes = c.bytes();
+  }
+};
+struct McFilterWorkspace {
+  long long nbv, nbf;
+  int* rank_v; int* rank_f; int* off_v; int* off_f;
+  int64_t bytes;
+  McFilterWorkspace(const void* base, int64_t V, int64_t T) : nbv(mc_blocks(V)), nbf(mc_blocks(T)) {
+    Carver c(base);
+    rank_v = c.take<int>(V);
+    rank_f = c.take<int>(T);
+    off_v = c.take<int>(nbv);
+    off_f = c.take<int>(nbf);
+    bytes = c.bytes();
+  }
+};
 
 }  // namespace
 
@@ -213,7 +219,7 @@ extern "C" {
 
 int64_t nerf_mesh_components_workspace_bytes(int64_t n_vertices, int64_t n_faces) {
   if (mc_sizes("nerf_mesh_components_workspace_bytes", n_vertices, n_faces)) return -1;
-  const int64_t a = mc_components_layout(n_vertices).total, b = mc_filter_layout(n_vertices, n_faces).total;
+  const int64_t a = McComponentsWorkspace(nullptr, n_vertices).bytes, b = McFilterWorkspace(nullptr, n_vertices, n_faces).bytes;
   return a > b ? a : b;
 }
 
@@ -234,29 +240,20 @@ int32_t nerf_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_ve
   }
   if (!workspace || !vertex_label || !comp_label || !comp_faces || !comp_vertices)
     return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mesh_components: null argument");
-  const McLayout L = mc_components_layout(V);
-  int* parent = (int*)workspace;
-  int* cnt_f = (int*)((char*)workspace + L.a);
-  int* cnt_v = (int*)((char*)workspace + L.b);
-  int* block = (int*)((char*)workspace + L.c);
+  const McComponentsWorkspace L(workspace, V);
   const unsigned gv = (unsigned)L.nbv, gf = (unsigned)mc_blocks(T), gvf = gv > gf ? gv : gf;
-  hipLaunchKernelGGL(nerf_mesh_init_kernel, dim3(gv), dim3(kMcBlock), 0, st, V, parent, cnt_f, cnt_v);
-  if ((rc = check_launch("nerf_mesh_init_kernel"))) return rc;
+  if ((rc = NERF_LAUNCH(nerf_mesh_init_kernel, dim3(gv), dim3(kMcBlock), st, V, L.parent, L.cnt_f, L.cnt_v))) return rc;
   if (T > 0) {
-    hipLaunchKernelGGL(nerf_mesh_union_kernel, dim3(gf), dim3(kMcBlock), 0, st, faces, T, V, parent);
-    if ((rc = check_launch("nerf_mesh_union_kernel"))) return rc;
+    if ((rc = NERF_LAUNCH(nerf_mesh_union_kernel, dim3(gf), dim3(kMcBlock), st, faces, T, V, L.parent))) return rc;
   }
-  hipLaunchKernelGGL(nerf_mesh_flatten_kernel, dim3(gv), dim3(kMcBlock), 0, st, V, parent, vertex_label);
-  if ((rc = check_launch("nerf_mesh_flatten_kernel"))) return rc;
-  hipLaunchKernelGGL(nerf_mesh_count_kernel, dim3(gvf), dim3(kMcBlock), 0, st, faces, T, V, vertex_label, face_label, cnt_f, cnt_v);
-  if ((rc = check_launch("nerf_mesh_count_kernel"))) return rc;
-  hipLaunchKernelGGL(nerf_mesh_roots_count_kernel, dim3(gv), dim3(kMcBlock), 0, st, V, vertex_label, block);
-  if ((rc = check_launch("nerf_mesh_roots_count_kernel"))) return rc;
-  hipLaunchKernelGGL(nerf_compact_scan_kernel, dim3(1), dim3(1024), 0, st, block, L.nbv, n_components);
-  if ((rc = check_launch("nerf_compact_scan_kernel"))) return rc;
-  hipLaunchKernelGGL(nerf_mesh_roots_scatter_kernel, dim3(gv), dim3(kMcBlock), 0, st, V, vertex_label, block, cnt_f, cnt_v, comp_label,
+  if ((rc = NERF_LAUNCH(nerf_mesh_flatten_kernel, dim3(gv), dim3(kMcBlock), st, V, L.parent, vertex_label))) return rc;
+  if ((rc = NERF_LAUNCH(nerf_mesh_count_kernel, dim3(gvf), dim3(kMcBlock), st, faces, T, V, vertex_label, face_label, L.cnt_f,
+                        L.cnt_v))) return rc;
+  if ((rc = NERF_LAUNCH(nerf_mesh_roots_count_kernel, dim3(gv), dim3(kMcBlock), st, V, vertex_label, L.block))) return rc;
+  if ((rc = NERF_LAUNCH(nerf_compact_scan_kernel, dim3(1), dim3(kScanThreads), st, L.block, L.nbv, n_components))) return rc;
+  return NERF_LAUNCH(nerf_mesh_roots_scatter_kernel, dim3(gv), dim3(kMcBlock), st, V, vertex_label, L.block, L.cnt_f, L.cnt_v,
+                     comp_label,
                      comp_faces, comp_vertices);
-  return check_launch("nerf_mesh_roots_scatter_kernel");
 }
 
 int32_t nerf_mesh_filter_count(const int32_t* vertex_label, const int32_t* face_label, const uint8_t* keep, int64_t n_vertices,
@@ -271,20 +268,14 @@ int32_t nerf_mesh_filter_count(const int32_t* vertex_label, const int32_t* face_
   if (V == 0) return NERF_OK;                                // no vertex, no label in range: nothing is kept
   if (!vertex_label || !keep || !workspace || (T > 0 && !face_label))
     return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mesh_filter_count: null argument");
-  const McLayout L = mc_filter_layout(V, T);
-  int* rank_v = (int*)workspace;
-  int* rank_f = (int*)((char*)workspace + L.a);
-  int* off_v = (int*)((char*)workspace + L.b);
-  int* off_f = (int*)((char*)workspace + L.c);
-  hipLaunchKernelGGL(nerf_mesh_filter_rank_kernel, dim3((unsigned)L.nbv), dim3(kMcBlock), 0, st, V, V, vertex_label, keep, rank_v, off_v);
-  if ((rc = check_launch("nerf_mesh_filter_rank_kernel"))) return rc;
-  hipLaunchKernelGGL(nerf_compact_scan_kernel, dim3(1), dim3(1024), 0, st, off_v, L.nbv, counts);
-  if ((rc = check_launch("nerf_compact_scan_kernel"))) return rc;
+  const McFilterWorkspace L(workspace, V, T);
+  if ((rc = NERF_LAUNCH(nerf_mesh_filter_rank_kernel, dim3((unsigned)L.nbv), dim3(kMcBlock), st, V, V, vertex_label, keep, L.rank_v,
+                        L.off_v))) return rc;
+  if ((rc = NERF_LAUNCH(nerf_compact_scan_kernel, dim3(1), dim3(kScanThreads), st, L.off_v, L.nbv, counts))) return rc;
   if (T > 0) {
-    hipLaunchKernelGGL(nerf_mesh_filter_rank_kernel, dim3((unsigned)L.nbf), dim3(kMcBlock), 0, st, T, V, face_label, keep, rank_f, off_f);
-    if ((rc = check_launch("nerf_mesh_filter_rank_kernel"))) return rc;
-    hipLaunchKernelGGL(nerf_compact_scan_kernel, dim3(1), dim3(1024), 0, st, off_f, L.nbf, counts + 1);
-    if ((rc = check_launch("nerf_compact_scan_kernel"))) return rc;
+    if ((rc = NERF_LAUNCH(nerf_mesh_filter_rank_kernel, dim3((unsigned)L.nbf), dim3(kMcBlock), st, T, V, face_label, keep, L.rank_f,
+                          L.off_f))) return rc;
+    if ((rc = NERF_LAUNCH(nerf_compact_scan_kernel, dim3(1), dim3(kScanThreads), st, L.off_f, L.nbf, counts + 1))) return rc;
   }
   return NERF_OK;
 }
@@ -297,15 +288,10 @@ int32_t nerf_mesh_filter_emit(const float* vertices, const int32_t* faces, int64
   if (V == 0) return NERF_OK;
   if (!vertices || !workspace || !out_vertices || !vertex_index || (T > 0 && (!faces || !out_faces)))
     return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_mesh_filter_emit: null argument");
-  const McLayout L = mc_filter_layout(V, T);
-  const int* rank_v = (const int*)workspace;
-  const int* rank_f = (const int*)((const char*)workspace + L.a);
-  const int* off_v = (const int*)((const char*)workspace + L.b);
-  const int* off_f = (const int*)((const char*)workspace + L.c);
+  const McFilterWorkspace L(workspace, V, T);
   const unsigned g = (unsigned)(L.nbv > L.nbf ? L.nbv : L.nbf);
-  hipLaunchKernelGGL(nerf_mesh_filter_emit_kernel, dim3(g), dim3(kMcBlock), 0, (hipStream_t)stream, vertices, faces, V, T, rank_v, off_v,
-                     rank_f, off_f, out_vertices, out_faces, vertex_index);
-  return check_launch("nerf_mesh_filter_emit_kernel");
+  return NERF_LAUNCH(nerf_mesh_filter_emit_kernel, dim3(g), dim3(kMcBlock), (hipStream_t)stream, vertices, faces, V, T, L.rank_v,
+                     L.off_v, L.rank_f, L.off_f, out_vertices, out_faces, vertex_index);
 }
 
 }  // extern "C"

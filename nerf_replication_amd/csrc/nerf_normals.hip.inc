@@ -1,6 +1,6 @@
 // Geometry outputs: the density gradient at points (nerf_density_gradient) and the composited surface normal / opacity of a ray
 // (nerf_composite_normals).  DESIGN.md section 2.10; the definitions are in include/nerf_mi355x.h.
-// Included at the end of nerf_kernels.hip (uses its fail / check_launch / align256 / forward_rays / backward_rays, CompositeWeight,
+// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH / Carver / forward_rays / backward_rays, CompositeWeight,
 // lane_bcast and kCbMaxSamples).
 //
 // No MLP kernel is added: a block of nerf_density_gradient is the density SAVE forward and the density chain (grads == NULL) of a
@@ -91,13 +91,12 @@ struct DensityGradWorkspace {
   float* save; float* gsave; float* raw; float* draw;
   int64_t bytes;
   DensityGradWorkspace(void* base, int64_t pts) {
-    uintptr_t p = (uintptr_t)base;
-    auto take = [&p](int64_t n) { void* q = (void*)p; p += (uintptr_t)align256(n); return q; };
-    save = (float*)take(TrainSave::floats(pts) * (int64_t)sizeof(float));
-    gsave = (float*)take(TrainGrad::floats(pts) * (int64_t)sizeof(float));
-    raw = (float*)take(pts * 4 * (int64_t)sizeof(float));
-    draw = (float*)take(pts * 4 * (int64_t)sizeof(float));
-    bytes = (int64_t)(p - (uintptr_t)base);
+    Carver c(base);
+    save = c.take<float>(TrainSave::floats(pts));
+    gsave = c.take<float>(TrainGrad::floats(pts));
+    raw = c.take<float>(pts * 4);
+    draw = c.take<float>(pts * 4);
+    bytes = c.bytes();
   }
 };
 static_assert(32 * kDensityGradPointBytes >= 4 * (TrainSave::floats(32) + TrainGrad::floats(32) + 2 * 32 * 4) + 4 * 255 &&
@@ -135,10 +134,8 @@ int32_t nerf_density_gradient(const float* rays_o, const float* rays_d, const fl
     const DensityGradWorkspace w(workspace, P);
     int rc = forward_rays(entry, o, d, t, t_ray_stride, nb, n_samples, packed, w.raw, true, w.save, true, false, precision, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(nerf_density_seed_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, w.raw, (long long)P, positive_only,
-                       w.draw, sigma ? sigma + p0 : nullptr);
-    rc = check_launch("nerf_density_seed_kernel");
-    if (rc) return rc;
+    if ((rc = NERF_LAUNCH(nerf_density_seed_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), st, w.raw, (long long)P,
+                          positive_only, w.draw, sigma ? sigma + p0 : nullptr))) return rc;
     rc = backward_rays(entry, o, d, t, t_ray_stride, nb, n_samples, packed_bwd, w.draw, w.save, w.gsave, nullptr, grad + 3 * p0, nullptr,
                        true, true, precision, stream);
     if (rc) return rc;
@@ -154,9 +151,8 @@ int32_t nerf_composite_normals(const float* raw, const float* tvals, int64_t t_r
   if (!raw || !tvals || !grad || !normal || !acc) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_composite_normals: null argument");
   const long long blocks = (n_rays + 3) / 4;
   if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_composite_normals: too many rays for one launch");
-  hipLaunchKernelGGL(nerf_composite_normals_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, tvals,
+  return NERF_LAUNCH(nerf_composite_normals_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, raw, tvals,
                      (long long)t_ray_stride, (long long)n_rays, n_samples, grad, normal, acc);
-  return check_launch("nerf_composite_normals_kernel");
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Occupancy grid: a bitfield over the cells of a density grid, and the per-sample lookup that culls empty space from a render
 // (DESIGN.md section 2.9; the definitions are in include/nerf_mi355x.h, nerf_occupancy_*).
-// Included at the end of nerf_kernels.hip (uses its fail / check_launch / masked_sizes_ok / render_frame).
+// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH / masked_sizes_ok / render_frame).
 //
 // Both kernels are memory-trivial: the bitfield is (nx-1)(ny-1)(nz-1) / 8 bytes (2 MB at 256^3) and stays in L2; the build reads
 // the field (2r + 2)^3 times per cell out of the same cache, once per grid; the mark reads 4 bytes and writes 1 per sample.
@@ -131,8 +131,7 @@ extern "C" {
 
 // the hook of render_frame (declared in front of it)
 static int occupancy_tally(const int* count, long long all, long long* evaluated, hipStream_t st) {
-  hipLaunchKernelGGL(nerf_occupancy_tally_kernel, dim3(1), dim3(1), 0, st, count, all, evaluated);
-  return check_launch("nerf_occupancy_tally_kernel");
+  return NERF_LAUNCH(nerf_occupancy_tally_kernel, dim3(1), dim3(1), st, count, all, evaluated);
 }
 
 int64_t nerf_occupancy_words(int32_t nx, int32_t ny, int32_t nz) {
@@ -153,9 +152,8 @@ int32_t nerf_occupancy_build(const float* field, int64_t stride, int32_t nx, int
   const int reach = nx > ny ? (nx > nz ? nx : nz) : (ny > nz ? ny : nz);       // a larger dilation reads the whole grid just the same
   const long long n_words64 = (G.cells + 63) / 64;
   const long long blocks = (n_words64 + kOccBlock / 64 - 1) / (kOccBlock / 64);
-  hipLaunchKernelGGL(nerf_occupancy_build_kernel, dim3((unsigned)blocks), dim3(kOccBlock), 0, (hipStream_t)stream, field, (long long)stride,
-                     G, level, dilate < reach ? dilate : reach, n_words64, bits);
-  return check_launch("nerf_occupancy_build_kernel");
+  return NERF_LAUNCH(nerf_occupancy_build_kernel, dim3((unsigned)blocks), dim3(kOccBlock), (hipStream_t)stream, field,
+                     (long long)stride, G, level, dilate < reach ? dilate : reach, n_words64, bits);
 }
 
 int32_t nerf_occupancy_age(const float* field, int64_t stride, int64_t n_points, float level, int32_t hold, uint8_t* age, float* on,
@@ -164,9 +162,8 @@ int32_t nerf_occupancy_age(const float* field, int64_t stride, int64_t n_points,
   if (stride < 1 || hold < 1 || hold > 255) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_occupancy_age: stride must be >= 1 and hold in [1, 255]");
   if (n_points == 0) return NERF_OK;
   if (!field || !age || !on) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_occupancy_age: null argument");
-  hipLaunchKernelGGL(nerf_occupancy_age_kernel, dim3((unsigned)((n_points + kOccBlock - 1) / kOccBlock)), dim3(kOccBlock), 0, (hipStream_t)stream,
-                     field, (long long)stride, (long long)n_points, level, hold, age, on);
-  return check_launch("nerf_occupancy_age_kernel");
+  return NERF_LAUNCH(nerf_occupancy_age_kernel, dim3((unsigned)((n_points + kOccBlock - 1) / kOccBlock)), dim3(kOccBlock),
+                     (hipStream_t)stream, field, (long long)stride, (long long)n_points, level, hold, age, on);
 }
 
 int32_t nerf_occupancy_mark(const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride, int64_t n_rays,
@@ -179,9 +176,9 @@ int32_t nerf_occupancy_mark(const float* rays_o, const float* rays_d, const floa
   if (n_rays == 0) return NERF_OK;
   if (!rays_o || !rays_d || !tvals || !bits || !valid) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_occupancy_mark: null argument");
   const long long np = n_rays * (long long)n_samples;
-  hipLaunchKernelGGL(nerf_occupancy_mark_kernel, dim3((unsigned)((np + kOccBlock - 1) / kOccBlock)), dim3(kOccBlock), 0, (hipStream_t)stream,
-                     rays_o, rays_d, tvals, (long long)t_ray_stride, np, n_samples, bits, L, and_with_existing, valid);
-  return check_launch("nerf_occupancy_mark_kernel");
+  return NERF_LAUNCH(nerf_occupancy_mark_kernel, dim3((unsigned)((np + kOccBlock - 1) / kOccBlock)), dim3(kOccBlock),
+                     (hipStream_t)stream, rays_o, rays_d, tvals, (long long)t_ray_stride, np, n_samples, bits, L, and_with_existing,
+                     valid);
 }
 
 int64_t nerf_render_occupancy_workspace_bytes(int64_t n_rays_frame, int32_t n_importance, int32_t fast_sampling) {

@@ -322,6 +322,36 @@ def test_masked_entries_with_nothing_listed(amd, synthetic_sd, precision):
     assert lib.nerf_compact_valid_workspace_bytes(1 << 31) == -1 and lib.nerf_mlp_backward_masked_workspace_bytes(1 << 31) == -1
 
 
+# 256 ids per block, one scan workgroup of 1024 threads over the block counts, ceil(blocks / 1024) consecutive blocks per thread:
+# 1023 / 1024 blocks (one per thread), 1025 / 1026 (two per thread: 513 threads busy, the others start past the end, the last
+# block ragged), 2050 (three per thread)
+@pytest.mark.parametrize("n_points", [1, 255, 256, 257, 256 * 1023, 256 * 1024, 256 * 1024 + 1, 256 * 1025 + 3, 256 * 2049 + 5])
+def test_compact_valid_lists_the_set_ids_in_ascending_order(amd, n_points):
+    """nerf_compact_valid against numpy.flatnonzero for an empty, a half-set and a full mask: the count, the ids in ascending
+    order, and nothing written behind them -- neither in the rest of `index` nor behind the buffer."""
+    import numpy as np
+    L, lib = amd._lib, amd._lib.load()
+    st = L.stream_of(torch.device("cuda"))
+    rng = np.random.default_rng(n_points)
+    ws_bytes = int(lib.nerf_compact_valid_workspace_bytes(n_points))
+    for density in (0.0, 0.5, 1.0):
+        mask = (rng.random(n_points) < density).astype(np.uint8) * rng.integers(1, 256, n_points, dtype=np.uint8)     # any non-zero byte is set
+        ref = np.flatnonzero(mask)
+        valid = torch.from_numpy(mask).cuda()
+        index = torch.full((n_points + 64,), -7, dtype=torch.int32, device="cuda")      # 64 ids of room behind the buffer the entry knows
+        count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        ws = torch.full((ws_bytes + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+        L.check(lib.nerf_compact_valid(L.ptr(valid, torch.uint8), n_points, L.ptr(index, torch.int32), L.ptr(count, torch.int32),
+                                       ws.data_ptr(), st))
+        torch.cuda.synchronize()
+        print(n_points, density, int(count.item()), int(mask.astype(bool).sum()))
+        assert int(count.item()) == int((mask != 0).sum()) == ref.size
+        got = index.cpu().numpy()
+        assert np.array_equal(got[:ref.size], ref)
+        assert np.all(got[ref.size:] == -7)
+        assert torch.all(ws[ws_bytes:] == 0xA5)
+
+
 # ================================================================================ 5: dead-tile switch
 @pytest.mark.parametrize("precision", ["f32", "f32x"])
 @pytest.mark.parametrize("tag,family,thr", MASKED_CASES[:2])

@@ -508,7 +508,8 @@ def test_density_only_pair_equals_full_pair_with_zero_colour_gradient(amd, net, 
     net.precision = "f32"
 
 
-@pytest.mark.parametrize("shape", [(48, 192), (1, 32), (7, 160)])       # 288 tiles; a single tile; 35 tiles (fewer than scan threads)
+# 288 tiles; a single tile; 35 tiles (fewer than scan threads); 1026 tiles (more than scan threads: two per thread, 513 threads busy)
+@pytest.mark.parametrize("shape", [(48, 192), (1, 32), (7, 160), (171, 192)])
 @pytest.mark.parametrize("precision", ["f32", "f32x"])
 @pytest.mark.parametrize("density_only", [False, True])
 @pytest.mark.parametrize("dead_frac", [0.0, 0.6, 1.0])

@@ -552,6 +552,35 @@ int32_t nerf_mesh_filter_emit(const float* vertices, const int32_t* faces, int64
                               const void* workspace, float* out_vertices, int32_t* out_faces, int32_t* vertex_index,
                               void* stream);
 
+/* ---- multiresolution hash-grid encoding (instant-NGP; the reference's src/models/encoding/hashencoder) -------
+ * x [B,D] in [0,1], emb [offsets[L],C], out / grad_out [B,L*C] (level-major columns: level l owns columns l*C .. l*C+C-1), fp32.
+ * D in {2,3,4}, C in {1,2,4,8}, 1 <= L <= 32.  Level l is the rows offsets[l] .. offsets[l+1]-1 of emb; n = their number.
+ * offsets_host (int32 [L+1], increasing, offsets[0] >= 0) and scales_host (float [L]) are HOST arrays; they travel inside the kernel
+ * arguments: no device allocation, no workspace, no host sync.  scales_host[l] is the level's grid scale, which the caller computes
+ * (nerf_replication_amd/hashgrid.py: float32(exp2(l * log2(per_level_scale)) * base_resolution - 1), in double, rounded once).
+ * Per point and level, in fp32 with every multiply and add rounded on its own:
+ *     pos_d = x_d * scale + 0.5,  g_d = floor(pos_d),  f_d = pos_d - g_d,  resolution = uint32(ceil(scale)) + 1
+ *     corner idx in 0 .. 2^D-1 sits at g_d + bit_d(idx) and weighs w = 1 * prod_d (bit_d(idx) ? f_d : 1 - f_d), d ascending
+ *     row(corner), in uint32 with wrap-around: stride = 1, index = 0; for d = 0..D-1 while stride <= n: index += g_d * stride,
+ *         stride *= resolution + 1; if then stride > n: index = XOR_d g_d * prime_d (1, 19349663, 83492791, 25165843); row = index mod n
+ *     out[b, l*C + c] = sum over idx ascending, from 0, of w * emb[offsets[l] + row, c]
+ * Every row is reduced modulo n, so inputs outside [0,1], infinities and NaN give unspecified values but never an access outside the
+ * level.
+ * nerf_hashgrid_backward: grad_emb (may be NULL) [offsets[L],C] is ACCUMULATED into with no-return fp32 atomic adds,
+ *     grad_emb[offsets[l] + row, c] += w * grad_out[b, l*C + c]  (the caller zeroes it; the arrival order, hence the last bits, vary
+ *     from run to run); grad_x (may be NULL) [B,D] is WRITTEN: the derivative of the forward with respect to x inside the cell,
+ *     sum_l sum_c grad_out[b, l*C + c] * sum over the corners of the other axes of scale * prod_(a != d) (their factor) * (emb[right,
+ *     c] - emb[left, c]), recomputed from x and emb (nothing is kept from the forward).  emb is read only when grad_x is given.
+ * emb, out and grad_out must be aligned to 4*C bytes (rows are moved as vectors).
+ * Refused before any launch, with nerf_last_error set: D, C or L outside the lists above (NERF_ERR_UNSUPPORTED); B <= 0 (unlike the
+ * ray entries, an empty batch is not a no-op here), B*L*C or B*D above 2^31 - 1 (the kernels index with 32 bits: encode in chunks),
+ * offsets that do not increase, null or misaligned pointers (NERF_ERR_INVALID_ARG). */
+int32_t nerf_hashgrid_forward(const float* x, const float* emb, int64_t B, int32_t D, int32_t C, int32_t L,
+                              const int32_t* offsets_host, const float* scales_host, float* out, void* stream);
+int32_t nerf_hashgrid_backward(const float* x, const float* emb, const float* grad_out, int64_t B, int32_t D, int32_t C, int32_t L,
+                               const int32_t* offsets_host, const float* scales_host, float* grad_emb, float* grad_x,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 Public surface mirrors rkin100g/Nerf-Replication (paths relative to the reference root):
     Renderer   <- src/models/nerf/renderer/volume_renderer.py  (Renderer(net).render(batch))
     Network    <- src/models/nerf/network.py                    (Network().forward(...), state_dict keys)
+    HashEncoder, TriPlane <- src/models/encoding/hashencoder/hashgrid.py  (constructor, `embeddings`, forward(xyz, wbounds, normalize))
 The arithmetic runs in hand-written HIP kernels (csrc/) reached through the C ABI declared in
 include/nerf_mi355x.h; there is no CPU or eager-PyTorch fallback: without the built library or a
 GPU the product path raises.
@@ -26,12 +27,13 @@ _LAZY = {
     "density_gradient": ".mesh", "vertex_normals": ".mesh",
     "mesh_components": ".mesh", "filter_components": ".mesh", "vertex_colors": ".mesh", "write_ply_colors": ".mesh",
     "OccupancyGrid": ".occupancy",
+    "HashEncoder": ".hashgrid", "TriPlane": ".hashgrid",
 }
-_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy")
+_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy", "hashgrid")
 
 __all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model",
            "density_grid", "isosurface", "write_ply", "extract_mesh", "density_gradient", "vertex_normals",
-           "mesh_components", "filter_components", "vertex_colors", "write_ply_colors", "OccupancyGrid"]
+           "mesh_components", "filter_components", "vertex_colors", "write_ply_colors", "OccupancyGrid", "HashEncoder", "TriPlane"]
 
 
 def __getattr__(name):

@@ -120,6 +120,11 @@ _PROTOS = {
     "nerf_mesh_components": (_c.c_int32, [_F, _c.c_int64, _c.c_int64, _F, _F, _F, _F, _F, _F, _F, _c.c_void_p]),
     "nerf_mesh_filter_count": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _F, _F, _c.c_void_p]),
     "nerf_mesh_filter_emit": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int64, _F, _F, _F, _F, _c.c_void_p]),
+    # multiresolution hash-grid encoding (hashgrid.py); offsets and scales are host arrays
+    "nerf_hashgrid_forward": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.POINTER(_c.c_int32),
+                                           _c.POINTER(_c.c_float), _F, _c.c_void_p]),
+    "nerf_hashgrid_backward": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.POINTER(_c.c_int32),
+                                            _c.POINTER(_c.c_float), _F, _F, _c.c_void_p]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -2481,3 +2481,5 @@ int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d,
 #include "nerf_normals.hip.inc"
 // ---- mesh clean-up: nerf_mesh_components and nerf_mesh_filter_*
 #include "nerf_mesh_components.hip.inc"
+// ---- multiresolution hash-grid encoding: nerf_hashgrid_forward / nerf_hashgrid_backward
+#include "nerf_hashgrid.hip.inc"

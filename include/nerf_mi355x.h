@@ -576,9 +576,9 @@ int32_t nerf_mesh_filter_emit(const float* vertices, const int32_t* faces, int64
  * ray entries, an empty batch is not a no-op here), B*L*C or B*D above 2^31 - 1 (the kernels index with 32 bits: encode in chunks),
  * offsets that do not increase, null or misaligned pointers (NERF_ERR_INVALID_ARG). */
 int32_t nerf_hashgrid_forward(const float* x, const float* emb, int64_t B, int32_t D, int32_t C, int32_t L,
-                              const int32_t* offsets_host, const float* scales_host, float* out, void* stream);
+                              const int32_t offsets_host[], const float scales_host[], float* out, void* stream);
 int32_t nerf_hashgrid_backward(const float* x, const float* emb, const float* grad_out, int64_t B, int32_t D, int32_t C, int32_t L,
-                               const int32_t* offsets_host, const float* scales_host, float* grad_emb, float* grad_x,
+                               const int32_t offsets_host[], const float scales_host[], float* grad_emb, float* grad_x,
                                void* stream);
 
 #ifdef __cplusplus

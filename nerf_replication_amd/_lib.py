@@ -21,112 +21,109 @@ PREC_F16S = 3          # fp16 arithmetic on 16x16x32 MFMA tiles (A/B partner of 
 # selects; "f16m32" selects the 32x32x16 kernel explicitly.
 PRECISIONS = {"f32": PREC_F32, "fp32": PREC_F32, "f16": PREC_F16S, "fp16": PREC_F16S, "f16s": PREC_F16S, "f16m32": PREC_F16, "f32x": PREC_F32X}
 
-_c = ctypes
-_F = _c.c_void_p   # device pointers travel as integers (tensor.data_ptr())
-_PROTOS = {
-    "nerf_abi_version": (_c.c_int32, []),
-    "nerf_build_flags": (_c.c_int32, []),
-    "nerf_last_error": (_c.c_char_p, []),
-    "nerf_packed_model_bytes": (_c.c_int64, [_c.c_int32]),
-    "nerf_pack_model": (_c.c_int32, [_c.POINTER(_c.c_void_p), _F, _c.c_int32, _c.c_void_p]),
-    "nerf_positional_encoding": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _F, _c.c_void_p]),
-    "nerf_mlp_forward": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int32, _F, _F, _c.c_int32, _c.c_void_p]),
-    "nerf_mlp_forward_rays": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F,
-                                           _c.c_int32, _c.c_void_p]),
-    "nerf_mlp_forward_rays_for_compositing": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F,
-                                                           _c.c_int32, _c.c_void_p]),
-    "nerf_mlp_forward_rays_density": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F,
-                                                   _c.c_int32, _c.c_void_p]),
-    "nerf_composite_backward": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32, _F, _F, _F, _F,
-                                             _c.c_void_p]),
-    "nerf_sample_fine_backward": (_c.c_int32, [_F, _F, _F, _c.c_int64, _F, _F, _F, _c.c_void_p]),
-    "nerf_adam_step": (_c.c_int32, [_c.c_int32, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
-                                    _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int64), _c.c_float, _c.c_float, _c.c_float,
-                                    _c.c_float, _c.c_float, _c.c_float, _c.c_int64, _c.c_void_p]),
-    "nerf_train_grad_floats": (_c.c_int64, [_c.c_int64]),
-    "nerf_train_live_count_offset": (_c.c_int64, [_c.c_int64]),
-    "nerf_packed_bwd_bytes": (_c.c_int64, [_c.c_int32]),
-    "nerf_pack_model_bwd": (_c.c_int32, [_c.POINTER(_c.c_void_p), _F, _c.c_int32, _c.c_void_p]),
-    "nerf_mlp_backward": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F,
-                                       _c.POINTER(_c.c_void_p), _c.c_int32, _c.c_void_p]),
-    "nerf_mlp_forward_rays_save_density": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_int32,
-                                                        _c.c_void_p]),
-    "nerf_mlp_backward_density": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F,
-                                               _c.POINTER(_c.c_void_p), _c.c_int32, _c.c_void_p]),
-    "nerf_mlp_forward_points_save": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_int32, _c.c_void_p]),
-    "nerf_mlp_backward_points": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F,
-                                              _c.POINTER(_c.c_void_p), _c.c_int32, _c.c_void_p]),
-    "nerf_viewdirs_backward": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_void_p]),
-    "nerf_wgrad": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _F, _c.c_int64, _c.c_int32, _c.c_int32, _F,
-                                _c.c_int64, _c.c_int32, _F, _c.c_int64, _c.c_void_p]),
-    "nerf_train_save_floats": (_c.c_int64, [_c.c_int64]),
-    "nerf_mlp_forward_rays_save": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_int32,
-                                                _c.c_void_p]),
-    "nerf_mlp_forward_rays_save_for_compositing": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_int32,
-                                                _c.c_void_p]),
-    "nerf_sample_fine": (_c.c_int32, [_F, _F, _F, _c.c_int64, _F, _F, _F, _c.c_float, _c.c_float, _c.c_void_p]),
-    "nerf_composite": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32, _F, _F, _F,
-                                    _c.c_void_p]),
-    "nerf_generate_rays": (_c.c_int32, [_c.POINTER(_c.c_double), _c.c_int32, _c.c_int32, _c.c_double, _c.c_int64,
-                                        _c.c_int64, _F, _F, _F, _c.c_void_p]),
-    "nerf_image_metrics": (_c.c_int32, [_F, _F, _c.c_int64, _F, _c.c_void_p]),
-    "nerf_image_ssim": (_c.c_int32, [_F, _F, _c.c_int32, _c.c_int32, _F, _c.c_void_p]),
-    "nerf_render_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int32, _c.c_int32]),
-    "nerf_render_forward": (_c.c_int32, [_F, _F, _c.c_int64, _F, _F, _F, _F, _c.c_int32, _c.c_int32,
-                                         _c.c_int32, _c.c_int32, _c.c_float, _F, _c.c_int64, _F, _F, _c.c_void_p]),
-    # stochastic sampling (task == "train")
-    "nerf_stratified_samples": (_c.c_int32, [_F, _F, _c.c_int64, _F, _c.c_void_p]),
-    "nerf_sample_fine_rays": (_c.c_int32, [_F, _F, _c.c_int64, _F, _c.c_int64, _c.c_int64, _F, _F, _F, _c.c_float, _c.c_float,
-                                           _c.c_void_p]),
-    "nerf_sample_fine_rays_backward": (_c.c_int32, [_F, _F, _c.c_int64, _F, _c.c_int64, _c.c_int64, _F, _F, _F, _c.c_void_p]),
-    "nerf_render_stochastic_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int32]),
-    "nerf_render_forward_stochastic": (_c.c_int32, [_F, _F, _c.c_int64, _F, _F, _F, _F, _F, _F, _c.c_int32, _c.c_int32,
-                                                    _c.c_int32, _c.c_int32, _c.c_float, _F, _c.c_int64, _F, _F, _c.c_void_p]),
-    # gradients with respect to the rays
-    "nerf_mlp_backward_rays_x": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F, _F,
-                                              _c.POINTER(_c.c_void_p), _c.c_int32, _c.c_int32, _c.c_void_p]),
-    "nerf_rays_viewdirs_backward": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_void_p]),
-    "nerf_rays_backward": (_c.c_int32, [_c.c_int64, _F, _c.c_int64, _F, _F, _F, _F, _F, _F, _c.c_void_p]),
-    # masked (fast_sampling) fine pass of a training step
-    "nerf_compact_valid_workspace_bytes": (_c.c_int64, [_c.c_int64]),
-    "nerf_compact_valid": (_c.c_int32, [_F, _c.c_int64, _F, _F, _F, _c.c_void_p]),
-    "nerf_mlp_forward_rays_save_masked": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F,
-                                                       _c.c_int32, _c.c_void_p]),
-    "nerf_mlp_backward_masked_workspace_bytes": (_c.c_int64, [_c.c_int64]),
-    "nerf_mlp_backward_masked": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _F, _F, _F, _F,
-                                              _c.POINTER(_c.c_void_p), _c.c_int32, _F, _c.c_void_p]),
-    # iso-surface of a scalar grid (mesh.py)
-    "nerf_isosurface_workspace_bytes": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32]),
-    "nerf_isosurface_count": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float, _F, _F, _c.c_void_p]),
-    "nerf_isosurface_emit": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float,
-                                          _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _F, _F, _F, _c.c_void_p]),
-    # occupancy grid (occupancy.py)
-    "nerf_occupancy_words": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32]),
-    "nerf_occupancy_build": (_c.c_int32, [_F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float, _c.c_int32, _F, _c.c_void_p]),
-    "nerf_occupancy_mark": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _c.POINTER(_c.c_int32),
-                                         _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _c.c_int32, _F, _c.c_void_p]),
-    "nerf_occupancy_age": (_c.c_int32, [_F, _c.c_int64, _c.c_int64, _c.c_float, _c.c_int32, _F, _F, _c.c_void_p]),
-    "nerf_render_occupancy_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int32, _c.c_int32]),
-    "nerf_render_forward_occupancy": (_c.c_int32, [_F, _F, _c.c_int64, _F, _F, _F, _F, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                                   _c.c_float, _F, _F, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_float),
-                                                   _c.POINTER(_c.c_float), _F, _F, _c.c_int64, _F, _F, _c.c_void_p]),
-    # geometry outputs: density gradient, composited normal and opacity (Renderer.render_geometry, mesh.vertex_normals)
-    "nerf_density_gradient_point_bytes": (_c.c_int64, []),
-    "nerf_density_gradient": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _c.c_int32, _F, _F, _c.c_int32,
-                                           _F, _c.c_int64, _c.c_void_p]),
-    "nerf_composite_normals": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int64, _c.c_int32, _F, _F, _F, _c.c_void_p]),
-    # mesh clean-up: connected components and the component filter (mesh.py)
-    "nerf_mesh_components_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int64]),
-    "nerf_mesh_components": (_c.c_int32, [_F, _c.c_int64, _c.c_int64, _F, _F, _F, _F, _F, _F, _F, _c.c_void_p]),
-    "nerf_mesh_filter_count": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int64, _F, _F, _c.c_void_p]),
-    "nerf_mesh_filter_emit": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int64, _F, _F, _F, _F, _c.c_void_p]),
-    # multiresolution hash-grid encoding (hashgrid.py); offsets and scales are host arrays
-    "nerf_hashgrid_forward": (_c.c_int32, [_F, _F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.POINTER(_c.c_int32),
-                                           _c.POINTER(_c.c_float), _F, _c.c_void_p]),
-    "nerf_hashgrid_backward": (_c.c_int32, [_F, _F, _F, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.POINTER(_c.c_int32),
-                                            _c.POINTER(_c.c_float), _F, _F, _c.c_void_p]),
-}
-EXPORTS = tuple(_PROTOS)
+
+def fp32_accurate(precision_name: str) -> bool:
+    """The precisions with fp32-accurate arithmetic: what stochastic sampling, occupancy culling and the gradient chain run in."""
+    return PRECISIONS[precision_name] in (PREC_F32, PREC_F32X)
+
+
+# The binding surface, one line per entry of include/nerf_mi355x.h: "name  return kind : one kind per parameter".  Kinds:
+#   i32 i64 f32 f64            scalars
+#   f32* i32* u8* i64* f64*    device pointer to elements of that type (uint32_t* is i32*: the bitfields are int32 tensors);
+#   void*                      device bytes of any element type (packed models, workspaces)
+#   T[N] / T[]                 HOST array of N (any number of) scalars;  f32*[N] / f32*[]: HOST array of device float pointers
+#   stream                     the trailing hipStream_t, which call() supplies
+# Return kinds: status (the int32_t nerf_status of an entry that takes a stream), i32, i64, str.  tests/test_abi_symbols.py parses
+# the header and compares every declaration with this table, kind by kind.
+_TABLE = """
+nerf_abi_version  i32 :
+nerf_build_flags  i32 :
+nerf_last_error  str :
+nerf_packed_model_bytes  i64 : i32
+nerf_pack_model  status : f32*[24] void* i32 stream
+nerf_positional_encoding  status : f32* i64 i32 f32* stream
+nerf_mlp_forward  status : f32* f32* i64 i32 void* f32* i32 stream
+nerf_mlp_forward_rays  status : f32* f32* f32* i64 i64 i32 void* f32* i32 stream
+nerf_mlp_forward_rays_for_compositing  status : f32* f32* f32* i64 i64 i32 void* f32* i32 stream
+nerf_mlp_forward_rays_density  status : f32* f32* f32* i64 i64 i32 void* f32* i32 stream
+nerf_composite_backward  status : f32* f32* i64 i64 i32 i32 f32* f32* f32* f32* stream
+nerf_sample_fine_backward  status : f32* f32* f32* i64 f32* f32* f32* stream
+nerf_adam_step  status : i32 f32*[] f32*[] f32*[] f32*[] i64[] f32 f32 f32 f32 f32 f32 i64 stream
+nerf_train_grad_floats  i64 : i64
+nerf_train_live_count_offset  i64 : i64
+nerf_packed_bwd_bytes  i64 : i32
+nerf_pack_model_bwd  status : f32*[24] void* i32 stream
+nerf_mlp_backward  status : f32* f32* f32* i64 i64 i32 void* f32* f32* f32* f32* f32*[24] i32 stream
+nerf_mlp_forward_rays_save_density  status : f32* f32* f32* i64 i64 i32 void* f32* f32* i32 stream
+nerf_mlp_backward_density  status : f32* f32* f32* i64 i64 i32 void* f32* f32* f32* f32* f32*[24] i32 stream
+nerf_mlp_forward_points_save  status : f32* f32* i64 i32 void* f32* f32* i32 stream
+nerf_mlp_backward_points  status : f32* i64 i32 void* f32* f32* f32* f32* f32*[24] i32 stream
+nerf_viewdirs_backward  status : f32* i64 i32 f32* f32* f32* stream
+nerf_wgrad  status : f32* i64 i32 i32 f32* i64 i32 i32 f32* i64 i32 f32* i64 stream
+nerf_train_save_floats  i64 : i64
+nerf_mlp_forward_rays_save  status : f32* f32* f32* i64 i64 i32 void* f32* f32* i32 stream
+nerf_mlp_forward_rays_save_for_compositing  status : f32* f32* f32* i64 i64 i32 void* f32* f32* i32 stream
+nerf_sample_fine  status : f32* f32* f32* i64 f32* f32* u8* f32 f32 stream
+nerf_composite  status : f32* f32* i64 i64 i32 i32 f32* f32* f32* stream
+nerf_generate_rays  status : f64[12] i32 i32 f64 i64 i64 i64* f32* f32* stream
+nerf_image_metrics  status : f32* f32* i64 f64* stream
+nerf_image_ssim  status : f32* f32* i32 i32 f64* stream
+nerf_render_workspace_bytes  i64 : i64 i32 i32
+nerf_render_forward  status : f32* f32* i64 void* void* f32* f32* i32 i32 i32 i32 f32 void* i64 f32* f32* stream
+nerf_stratified_samples  status : f32* f32* i64 f32* stream
+nerf_sample_fine_rays  status : f32* f32* i64 f32* i64 i64 f32* f32* u8* f32 f32 stream
+nerf_sample_fine_rays_backward  status : f32* f32* i64 f32* i64 i64 f32* f32* f32* stream
+nerf_render_stochastic_workspace_bytes  i64 : i64 i32
+nerf_render_forward_stochastic  status : f32* f32* i64 void* void* f32* f32* f32* f32* i32 i32 i32 i32 f32 void* i64 f32* f32* stream
+nerf_mlp_backward_rays_x  status : f32* f32* f32* i64 i64 i32 void* f32* f32* f32* f32* f32* f32*[24] i32 i32 stream
+nerf_rays_viewdirs_backward  status : f32* i64 i32 f32* f32* f32* stream
+nerf_rays_backward  status : i64 f32* i64 f32* f32* f32* f32* f32* f32* stream
+nerf_compact_valid_workspace_bytes  i64 : i64
+nerf_compact_valid  status : u8* i64 i32* i32* void* stream
+nerf_mlp_forward_rays_save_masked  status : f32* f32* f32* i64 i64 i32 i32* i32* void* f32* f32* i32 stream
+nerf_mlp_backward_masked_workspace_bytes  i64 : i64
+nerf_mlp_backward_masked  status : f32* f32* f32* i64 i64 i32 i32* i32* void* f32* f32* f32* f32* f32*[24] i32 void* stream
+nerf_isosurface_workspace_bytes  i64 : i32 i32 i32
+nerf_isosurface_count  status : f32* i64 i32 i32 i32 f32 void* i32* stream
+nerf_isosurface_emit  status : f32* i64 i32 i32 i32 f32 f64[3] f64[3] void* f32* i32* stream
+nerf_occupancy_words  i64 : i32 i32 i32
+nerf_occupancy_build  status : f32* i64 i32 i32 i32 f32 i32 i32* stream
+nerf_occupancy_mark  status : f32* f32* f32* i64 i64 i32 i32* i32[3] f32[3] f32[3] i32 u8* stream
+nerf_occupancy_age  status : f32* i64 i64 f32 i32 u8* f32* stream
+nerf_render_occupancy_workspace_bytes  i64 : i64 i32 i32
+nerf_render_forward_occupancy  status : f32* f32* i64 void* void* f32* f32* i32 i32 i32 i32 f32 i32* i32* i32[3] f32[3] f32[3] i64* void* i64 f32* f32* stream
+nerf_density_gradient_point_bytes  i64 :
+nerf_density_gradient  status : f32* f32* f32* i64 i64 i32 void* void* i32 f32* f32* i32 void* i64 stream
+nerf_composite_normals  status : f32* f32* i64 i64 i32 f32* f32* f32* stream
+nerf_mesh_components_workspace_bytes  i64 : i64 i64
+nerf_mesh_components  status : i32* i64 i64 void* i32* i32* i32* i32* i32* i32* stream
+nerf_mesh_filter_count  status : i32* i32* u8* i64 i64 void* i32* stream
+nerf_mesh_filter_emit  status : f32* i32* i64 i64 void* f32* i32* i32* stream
+nerf_hashgrid_forward  status : f32* f32* i64 i32 i32 i32 i32[] f32[] f32* stream
+nerf_hashgrid_backward  status : f32* f32* f32* i64 i32 i32 i32 i32[] f32[] f32* f32* stream
+"""
+SIGNATURES = {}       # name -> (return kind, (parameter kinds))
+for _line in _TABLE.strip().splitlines():
+    _head, _, _kinds = _line.partition(":")
+    SIGNATURES[_head.split()[0]] = (_head.split()[1], tuple(_kinds.split()))
+EXPORTS = tuple(SIGNATURES)
+
+_SCALAR = {"i32": ctypes.c_int32, "i64": ctypes.c_int64, "f32": ctypes.c_float, "f64": ctypes.c_double}
+_DTYPE = {"f32*": torch.float32, "i32*": torch.int32, "u8*": torch.uint8, "i64*": torch.int64, "f64*": torch.float64, "void*": None}
+_RETURN = {"status": ctypes.c_int32, "i32": ctypes.c_int32, "i64": ctypes.c_int64, "str": ctypes.c_char_p}
+
+
+def _ctype(kind):
+    """Device pointers and the stream travel as integers (c_void_p); a host array as a pointer to its element type."""
+    if kind in _SCALAR:
+        return _SCALAR[kind]
+    if kind[-1] != "]":
+        return ctypes.c_void_p
+    return ctypes.POINTER(_SCALAR.get(kind[:kind.index("[")], ctypes.c_void_p))
+
+
+# the ctypes view of the table, {name: (restype, [argtypes])}: what load() installs (tools/ab_*.py install it on their own builds)
+_PROTOS = {name: (_RETURN[ret], [_ctype(k) for k in kinds]) for name, (ret, kinds) in SIGNATURES.items()}
 
 _lib = None
 
@@ -166,6 +163,71 @@ def load():
     return _lib
 
 
+class strided:
+    """Marks a tensor argument of call() whose layout the caller has validated itself and describes to the entry with an explicit
+    element stride (the `field` of nerf_isosurface_* and nerf_occupancy_build): dtype and device are checked, contiguity is not."""
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+
+def call(name, *args):
+    """Call entry `name` of the library with `args` as its header lists them, minus the stream: tensors (None: NULL) for device
+    pointers, numbers for scalars, sequences or ctypes arrays for host arrays.  Every argument is checked against the entry's kinds
+    in SIGNATURES before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
+    is checked (NerfLibraryError with nerf_last_error's text); any other return value comes back as it is."""
+    ret, kinds = SIGNATURES[name]
+    has_stream = kinds[-1:] == ("stream",)
+    if len(args) != len(kinds) - has_stream:
+        raise TypeError(f"{name} takes {len(kinds) - has_stream} arguments ({len(args)} given)")
+    dev = None
+
+    def device_pointer(t, dtype, i):
+        nonlocal dev
+        if t is None:
+            return None
+        dense = not isinstance(t, strided)
+        if not dense:
+            t = t.tensor
+        if not t.is_cuda:
+            raise NerfLibraryError(f"{name}, argument {i}: the HIP render path needs tensors on a GPU (cuda) device; got a CPU tensor")
+        if (dtype is not None and t.dtype != dtype) or (dense and not t.is_contiguous()):
+            raise NerfLibraryError(f"{name}, argument {i}: expected a contiguous {dtype or 'byte'} tensor, got {t.dtype} with "
+                                   f"strides {tuple(t.stride())}")
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
+            raise NerfLibraryError(f"{name}, argument {i}: a tensor on {t.device}, the earlier ones on {dev}")
+        return t.data_ptr()
+
+    cargs = []
+    for i, (kind, a) in enumerate(zip(kinds, args)):
+        if kind in _DTYPE:
+            a = device_pointer(a, _DTYPE[kind], i)
+        elif kind not in _SCALAR and a is not None:                 # a host array
+            elem, _, length = kind[:-1].partition("[")
+            if length and len(a) != int(length):
+                raise NerfLibraryError(f"{name}, argument {i}: a host array of {length} is needed, got {len(a)}")
+            if elem in _DTYPE:
+                a = (ctypes.c_void_p * len(a))(*[device_pointer(t, _DTYPE[elem], i) for t in a])
+            elif not isinstance(a, ctypes.Array):
+                a = (_SCALAR[elem] * len(a))(*a)
+        cargs.append(a)
+    fn = getattr(load(), name)
+    if not has_stream:
+        return fn(*cargs)
+    if dev is None or dev.index == torch.cuda.current_device():
+        rc = fn(*cargs, None if dev is None else torch.cuda.current_stream(dev).cuda_stream)
+    else:
+        with torch.cuda.device(dev):
+            rc = fn(*cargs, torch.cuda.current_stream(dev).cuda_stream)
+    if ret == "status":
+        check(rc, name)
+    return rc
+
+
+# The helpers below are the direct path to the C ABI: load() plus check / ptr / ptr_array / stream_of at the call site.  The package
+# itself goes through call(); bench.py, tests/ and tools/ call entries directly through these, so they stay.
 def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().nerf_last_error().decode("utf-8", "replace")

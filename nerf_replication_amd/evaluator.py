@@ -17,29 +17,23 @@ from . import _lib
 
 def image_sums(pred, gt):
     """-> (sum of squared float differences of the clipped images, sum of the uint8-wrapped integrand, n)."""
-    lib = _lib.load()
     pred = pred.detach().reshape(-1).to(torch.float32).contiguous()
     gt = gt.detach().reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
     if pred.numel() != gt.numel():
         raise ValueError("pred and gt must have the same number of values")
     sums = torch.empty(2, dtype=torch.float64, device=pred.device)
-    with torch.cuda.device(pred.device):
-        _lib.check(lib.nerf_image_metrics(_lib.ptr(pred), _lib.ptr(gt), pred.numel(), sums.data_ptr(),
-                                          _lib.stream_of(pred.device)), "nerf_image_metrics")
+    _lib.call("nerf_image_metrics", pred, gt, pred.numel(), sums)
     s = sums.cpu().tolist()
     return s[0], s[1], pred.numel()
 
 
 def image_ssim(pred_hw3, gt_hw3):
     """SSIM as ssim_metric computes it (evaluators/nerf.py:49-77), on [H,W,3] float images in [0,1]."""
-    lib = _lib.load()
     H, W = int(pred_hw3.shape[0]), int(pred_hw3.shape[1])
     pred = pred_hw3.detach().to(torch.float32).contiguous()
     gt = gt_hw3.detach().to(device=pred.device, dtype=torch.float32).contiguous()
     out = torch.empty(1, dtype=torch.float64, device=pred.device)
-    with torch.cuda.device(pred.device):
-        _lib.check(lib.nerf_image_ssim(_lib.ptr(pred), _lib.ptr(gt), H, W, out.data_ptr(), _lib.stream_of(pred.device)),
-                   "nerf_image_ssim")
+    _lib.call("nerf_image_ssim", pred, gt, H, W, out)
     return out.item() / ((H - 6) * (W - 6) * 3)
 
 

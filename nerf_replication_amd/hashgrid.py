@@ -57,17 +57,16 @@ def _f32(t, what):
 class _HashEncode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inputs, embeddings, offsets, scales):
-        # inputs [B, D] in [0, 1], embeddings [offsets[-1], C], offsets int32 [L+1] and scales float32 [L] (host arrays) -> [B, L*C]
+        # inputs [B, D] in [0, 1], embeddings [offsets[-1], C], offsets int32 [L+1] and scales float32 [L] (ctypes host arrays)
+        # -> [B, L*C]
         x = inputs.detach().contiguous()
         emb = embeddings.detach().contiguous()
         B, D = x.shape
-        C, L = emb.shape[1], offsets.shape[0] - 1
-        if emb.shape[0] < int(offsets[-1]):
-            raise _lib.NerfLibraryError(f"hash_encode: embeddings has {emb.shape[0]} rows, the level table needs {int(offsets[-1])}")
+        C, L = emb.shape[1], len(scales)
+        if emb.shape[0] < offsets[L]:
+            raise _lib.NerfLibraryError(f"hash_encode: embeddings has {emb.shape[0]} rows, the level table needs {offsets[L]}")
         out = torch.empty(B, L * C, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().nerf_hashgrid_forward(
-            _lib.ptr(x), _lib.ptr(emb), B, D, C, L, offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-            scales.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _lib.ptr(out), _lib.stream_of(x.device)), "nerf_hashgrid_forward")
+        _lib.call("nerf_hashgrid_forward", x, emb, B, D, C, L, offsets, scales, out)
         ctx.save_for_backward(x, emb)
         ctx.level_table = (offsets, scales)
         return out
@@ -78,14 +77,11 @@ class _HashEncode(torch.autograd.Function):
         x, emb = ctx.saved_tensors
         offsets, scales = ctx.level_table
         B, D = x.shape
-        C, L = emb.shape[1], offsets.shape[0] - 1
+        C, L = emb.shape[1], len(scales)
         grad = _f32(grad, "the output gradient").contiguous()
         grad_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         grad_emb = torch.zeros_like(emb) if ctx.needs_input_grad[1] else None
-        _lib.check(_lib.load().nerf_hashgrid_backward(
-            _lib.ptr(x), _lib.ptr(emb), _lib.ptr(grad), B, D, C, L, offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-            scales.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _lib.ptr(grad_emb), _lib.ptr(grad_x), _lib.stream_of(x.device)),
-            "nerf_hashgrid_backward")
+        _lib.call("nerf_hashgrid_backward", x, emb, grad, B, D, C, L, offsets, scales, grad_emb, grad_x)
         return grad_x, grad_emb, None, None
 
 
@@ -102,7 +98,9 @@ def hash_encode(inputs, embeddings, offsets, per_level_scale, base_resolution):
     L = offsets.shape[0] - 1
     if inputs.shape[0] == 0:            # nothing to encode (the C entry refuses an empty batch)
         return inputs.new_zeros(0, L * embeddings.shape[1])
-    return _HashEncode.apply(inputs, embeddings, offsets, level_scales(L, per_level_scale, base_resolution))
+    # the level tables as the host arrays the two entries take, made once for the forward and the backward
+    scales = level_scales(L, per_level_scale, base_resolution)
+    return _HashEncode.apply(inputs, embeddings, (ctypes.c_int32 * (L + 1))(*offsets.tolist()), (ctypes.c_float * L)(*scales.tolist()))
 
 
 def normalize_to_bounds(xyz, wbounds):

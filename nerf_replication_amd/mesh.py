@@ -12,7 +12,6 @@ comes out of a HIP kernel, torch only moves tensors (and normalises the [V,3] gr
 [V,3] colours, and picks rows of the per-component table).
 """
 import collections
-import ctypes
 import numbers
 
 import numpy as np
@@ -84,7 +83,6 @@ def density_grid(net, bbox, N, model="fine", chunk_lines=None):
         chunk_lines = max(1, CHUNK_POINTS // nz)
     if not isinstance(chunk_lines, numbers.Integral) or chunk_lines < 1:
         raise ValueError(f"chunk_lines must be a positive int, got {chunk_lines!r}")
-    lib = _lib.load()
     packed = net.packed(model)                     # raises for a network on the CPU
     dev = packed.device
     prec = _lib.PRECISIONS[net.precision]
@@ -98,14 +96,10 @@ def density_grid(net, bbox, N, model="fine", chunk_lines=None):
     rays_o, rays_d, t = rays_o.to(dev), rays_d.to(dev), z.to(dev)
     grid = torch.empty((lines, nz), dtype=torch.float32, device=dev)
     raw = torch.empty((min(lines, int(chunk_lines)), nz, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.stream_of(dev)
-        for l0 in range(0, lines, int(chunk_lines)):
-            l1 = min(lines, l0 + int(chunk_lines))
-            _lib.check(lib.nerf_mlp_forward_rays_density(_lib.ptr(rays_o[l0:l1]), _lib.ptr(rays_d[l0:l1]), _lib.ptr(t), 0, l1 - l0,
-                                                         nz, packed.data_ptr(), _lib.ptr(raw), prec, st),
-                       "nerf_mlp_forward_rays_density")
-            grid[l0:l1].copy_(raw[:l1 - l0, :, 3])
+    for l0 in range(0, lines, int(chunk_lines)):
+        l1 = min(lines, l0 + int(chunk_lines))
+        _lib.call("nerf_mlp_forward_rays_density", rays_o[l0:l1], rays_d[l0:l1], t, 0, l1 - l0, nz, packed, raw, prec)
+        grid[l0:l1].copy_(raw[:l1 - l0, :, 3])
     return grid.view(nx, ny, nz)
 
 
@@ -151,7 +145,6 @@ def isosurface(field, level, origin, step):
     field, stride, (nx, ny, nz) = _field_layout(field)
     level = float(level)
     origin, step = _vec3(origin, "origin"), _vec3(step, "step")
-    lib = _lib.load()
     if not field.is_cuda:
         raise _lib.NerfLibraryError("isosurface needs the field on a GPU (cuda) device; there is no CPU fallback")
     dev = field.device
@@ -159,25 +152,21 @@ def isosurface(field, level, origin, step):
     faces = torch.empty((0, 3), dtype=torch.int32, device=dev)
     if min(nx, ny, nz) < 2:
         return vertices, faces
-    nbytes = int(lib.nerf_isosurface_workspace_bytes(nx, ny, nz))
+    nbytes = int(_lib.call("nerf_isosurface_workspace_bytes", nx, ny, nz))
     if nbytes < 0:
         raise _lib.NerfLibraryError(f"nerf_isosurface_workspace_bytes refused a grid of {nx} x {ny} x {nz} points")
-    with torch.cuda.device(dev):
-        st = _lib.stream_of(dev)
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        counts = torch.empty(2, dtype=torch.int32, device=dev)
-        _lib.check(lib.nerf_isosurface_count(field.data_ptr(), stride, nx, ny, nz, level, workspace.data_ptr(), counts.data_ptr(),
-                                             st), "nerf_isosurface_count")
-        n_v, n_t = (int(c) for c in counts.cpu())
-        if n_v < 0 or n_t < 0:
-            raise _lib.NerfLibraryError("isosurface: more than 2^31 - 1 vertices or triangles")
-        if n_t == 0:
-            return vertices, faces
-        vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
-        faces = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
-        c3 = ctypes.c_double * 3
-        _lib.check(lib.nerf_isosurface_emit(field.data_ptr(), stride, nx, ny, nz, level, c3(*origin), c3(*step), workspace.data_ptr(),
-                                            vertices.data_ptr(), faces.data_ptr(), st), "nerf_isosurface_emit")
+    field = _lib.strided(field)                    # _field_layout has checked the layout that `stride` describes
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.call("nerf_isosurface_count", field, stride, nx, ny, nz, level, workspace, counts)
+    n_v, n_t = (int(c) for c in counts.cpu())
+    if n_v < 0 or n_t < 0:
+        raise _lib.NerfLibraryError("isosurface: more than 2^31 - 1 vertices or triangles")
+    if n_t == 0:
+        return vertices, faces
+    vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+    _lib.call("nerf_isosurface_emit", field, stride, nx, ny, nz, level, origin, step, workspace, vertices, faces)
     return vertices, faces
 
 
@@ -197,7 +186,6 @@ def density_gradient(net, points, model="fine", positive_only=False, block_point
         raise ValueError(f"block_points must be a positive int, got {block_points!r}")
     if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("points must be a tensor [P,3]")
-    lib = _lib.load()
     packed = net.packed(model)                     # raises for a network on the CPU
     packed_bwd = net.packed_bwd(model)             # raises for an fp16 precision
     dev = packed.device
@@ -211,12 +199,9 @@ def density_gradient(net, points, model="fine", positive_only=False, block_point
     rays_d[:, 2] = 1.0
     t = torch.zeros(1, dtype=torch.float32, device=dev)
     rows = (min(int(block_points), P) + 31) // 32 * 32
-    with torch.cuda.device(dev):
-        ws = torch.empty(int(lib.nerf_density_gradient_point_bytes()) * rows, dtype=torch.uint8, device=dev)
-        _lib.check(lib.nerf_density_gradient(_lib.ptr(pts), _lib.ptr(rays_d), _lib.ptr(t), 0, P, 1, packed.data_ptr(),
-                                             packed_bwd.data_ptr(), int(bool(positive_only)), _lib.ptr(sigma), _lib.ptr(grad),
-                                             _lib.PRECISIONS[net.precision], ws.data_ptr(), ws.numel(), _lib.stream_of(dev)),
-                   "nerf_density_gradient")
+    ws = torch.empty(int(_lib.call("nerf_density_gradient_point_bytes")) * rows, dtype=torch.uint8, device=dev)
+    _lib.call("nerf_density_gradient", pts, rays_d, t, 0, P, 1, packed, packed_bwd, int(bool(positive_only)), sigma, grad,
+              _lib.PRECISIONS[net.precision], ws, ws.numel())
     return sigma, grad
 
 
@@ -256,25 +241,21 @@ class _Components:
     """The labels and the table of one mesh, with the workspace they share with the filter."""
 
     def __init__(self, faces, n_vertices):
-        lib = _lib.load()
         if not faces.is_cuda:
             raise _lib.NerfLibraryError("mesh_components needs the faces on a GPU (cuda) device; there is no CPU fallback")
         dev = faces.device
         self.faces = faces.detach().to(torch.int32).contiguous()
         self.V, self.T = V, T = int(n_vertices), int(faces.shape[0])
-        nbytes = int(lib.nerf_mesh_components_workspace_bytes(V, T))
+        nbytes = int(_lib.call("nerf_mesh_components_workspace_bytes", V, T))
         if nbytes < 0:
             raise _lib.NerfLibraryError(f"nerf_mesh_components_workspace_bytes refused {V} vertices and {T} faces")
-        with torch.cuda.device(dev):
-            self.workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            self.vertex_label = torch.empty(V, dtype=torch.int32, device=dev)
-            self.face_label = torch.empty(T, dtype=torch.int32, device=dev)
-            rows = torch.empty((3, V), dtype=torch.int32, device=dev)
-            n_comp = torch.empty(1, dtype=torch.int32, device=dev)
-            _lib.check(lib.nerf_mesh_components(self.faces.data_ptr(), T, V, self.workspace.data_ptr(), self.vertex_label.data_ptr(),
-                                                self.face_label.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(),
-                                                n_comp.data_ptr(), _lib.stream_of(dev)), "nerf_mesh_components")
-            C = int(n_comp.item())
+        self.workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        self.vertex_label = torch.empty(V, dtype=torch.int32, device=dev)
+        self.face_label = torch.empty(T, dtype=torch.int32, device=dev)
+        rows = torch.empty((3, V), dtype=torch.int32, device=dev)
+        n_comp = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.call("nerf_mesh_components", self.faces, T, V, self.workspace, self.vertex_label, self.face_label, *rows, n_comp)
+        C = int(n_comp.item())
         self.table = ComponentTable(rows[0, :C], rows[1, :C], rows[2, :C])
 
     def select(self, min_triangles, keep_largest):
@@ -293,21 +274,16 @@ class _Components:
         return keep
 
     def filter(self, vertices, keep):
-        lib = _lib.load()
         dev = self.faces.device
         V, T = self.V, self.T
-        with torch.cuda.device(dev):
-            st = _lib.stream_of(dev)
-            counts = torch.empty(2, dtype=torch.int32, device=dev)
-            _lib.check(lib.nerf_mesh_filter_count(self.vertex_label.data_ptr(), self.face_label.data_ptr(), _lib.ptr(keep, torch.uint8), V, T,
-                                                  self.workspace.data_ptr(), counts.data_ptr(), st), "nerf_mesh_filter_count")
-            n_v, n_t = (int(c) for c in counts.cpu())
-            out_v = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
-            out_f = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
-            index = torch.empty(n_v, dtype=torch.int32, device=dev)
-            if n_v > 0:
-                _lib.check(lib.nerf_mesh_filter_emit(_lib.ptr(vertices), self.faces.data_ptr(), V, T, self.workspace.data_ptr(),
-                                                     out_v.data_ptr(), out_f.data_ptr(), index.data_ptr(), st), "nerf_mesh_filter_emit")
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        _lib.call("nerf_mesh_filter_count", self.vertex_label, self.face_label, keep, V, T, self.workspace, counts)
+        n_v, n_t = (int(c) for c in counts.cpu())
+        out_v = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+        out_f = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+        index = torch.empty(n_v, dtype=torch.int32, device=dev)
+        if n_v > 0:
+            _lib.call("nerf_mesh_filter_emit", vertices, self.faces, V, T, self.workspace, out_v, out_f, index)
         return out_v, out_f, index
 
 

@@ -97,34 +97,9 @@ class Network(nn.Module):
         self._packed = {}       # tag -> (key, tensor)
 
     # ---- packed weight stream (csrc/nerf_layout.h) -------------------------------------------
-    def packed(self, model=""):
-        """Device byte tensor with the kernel's weight stream (for self.precision: "f32" exact fp32 MFMA,
-        "f16" fp16 activations / fp32 accumulate) of the coarse ("") or fine model; repacked
-        on the device whenever a parameter's storage or version changed (load_state_dict, .to(),
-        optimizer.step())."""
-        tag = "fine" if model == "fine" else ""
-        sub = self.model_fine if tag == "fine" else self.model
-        params = sub.ordered_params()
-        dev = params[0].device
-        if dev.type != "cuda":
-            raise _lib.NerfLibraryError("Network parameters are on the CPU: call .cuda() first; the render path is "
-                                        "HIP-only (no CPU fallback)")
-        prec = _lib.PRECISIONS[self.precision]
-        key = (prec,) + tuple((p.data_ptr(), p._version) for p in params)
-        hit = self._packed.get(tag)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        lib = _lib.load()
-        out = torch.empty(_lib.packed_model_bytes(prec), dtype=torch.uint8, device=dev)
-        arr = _lib.ptr_array([p.detach().contiguous() for p in params], torch.float32)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_pack_model(arr, out.data_ptr(), prec, _lib.stream_of(dev)), "nerf_pack_model")
-        self._packed[tag] = (key, out)
-        return out
-
-    def packed_bwd(self, model=""):
-        """The transposed weight stream of the data-gradient chain (nerf_pack_model_bwd) for self.precision ("f32" / "f32x"), cached
-        and refreshed like packed(): what a frozen network's point gradients read (render_geometry, mesh.vertex_normals)."""
+    def _stream(self, model, bwd):
+        """The cached weight stream of the coarse ("") or fine model, forward or transposed: repacked on the device whenever the
+        precision or a parameter's storage or version changed (load_state_dict, .to(), optimizer.step())."""
         tag = "fine" if model == "fine" else ""
         params = (self.model_fine if tag == "fine" else self.model).ordered_params()
         dev = params[0].device
@@ -132,20 +107,31 @@ class Network(nn.Module):
             raise _lib.NerfLibraryError("Network parameters are on the CPU: call .cuda() first; the render path is "
                                         "HIP-only (no CPU fallback)")
         prec = _lib.PRECISIONS[self.precision]
-        lib = _lib.load()
-        nbytes = int(lib.nerf_packed_bwd_bytes(prec))
-        if nbytes <= 0:
-            raise NotImplementedError(f"the data-gradient chain runs in precision 'f32' or 'f32x', not {self.precision!r}")
+        if bwd:
+            nbytes = int(_lib.call("nerf_packed_bwd_bytes", prec))
+            if nbytes <= 0:
+                raise NotImplementedError(f"the data-gradient chain runs in precision 'f32' or 'f32x', not {self.precision!r}")
+            tag = "bwd" + tag
         key = (prec,) + tuple((p.data_ptr(), p._version) for p in params)
-        hit = self._packed.get("bwd" + tag)
+        hit = self._packed.get(tag)
         if hit is not None and hit[0] == key:
             return hit[1]
-        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        arr = _lib.ptr_array([p.detach().contiguous() for p in params], torch.float32)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_pack_model_bwd(arr, out.data_ptr(), prec, _lib.stream_of(dev)), "nerf_pack_model_bwd")
-        self._packed["bwd" + tag] = (key, out)
+        out = torch.empty(nbytes if bwd else _lib.packed_model_bytes(prec), dtype=torch.uint8, device=dev)
+        _lib.call("nerf_pack_model_bwd" if bwd else "nerf_pack_model", [p.detach().contiguous() for p in params], out, prec)
+        self._packed[tag] = (key, out)
         return out
+
+    def packed(self, model=""):
+        """Device byte tensor with the kernel's weight stream (for self.precision: "f32" exact fp32 MFMA,
+        "f16" fp16 activations / fp32 accumulate) of the coarse ("") or fine model; repacked
+        on the device whenever a parameter's storage or version changed (load_state_dict, .to(),
+        optimizer.step())."""
+        return self._stream(model, False)
+
+    def packed_bwd(self, model=""):
+        """The transposed weight stream of the data-gradient chain (nerf_pack_model_bwd) for self.precision ("f32" / "f32x"), cached
+        and refreshed like packed(): what a frozen network's point gradients read (render_geometry, mesh.vertex_normals)."""
+        return self._stream(model, True)
 
     def forward(self, inputs, viewdirs, valid_mask, model=""):
         """inputs [n,s,3], viewdirs [n,3], valid_mask BoolTensor[n,s] | None, model "" | "fine"
@@ -159,7 +145,6 @@ class Network(nn.Module):
         if torch.is_grad_enabled() and (inputs.requires_grad or viewdirs.requires_grad or
                                         (self.training and any(p.requires_grad for p in sub.parameters()))):
             return self._forward_with_grad(inputs, viewdirs, valid_mask, model, sub)
-        lib = _lib.load()
         dev = inputs.device
         n, s = inputs.shape[0], inputs.shape[1]
         packed = self.packed(model)
@@ -168,9 +153,7 @@ class Network(nn.Module):
             pts = inputs.detach().to(torch.float32).contiguous()
             dirs = viewdirs.detach().to(torch.float32).contiguous()
             raw = torch.empty((n, s, 4), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.nerf_mlp_forward(_lib.ptr(pts), _lib.ptr(dirs), n, s, packed.data_ptr(),
-                                                _lib.ptr(raw), prec, _lib.stream_of(dev)), "nerf_mlp_forward")
+            _lib.call("nerf_mlp_forward", pts, dirs, n, s, packed, raw, prec)
             return raw
         # ESS/ERT path (network.py:207-214, :238-253): run only the valid points, zeros elsewhere
         flat = valid_mask.reshape(-1)
@@ -178,9 +161,7 @@ class Network(nn.Module):
         dirs = viewdirs.detach()[:, None].expand(n, s, 3).reshape(-1, 3)[flat].to(torch.float32).contiguous()
         m = pts.shape[0]
         raw_valid = torch.empty((m, 1, 4), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_mlp_forward(_lib.ptr(pts), _lib.ptr(dirs), m, 1, packed.data_ptr(),
-                                            _lib.ptr(raw_valid), prec, _lib.stream_of(dev)), "nerf_mlp_forward")
+        _lib.call("nerf_mlp_forward", pts, dirs, m, 1, packed, raw_valid, prec)
         out = torch.zeros((n * s, 4), dtype=torch.float32, device=dev)
         out[flat] = raw_valid.reshape(m, 4)
         return out.reshape(n, s, 4)
@@ -209,20 +190,15 @@ class _MlpFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, model, inputs, viewdirs, *params):
-        lib = _lib.load()
         dev = inputs.device
         n, s = inputs.shape[0], inputs.shape[1]
         prec = _lib.PRECISIONS[net.precision]
         pts = inputs.detach().contiguous()
         dirs = viewdirs.detach().contiguous()
         raw = torch.empty((n, s, 4), dtype=torch.float32, device=dev)
-        save = torch.empty(max(1, int(lib.nerf_train_save_floats(n * s))), dtype=torch.float32, device=dev)
+        save = torch.empty(max(1, int(_lib.call("nerf_train_save_floats", n * s))), dtype=torch.float32, device=dev)
         if n * s > 0:
-            packed = net.packed(model)
-            with torch.cuda.device(dev):
-                _lib.check(lib.nerf_mlp_forward_points_save(_lib.ptr(pts), _lib.ptr(dirs), n, s, packed.data_ptr(),
-                                                            _lib.ptr(raw), _lib.ptr(save), prec, _lib.stream_of(dev)),
-                           "nerf_mlp_forward_points_save")
+            _lib.call("nerf_mlp_forward_points_save", pts, dirs, n, s, net.packed(model), raw, save, prec)
         ctx.prec, ctx.shape = prec, (n, s)
         # the parameters go through save_for_backward: an in-place update between forward and backward (optimizer.step(),
         # load_state_dict) then raises autograd's version-counter error instead of pairing new weights with old activations
@@ -231,41 +207,29 @@ class _MlpFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_raw):
-        lib = _lib.load()
         pts, save, dirs, *params = ctx.saved_tensors
         (n, s), prec = ctx.shape, ctx.prec
         dev = pts.device
-        st = _lib.stream_of(dev)
         grads = _lib.zeroed_grads(params, dev)
         g_pts = torch.zeros((n, s, 3), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
         if n * s > 0:
             g_raw = g_raw.contiguous().to(torch.float32)
-            arr = _lib.ptr_array([p.detach().contiguous() for p in params])
-            garr = _lib.ptr_array(grads)
-            with torch.cuda.device(dev):
-                pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device=dev)
-                _lib.check(lib.nerf_pack_model_bwd(arr, pk_b.data_ptr(), prec, st), "nerf_pack_model_bwd")
-                gsave = torch.empty(int(lib.nerf_train_grad_floats(n * s)), dtype=torch.float32, device=dev)
-                _lib.check(lib.nerf_mlp_backward_points(_lib.ptr(pts), n, s, pk_b.data_ptr(), _lib.ptr(g_raw), _lib.ptr(save),
-                                                        _lib.ptr(gsave), None if g_pts is None else _lib.ptr(g_pts), garr,
-                                                        prec, st), "nerf_mlp_backward_points")
+            pk_b = torch.empty(int(_lib.call("nerf_packed_bwd_bytes", prec)), dtype=torch.uint8, device=dev)
+            _lib.call("nerf_pack_model_bwd", [p.detach().contiguous() for p in params], pk_b, prec)
+            gsave = torch.empty(int(_lib.call("nerf_train_grad_floats", n * s)), dtype=torch.float32, device=dev)
+            _lib.call("nerf_mlp_backward_points", pts, n, s, pk_b, g_raw, save, gsave, g_pts, grads, prec)
         g_dirs = None
         if ctx.needs_input_grad[3]:
             g_dirs = torch.zeros((n, 3), dtype=torch.float32, device=dev)
             if n * s > 0:
                 w_views = params[16].detach().contiguous()          # views_linears.0.weight [128, 283]
-                with torch.cuda.device(dev):
-                    _lib.check(lib.nerf_viewdirs_backward(_lib.ptr(gsave), n, s, _lib.ptr(w_views), _lib.ptr(dirs),
-                                                          _lib.ptr(g_dirs), st), "nerf_viewdirs_backward")
+                _lib.call("nerf_viewdirs_backward", gsave, n, s, w_views, dirs, g_dirs)
         return (None, None, g_pts, g_dirs) + tuple(g.to(p.dtype) if p.requires_grad else None for g, p in zip(grads, params))
 
 
 def positional_encoding(x, n_freqs):
     """Encoder.embed (src/models/encoding/freq.py:31-32) on the device: [..., 3] -> [..., 3+6*n_freqs]."""
-    lib = _lib.load()
     flat = x.detach().reshape(-1, 3).to(torch.float32).contiguous()
     out = torch.empty((flat.shape[0], 3 + 6 * n_freqs), dtype=torch.float32, device=flat.device)
-    with torch.cuda.device(flat.device):
-        _lib.check(lib.nerf_positional_encoding(_lib.ptr(flat), flat.shape[0], n_freqs, _lib.ptr(out),
-                                                _lib.stream_of(flat.device)), "nerf_positional_encoding")
+    _lib.call("nerf_positional_encoding", flat, flat.shape[0], n_freqs, out)
     return out.reshape(*x.shape[:-1], 3 + 6 * n_freqs)

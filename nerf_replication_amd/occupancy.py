@@ -170,7 +170,6 @@ class OccupancyGrid:
             raise ValueError(f'models must be a non-empty sequence out of ("", "fine") without repeats, got {models!r}')
         for m in models:
             self._bits(m)
-        lib = _lib.load()
         nx, ny, nz = self.dims
         with torch.no_grad():
             for m in models:
@@ -178,18 +177,14 @@ class OccupancyGrid:
                 field = density_grid(net, self.bbox.reshape(-1), self.dims, model=m, chunk_lines=self.chunk_lines)
                 if field.device != self.device:
                     raise ValueError(f"the occupancy grid is on {self.device}, the network on {field.device}")
-                if int(lib.nerf_occupancy_words(nx, ny, nz)) != bits.numel():
+                if int(_lib.call("nerf_occupancy_words", nx, ny, nz)) != bits.numel():
                     raise _lib.NerfLibraryError(f"the bitfield of model {m!r} does not have the words of a {self.dims} grid")
                 age = self._age.get(m)
                 if age is None:
                     age = self._age[m] = torch.full((field.numel(),), 255, dtype=torch.uint8, device=self.device)
-                with torch.cuda.device(self.device):
-                    st = _lib.stream_of(self.device)
-                    # `on` overwrites the field: it is not needed again
-                    _lib.check(lib.nerf_occupancy_age(_lib.ptr(field), 1, field.numel(), self.level, hold, _lib.ptr(age, torch.uint8),
-                                                      _lib.ptr(field), st), "nerf_occupancy_age")
-                    _lib.check(lib.nerf_occupancy_build(_lib.ptr(field), 1, nx, ny, nz, 0.0, self.dilate, bits.data_ptr(), st),
-                               "nerf_occupancy_build")
+                # `on` overwrites the field: it is not needed again
+                _lib.call("nerf_occupancy_age", field, 1, field.numel(), self.level, hold, age, field)
+                _lib.call("nerf_occupancy_build", field, 1, nx, ny, nz, 0.0, self.dilate, bits)
                 if self.keys is None:
                     self.keys = {}
                 self.keys[m] = key
@@ -204,14 +199,11 @@ class OccupancyGrid:
 def _build(field, level, dilate):
     """nerf_occupancy_build of one field -> int32 [words]."""
     field, stride, (nx, ny, nz) = _field_layout(field)
-    lib = _lib.load()
     if not field.is_cuda:
         raise _lib.NerfLibraryError("an occupancy grid needs its field on a GPU (cuda) device; there is no CPU fallback")
-    n_words = int(lib.nerf_occupancy_words(nx, ny, nz))
+    n_words = int(_lib.call("nerf_occupancy_words", nx, ny, nz))
     if n_words < 0:
         raise _lib.NerfLibraryError(f"nerf_occupancy_words refused a grid of {nx} x {ny} x {nz} points")
     bits = torch.empty(n_words, dtype=torch.int32, device=field.device)
-    with torch.cuda.device(field.device):
-        _lib.check(lib.nerf_occupancy_build(field.data_ptr(), stride, nx, ny, nz, level, dilate, bits.data_ptr(),
-                                            _lib.stream_of(field.device)), "nerf_occupancy_build")
+    _lib.call("nerf_occupancy_build", _lib.strided(field), stride, nx, ny, nz, level, dilate, bits)     # layout: _field_layout
     return bits

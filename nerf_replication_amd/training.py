@@ -26,8 +26,6 @@ bitfield keeps, deterministic or stochastic, through the same masked entries; wi
 the lookup.  Compositing's adjoint is exactly zero wherever sigma <= 0, so the step has the plain step's gradients wherever the
 grid is right.
 """
-import ctypes
-
 import torch
 
 from . import _lib
@@ -40,10 +38,8 @@ class _Step:
     S_c, S_f = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
 
     def __init__(self, renderer, rays_o, rays_d, prec=None, stochastic=None):
-        self.lib = _lib.load()
         self.renderer, self.rays_o, self.rays_d = renderer, rays_o, rays_d
         self.dev, self.n = rays_o.device, rays_o.shape[0]
-        self.st = _lib.stream_of(self.dev)
         self.prec = _lib.PRECISIONS[getattr(renderer.net, "precision", "f32")] if prec is None else prec
         self.white = int(bool(renderer.white_bkgd))
         # the coarse depths and u with their per-ray strides (0: the shared tables)
@@ -57,15 +53,14 @@ class _Step:
         return torch.empty(shape, dtype=dtype, device=self.dev)
 
     def _rays(self, tvals, stride, S):
-        return _lib.ptr(self.rays_o), _lib.ptr(self.rays_d), _lib.ptr(tvals), stride, self.n, S
+        return self.rays_o, self.rays_d, tvals, stride, self.n, S
 
     # ---- forward stages
     def use_draws(self, jitter, u_rays):
         """The reference's training-mode draws: jittered coarse depths [n,64] and / or a per-ray u [n,128]."""
         if jitter is not None:
             t_lin, self.t_c, self.t_cs = self.t_c, self.empty(self.n, self.S_c), self.S_c
-            _lib.check(self.lib.nerf_stratified_samples(_lib.ptr(t_lin), _lib.ptr(jitter), self.n, _lib.ptr(self.t_c), self.st),
-                       "nerf_stratified_samples")
+            _lib.call("nerf_stratified_samples", t_lin, jitter, self.n, self.t_c)
         if u_rays is not None:
             self.u, self.u_s = u_rays, _lib.N_IMPORTANCE
         return self.t_c, self.t_cs, self.u, self.u_s
@@ -76,16 +71,14 @@ class _Step:
         tiles without density skip the colour branch and its stores (exact, see the header).  masked = (index, count): the compact
         rows of those samples alone; the others keep what `raw` holds."""
         raw = self.empty(self.n, S, 4) if raw is None else raw
-        save = self.empty(int(self.lib.nerf_train_save_floats(self.n * S)))
-        tail = (packed.data_ptr(), _lib.ptr(raw), _lib.ptr(save), self.prec, self.st)
+        save = self.empty(int(_lib.call("nerf_train_save_floats", self.n * S)))
+        tail = (packed, raw, save, self.prec)
         if masked is not None:
-            rc = self.lib.nerf_mlp_forward_rays_save_masked(*self._rays(tvals, stride, S), _lib.ptr(masked[0], torch.int32),
-                                                            _lib.ptr(masked[1], torch.int32), *tail)
+            _lib.call("nerf_mlp_forward_rays_save_masked", *self._rays(tvals, stride, S), *masked, *tail)
         elif density_only:
-            rc = self.lib.nerf_mlp_forward_rays_save_density(*self._rays(tvals, stride, S), *tail)
+            _lib.call("nerf_mlp_forward_rays_save_density", *self._rays(tvals, stride, S), *tail)
         else:
-            rc = self.lib.nerf_mlp_forward_rays_save_for_compositing(*self._rays(tvals, stride, S), *tail)
-        _lib.check(rc, "SAVE forward over %d samples" % S)
+            _lib.call("nerf_mlp_forward_rays_save_for_compositing", *self._rays(tvals, stride, S), *tail)
         return raw, save
 
     def sample_fine(self, raw_c, fast_sampling=False):
@@ -93,32 +86,26 @@ class _Step:
         t_sorted = self.empty(self.n, self.S_f)
         valid = self.empty(self.n, self.S_f, dtype=torch.uint8) if fast_sampling else None
         thresholds = (float(self.renderer.weights_threshold), 0.45) if fast_sampling else (0.0, 0.0)
-        _lib.check(self.lib.nerf_sample_fine_rays(_lib.ptr(raw_c), _lib.ptr(self.t_c), self.t_cs, _lib.ptr(self.u), self.u_s, self.n,
-                                                  _lib.ptr(t_sorted), None, _lib.ptr(valid, torch.uint8), *thresholds, self.st),
-                   "nerf_sample_fine_rays")
+        _lib.call("nerf_sample_fine_rays", raw_c, self.t_c, self.t_cs, self.u, self.u_s, self.n, t_sorted, None, valid, *thresholds)
         return t_sorted, valid
 
     def mark(self, grid, tvals, S, valid=None):
         """The grid's fine bitfield looked up at the S depths of every ray -> valid [n,S] uint8; ANDed into `valid` if given."""
         out = self.empty(self.n, S, dtype=torch.uint8) if valid is None else valid
-        _lib.check(self.lib.nerf_occupancy_mark(_lib.ptr(self.rays_o), _lib.ptr(self.rays_d), _lib.ptr(tvals), S, self.n, S,
-                                                _lib.ptr(grid.bits["fine"], torch.int32), *grid.lookup_args(), int(valid is not None),
-                                                _lib.ptr(out, torch.uint8), self.st), "nerf_occupancy_mark")
+        _lib.call("nerf_occupancy_mark", *self._rays(tvals, S, S), grid.bits["fine"], *grid.lookup_args(), int(valid is not None), out)
         return out
 
     def compact(self, valid):
         """-> (ids of the valid samples, their number), both on the device."""
         P = valid.numel()
         index, count = self.empty(P, dtype=torch.int32), self.empty(1, dtype=torch.int32)
-        ws = self.empty(int(self.lib.nerf_compact_valid_workspace_bytes(P)), dtype=torch.uint8)
-        _lib.check(self.lib.nerf_compact_valid(_lib.ptr(valid, torch.uint8), P, _lib.ptr(index, torch.int32),
-                                               _lib.ptr(count, torch.int32), ws.data_ptr(), self.st), "nerf_compact_valid")
+        ws = self.empty(int(_lib.call("nerf_compact_valid_workspace_bytes", P)), dtype=torch.uint8)
+        _lib.call("nerf_compact_valid", valid, P, index, count, ws)
         return index, count
 
     def composite(self, raw, tvals, stride, S):
         rgb, depth = self.empty(self.n, 3), self.empty(self.n)
-        _lib.check(self.lib.nerf_composite(_lib.ptr(raw), _lib.ptr(tvals), stride, self.n, S, self.white, _lib.ptr(rgb),
-                                           _lib.ptr(depth), None, self.st), "nerf_composite")
+        _lib.call("nerf_composite", raw, tvals, stride, self.n, S, self.white, rgb, depth, None)
         return rgb, depth
 
     # ---- backward stages
@@ -138,21 +125,18 @@ class _Step:
         """image -> (g_raw [n,S,4], g_t [n,S] | None: the depths are constants)"""
         g_raw = self.empty(self.n, S, 4)
         g_t = self.empty(self.n, S) if depths else None
-        _lib.check(self.lib.nerf_composite_backward(_lib.ptr(raw), _lib.ptr(tvals), stride, self.n, S, self.white, _lib.ptr(self.g_rgb),
-                                                    _lib.ptr(self.g_depth), _lib.ptr(g_raw), _lib.ptr(g_t), self.st),
-                   "nerf_composite_backward")
+        _lib.call("nerf_composite_backward", raw, tvals, stride, self.n, S, self.white, self.g_rgb, self.g_depth, g_raw, g_t)
         return g_raw, g_t
 
     def _pack_bwd(self, params):
         if self.pk_b is None:
-            self.pk_b = self.empty(int(self.lib.nerf_packed_bwd_bytes(self.prec)), dtype=torch.uint8)
-        _lib.check(self.lib.nerf_pack_model_bwd(_lib.ptr_array([p.detach().contiguous() for p in params]), self.pk_b.data_ptr(),
-                                                self.prec, self.st), "nerf_pack_model_bwd")
-        return self.pk_b.data_ptr()
+            self.pk_b = self.empty(int(_lib.call("nerf_packed_bwd_bytes", self.prec)), dtype=torch.uint8)
+        _lib.call("nerf_pack_model_bwd", [p.detach().contiguous() for p in params], self.pk_b, self.prec)
+        return self.pk_b
 
     def _gsave(self, S):
         """The chain's buffer: allocated by the first (fine) pass, its head reused by the coarse one."""
-        floats = int(self.lib.nerf_train_grad_floats(self.n * S))
+        floats = int(_lib.call("nerf_train_grad_floats", self.n * S))
         if self.gsave is None:
             self.gsave = self.empty(floats)
         return self.gsave[:floats]
@@ -162,7 +146,7 @@ class _Step:
         device tensor (no host sync here).  A clone: the next pass reuses gsave."""
         if getattr(self.renderer, "live_tile_stats", None) is None:
             return None
-        return self._gsave(S)[int(self.lib.nerf_train_live_count_offset(self.n * S))].view(torch.int32).clone()
+        return self._gsave(S)[int(_lib.call("nerf_train_live_count_offset", self.n * S))].view(torch.int32).clone()
 
     def mlp_backward(self, params, grads, tvals, stride, S, g_raw, save, density_only=False, depths=True, points=False):
         """g_raw -> the gradients of `params` accumulated into `grads` (None: no parameter needs grad, the chain runs alone),
@@ -170,35 +154,28 @@ class _Step:
         pk_b = self._pack_bwd(params)
         g_t = self.empty(self.n, S) if depths else None
         g_x = self.empty(self.n, S, 3) if points else None
-        head = self._rays(tvals, stride, S) + (pk_b, _lib.ptr(g_raw), _lib.ptr(save), _lib.ptr(self._gsave(S)), _lib.ptr(g_t))
-        garr = None if grads is None else _lib.ptr_array(grads)
+        head = self._rays(tvals, stride, S) + (pk_b, g_raw, save, self._gsave(S), g_t)
         if points:
-            rc = self.lib.nerf_mlp_backward_rays_x(*head, _lib.ptr(g_x), garr, int(density_only), self.prec, self.st)
+            _lib.call("nerf_mlp_backward_rays_x", *head, g_x, grads, int(density_only), self.prec)
         elif density_only:
-            rc = self.lib.nerf_mlp_backward_density(*head, garr, self.prec, self.st)
+            _lib.call("nerf_mlp_backward_density", *head, grads, self.prec)
         else:
-            rc = self.lib.nerf_mlp_backward(*head, garr, self.prec, self.st)
-        _lib.check(rc, "MLP backward over %d samples" % S)
+            _lib.call("nerf_mlp_backward", *head, grads, self.prec)
         return g_t, g_x
 
     def mlp_backward_masked(self, params, grads, tvals, S, masked, g_raw, save):
         """The MLP backward over the compact rows of the valid samples -> their g_t scattered back, 0 at the masked ones."""
         pk_b = self._pack_bwd(params)
         g_t = self.empty(self.n, S)
-        ws = self.empty(int(self.lib.nerf_mlp_backward_masked_workspace_bytes(self.n * S)), dtype=torch.uint8)
-        _lib.check(self.lib.nerf_mlp_backward_masked(*self._rays(tvals, S, S), _lib.ptr(masked[0], torch.int32),
-                                                     _lib.ptr(masked[1], torch.int32), pk_b, _lib.ptr(g_raw), _lib.ptr(save),
-                                                     _lib.ptr(self._gsave(S)), _lib.ptr(g_t), _lib.ptr_array(grads), self.prec,
-                                                     ws.data_ptr(), self.st), "nerf_mlp_backward_masked(fine)")
+        ws = self.empty(int(_lib.call("nerf_mlp_backward_masked_workspace_bytes", self.n * S)), dtype=torch.uint8)
+        _lib.call("nerf_mlp_backward_masked", *self._rays(tvals, S, S), *masked, pk_b, g_raw, save, self._gsave(S), g_t, grads, self.prec, ws)
         return g_t
 
     def coarse_backward(self, raw_c, save_c, t_sorted, g_t, cnt_f, ray_terms=None):
         """The coarse pass of a hierarchical step: depths -> coarse density -> coarse MLP parameters.  ray_terms = (g_x_fine,
         g_dview) when the rays require grad: -> (g_rays_o, g_rays_d)."""
         g_raw_c = self.empty(self.n, self.S_c, 4)
-        _lib.check(self.lib.nerf_sample_fine_rays_backward(_lib.ptr(raw_c), _lib.ptr(self.t_c), self.t_cs, _lib.ptr(self.u), self.u_s,
-                                                           self.n, _lib.ptr(t_sorted), _lib.ptr(g_t), _lib.ptr(g_raw_c), self.st),
-                   "nerf_sample_fine_rays_backward")
+        _lib.call("nerf_sample_fine_rays_backward", raw_c, self.t_c, self.t_cs, self.u, self.u_s, self.n, t_sorted, g_t, g_raw_c)
         cap = getattr(self.renderer, "capture_adjoints", None)
         if cap is not None:       # tests: the per-ray sampler adjoint d loss / d raw_coarse and d loss / d t_sorted (parity attribution)
             cap["g_raw_coarse"], cap["g_t_sorted"], cap["raw_coarse"] = g_raw_c.clone(), g_t.clone(), raw_c.clone()
@@ -209,9 +186,7 @@ class _Step:
         g_rays = None
         if ray_terms is not None:
             g_rays = self.empty(self.n, 3), self.empty(self.n, 3)
-            _lib.check(self.lib.nerf_rays_backward(self.n, _lib.ptr(self.t_c), self.t_cs, _lib.ptr(g_x_c), _lib.ptr(t_sorted),
-                                                   _lib.ptr(ray_terms[0]), _lib.ptr(ray_terms[1]), _lib.ptr(g_rays[0]),
-                                                   _lib.ptr(g_rays[1]), self.st), "nerf_rays_backward")
+            _lib.call("nerf_rays_backward", self.n, self.t_c, self.t_cs, g_x_c, t_sorted, *ray_terms, *g_rays)
         stats = getattr(self.renderer, "live_tile_stats", None)
         if stats is not None:     # (live tiles, tiles) of the fine and of the coarse pass
             stats.append((cnt_f, self.n * self.S_f // 32, self.live_count(self.S_c), self.n * self.S_c // 32))
@@ -222,15 +197,14 @@ class RenderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, renderer, rays_o, rays_d, draws, *params):
         s = _Step(renderer, rays_o, rays_d)
-        with torch.cuda.device(s.dev):
-            ctx.stochastic = s.use_draws(*draws) if draws is not None else None
-            pk_c, pk_f = renderer.net.packed(""), renderer.net.packed("fine")
-            # coarse pass: only its sigma is ever used (it places the fine samples; the coarse colour is never
-            # composited) -> the density-only forward / backward pair
-            raw_c, save_c = s.forward_save(pk_c, s.t_c, s.t_cs, s.S_c, density_only=True)
-            t_sorted, _ = s.sample_fine(raw_c)
-            raw_f, save_f = s.forward_save(pk_f, t_sorted, s.S_f, s.S_f)
-            rgb, depth = s.composite(raw_f, t_sorted, s.S_f, s.S_f)
+        ctx.stochastic = s.use_draws(*draws) if draws is not None else None
+        pk_c, pk_f = renderer.net.packed(""), renderer.net.packed("fine")
+        # coarse pass: only its sigma is ever used (it places the fine samples; the coarse colour is never
+        # composited) -> the density-only forward / backward pair
+        raw_c, save_c = s.forward_save(pk_c, s.t_c, s.t_cs, s.S_c, density_only=True)
+        t_sorted, _ = s.sample_fine(raw_c)
+        raw_f, save_f = s.forward_save(pk_f, t_sorted, s.S_f, s.S_f)
+        rgb, depth = s.composite(raw_f, t_sorted, s.S_f, s.S_f)
         ctx.renderer, ctx.prec, ctx.params = renderer, s.prec, params
         ctx.save_for_backward(rays_o, rays_d, raw_c, save_c, t_sorted, raw_f, save_f)
         return rgb, depth
@@ -241,21 +215,19 @@ class RenderFunction(torch.autograd.Function):
         s = _Step(ctx.renderer, rays_o, rays_d, ctx.prec, ctx.stochastic)
         need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         s.begin_backward(ctx, g_rgb, g_depth, 4)
-        with torch.cuda.device(s.dev):
-            # fine pass: image -> raw_fine and depths; MLP backward; points -> depths
-            g_raw_f, g_t = s.composite_backward(raw_f, t_sorted, s.S_f, s.S_f)
-            g_t_pts, g_x_f = s.mlp_backward(s.params[24:], None if s.grads is None else s.grads[24:], t_sorted, s.S_f, s.S_f,
-                                            g_raw_f, save_f, points=need_rays)
-            ray_terms = None
-            if need_rays:
-                # the view-direction term reads the fine g_zv rows: before the coarse pass reuses gsave
-                g_dview = s.empty(s.n, 3)
-                w_views = s.params[24 + 16].detach().contiguous()           # model_fine views_linears.0.weight [128,283]
-                _lib.check(s.lib.nerf_rays_viewdirs_backward(_lib.ptr(rays_d), s.n, s.S_f, _lib.ptr(s.gsave), _lib.ptr(w_views),
-                                                             _lib.ptr(g_dview), s.st), "nerf_rays_viewdirs_backward")
-                ray_terms = (g_x_f, g_dview)
-            g_t.add_(g_t_pts)                     # plumbing: one elementwise add of two [n,192] buffers
-            g_rays = s.coarse_backward(raw_c, save_c, t_sorted, g_t, s.live_count(s.S_f), ray_terms)
+        # fine pass: image -> raw_fine and depths; MLP backward; points -> depths
+        g_raw_f, g_t = s.composite_backward(raw_f, t_sorted, s.S_f, s.S_f)
+        g_t_pts, g_x_f = s.mlp_backward(s.params[24:], None if s.grads is None else s.grads[24:], t_sorted, s.S_f, s.S_f,
+                                        g_raw_f, save_f, points=need_rays)
+        ray_terms = None
+        if need_rays:
+            # the view-direction term reads the fine g_zv rows: before the coarse pass reuses gsave
+            g_dview = s.empty(s.n, 3)
+            w_views = s.params[24 + 16].detach().contiguous()           # model_fine views_linears.0.weight [128,283]
+            _lib.call("nerf_rays_viewdirs_backward", rays_d, s.n, s.S_f, s.gsave, w_views, g_dview)
+            ray_terms = (g_x_f, g_dview)
+        g_t.add_(g_t_pts)                     # plumbing: one elementwise add of two [n,192] buffers
+        g_rays = s.coarse_backward(raw_c, save_c, t_sorted, g_t, s.live_count(s.S_f), ray_terms)
         g_rays = (g_rays[0] if need_rays and ctx.needs_input_grad[1] else None, g_rays[1] if need_rays and ctx.needs_input_grad[2] else None)
         return (None,) + g_rays + (None,) + s.param_grads()
 
@@ -266,15 +238,14 @@ def _masked_forward(ctx, renderer, rays_o, rays_d, draws, grid, params):
     s = _Step(renderer, rays_o, rays_d)
     pk_c, pk_f = renderer.net.packed(""), renderer.net.packed("fine")
     raw_f = torch.zeros((s.n, s.S_f, 4), dtype=torch.float32, device=s.dev)           # unlisted samples keep raw = 0
-    with torch.cuda.device(s.dev):
-        ctx.stochastic = s.use_draws(*draws) if draws is not None else None
-        raw_c, save_c = s.forward_save(pk_c, s.t_c, s.t_cs, s.S_c, density_only=True)
-        t_sorted, valid = s.sample_fine(raw_c, fast_sampling=grid is None or bool(renderer.fast_sampling))
-        if grid is not None:
-            valid = s.mark(grid, t_sorted, s.S_f, valid)
-        index, count = s.compact(valid)
-        raw_f, save_f = s.forward_save(pk_f, t_sorted, s.S_f, s.S_f, masked=(index, count), raw=raw_f)
-        rgb, depth = s.composite(raw_f, t_sorted, s.S_f, s.S_f)
+    ctx.stochastic = s.use_draws(*draws) if draws is not None else None
+    raw_c, save_c = s.forward_save(pk_c, s.t_c, s.t_cs, s.S_c, density_only=True)
+    t_sorted, valid = s.sample_fine(raw_c, fast_sampling=grid is None or bool(renderer.fast_sampling))
+    if grid is not None:
+        valid = s.mark(grid, t_sorted, s.S_f, valid)
+    index, count = s.compact(valid)
+    raw_f, save_f = s.forward_save(pk_f, t_sorted, s.S_f, s.S_f, masked=(index, count), raw=raw_f)
+    rgb, depth = s.composite(raw_f, t_sorted, s.S_f, s.S_f)
     stats = getattr(renderer, "masked_stats", None)
     if stats is not None:         # (points the fine network evaluated as a 1-element device tensor, capacity): no host sync here
         stats.append((count.clone(), s.n * s.S_f))
@@ -293,12 +264,11 @@ def _masked_backward(ctx, g_rgb, g_depth, n_inputs):
     s.begin_backward(ctx, g_rgb, g_depth, n_inputs)
     if s.grads is None:
         return (None,) * (n_inputs + len(s.params))
-    with torch.cuda.device(s.dev):
-        # fine pass: image -> raw_fine and depths (all 192 samples; g_raw is exactly zero at the masked ones: sigma = 0)
-        g_raw_f, g_t = s.composite_backward(raw_f, t_sorted, s.S_f, s.S_f)
-        g_t.add_(s.mlp_backward_masked(s.params[24:], s.grads[24:], t_sorted, s.S_f, (index, count), g_raw_f, save_f))
-        # coarse pass, as in the unmasked step
-        s.coarse_backward(raw_c, save_c, t_sorted, g_t, s.live_count(s.S_f))
+    # fine pass: image -> raw_fine and depths (all 192 samples; g_raw is exactly zero at the masked ones: sigma = 0)
+    g_raw_f, g_t = s.composite_backward(raw_f, t_sorted, s.S_f, s.S_f)
+    g_t.add_(s.mlp_backward_masked(s.params[24:], s.grads[24:], t_sorted, s.S_f, (index, count), g_raw_f, save_f))
+    # coarse pass, as in the unmasked step
+    s.coarse_backward(raw_c, save_c, t_sorted, g_t, s.live_count(s.S_f))
     return (None,) * n_inputs + s.param_grads()
 
 
@@ -341,9 +311,8 @@ class CoarseRenderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, renderer, rays_o, rays_d, *params):
         s = _Step(renderer, rays_o, rays_d)
-        with torch.cuda.device(s.dev):
-            raw_c, save_c = s.forward_save(renderer.net.packed(""), s.t_c, 0, s.S_c)
-            rgb, depth = s.composite(raw_c, s.t_c, 0, s.S_c)
+        raw_c, save_c = s.forward_save(renderer.net.packed(""), s.t_c, 0, s.S_c)
+        rgb, depth = s.composite(raw_c, s.t_c, 0, s.S_c)
         ctx.renderer, ctx.prec, ctx.params = renderer, s.prec, params
         ctx.save_for_backward(rays_o, rays_d, raw_c, save_c)
         return rgb, depth
@@ -355,12 +324,11 @@ class CoarseRenderFunction(torch.autograd.Function):
         s.begin_backward(ctx, g_rgb, g_depth, 3)
         if s.grads is None:
             return (None,) * (3 + len(s.params))
-        with torch.cuda.device(s.dev):
-            g_raw_c, _ = s.composite_backward(raw_c, s.t_c, 0, s.S_c, depths=False)
-            s.mlp_backward(s.params, s.grads, s.t_c, 0, s.S_c, g_raw_c, save_c, depths=False)
-            stats = getattr(ctx.renderer, "live_tile_stats", None)
-            if stats is not None:
-                stats.append((None, 0, s.live_count(s.S_c), s.n * s.S_c // 32))
+        g_raw_c, _ = s.composite_backward(raw_c, s.t_c, 0, s.S_c, depths=False)
+        s.mlp_backward(s.params, s.grads, s.t_c, 0, s.S_c, g_raw_c, save_c, depths=False)
+        stats = getattr(ctx.renderer, "live_tile_stats", None)
+        if stats is not None:
+            stats.append((None, 0, s.live_count(s.S_c), s.n * s.S_c // 32))
         return (None, None, None) + s.param_grads()
 
 
@@ -471,8 +439,6 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.load()
-        arr = _lib.ptr_array
         bump = getattr(torch.autograd.graph, "increment_version", None)
         for g in self.param_groups:
             if g.get("amsgrad", False) or g.get("maximize", False):
@@ -491,13 +457,9 @@ class FusedAdam(torch.optim.Optimizer):
                     if st[k].device != dev:
                         st[k] = st[k].to(dev)
             grads = [p.grad.contiguous() for p in live]
-            numel = (ctypes.c_int64 * len(live))(*[p.numel() for p in live])
-            with torch.cuda.device(dev):
-                _lib.check(lib.nerf_adam_step(len(live), arr(live), arr(grads), arr([st["exp_avg"] for st in states]),
-                                              arr([st["exp_avg_sq"] for st in states]), numel, float(g["lr"]),
-                                              float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                              float(g["weight_decay"]), float(g.get("clip_value", 40.0)), step,
-                                              _lib.stream_of(dev)), "nerf_adam_step")
+            _lib.call("nerf_adam_step", len(live), live, grads, [st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states],
+                      [p.numel() for p in live], float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                      float(g["weight_decay"]), float(g.get("clip_value", 40.0)), step)
             for p, st in zip(live, states):
                 st["step"] = torch.tensor(float(step))
                 # the packed weight streams are keyed on (data_ptr, _version): tell autograd the HIP kernel wrote in

@@ -101,20 +101,25 @@ class Renderer:
             ws = self._workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         return ws
 
+    def _with_grad(self, rays_grad):
+        """Is this a training call (autograd on, a .train() network with parameters that require grad), or one whose rays require
+        grad?"""
+        return rays_grad or (torch.is_grad_enabled() and getattr(self.net, "training", False) and
+                             any(p.requires_grad for p in self.net.parameters()))
+
     def _check_occupancy(self, dev, rays_grad, stochastic):
         """What a render with self.occupancy set refuses, before anything is launched."""
         grid = self.occupancy
         if not isinstance(grid, _sibling("occupancy").OccupancyGrid):
             raise TypeError("Renderer.occupancy must be an OccupancyGrid or None")
-        if rays_grad or (torch.is_grad_enabled() and getattr(self.net, "training", False) and
-                         any(p.requires_grad for p in self.net.parameters())):
+        if self._with_grad(rays_grad):
             raise NotImplementedError("occupancy culling is an inference feature: no training step and no ray gradients with "
                                       "Renderer.occupancy set")
         if stochastic:
             raise NotImplementedError(f"occupancy culling is not built for stochastic sampling (task={self.task!r}, "
                                       f"perturb={bool(self.perturb)})")
         prec_name = getattr(self.net, "precision", "f32")
-        if _lib.PRECISIONS[prec_name] not in (_lib.PREC_F32, _lib.PREC_F32X):
+        if not _lib.fp32_accurate(prec_name):
             raise NotImplementedError(f"occupancy culling runs in precision 'f32' or 'f32x', not {prec_name!r}: the fp16 far-plane "
                                       "guard is not defined on a culled list")
         if grid.device != dev:
@@ -151,7 +156,6 @@ class Renderer:
         self.device = dev = rays_o.device
         if dev.type != "cuda":
             raise _lib.NerfLibraryError("Renderer.render needs rays on a GPU: the render path is HIP-only")
-        lib = _lib.load()
         B, N, _ = rays_o.shape
         n = B * N
         # rays that require grad stay in the graph (pose refinement): reshape / cast / contiguous map the gradient back to [B,N,3]
@@ -168,14 +172,13 @@ class Renderer:
             self._check_occupancy(dev, rays_grad, stochastic)          # refused before any launch
         if stochastic:
             prec_name = getattr(self.net, "precision", "f32")
-            if _lib.PRECISIONS[prec_name] not in (_lib.PREC_F32, _lib.PREC_F32X):
+            if not _lib.fp32_accurate(prec_name):
                 raise NotImplementedError(f"stochastic sampling (task={self.task!r}, perturb={bool(self.perturb)}) runs in "
                                           f"precision 'f32' or 'f32x', not {prec_name!r}")
             if self.fast_sampling:
                 raise NotImplementedError(f"stochastic sampling (task={self.task!r}, perturb={bool(self.perturb)}) is not "
                                           "built with fast_sampling")
-        with_grad = rays_grad or (torch.is_grad_enabled() and getattr(self.net, "training", False) and
-                                  any(p.requires_grad for p in self.net.parameters()))
+        with_grad = self._with_grad(rays_grad)
         train_grid = self._train_grid(dev, rays_grad) if with_grad and self.train_occupancy is not None else None
         if stochastic:
             jitter, u_rays = self._draws(n, dev)
@@ -196,45 +199,26 @@ class Renderer:
         depth = torch.empty((n,), dtype=torch.float32, device=dev)
         if n == 0:
             return rgb, depth
-        if stochastic:
-            nbytes = int(lib.nerf_render_stochastic_workspace_bytes(n, self.N_importance))
-            ws = self._get_workspace(nbytes, dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.nerf_render_forward_stochastic(
-                    _lib.ptr(o), _lib.ptr(d), n, pk_c.data_ptr(), pk_f.data_ptr() if pk_f is not None else None,
-                    _lib.ptr(t_c), _lib.ptr(u), _lib.ptr(jitter), _lib.ptr(u_rays),
-                    int(self.N_importance), int(bool(self.white_bkgd)), _lib.PRECISIONS[prec_name], 0,
-                    float(self.weights_threshold), ws.data_ptr(), ws.numel(),
-                    _lib.ptr(rgb), _lib.ptr(depth), _lib.stream_of(dev)), "nerf_render_forward_stochastic")
-            return rgb, depth
-        fast = int(bool(self.fast_sampling) and self.N_importance > 0)
+        fast = int(bool(self.fast_sampling) and self.N_importance > 0)       # (0 when stochastic: refused above)
         prec = _lib.PRECISIONS[getattr(self.net, "precision", "f32")]
-        if self.occupancy is not None:
+        # what the three whole-frame entries have in common: rays, models, tables, modes
+        head = (o, d, n, pk_c, pk_f, t_c, u)
+        modes = (int(self.N_importance), int(bool(self.white_bkgd)), prec, fast, float(self.weights_threshold))
+        if stochastic:
+            ws = self._get_workspace(int(_lib.call("nerf_render_stochastic_workspace_bytes", n, self.N_importance)), dev)
+            _lib.call("nerf_render_forward_stochastic", *head, jitter, u_rays, *modes, ws, ws.numel(), rgb, depth)
+        elif self.occupancy is not None:
             grid = self.occupancy
             occ_c, occ_f = grid.bits[""], grid.bits["fine"] if self.N_importance > 0 else None
-            dims, box_min, inv_step = grid.lookup_args()
-            ws = self._get_workspace(int(lib.nerf_render_occupancy_workspace_bytes(n, self.N_importance, fast)), dev)
+            ws = self._get_workspace(int(_lib.call("nerf_render_occupancy_workspace_bytes", n, self.N_importance, fast)), dev)
             evaluated = torch.empty(2, dtype=torch.int64, device=dev) if self.occupancy_stats is not None else None
-            with torch.cuda.device(dev):
-                _lib.check(lib.nerf_render_forward_occupancy(
-                    _lib.ptr(o), _lib.ptr(d), n, pk_c.data_ptr(), pk_f.data_ptr() if pk_f is not None else None,
-                    _lib.ptr(t_c), _lib.ptr(u),
-                    int(self.N_importance), int(bool(self.white_bkgd)), prec, fast, float(self.weights_threshold),
-                    _lib.ptr(occ_c, torch.int32), _lib.ptr(occ_f, torch.int32), dims, box_min, inv_step,
-                    evaluated.data_ptr() if evaluated is not None else None, ws.data_ptr(), ws.numel(),
-                    _lib.ptr(rgb), _lib.ptr(depth), _lib.stream_of(dev)), "nerf_render_forward_occupancy")
+            _lib.call("nerf_render_forward_occupancy", *head, *modes, occ_c, occ_f, *grid.lookup_args(), evaluated, ws, ws.numel(),
+                      rgb, depth)
             if evaluated is not None:
                 self.occupancy_stats.append((evaluated.clone(), (_lib.N_SAMPLES * n, (_lib.N_SAMPLES + _lib.N_IMPORTANCE) * n)))
-            return rgb, depth
-        nbytes = int(lib.nerf_render_workspace_bytes(n, self.N_importance, fast))
-        ws = self._get_workspace(nbytes, dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_render_forward(
-                _lib.ptr(o), _lib.ptr(d), n, pk_c.data_ptr(), pk_f.data_ptr() if pk_f is not None else None,
-                _lib.ptr(t_c), _lib.ptr(u),
-                int(self.N_importance), int(bool(self.white_bkgd)), prec, fast, float(self.weights_threshold),
-                ws.data_ptr(), ws.numel(),
-                _lib.ptr(rgb), _lib.ptr(depth), _lib.stream_of(dev)), "nerf_render_forward")
+        else:
+            ws = self._get_workspace(int(_lib.call("nerf_render_workspace_bytes", n, self.N_importance, fast)), dev)
+            _lib.call("nerf_render_forward", *head, *modes, ws, ws.numel(), rgb, depth)
         return rgb, depth
 
     def render_geometry(self, batch):
@@ -256,7 +240,7 @@ class Renderer:
             raise NotImplementedError("render_geometry has no autograd path: rays that require grad are refused (detach them; "
                                       "render() is the differentiable call)")
         prec_name = getattr(self.net, "precision", "f32")
-        if _lib.PRECISIONS[prec_name] not in (_lib.PREC_F32, _lib.PREC_F32X):
+        if not _lib.fp32_accurate(prec_name):
             raise NotImplementedError(f"render_geometry runs in precision 'f32' or 'f32x', not {prec_name!r}: the gradient chain "
                                       "has no fp16 form")
         if self.fast_sampling:
@@ -269,7 +253,6 @@ class Renderer:
         block = self.geometry_block_rays
         if isinstance(block, bool) or not isinstance(block, int) or block < 1:
             raise ValueError(f"Renderer.geometry_block_rays must be an int >= 1 (rays), got {block!r}")
-        lib = _lib.load()
         B, N, _ = rays_o.shape
         n = B * N
         o = rays_o.detach().reshape(n, 3).to(torch.float32).contiguous()
@@ -290,31 +273,20 @@ class Renderer:
         raw_c = new(nb_max, S_c, 4)
         t_sorted, raw_f = (new(nb_max, S), new(nb_max, S, 4)) if fine else (None, None)
         grad = new(nb_max, S, 3)
-        ws = torch.empty(int(lib.nerf_density_gradient_point_bytes()) * ((nb_max * S + 31) // 32 * 32), dtype=torch.uint8, device=dev)
+        ws = torch.empty(int(_lib.call("nerf_density_gradient_point_bytes")) * ((nb_max * S + 31) // 32 * 32), dtype=torch.uint8, device=dev)
         white = int(bool(self.white_bkgd))
-        with torch.cuda.device(dev):
-            st = _lib.stream_of(dev)
-            for r0 in range(0, n, block):
-                nb = min(block, n - r0)
-                ob, db = _lib.ptr(o[r0:r0 + nb]), _lib.ptr(d[r0:r0 + nb])
-                if fine:
-                    _lib.check(lib.nerf_mlp_forward_rays_density(ob, db, _lib.ptr(t_c), 0, nb, S_c, pk_c.data_ptr(), _lib.ptr(raw_c),
-                                                                 prec, st), "nerf_mlp_forward_rays_density")
-                    _lib.check(lib.nerf_sample_fine(_lib.ptr(raw_c), _lib.ptr(t_c), _lib.ptr(u), nb, _lib.ptr(t_sorted), None, None,
-                                                    0.0, 0.0, st), "nerf_sample_fine")
-                    _lib.check(lib.nerf_mlp_forward_rays_for_compositing(ob, db, _lib.ptr(t_sorted), S, nb, S, pk.data_ptr(),
-                                                                         _lib.ptr(raw_f), prec, st),
-                               "nerf_mlp_forward_rays_for_compositing")
-                    raw, tv, stride = raw_f, t_sorted, S
-                else:
-                    _lib.check(lib.nerf_mlp_forward_rays(ob, db, _lib.ptr(t_c), 0, nb, S_c, pk_c.data_ptr(), _lib.ptr(raw_c), prec, st),
-                               "nerf_mlp_forward_rays")
-                    raw, tv, stride = raw_c, t_c, 0
-                _lib.check(lib.nerf_composite(_lib.ptr(raw), _lib.ptr(tv), stride, nb, S, white, _lib.ptr(out["rgb"][r0:r0 + nb]),
-                                              _lib.ptr(out["depth"][r0:r0 + nb]), None, st), "nerf_composite")
-                _lib.check(lib.nerf_density_gradient(ob, db, _lib.ptr(tv), stride, nb, S, pk.data_ptr(), pk_b.data_ptr(), 1, None,
-                                                     _lib.ptr(grad), prec, ws.data_ptr(), ws.numel(), st), "nerf_density_gradient")
-                _lib.check(lib.nerf_composite_normals(_lib.ptr(raw), _lib.ptr(tv), stride, nb, S, _lib.ptr(grad),
-                                                      _lib.ptr(out["normal"][r0:r0 + nb]), _lib.ptr(out["acc"][r0:r0 + nb]), st),
-                           "nerf_composite_normals")
+        for r0 in range(0, n, block):
+            nb = min(block, n - r0)
+            ob, db = o[r0:r0 + nb], d[r0:r0 + nb]
+            if fine:
+                _lib.call("nerf_mlp_forward_rays_density", ob, db, t_c, 0, nb, S_c, pk_c, raw_c, prec)
+                _lib.call("nerf_sample_fine", raw_c, t_c, u, nb, t_sorted, None, None, 0.0, 0.0)
+                _lib.call("nerf_mlp_forward_rays_for_compositing", ob, db, t_sorted, S, nb, S, pk, raw_f, prec)
+                raw, tv, stride = raw_f, t_sorted, S
+            else:
+                _lib.call("nerf_mlp_forward_rays", ob, db, t_c, 0, nb, S_c, pk_c, raw_c, prec)
+                raw, tv, stride = raw_c, t_c, 0
+            _lib.call("nerf_composite", raw, tv, stride, nb, S, white, out["rgb"][r0:r0 + nb], out["depth"][r0:r0 + nb], None)
+            _lib.call("nerf_density_gradient", ob, db, tv, stride, nb, S, pk, pk_b, 1, None, grad, prec, ws, ws.numel())
+            _lib.call("nerf_composite_normals", raw, tv, stride, nb, S, grad, out["normal"][r0:r0 + nb], out["acc"][r0:r0 + nb])
         return out

@@ -15,9 +15,45 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(nerf_[a-z_0-9]+)\s*\(", text)))
 
 
+_C_TYPES = {"int32_t": "i32", "uint32_t": "i32", "int64_t": "i64", "float": "f32", "double": "f64", "uint8_t": "u8", "void": "void"}
+
+
+def _declared_signatures():
+    """{name: (return kind, (parameter kinds))} of every declaration in the header, in the vocabulary of _lib.SIGNATURES: a
+    pointer is a device pointer to its element type (constness ignored, uint32_t as i32), array syntax is a host array (of
+    device pointers when the element is one), `void* stream` is the stream, and an int32_t return of an entry that takes a
+    stream is a status."""
+    text = open(os.path.join(REPO, "include", "nerf_mi355x.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"\b(const\s+char\s*\*|int32_t|int64_t)\s+(nerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
+        kinds = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(?:const\s+)?(\w+)\s*(\[\d*\])?", " ".join(p.split()))
+            assert m, (name, p)
+            ctype, star, pname, array = m.groups()
+            kind = _C_TYPES[ctype] + star + (array or "")
+            assert kind != "void", (name, p)
+            kinds.append("stream" if (kind, pname) == ("void*", "stream") else kind)
+        assert "stream" not in kinds[:-1], name
+        ret = "str" if "char" in ret else "i64" if ret == "int64_t" else "status" if kinds[-1:] == ["stream"] else "i32"
+        assert name not in out, name
+        out[name] = (ret, tuple(kinds))
+    return out
+
+
 def test_header_declares_the_binding_surface():
+    """The binding table against the header: the same names, and for every entry the same return kind and the same kind for every
+    parameter, in order, host-array lengths included.  A declaration the parser missed would show as a name without a signature."""
     import nerf_replication_amd._lib as L
     assert sorted(L.EXPORTS) == _declared_symbols()
+    declared = _declared_signatures()
+    assert len(declared) == len(L.EXPORTS) == 65 and sorted(declared) == _declared_symbols()
+    assert sum(len(kinds) for _, kinds in declared.values()) == 530
+    for name in L.EXPORTS:
+        assert L.SIGNATURES[name] == declared[name], name
+    # the ctypes prototypes load() installs are derived from the same table, one argtype per parameter
+    assert all(len(L._PROTOS[name][1]) == len(declared[name][1]) for name in L.EXPORTS)
 
 
 def test_library_builds_loads_and_exports():

@@ -29,7 +29,7 @@ _LAZY = {
     "OccupancyGrid": ".occupancy",
     "HashEncoder": ".hashgrid", "TriPlane": ".hashgrid",
 }
-_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy", "hashgrid")
+_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy", "hashgrid", "modes")
 
 __all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model",
            "density_grid", "isosurface", "write_ply", "extract_mesh", "density_gradient", "vertex_normals",

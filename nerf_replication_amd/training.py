@@ -28,7 +28,7 @@ grid is right.
 """
 import torch
 
-from . import _lib
+from . import _lib, modes
 
 
 class _Step:
@@ -40,7 +40,7 @@ class _Step:
     def __init__(self, renderer, rays_o, rays_d, prec=None, stochastic=None):
         self.renderer, self.rays_o, self.rays_d = renderer, rays_o, rays_d
         self.dev, self.n = rays_o.device, rays_o.shape[0]
-        self.prec = _lib.PRECISIONS[getattr(renderer.net, "precision", "f32")] if prec is None else prec
+        self.prec = _lib.PRECISIONS[modes.precision_of(renderer.net)] if prec is None else prec
         self.white = int(bool(renderer.white_bkgd))
         # the coarse depths and u with their per-ray strides (0: the shared tables)
         self.t_c, self.u = renderer._get_tables(self.dev)
@@ -333,41 +333,34 @@ class CoarseRenderFunction(torch.autograd.Function):
 
 
 def check_differentiable(renderer, rays_grad=False):
-    """Raise NotImplementedError for the modes without adjoint kernels: fp16 precisions, and gradients with respect to the rays
-    (`rays_grad`) with fast_sampling or N_importance == 0 -- those two modes train their parameters only."""
-    if getattr(renderer.net, "precision", "f32") not in ("f32", "f32x"):
-        raise NotImplementedError("training runs on the fp32-accurate paths: precision 'f32' (exact fp32 MFMA) or 'f32x' "
-                                  "(forward on split-fp16 MFMA; the backward kernels are fp32 MFMA either way)")
-    if renderer.N_importance not in (0, _lib.N_IMPORTANCE):
-        raise NotImplementedError("training path is built for N_importance in {0, 128}")
-    if rays_grad and (renderer.N_importance != _lib.N_IMPORTANCE or renderer.fast_sampling):
-        raise NotImplementedError("gradients with respect to the rays are built for N_importance=128 without fast_sampling")
+    """Raise NotImplementedError for the modes without adjoint kernels (modes.DIFFERENTIABLE): fp16 precisions, and gradients with
+    respect to the rays (`rays_grad`) with fast_sampling or N_importance == 0 -- those two modes train their parameters only."""
+    modes.resolve(modes.facts(renderer, modes.STEP, rays_grad, 1), table=modes.CHECK_DIFFERENTIABLE)
+
+
+def _all_params(net):
+    return tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
+
+
+# the path modes.resolve names -> (renderer, rays_o, rays_d, draws, grid) -> (rgb, depth)
+_STEPS = {
+    "step": lambda r, o, d, draws, grid: RenderFunction.apply(r, o, d, draws, *_all_params(r.net)),
+    "step_masked": lambda r, o, d, draws, grid: MaskedRenderFunction.apply(r, o, d, *_all_params(r.net)),
+    "step_coarse": lambda r, o, d, draws, grid: CoarseRenderFunction.apply(r, o, d, *r.net.model.ordered_params()),
+    "step_culled": lambda r, o, d, draws, grid: CulledRenderFunction.apply(r, o, d, draws, grid, *_all_params(r.net)),
+}
 
 
 def render_with_grad(renderer, rays_o, rays_d, jitter=None, u=None, occupancy=None):
     """rays [n,3] (contiguous fp32, on the GPU) -> (rgb [n,3], depth [n]) attached to the autograd graph of
     the 48 network parameters (coarse sub-model first, then fine, state_dict order) and of the rays, each where it
     requires grad.  `jitter` [n,64] / `u` [n,128]: the reference's training-mode draws (Renderer._draws); None keeps the
-    shared deterministic table.  `occupancy`: an OccupancyGrid whose fine bitfield culls the fine pass (Renderer._train_grid has
+    shared deterministic table.  `occupancy`: an OccupancyGrid whose fine bitfield culls the fine pass (Renderer.render has
     checked it); parameter gradients only, N_importance = 128."""
-    net = renderer.net
-    rays_grad = rays_o.requires_grad or rays_d.requires_grad
-    check_differentiable(renderer, rays_grad)
     draws = (jitter, u) if (jitter is not None or u is not None) else None
-    if occupancy is not None:
-        if rays_grad or renderer.N_importance != _lib.N_IMPORTANCE or (draws is not None and renderer.fast_sampling):
-            raise NotImplementedError("the culled step trains parameters with N_importance=128; fast_sampling with deterministic sampling only")
-        params = tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
-        return CulledRenderFunction.apply(renderer, rays_o, rays_d, draws, occupancy, *params)
-    if renderer.N_importance == 0 or renderer.fast_sampling:
-        if draws is not None:
-            raise NotImplementedError("stochastic sampling trains with N_importance=128 without fast_sampling only")
-        if renderer.N_importance == 0:
-            return CoarseRenderFunction.apply(renderer, rays_o, rays_d, *net.model.ordered_params())
-        params = tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
-        return MaskedRenderFunction.apply(renderer, rays_o, rays_d, *params)
-    params = tuple(net.model.ordered_params()) + tuple(net.model_fine.ordered_params())
-    return RenderFunction.apply(renderer, rays_o, rays_d, draws, *params)
+    facts = modes.facts(renderer, modes.STEP, rays_o.requires_grad or rays_d.requires_grad, rays_o.shape[0],
+                        draws=draws is not None, train_occupancy=occupancy is not None)
+    return _STEPS[modes.resolve(facts)](renderer, rays_o, rays_d, draws, occupancy)
 
 
 class FusedAdam(torch.optim.Optimizer):

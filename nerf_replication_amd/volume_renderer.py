@@ -29,6 +29,7 @@ def _sibling(name):
 
 
 _lib = _sibling("_lib")
+modes = _sibling("modes")
 
 
 def _reference_cfg():
@@ -101,52 +102,11 @@ class Renderer:
             ws = self._workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         return ws
 
-    def _with_grad(self, rays_grad):
-        """Is this a training call (autograd on, a .train() network with parameters that require grad), or one whose rays require
-        grad?"""
-        return rays_grad or (torch.is_grad_enabled() and getattr(self.net, "training", False) and
-                             any(p.requires_grad for p in self.net.parameters()))
-
-    def _check_occupancy(self, dev, rays_grad, stochastic):
-        """What a render with self.occupancy set refuses, before anything is launched."""
-        grid = self.occupancy
-        if not isinstance(grid, _sibling("occupancy").OccupancyGrid):
-            raise TypeError("Renderer.occupancy must be an OccupancyGrid or None")
-        if self._with_grad(rays_grad):
-            raise NotImplementedError("occupancy culling is an inference feature: no training step and no ray gradients with "
-                                      "Renderer.occupancy set")
-        if stochastic:
-            raise NotImplementedError(f"occupancy culling is not built for stochastic sampling (task={self.task!r}, "
-                                      f"perturb={bool(self.perturb)})")
-        prec_name = getattr(self.net, "precision", "f32")
-        if not _lib.fp32_accurate(prec_name):
-            raise NotImplementedError(f"occupancy culling runs in precision 'f32' or 'f32x', not {prec_name!r}: the fp16 far-plane "
-                                      "guard is not defined on a culled list")
-        if grid.device != dev:
-            raise ValueError(f"the occupancy grid is on {grid.device}, the rays on {dev}")
-        for model in ("", "fine") if self.N_importance > 0 else ("",):
-            if grid.stale(self.net, model):
-                raise RuntimeError("the network's parameters changed since the occupancy grid was built from them: rebuild the "
-                                   "grid (OccupancyGrid.from_network), or set Renderer.occupancy = None")
-
-    def _train_grid(self, dev, rays_grad):
-        """The grid of a training call with self.train_occupancy set: what that call refuses, before anything is launched, then the
-        refresh schedule -- one build serves train_occupancy_every steps, and a grid whose network did not move is never rebuilt."""
-        _sibling("training").check_differentiable(self, rays_grad)
-        grid, every = self.train_occupancy, self.train_occupancy_every
-        if not isinstance(grid, _sibling("occupancy").OccupancyGrid):
-            raise TypeError("Renderer.train_occupancy must be an OccupancyGrid or None")
-        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
-            raise ValueError(f"Renderer.train_occupancy_every must be an int >= 1 (steps), got {every!r}")
-        if grid.bits["fine"] is None:
-            raise ValueError("Renderer.train_occupancy needs a grid with a fine bitfield: the training step culls the fine pass only")
-        if grid.device != dev:
-            raise ValueError(f"the occupancy grid is on {grid.device}, the rays on {dev}")
-        if rays_grad:
-            raise NotImplementedError("no ray gradients with Renderer.train_occupancy set: the masked backward forms no point gradients")
-        if self.N_importance == 0:
-            raise NotImplementedError("Renderer.train_occupancy culls the fine pass: there is none with N_importance = 0")
-        if grid.stale(self.net, "fine") and grid.uses >= every:
+    def _scheduled_grid(self):
+        """The grid of an accepted training call with self.train_occupancy set, after the refresh schedule: one build serves
+        train_occupancy_every steps, and a grid whose network did not move is never rebuilt."""
+        grid = self.train_occupancy
+        if grid.stale(self.net, "fine") and grid.uses >= self.train_occupancy_every:
             grid.refresh(self.net, models=("fine",))
         grid.uses += 1
         return grid
@@ -164,62 +124,62 @@ class Renderer:
             rays_o, rays_d = rays_o.detach(), rays_d.detach()
         o = rays_o.reshape(n, 3).to(torch.float32).contiguous()
         d = rays_d.reshape(n, 3).to(torch.float32).contiguous()
-        if rays_grad:
-            # refused before any launch: never a detached result for rays that require grad
-            _sibling("training").check_differentiable(self, True)
-        stochastic = bool(self.perturb) or self.task == "train"
-        if self.occupancy is not None:
-            self._check_occupancy(dev, rays_grad, stochastic)          # refused before any launch
-        if stochastic:
-            prec_name = getattr(self.net, "precision", "f32")
-            if not _lib.fp32_accurate(prec_name):
-                raise NotImplementedError(f"stochastic sampling (task={self.task!r}, perturb={bool(self.perturb)}) runs in "
-                                          f"precision 'f32' or 'f32x', not {prec_name!r}")
-            if self.fast_sampling:
-                raise NotImplementedError(f"stochastic sampling (task={self.task!r}, perturb={bool(self.perturb)}) is not "
-                                          "built with fast_sampling")
-        with_grad = self._with_grad(rays_grad)
-        train_grid = self._train_grid(dev, rays_grad) if with_grad and self.train_occupancy is not None else None
-        if stochastic:
-            jitter, u_rays = self._draws(n, dev)
-        if with_grad:
-            # training call (trainers/nerf.py:27 under trainer.py:53-60), or rays that require grad: forward with activation
-            # save, backward through the adjoint HIP kernels (training.py)
-            render_with_grad = _sibling("training").render_with_grad
-            if n == 0:
-                return torch.empty((0, 3), device=dev), torch.empty((0,), device=dev)
-            kw = {} if train_grid is None else {"occupancy": train_grid}
-            if stochastic:
-                return render_with_grad(self, o, d, jitter, u_rays, **kw)
-            return render_with_grad(self, o, d, **kw)
+        facts = modes.facts(self, modes.RENDER, rays_grad, n)
+        path = modes.resolve(facts, self, dev)                              # every refusal comes before any launch
+        grid = self._scheduled_grid() if facts.with_grad and facts.train_occupancy else None
+        draws = self._draws(n, dev) if facts.stochastic else ()
+        return self._RENDER[path](self, facts, o, d, draws, grid)
+
+    def _empty(self, facts, o, d, draws, grid):
+        if facts.with_grad:
+            return torch.empty((0, 3), device=o.device), torch.empty((0,), device=o.device)
+        return self._frame_arguments(facts, o, d)[-2:]
+
+    def _step(self, facts, o, d, draws, grid):
+        """A training call (trainers/nerf.py:27 under trainer.py:53-60), or rays that require grad: forward with activation save,
+        backward through the adjoint HIP kernels (training.py)."""
+        kw = {} if grid is None else {"occupancy": grid}
+        return _sibling("training").render_with_grad(self, o, d, *draws, **kw)
+
+    def _frame_arguments(self, facts, o, d):
+        """What the three whole-frame entries have in common: (rays, models, tables), (modes), fast, and the outputs."""
+        n, dev = o.shape[0], o.device
         t_c, u = self._get_tables(dev)
         pk_c = self.net.packed("")
         pk_f = self.net.packed("fine") if self.N_importance > 0 else None
         rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
         depth = torch.empty((n,), dtype=torch.float32, device=dev)
-        if n == 0:
-            return rgb, depth
-        fast = int(bool(self.fast_sampling) and self.N_importance > 0)       # (0 when stochastic: refused above)
-        prec = _lib.PRECISIONS[getattr(self.net, "precision", "f32")]
-        # what the three whole-frame entries have in common: rays, models, tables, modes
-        head = (o, d, n, pk_c, pk_f, t_c, u)
-        modes = (int(self.N_importance), int(bool(self.white_bkgd)), prec, fast, float(self.weights_threshold))
-        if stochastic:
-            ws = self._get_workspace(int(_lib.call("nerf_render_stochastic_workspace_bytes", n, self.N_importance)), dev)
-            _lib.call("nerf_render_forward_stochastic", *head, jitter, u_rays, *modes, ws, ws.numel(), rgb, depth)
-        elif self.occupancy is not None:
-            grid = self.occupancy
-            occ_c, occ_f = grid.bits[""], grid.bits["fine"] if self.N_importance > 0 else None
-            ws = self._get_workspace(int(_lib.call("nerf_render_occupancy_workspace_bytes", n, self.N_importance, fast)), dev)
-            evaluated = torch.empty(2, dtype=torch.int64, device=dev) if self.occupancy_stats is not None else None
-            _lib.call("nerf_render_forward_occupancy", *head, *modes, occ_c, occ_f, *grid.lookup_args(), evaluated, ws, ws.numel(),
-                      rgb, depth)
-            if evaluated is not None:
-                self.occupancy_stats.append((evaluated.clone(), (_lib.N_SAMPLES * n, (_lib.N_SAMPLES + _lib.N_IMPORTANCE) * n)))
-        else:
-            ws = self._get_workspace(int(_lib.call("nerf_render_workspace_bytes", n, self.N_importance, fast)), dev)
-            _lib.call("nerf_render_forward", *head, *modes, ws, ws.numel(), rgb, depth)
+        fast = int(bool(self.fast_sampling) and self.N_importance > 0)       # (0 when stochastic: refused)
+        modes_ = (int(self.N_importance), int(bool(self.white_bkgd)), _lib.PRECISIONS[facts.precision], fast, float(self.weights_threshold))
+        return (o, d, n, pk_c, pk_f, t_c, u), modes_, fast, rgb, depth
+
+    def _frame(self, facts, o, d, draws, grid):
+        head, modes_, fast, rgb, depth = self._frame_arguments(facts, o, d)
+        ws = self._get_workspace(int(_lib.call("nerf_render_workspace_bytes", head[2], self.N_importance, fast)), o.device)
+        _lib.call("nerf_render_forward", *head, *modes_, ws, ws.numel(), rgb, depth)
         return rgb, depth
+
+    def _frame_stochastic(self, facts, o, d, draws, grid):
+        head, modes_, _, rgb, depth = self._frame_arguments(facts, o, d)
+        ws = self._get_workspace(int(_lib.call("nerf_render_stochastic_workspace_bytes", head[2], self.N_importance)), o.device)
+        _lib.call("nerf_render_forward_stochastic", *head, *draws, *modes_, ws, ws.numel(), rgb, depth)
+        return rgb, depth
+
+    def _frame_occupancy(self, facts, o, d, draws, grid):
+        head, modes_, fast, rgb, depth = self._frame_arguments(facts, o, d)
+        n, occ = head[2], self.occupancy
+        occ_c, occ_f = occ.bits[""], occ.bits["fine"] if self.N_importance > 0 else None
+        ws = self._get_workspace(int(_lib.call("nerf_render_occupancy_workspace_bytes", n, self.N_importance, fast)), o.device)
+        evaluated = torch.empty(2, dtype=torch.int64, device=o.device) if self.occupancy_stats is not None else None
+        _lib.call("nerf_render_forward_occupancy", *head, *modes_, occ_c, occ_f, *occ.lookup_args(), evaluated, ws, ws.numel(),
+                  rgb, depth)
+        if evaluated is not None:
+            self.occupancy_stats.append((evaluated.clone(), (_lib.N_SAMPLES * n, (_lib.N_SAMPLES + _lib.N_IMPORTANCE) * n)))
+        return rgb, depth
+
+    # the path modes.resolve names -> what runs it
+    _RENDER = {"empty": _empty, "frame": _frame, "frame_stochastic": _frame_stochastic, "frame_occupancy": _frame_occupancy,
+               "step": _step, "step_masked": _step, "step_coarse": _step, "step_culled": _step}
 
     def render_geometry(self, batch):
         """rgb [n,3] and depth [n] as render(batch) returns them (bit-equal), plus the two other geometry outputs of the composited
@@ -235,33 +195,18 @@ class Renderer:
         self.device = dev = rays_o.device
         if dev.type != "cuda":
             raise _lib.NerfLibraryError("Renderer.render_geometry needs rays on a GPU: the render path is HIP-only")
-        # refused before any launch, each with the mode's name
-        if rays_o.requires_grad or rays_d.requires_grad:
-            raise NotImplementedError("render_geometry has no autograd path: rays that require grad are refused (detach them; "
-                                      "render() is the differentiable call)")
-        prec_name = getattr(self.net, "precision", "f32")
-        if not _lib.fp32_accurate(prec_name):
-            raise NotImplementedError(f"render_geometry runs in precision 'f32' or 'f32x', not {prec_name!r}: the gradient chain "
-                                      "has no fp16 form")
-        if self.fast_sampling:
-            raise NotImplementedError("render_geometry is not built with fast_sampling")
-        if self.occupancy is not None:
-            raise NotImplementedError("render_geometry is not built with occupancy culling: set Renderer.occupancy = None")
-        if bool(self.perturb) or self.task == "train":
-            raise NotImplementedError(f"render_geometry is not built for stochastic sampling (task={self.task!r}, "
-                                      f"perturb={bool(self.perturb)})")
-        block = self.geometry_block_rays
-        if isinstance(block, bool) or not isinstance(block, int) or block < 1:
-            raise ValueError(f"Renderer.geometry_block_rays must be an int >= 1 (rays), got {block!r}")
         B, N, _ = rays_o.shape
         n = B * N
+        facts = modes.facts(self, modes.GEOMETRY, rays_o.requires_grad or rays_d.requires_grad, n)
+        path = modes.resolve(facts, self, dev)                              # every refusal comes before any launch
+        block = self.geometry_block_rays
         o = rays_o.detach().reshape(n, 3).to(torch.float32).contiguous()
         d = rays_d.detach().reshape(n, 3).to(torch.float32).contiguous()
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         out = {"rgb": new(n, 3), "depth": new(n), "acc": new(n), "normal": new(n, 3)}
-        if n == 0:
+        if path == "empty":
             return out
-        prec = _lib.PRECISIONS[prec_name]
+        prec = _lib.PRECISIONS[facts.precision]
         t_c, u = self._get_tables(dev)
         fine = self.N_importance > 0
         model = "fine" if fine else ""

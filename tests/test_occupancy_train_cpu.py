@@ -1,5 +1,5 @@
 """CPU checks of training with an occupancy grid: the defaults and refusals of Renderer.train_occupancy
-(before any library call), the refresh schedule with the refresh and the step stubbed, the size checks of nerf_occupancy_age, and the
+(modes.resolve, before any library call), the refresh schedule with the refresh and the step stubbed, the size checks of nerf_occupancy_age, and the
 NumPy restatement tests/occupancy_train_reference.py against its definition.  The kernel and the step are compared on the GPU in
 tests/test_gpu_occupancy_train.py."""
 import numpy as np
@@ -36,15 +36,21 @@ def test_defaults():
 def test_refusals_come_before_any_library_call(monkeypatch):
     """The checks of a training call with a grid, in their order, each one launch-free: the library is not even loaded."""
     import nerf_replication_amd as pkg
+    from nerf_replication_amd import modes
     monkeypatch.setattr(pkg._lib, "load", lambda: pytest.fail("refusals must not reach the library"))
     net = pkg.Network()
     cpu = torch.device("cpu")
     r = pkg.Renderer(net)
     grid = _grid(pkg, net)
 
+    def train_call(dev, rays_grad):
+        """What render() does with a training call before the step: resolve, then the grid's schedule."""
+        path = modes.resolve(modes.facts(r, modes.RENDER, rays_grad, 8), r, dev)
+        return path, r._scheduled_grid()
+
     def refused(exc, rays_grad=False, dev=cpu):
         with pytest.raises(exc):
-            r._train_grid(dev, rays_grad)
+            train_call(dev, rays_grad)
         assert grid.uses == 0                                      # a refused call does not count as a step
 
     for bad in ("grid", 3, object()):
@@ -70,7 +76,7 @@ def test_refusals_come_before_any_library_call(monkeypatch):
         refused(NotImplementedError)
     net.precision = "f32"
     r.train_occupancy = grid
-    assert r._train_grid(cpu, False) is grid and grid.uses == 1    # nothing to refuse, not stale: no refresh, one use
+    assert train_call(cpu, False) == ("step_culled", grid) and grid.uses == 1    # nothing to refuse, not stale: no refresh, one use
 
     # hold is validated by refresh, before the library and before the network is looked at
     for bad_hold in (0, 256, -1, 1.5, "2", None, True):

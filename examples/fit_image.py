@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Fits a 2-D image with the hash-grid encoding: a 2-D HashEncoder (HIP kernels, forward and gradients) feeding a small
-eager-PyTorch MLP, trained with Adam on random pixels of a procedurally generated image (no file input).  Prints the PSNR of the
-whole image before and after, and the time per step.  The MLP is plain torch on purpose: the encoder is the product here.
+"""Fits a 2-D image with the hash-grid encoding: a 2-D HashEncoder (HIP kernels, forward and gradients) feeding a small MLP,
+trained with Adam on random pixels of a procedurally generated image (no file input).  Prints the PSNR of the whole image before and
+after, and the time per step.  The MLP is eager PyTorch by default (a dozen ATen launches per step); --fused runs the same network,
+sigmoid included, through nerf.FusedMLP: one HIP kernel forward, one for the gradient chain.
 
-    python examples/fit_image.py [--size 512] [--steps 1000] [--batch 65536] [--out fit.ppm]
+    python examples/fit_image.py [--size 512] [--steps 1000] [--batch 65536] [--fused] [--width 64] [--hidden 2] [--out fit.ppm]
 """
 import argparse
 import math
@@ -46,6 +47,9 @@ def main():
     ap.add_argument("--levels", type=int, default=16)
     ap.add_argument("--log2-hashmap-size", type=int, default=15)
     ap.add_argument("--lr", type=float, default=1e-2)
+    ap.add_argument("--fused", action="store_true", help="run the MLP through nerf.FusedMLP instead of eager torch")
+    ap.add_argument("--width", type=int, default=64, help="hidden width (--fused: 64 or 128)")
+    ap.add_argument("--hidden", type=int, default=2, help="hidden layers (--fused: 1..8)")
     ap.add_argument("--out", default="", help="write the fitted image as a binary PPM")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "fit_image.py needs a GPU"
@@ -56,13 +60,22 @@ def main():
     coords = (torch.stack([u, v], dim=-1).float() + 0.5) / args.size              # pixel centres in [0, 1]^2
     enc = nerf.HashEncoder(input_dim=2, num_levels=args.levels, level_dim=2, base_resolution=16,
                            log2_hashmap_size=args.log2_hashmap_size, desired_resolution=args.size).to(dev)
-    mlp = nn.Sequential(nn.Linear(enc.out_dim, 64), nn.ReLU(), nn.Linear(64, 64), nn.ReLU(), nn.Linear(64, 3)).to(dev)
+    if args.fused:
+        mlp = nerf.FusedMLP(enc.out_dim, 3, width=args.width, n_hidden=args.hidden, output_activation="sigmoid").to(dev)
+        network = mlp
+    else:
+        dims = [enc.out_dim] + [args.width] * args.hidden
+        layers = [m for i, o in zip(dims[:-1], dims[1:]) for m in (nn.Linear(i, o), nn.ReLU())]
+        mlp = nn.Sequential(*layers, nn.Linear(args.width, 3)).to(dev)
+
+        def network(h):
+            return torch.sigmoid(mlp(h))
     opt = torch.optim.Adam([{"params": enc.parameters()}, {"params": mlp.parameters(), "weight_decay": 1e-6}], lr=args.lr,
                            betas=(0.9, 0.99), eps=1e-15)
 
     def render():
         with torch.no_grad():
-            return torch.sigmoid(mlp(enc(coords, normalize=False)))
+            return network(enc(coords, normalize=False))
 
     print(f"{enc}  table {enc.embeddings.numel() * 4 / 2 ** 20:.1f} MiB, image {args.size}x{args.size}, batch {args.batch}")
     print(f"PSNR before: {psnr(render(), img):.2f} dB")
@@ -72,7 +85,7 @@ def main():
     t0 = time.perf_counter()
     for step in range(args.steps):
         ids = torch.randint(0, flat_xy.shape[0], (args.batch,), device=dev, generator=gen)
-        pred = torch.sigmoid(mlp(enc(flat_xy[ids], normalize=False)))
+        pred = network(enc(flat_xy[ids], normalize=False))
         loss = ((pred - flat_rgb[ids]) ** 2).mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -82,7 +95,7 @@ def main():
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / max(args.steps, 1) * 1e3
     out = render()
-    print(f"PSNR after {args.steps} steps: {psnr(out, img):.2f} dB   ({ms:.2f} ms per step, encoder + eager MLP + Adam)")
+    print(f"PSNR after {args.steps} steps: {psnr(out, img):.2f} dB   ({ms:.2f} ms per step, encoder + {'fused' if args.fused else 'eager'} MLP + Adam)")
     if args.out:
         with open(args.out, "wb") as f:
             f.write(f"P6 {args.size} {args.size} 255\n".encode())

@@ -4,6 +4,8 @@ Public surface mirrors rkin100g/Nerf-Replication (paths relative to the referenc
     Renderer   <- src/models/nerf/renderer/volume_renderer.py  (Renderer(net).render(batch))
     Network    <- src/models/nerf/network.py                    (Network().forward(...), state_dict keys)
     HashEncoder, TriPlane <- src/models/encoding/hashencoder/hashgrid.py  (constructor, `embeddings`, forward(xyz, wbounds, normalize))
+    ImageFitNetwork <- src/models/img_fit/network.py              (state_dict keys, render(uv, batch), forward(batch)); FusedMLP and
+                       fused_mlp are the small fused ReLU MLP it runs on (include/nerf_mi355x_nn.h)
 The arithmetic runs in hand-written HIP kernels (csrc/) reached through the C ABI declared in
 include/nerf_mi355x.h; there is no CPU or eager-PyTorch fallback: without the built library or a
 GPU the product path raises.
@@ -28,12 +30,14 @@ _LAZY = {
     "mesh_components": ".mesh", "filter_components": ".mesh", "vertex_colors": ".mesh", "write_ply_colors": ".mesh",
     "OccupancyGrid": ".occupancy",
     "HashEncoder": ".hashgrid", "TriPlane": ".hashgrid",
+    "fused_mlp": ".fused_mlp", "FusedMLP": ".fused_mlp", "ImageFitNetwork": ".fused_mlp",
 }
 _SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy", "hashgrid", "modes")
 
 __all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model",
            "density_grid", "isosurface", "write_ply", "extract_mesh", "density_gradient", "vertex_normals",
-           "mesh_components", "filter_components", "vertex_colors", "write_ply_colors", "OccupancyGrid", "HashEncoder", "TriPlane"]
+           "mesh_components", "filter_components", "vertex_colors", "write_ply_colors", "OccupancyGrid", "HashEncoder", "TriPlane",
+           "fused_mlp", "FusedMLP", "ImageFitNetwork"]
 
 
 def __getattr__(name):

@@ -1,4 +1,4 @@
-"""ctypes binding of libnerf_mi355x.so (include/nerf_mi355x.h).  Plumbing only: device memory,
+"""ctypes binding of libnerf_mi355x.so (include/nerf_mi355x.h and, for the small-network entries, include/nerf_mi355x_nn.h).  Plumbing only: device memory,
 streams and error translation.  Fails loudly when the library is missing -- no fallback."""
 import ctypes
 import os
@@ -102,10 +102,16 @@ nerf_mesh_filter_emit  status : f32* i32* i64 i64 void* f32* i32* i32* stream
 nerf_hashgrid_forward  status : f32* f32* i64 i32 i32 i32 i32[] f32[] f32* stream
 nerf_hashgrid_backward  status : f32* f32* f32* i64 i32 i32 i32 i32[] f32[] f32* f32* stream
 """
-SIGNATURES = {}       # name -> (return kind, (parameter kinds))
-for _line in _TABLE.strip().splitlines():
-    _head, _, _kinds = _line.partition(":")
-    SIGNATURES[_head.split()[0]] = (_head.split()[1], tuple(_kinds.split()))
+def _parse_table(table):
+    """{name: (return kind, (parameter kinds))} of a binding table, in its order."""
+    signatures = {}
+    for line in table.strip().splitlines():
+        head, _, kinds = line.partition(":")
+        signatures[head.split()[0]] = (head.split()[1], tuple(kinds.split()))
+    return signatures
+
+
+SIGNATURES = _parse_table(_TABLE)
 EXPORTS = tuple(SIGNATURES)
 
 _SCALAR = {"i32": ctypes.c_int32, "i64": ctypes.c_int64, "f32": ctypes.c_float, "f64": ctypes.c_double}
@@ -123,7 +129,24 @@ def _ctype(kind):
 
 
 # the ctypes view of the table, {name: (restype, [argtypes])}: what load() installs (tools/ab_*.py install it on their own builds)
-_PROTOS = {name: (_RETURN[ret], [_ctype(k) for k in kinds]) for name, (ret, kinds) in SIGNATURES.items()}
+def _protos(signatures):
+    return {name: (_RETURN[ret], [_ctype(k) for k in kinds]) for name, (ret, kinds) in signatures.items()}
+
+
+_PROTOS = _protos(SIGNATURES)
+
+# The small-network entries, one line per entry of include/nerf_mi355x_nn.h (the second header of the same library): the same kinds,
+# the same parser.  tests/test_fused_mlp_cpu.py compares this table with that header as tests/test_abi_symbols.py does the core one.
+_TABLE_NN = """
+nerf_nn_abi_version  i32 :
+nerf_fused_mlp_save_floats  i64 : i64 i32 i32
+nerf_fused_mlp_grad_floats  i64 : i64 i32 i32 i32
+nerf_fused_mlp_forward  status : f32* i64 i32 i32 i32 i32 i32 f32*[] f32*[] f32* f32* stream
+nerf_fused_mlp_backward  status : f32* f32* f32* i64 i32 i32 i32 i32 i32 f32*[] f32* f32* f32*[] f32*[] f32* stream
+"""
+NN_SIGNATURES = _parse_table(_TABLE_NN)
+NN_EXPORTS = tuple(NN_SIGNATURES)
+_NN_PROTOS = _protos(NN_SIGNATURES)
 
 _lib = None
 
@@ -151,11 +174,13 @@ def load():
                 f"{LIB_PATH} is missing: build it with `make -C {CSRC}` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the render path")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in list(_PROTOS.items()) + list(_NN_PROTOS.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.nerf_abi_version() != 2:
             raise NerfLibraryError("libnerf_mi355x.so ABI version mismatch")
+        if lib.nerf_nn_abi_version() != 1:
+            raise NerfLibraryError("libnerf_mi355x.so small-network ABI version mismatch (include/nerf_mi355x_nn.h)")
         if lib.nerf_build_flags() != 0:
             raise NerfLibraryError(f"{LIB_PATH} is a timing build (nerf_build_flags() = {lib.nerf_build_flags()}): kernels "
                                    "compiled with NERF_*_HACK_* switches compute wrong results; rebuild with `make -C csrc`")
@@ -174,9 +199,9 @@ class strided:
 def call(name, *args):
     """Call entry `name` of the library with `args` as its header lists them, minus the stream: tensors (None: NULL) for device
     pointers, numbers for scalars, sequences or ctypes arrays for host arrays.  Every argument is checked against the entry's kinds
-    in SIGNATURES before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
+    in SIGNATURES (or NN_SIGNATURES, the small-network entries) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
     is checked (NerfLibraryError with nerf_last_error's text); any other return value comes back as it is."""
-    ret, kinds = SIGNATURES[name]
+    ret, kinds = SIGNATURES[name] if name in SIGNATURES else NN_SIGNATURES[name]
     has_stream = kinds[-1:] == ("stream",)
     if len(args) != len(kinds) - has_stream:
         raise TypeError(f"{name} takes {len(kinds) - has_stream} arguments ({len(args)} given)")

@@ -1793,9 +1793,14 @@ static int32_t wgrad_impl(const float* dz, int64_t ldz, int32_t zc0, int32_t n_o
     a.osplit = OS; a.isplit = IS; \
     return NERF_LAUNCH((nerf_wgrad_f32_kernel<TO, TI>), grid, blk, st, a); \
   } while (0)
-  if (to > 4 && ti > 4) GEN(4, 4, 2, 2);
+  // (an instance covers 32*TO*OS outputs and 32*TI*IS inputs; the rows with ti in 2..4 serve the square and near-square layers
+  // of nerf_fused_mlp_backward, 64 x 64 and 128 x 128, which the lego network does not have)
+  if (to > 4 && ti > 2) GEN(4, 4, 2, 2);
   if (to > 4) GEN(4, 1, 2, 2);
   if (to > 1 && ti > 4) GEN(2, 4, 2, 2);
+  if (to > 2 && ti > 1) GEN(2, 2, 2, 2);
+  if (to > 1 && ti > 2) GEN(1, 2, 2, 2);
+  if (to > 1 && ti > 1) GEN(1, 1, 2, 2);
   if (to > 1) GEN(1, 1, 4, 1);
   if (ti > 4) GEN(1, 2, 1, 4);
   GEN(1, 1, 1, 4);
@@ -2483,3 +2488,5 @@ int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d,
 #include "nerf_mesh_components.hip.inc"
 // ---- multiresolution hash-grid encoding: nerf_hashgrid_forward / nerf_hashgrid_backward
 #include "nerf_hashgrid.hip.inc"
+// ---- small fused ReLU MLP (include/nerf_mi355x_nn.h): nerf_fused_mlp_forward / nerf_fused_mlp_backward
+#include "nerf_fused_mlp.hip.inc"

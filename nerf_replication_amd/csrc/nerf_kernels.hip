@@ -6,9 +6,11 @@
 #include <string.h>
 #include <math.h>
 #include <mutex>
+#include <utility>
 
 #include "../../include/nerf_mi355x.h"
 #include "nerf_layout.h"
+#include "nerf_wgrad_table.h"
 #include "nerf_scan.hip.inc"
 #include "nerf_mlp_f32.hip.inc"
 #include "nerf_mlp_f16.hip.inc"
@@ -1734,6 +1736,43 @@ int32_t nerf_image_metrics(const float* pred, const float* gt, int64_t n_values,
                      sums2);
 }
 
+// The 256 x 256 layers on the operand ring, 1..8 of them in one launch of `slices` workgroups per job.  The caller has checked the
+// ring's host contract (nerf_wgrad_f32.hip.inc): aligned 256 x 256 jobs of n_points % 16 == 0 points with ld * 8 < 2^31
+static int32_t wgrad256_ring(WgradBatch& wb, long long slices, const int* live, const int* n_live, hipStream_t st) {
+  for (int i = 0; i < wb.n_jobs; ++i) {
+    WgradArgs& j = wb.job[i];
+    j.n_out = 256; j.n_in = 256; j.osplit = 2; j.isplit = 2; j.live_tiles = live; j.n_live = n_live;
+  }
+  const dim3 grid((unsigned)(slices * wb.n_jobs)), blk(256);
+  return live ? NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<true>, grid, blk, st, wb)
+              : NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<false>, grid, blk, st, wb);
+}
+
+// Row R of nerf::kWgRows in the form wg_choose picked: the kernels are instantiated from the table's own numbers.  With a list
+// every CU's workgroup reads *n_live itself; without one the ring form takes one workgroup per group of 16 k-steps, at most one
+// per CU; the plain forms take `grid` (one workgroup per CU too: more resident waves measured no faster)
+extern "C++" {
+template <int R>
+static int32_t wgrad_launch_row(nerf::WgForm form, WgradArgs& a, dim3 grid, hipStream_t st) {
+  constexpr nerf::WgRow r = nerf::kWgRows[R];
+  const dim3 blk(256);
+  a.osplit = r.osplit; a.isplit = r.isplit;
+  if constexpr (r.kind == nerf::kWgVecRing) {
+    const long long groups = a.n_points / 32;
+    if (form == nerf::kWgList) return NERF_LAUNCH((nerf_wgrad_vec_f32_asm_kernel<r.wo, r.wi, 16, true>), dim3((unsigned)num_cus()), blk, st, a);
+    if (form == nerf::kWgRing) return NERF_LAUNCH((nerf_wgrad_vec_f32_asm_kernel<r.wo, r.wi, 16>), dim3((unsigned)(groups < num_cus() ? groups : num_cus())), blk, st, a);
+  }
+  if constexpr (r.kind == nerf::kWgGeneric) return NERF_LAUNCH((nerf_wgrad_f32_kernel<r.wo, r.wi>), grid, blk, st, a);
+  else return NERF_LAUNCH((nerf_wgrad_vec_f32_kernel<r.wo, r.wi>), grid, blk, st, a);
+}
+template <int... R>
+static int32_t wgrad_launch(nerf::WgChoice c, WgradArgs& a, dim3 grid, hipStream_t st, std::integer_sequence<int, R...>) {
+  int32_t rc = NERF_ERR_INVALID_ARG;
+  (void)((c.row == R && ((rc = wgrad_launch_row<R>(c.form, a, grid, st)), true)) || ...);
+  return rc;
+}
+}  // extern "C++"
+
 // live / n_live: the live-tile list of a backward pass (device pointers) or nullptr for the whole point range; with a list,
 // only the asm-ring kernels of the small layers apply (the caller checks list_mode_ok) and each workgroup reads *n_live itself
 static int32_t wgrad_impl(const float* dz, int64_t ldz, int32_t zc0, int32_t n_out, const float* hin, int64_t ldh,
@@ -1745,66 +1784,29 @@ static int32_t wgrad_impl(const float* dz, int64_t ldz, int32_t zc0, int32_t n_o
   WgradArgs a;
   a.dz = dz; a.ldz = ldz; a.zc0 = zc0; a.n_out = n_out; a.hin = hin; a.ldh = ldh; a.hc0 = hc0; a.n_in = n_in;
   a.dw = dw; a.ldw = ldw; a.wc0 = wc0; a.db = db; a.n_points = n_points; a.live_tiles = live; a.n_live = n_live;
-  const int to = (n_out + 31) / 32, ti = (n_in + 31) / 32;
   const long long pairs = (n_points + 1) / 2;
   long long blocks = (pairs + 255) / 256;            // >= 256 point pairs per workgroup
   if (blocks > num_cus()) blocks = num_cus();
   if (blocks < 1) blocks = 1;
-  // (the small-layer vector-load kernels too: one workgroup per CU, more resident waves measured no faster)
-  const dim3 grid((unsigned)blocks), blk(256);
   hipStream_t st = (hipStream_t)stream;
-  const bool aligned = ldz % 4 == 0 && ldh % 4 == 0 && zc0 % 4 == 0 && hc0 % 4 == 0 &&
-                       (uintptr_t)dz % 16 == 0 && (uintptr_t)hin % 16 == 0;
-  if (n_out == 256 && n_in == 256 && aligned && n_points % 16 == 0 && n_points / 16 >= blocks &&
-      ldz * 8 < (1ll << 31) && ldh * 8 < (1ll << 31)) {
-    a.osplit = 2; a.isplit = 2;        // whole groups of 8 k-steps per workgroup: the clamp-free asm-load form
-    WgradBatch wb;
-    wb.job[0] = a; wb.n_jobs = 1;
-    return live ? NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<true>, grid, blk, st, wb)
-                : NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<false>, grid, blk, st, wb);
-  }
+  nerf::WgFacts f;
+  f.aligned = ldz % 4 == 0 && ldh % 4 == 0 && zc0 % 4 == 0 && hc0 % 4 == 0 && (uintptr_t)dz % 16 == 0 && (uintptr_t)hin % 16 == 0;
+  f.hin8 = ldh % 2 == 0 && hc0 % 2 == 0 && (uintptr_t)hin % 8 == 0;
   // the asm-ring form of the small-layer kernels: the point range splits into whole groups of 16 k-steps (32 points) per
   // workgroup (every training shape does: P is a multiple of 64).  List mode needs it (whole 32-point tiles)
-  const bool ring = n_points % 32 == 0 && ldz < (1ll << 28) && ldh < (1ll << 28);
-  const char* no_list_kernel = "nerf_wgrad: live-tile list on a shape without an asm-ring kernel";
-  if (live && !ring) return fail(NERF_ERR_INVALID_ARG, "%s", no_list_kernel);
-  if (!live && n_out == 256 && n_in == 256 && aligned) {
-    a.osplit = 2; a.isplit = 2;
-    return NERF_LAUNCH(nerf_wgrad256_f32_kernel, grid, blk, st, a);
+  f.ring = n_points % 32 == 0 && ldz < (1ll << 28) && ldh < (1ll << 28);
+  f.live = live != nullptr;
+  // one 256 x 256 layer on the batched ring launch: whole groups of 8 k-steps and at least one per workgroup of the plain grid
+  // (mlp_backward_impl asks for num_cus() / 8 groups instead, whatever the grid: the two tests were written apart and stay apart)
+  if (n_out == 256 && n_in == 256 && f.aligned && n_points % 16 == 0 && n_points / 16 >= blocks &&
+      ldz * 8 < (1ll << 31) && ldh * 8 < (1ll << 31)) {
+    WgradBatch wb;
+    wb.job[0] = a; wb.n_jobs = 1;
+    return wgrad256_ring(wb, blocks, live, n_live, st);
   }
-  // small layers on the vector-load kernel: (floats per lane, wave split) chosen so that 32*AV*osplit covers n_out
-  // and 32*BV*isplit covers n_in; operands must be aligned to their vector width.  With a list every CU's workgroup reads
-  // *n_live itself; without one the ring form takes one workgroup per group of 16 k-steps, at most one per CU
-  const long long groups = n_points / 32;
-#define VEC(AV, BV, OS, IS) do { \
-    a.osplit = OS; a.isplit = IS; \
-    if (live) return NERF_LAUNCH((nerf_wgrad_vec_f32_asm_kernel<AV, BV, 16, true>), dim3((unsigned)num_cus()), blk, st, a); \
-    if (ring) return NERF_LAUNCH((nerf_wgrad_vec_f32_asm_kernel<AV, BV, 16>), dim3((unsigned)(groups < num_cus() ? groups : num_cus())), blk, st, a); \
-    return NERF_LAUNCH((nerf_wgrad_vec_f32_kernel<AV, BV>), grid, blk, st, a); \
-  } while (0)
-  if (n_out == 256 && n_in <= 64 && aligned) VEC(4, 1, 2, 2);                  // PE -> 256 (layers 0 and 5)
-  if (n_out == 128 && n_in == 256 && aligned) VEC(4, 2, 1, 4);                 // views_linears.0, feature part
-  if (n_out == 128 && n_in <= 32) VEC(1, 1, 4, 1);                             // views_linears.0, direction part
-  if (n_out <= 32 && n_in == 256 && ldh % 2 == 0 && hc0 % 2 == 0 && (uintptr_t)hin % 8 == 0) VEC(1, 2, 1, 4);     // alpha_linear
-  if (n_out <= 32 && n_in <= 128) VEC(1, 1, 1, 4);                             // rgb_linear
-#undef VEC
-  if (live) return fail(NERF_ERR_INVALID_ARG, "%s", no_list_kernel);
-#define GEN(TO, TI, OS, IS) do { \
-    a.osplit = OS; a.isplit = IS; \
-    return NERF_LAUNCH((nerf_wgrad_f32_kernel<TO, TI>), grid, blk, st, a); \
-  } while (0)
-  // (an instance covers 32*TO*OS outputs and 32*TI*IS inputs; the rows with ti in 2..4 serve the square and near-square layers
-  // of nerf_fused_mlp_backward, 64 x 64 and 128 x 128, which the lego network does not have)
-  if (to > 4 && ti > 2) GEN(4, 4, 2, 2);
-  if (to > 4) GEN(4, 1, 2, 2);
-  if (to > 1 && ti > 4) GEN(2, 4, 2, 2);
-  if (to > 2 && ti > 1) GEN(2, 2, 2, 2);
-  if (to > 1 && ti > 2) GEN(1, 2, 2, 2);
-  if (to > 1 && ti > 1) GEN(1, 1, 2, 2);
-  if (to > 1) GEN(1, 1, 4, 1);
-  if (ti > 4) GEN(1, 2, 1, 4);
-  GEN(1, 1, 1, 4);
-#undef GEN
+  const nerf::WgChoice c = nerf::wg_choose(n_out, n_in, f);
+  if (c.form == nerf::kWgNoListKernel) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_wgrad: live-tile list on a shape without an asm-ring kernel");
+  return wgrad_launch(c, a, dim3((unsigned)blocks), st, std::make_integer_sequence<int, nerf::kWgNumRows>());
 }
 
 int32_t nerf_wgrad(const float* dz, int64_t ldz, int32_t zc0, int32_t n_out, const float* hin, int64_t ldh,
@@ -2058,20 +2060,18 @@ static int32_t mlp_backward_impl(const BwdArgs& a_in, bool pts_mode, float* cons
     if (slices < 1) slices = 1;
     return NERF_LAUNCH(nerf_wgrad256_bf16x3_kernel, dim3((unsigned)(slices * n_jobs)), dim3(256), st, w);
   } else if (P % 16 == 0 && P / 16 >= num_cus() / 8) {
-    // fp32 MFMA, in one launch of the asm-load kernel
+    // fp32 MFMA, in one launch of the ring kernel (a test on the point count alone, where wgrad_impl's is on its own grid: the
+    // two were written apart and stay apart; below it the layers go one by one, through wgrad_impl's test)
     WgradBatch wb;
     wb.n_jobs = n_jobs;
     for (int i = 0; i < n_jobs; ++i) {
       WgradArgs& j = wb.job[i];
-      j.dz = job[i].dz; j.ldz = 256; j.zc0 = 0; j.n_out = 256; j.hin = job[i].hin; j.ldh = 256; j.hc0 = 0; j.n_in = 256;
-      j.dw = job[i].dw; j.ldw = job[i].ldw; j.wc0 = job[i].wc0; j.db = job[i].db; j.n_points = P; j.osplit = 2; j.isplit = 2;
-      j.live_tiles = live; j.n_live = n_live;
+      j.dz = job[i].dz; j.ldz = 256; j.zc0 = 0; j.hin = job[i].hin; j.ldh = 256; j.hc0 = 0;
+      j.dw = job[i].dw; j.ldw = job[i].ldw; j.wc0 = job[i].wc0; j.db = job[i].db; j.n_points = P;
     }
     long long slices = num_cus() / n_jobs;
     if (slices < 1) slices = 1;                       // a device with fewer CUs than jobs still gets a non-empty grid
-    const dim3 grid((unsigned)(slices * n_jobs));
-    return live ? NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<true>, grid, dim3(256), st, wb)
-                : NERF_LAUNCH(nerf_wgrad256_f32_asm_kernel<false>, grid, dim3(256), st, wb);
+    return wgrad256_ring(wb, slices, live, n_live, st);
   } else {
     for (int i = 0; i < n_jobs; ++i) WG(job[i].dz, 256, 0, 256, job[i].hin, 256, 0, 256, job[i].dw, job[i].ldw, job[i].wc0, job[i].db);
   }

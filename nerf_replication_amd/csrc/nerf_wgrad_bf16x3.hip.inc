@@ -8,7 +8,7 @@
 // scale cannot be factored out, and gradients (1e-6 .. 1e-8 with a mean-reduced loss) are far outside the
 // fp16 range.  bf16 has the fp32 exponent, so no scaling and no statistics pass are needed.  Per 16 points
 // a wave issues 6 x 16 v_mfma_f32_32x32x16_bf16 (3072 cycles) against 16 x 8 fp32 MFMAs (8192 cycles) of
-// nerf_wgrad256_f32_kernel.  All 256 x 256 layers of one sub-network are one launch ("jobs": blockIdx % n_jobs),
+// nerf_wgrad256_f32_asm_kernel.  All 256 x 256 layers of one sub-network are one launch ("jobs": blockIdx % n_jobs),
 // so a workgroup integrates 8x more points before its 65536 atomic adds and concurrently running workgroups
 // add to different matrices.
 struct WgradXJob {

@@ -75,10 +75,19 @@ def test_forward_save_matches_reference_activations(amd, net, golden, precision)
     net.precision = "f32"
 
 
+# Every row of csrc/nerf_wgrad_table.h at its smallest shapes: the five small-layer rows (256 x 64 is what `aligned` lets reach
+# the PE -> 256 row), then one shape per generic row that the larger cases below do not reach.  Point counts: a half-empty pair,
+# one short of a ring group (32 points), exactly one group, the fallback just past it, two groups
+_WGRAD_ROW_SHAPES = [(256, 64), (128, 256), (128, 27), (1, 256), (3, 128),
+                     (33, 27), (33, 33), (64, 64), (64, 128), (65, 97), (128, 128)]
+_WGRAD_ROW_CASES = [(n_out, n_in, P) for n_out, n_in in _WGRAD_ROW_SHAPES for P in (1, 31, 32, 33, 64)]
+
+
 @pytest.mark.parametrize("aligned", [False, True])
 @pytest.mark.parametrize("n_out,n_in,P", [(256, 256, 4099), (256, 63, 777), (128, 256, 1000), (128, 27, 333),
                                            (3, 128, 2050), (1, 256, 513), (256, 256, 1), (256, 256, 200001),
-                                           (256, 256, 4096), (256, 256, 200000), (256, 256, 48)])   # multiples of 16: asm-load kernel
+                                           (256, 256, 4096), (256, 256, 200000), (256, 256, 48),     # multiples of 16: asm-load kernel
+                                           (256, 256, 16), (256, 256, 17)] + _WGRAD_ROW_CASES)      # one ring group; the <4,4> fallback
 def test_wgrad_gemm(amd, n_out, n_in, P, aligned):
     """grad_weight = grad_out^T @ input and grad_bias = grad_out.sum(0), written into a column block of an
     nn.Linear-shaped [out, in_total] gradient (the skip / view concatenations are column blocks)."""

@@ -2274,13 +2274,15 @@ int32_t nerf_image_ssim(const float* pred, const float* gt, int32_t H, int32_t W
 static constexpr int64_t kRenderBlockRays = 1 << 20;
 static int64_t render_block_rays() {
   const char* env = getenv("NERF_RENDER_BLOCK_RAYS");
-  if (env) { const long long v = atoll(env); if (v >= 64) return (int64_t)v; }
+  // capped at the rays whose 192 point ids fit in int32: a larger block would switch the fp16 far-plane guard off (render_frame)
+  constexpr long long kMax = 0x7fffffff / (NERF_N_SAMPLES + NERF_N_IMPORTANCE);
+  if (env) { const long long v = atoll(env); if (v >= 64) return (int64_t)(v < kMax ? v : kMax); }
   return kRenderBlockRays;
 }
 
 // The workspace of one block of `n_rays` rays, carved in this order, every piece 256-byte aligned.  index / count: with fast_sampling
-// the compacted ids of the valid merged samples and their number, otherwise the last-sample ids of the fp16 far-plane guard and
-// their number.  t_jit: the jittered coarse depths [n,64] of a stochastic render.  occupancy (nerf_render_forward_occupancy): the
+// the compacted ids of the valid merged samples and their number (and, once that list is consumed, the guard's), otherwise the
+// last-sample ids of the fp16 far-plane guard and their number.  t_jit: the jittered coarse depths [n,64] of a stochastic render.  occupancy (nerf_render_forward_occupancy): the
 // fine pass may be listed without fast_sampling too, and the coarse pass gets a mask [n,64] and an id list of its own behind.
 struct RenderWorkspace {
   float* raw_c; float* t_sorted = nullptr; float* raw_f = nullptr; uint8_t* valid = nullptr; int* index; int* count; float* t_jit = nullptr;
@@ -2393,7 +2395,15 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
       rc = list_pass(w.valid_c, nb * NERF_N_SAMPLES, w.index_c, w.raw_c);
       if (rc) return rc;
     }
-    rc = forward_rays(entry, o, d, tc, tcs, nb, NERF_N_SAMPLES, packed_coarse, w.raw_c, false, nullptr, n_importance != 0, false, precision, stream,
+    // fp16 with fast_sampling: the coarse sigma also DECIDES -- the ESS / ERT mask compares the coarse weights with thresholds, and a
+    // weight that crosses one keeps or drops all the fine samples in front of a surface.  With the fp16 coarse sigma the masked render
+    // stood at 41-47 dB against the masked f32 render where the plain one stands at 54-58, single rays 1.1 off in depth; so the
+    // density pass of that combination runs on the split-fp16 stream behind the packed model (fp32-accurate, as the guard below):
+    // 54-88 dB, no ray above 0.27.  It costs the masked fp16 frame 91.5 -> 151.6 ms at 800x800 (LAB_NOTEBOOK).
+    const bool fp16 = precision == NERF_PREC_F16 || precision == NERF_PREC_F16S;
+    const bool exact_coarse = fp16 && fast_sampling && n_importance;
+    rc = forward_rays(entry, o, d, tc, tcs, nb, NERF_N_SAMPLES, exact_coarse ? (const char*)packed_coarse + nerf::kF16PackedBytes : packed_coarse,
+                      w.raw_c, false, nullptr, n_importance != 0, false, exact_coarse ? NERF_PREC_F32X : precision, stream,
                       cull_c ? w.index_c : nullptr, cull_c ? w.count : nullptr);
     if (rc) return rc;
     rc = tally(0, cull_c, nb * NERF_N_SAMPLES);
@@ -2403,7 +2413,7 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
     // single rays off by 0.64 in rgb and 6.0 in depth, which alone set the fp16 PSNR).  Every other sample's alpha moves by
     // |d sigma| * delta ~ 1e-4.  So the fp16 precisions re-evaluate exactly that sample of every ray (0.5 % of the points) with the
     // split-fp16 stream that rides behind their packed model: fp32-accurate sigma and colour where it matters, ~1.5 % of the frame.
-    const bool guard = (precision == NERF_PREC_F16 || precision == NERF_PREC_F16S) && nb <= (int64_t)0x7fffffff / S;
+    const bool guard = fp16 && nb <= (int64_t)0x7fffffff / S;
     auto far_plane_guard = [&](const float* tvals, int64_t stride, int32_t S_, const void* packed_f16, float* raw) -> int {
       if (const int r2 = NERF_LAUNCH(nerf_last_sample_index_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), st, w.index, w.count,
                                      (long long)nb, S_)) return r2;
@@ -2447,6 +2457,15 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
     }
     rc = tally(1, fast_sampling || cull_f, nb * S);
     if (rc) return rc;
+    // the guard of the masked fine pass.  Under fast_sampling alone the last merged sample of every ray is its coarse far sample,
+    // and coarse samples are always valid: it is in the list, the fp16 network has just written it, and the exposure is the plain
+    // branch's.  The list has been consumed (the forward and the tally are enqueued), so w.index / w.count are free for the guard's
+    // ids.  With a fine occupancy field a last sample may be unlisted and must keep raw = 0: that combination stays as it is (the
+    // package refuses fp16 with occupancy, modes.py).
+    if (guard && fast_sampling && !cull_f) {
+      rc = far_plane_guard(w.t_sorted, S, (int32_t)S, packed_fine, w.raw_f);
+      if (rc) return rc;
+    }
     rc = nerf_composite(w.raw_f, w.t_sorted, S, nb, (int32_t)S, white_bkgd, rgb_b, depth_b, nullptr, stream);
     if (rc) return rc;
   }

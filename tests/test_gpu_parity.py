@@ -1009,3 +1009,49 @@ def test_f16_and_f32x_psnr_on_every_family(amd, oracle, golden, family_sd, famil
     assert out["f32x/worst_psnr_db"] >= {"base": 95.0, "sharp": 95.0, "white": 55.0, "trained": 105.0}[family], out
     for rays in ("seed", "pin"):
         assert out[f"f32x/{rays}"]["rays_over_tolerance"] <= max(1, MAX_OVER_FRAC[family] * 512), out
+
+
+@pytest.mark.parametrize("family", ["base", "sharp", "white", "trained"])
+def test_f16_far_plane_guard_under_fast_sampling(amd, oracle, golden, family_sd, family):
+    """The masked (fast_sampling) fine pass evaluates the last sample of every ray -- its coarse far sample, always valid -- with the
+    fp16 network like the plain pass, so it needs the plain pass's far-plane guard: without it an fp16 sign flip of a sigma near zero
+    at delta = 1e10 turns a background ray into a far-plane hit (depth off by up to 6).  Both fp16 precisions against the masked f32
+    render of the HIP path (itself pinned to the reference by test_render_masked_golden), both ray sets, both thresholds: no ray's
+    depth moves by more than 1.0, and PSNR >= 40 dB (the floor test_render_masked_golden uses for this combination).
+
+    Two things make it hold (render_frame).  The guard after the listed fine forward: without it the seeded rays of "base" and
+    "sharp" had depth max 6.0 / rgb max 0.64-0.66 / 33-34 dB in all eight cases; with it alone 0.27-0.65 / 0.04-0.12 / 43.8-51.5 dB.
+    And the coarse density pass of this combination on the split-fp16 stream: with the fp16 coarse sigma one pinhole ray of "sharp"
+    per threshold stayed at 1.03 (thr 0.25) and 1.10 / 1.08 (thr 0.02), 42.4-43.5 dB, guarded or not -- a coarse weight crossing the
+    ESS threshold between the two arithmetics keeps or drops all the fine samples in front of a hard surface (a CPU replay with
+    tests/f16_reference.emulate as the network gives the same ray and figure, 1.027, and 0.07 with identical samples and mask).
+    Measured now (profiles/f16_parity.json): depth max 0.04 / 0.08 / 0.27 / 0.006, PSNR >= 53.9 / 56.5 / 57.2 / 86.5 dB
+    (base / sharp / white / trained)."""
+    import f16_reference
+    g = golden(f"render_family_{family}.npz")
+    sd = family_sd(family)
+    nets = {}
+    for prec in ("f32", "f16", "f16m32"):
+        nets[prec] = amd.Network()
+        nets[prec].load_state_dict(sd, strict=True)
+        nets[prec] = nets[prec].cuda().eval()
+        nets[prec].precision = prec
+    out = {}
+    for rays in ("seed", "pin"):
+        batch = {"rays_o": g[f"{rays}_rays_o"][None].cuda(), "rays_d": g[f"{rays}_rays_d"][None].cuda()}
+        for thr in (0.25, 0.02):
+            img = {}
+            for prec, net in nets.items():
+                r = amd.Renderer(net)
+                r.fast_sampling, r.weights_threshold = True, thr
+                with torch.no_grad():
+                    rgb, dep = r.render(batch)
+                img[prec] = (rgb.cpu(), dep.cpu())
+            for prec in ("f16", "f16m32"):
+                st, _ = image_stats(oracle, img[prec][0], img[prec][1], img["f32"][0], img["f32"][1])
+                out[f"{prec}/{rays}/thr{thr}"] = {k: st[k] for k in ("psnr_db", "rgb_max", "depth_max")}
+    f16_reference.parity_record("fast_sampling_guard", family, out)
+    print(family, out)
+    for key, st in out.items():
+        assert st["depth_max"] <= 1.0, (key, out)
+        assert st["psnr_db"] >= 40.0, (key, out)

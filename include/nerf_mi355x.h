@@ -14,19 +14,10 @@
  * on success or a negative nerf_status, never an exception; nerf_last_error() gives the message of
  * the calling thread's last failure.  n_rays == 0 is a successful no-op everywhere.
  *
- * Library-owned memory: an fp32 forward launch that evaluates colours (everything but the density-only
- * entries) enqueues one extra small kernel in front of the MLP kernel -- it folds feature_linear into
- * the views layer for the weights of that launch -- and uses about 150 KB of device memory that the
- * library owns: one buffer per (device, stream), allocated on the stream's first such launch (the
- * only call that may allocate and wait; never during a capture: make one eager call on a stream
- * before capturing on it), kept until the process ends, at most 64 per process.  Stream order
- * protects the buffer, so: (1) a graph captured from these calls holds its capture stream's buffer --
- * replay it where its replays are ordered with that stream's other fp32 launches and with each
- * other (two graphs captured on one stream must not replay concurrently); (2) host threads may share
- * a stream (the fold and the MLP kernel are enqueued under one lock), but a handle that names a
- * different stream in every thread (hipStreamPerThread) is not supported: pass real stream handles;
- * (3) that first, allocating call must not run while another thread captures in global mode
- * (hipMalloc would invalidate that capture).
+ * The library allocates no device memory and keeps no state between calls beyond the thread-local
+ * error text (and the device's compute-unit count, read once).  The fp32 kernels evaluate the colour branch on
+ * feature_linear folded into the views layer; that fold is part of the packed fp32 model
+ * (nerf_pack_model writes it behind the weight stream) and is as fresh as the pack.
  */
 #ifndef NERF_MI355X_H
 #define NERF_MI355X_H
@@ -37,7 +28,11 @@
 extern "C" {
 #endif
 
-/* Version 2 (round 3).  Contracts that changed since version 1 (entry names and signatures did not):
+/* Version 3.  Contracts that changed since version 2 (entry names and signatures did not):
+ *   - the packed fp32 model carries the fold of feature_linear into the views layer behind its weight stream:
+ *     nerf_packed_model_bytes(NERF_PREC_F32) grew, a version-2 packed model lacks the fold and a version-2-sized buffer is too
+ *     small for nerf_pack_model; `packed` must be 256-byte aligned.
+ * Version 2 (round 3).  Contracts that changed since version 1:
  *   - the TrainSave / TrainGrad buffers (nerf_train_save_floats / nerf_train_grad_floats) hold pad32(P) rows per region, with the
  *     ReLU sign-bit blocks, the live-tile flags / list / count and a "rows skipped" stamp appended;
  *     nerf_mlp_backward (both precisions) takes its ReLU masks from those sign bits (written by the SAVE forwards only);
@@ -49,7 +44,7 @@ extern "C" {
  *   - nerf_mlp_forward_rays_save_for_compositing may omit the rows of density-free tiles; it stamps the buffer, and a backward pass
  *     that runs without the live-tile list on such a buffer poisons grads[alpha_linear.bias] with NaN instead of reading them;
  *   - nerf_composite_backward refuses more than 192 samples per ray. */
-#define NERF_ABI_VERSION 2
+#define NERF_ABI_VERSION 3
 
 enum nerf_status {
   NERF_OK = 0,
@@ -82,7 +77,8 @@ enum nerf_build_flag { NERF_BUILD_TIMING = 1, NERF_BUILD_WRONG_NUMERICS = 2 };
 int32_t nerf_build_flags(void);
 const char* nerf_last_error(void);
 
-/* Size in bytes of one packed sub-model (coarse or fine) for a precision; -1 if unknown. */
+/* Size in bytes of one packed sub-model (coarse or fine) for a precision; -1 if unknown.  A packed model is a caller-owned
+ * buffer of this size, 256-byte aligned (a torch allocation is). */
 int64_t nerf_packed_model_bytes(int32_t precision);
 
 /* Permute the 24 parameter tensors of one NeRF sub-model into the kernel's weight stream

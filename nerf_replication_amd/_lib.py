@@ -177,7 +177,7 @@ def load():
         for name, (res, args) in list(_PROTOS.items()) + list(_NN_PROTOS.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
-        if lib.nerf_abi_version() != 2:
+        if lib.nerf_abi_version() != 3:
             raise NerfLibraryError("libnerf_mi355x.so ABI version mismatch")
         if lib.nerf_nn_abi_version() != 1:
             raise NerfLibraryError("libnerf_mi355x.so small-network ABI version mismatch (include/nerf_mi355x_nn.h)")

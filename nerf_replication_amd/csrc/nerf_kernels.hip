@@ -5,7 +5,6 @@
 #include <stdio.h>
 #include <string.h>
 #include <math.h>
-#include <mutex>
 #include <utility>
 
 #include "../../include/nerf_mi355x.h"
@@ -101,7 +100,7 @@ __device__ __forceinline__ float pack_head_bias_value(const PackArgs& a, int rel
 __global__ void nerf_pack_kernel(PackArgs a) {
   using namespace nerf;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= kPackedFloats) return;
+  if (i >= kUnfoldedFloats) return;
   constexpr long long WS = wsize(128, 8);
   float v;
   if (i < kOffL1) v = pack_weight_elem(a, i - kOffL0, 8, 0, 0);
@@ -120,19 +119,30 @@ __global__ void nerf_pack_kernel(PackArgs a) {
 }
 
 // ------------------------------------------------------------------------------------ fold (nerf_layout.h kFold*)
-// feature_linear folded into the views layer, from the PACKED fp32 stream (so it sees exactly the weights the MLP kernel of the
-// same launch sees): Wvf = Wv[:, :256] . Wf and bvf = Wv[:, :256] . bf + bv, every element accumulated in float64 (products of
-// two floats are exact there) in one fixed order and rounded once to fp32.  Blocks of 256 threads = 64 outputs x 4 quarters of
-// the 256-term sum (partial sums meet in LDS, combined as (0 + 1) + (2 + 3)):
+// feature_linear folded into the views layer, from the PACKED fp32 stream, behind which nerf_pack_model writes the result (the
+// fold is as fresh as the pack): Wvf = Wv[:, :256] . Wf and bvf = Wv[:, :256] . bf + bv, every element accumulated in float64
+// (products of two floats are exact there) in one fixed order and rounded once to fp32.  Blocks of 256 threads = 64 outputs x 4
+// quarters of the 256-term sum (partial sums meet in LDS, combined as (0 + 1) + (2 + 3)):
 //   blocks 0..127    one 1-KiB block (g, j) of Wvf each: thread (lane, part) -> float4 of lane
 //   blocks 128, 129  64 values of bvf each
 //   blocks 130..133  copy of the views layer's direction-part blocks
+//   blocks 134..136  zeros: the padding behind bvf with the ring slack, and the alignment gap in front of the region
 // Element m of the inner dimension is feature act_feat(t, r, h) with  t = m >> 5, h = (m >> 2) & 1, r = (m & 3) + 4 ((m & 31) >> 3).
-constexpr int kFoldBlocks = 128 + 2 + 4;
+constexpr int kFoldBlocks = 128 + 2 + 4 + 3;
+// `fold` = pk + kOffFold: what is read through pk ends at kUnfoldedFloats, what is written through fold starts there
 __global__ __launch_bounds__(256) void nerf_fold_f32_kernel(const float* __restrict__ pk, float* __restrict__ fold) {
   using namespace nerf;
   __shared__ double part_sum[4][64][4];
   const int lane = threadIdx.x & 63, part = threadIdx.x >> 6, b = blockIdx.x;
+  if (b >= 134) {                                   // zeros, as float4: [bvf + 128, end of the region), then [kUnfoldedFloats, kOffFold)
+    constexpr int kTail4 = (int)(kFoldFloats - kFoldOffBias - 128) / 4, kGap4 = (int)(kOffFold - kUnfoldedFloats) / 4;
+    static_assert(kUnfoldedFloats % 4 == 0 && kOffFold % 4 == 0 && kFoldFloats % 4 == 0 && kTail4 + kGap4 <= 3 * 256, "zero blocks");
+    const int i = (b - 134) * 256 + threadIdx.x;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    if (i < kTail4) reinterpret_cast<f32x4*>(fold + kFoldOffBias + 128)[i] = zero;
+    else if (i < kTail4 + kGap4) reinterpret_cast<f32x4*>(fold - 4 * kGap4)[i - kTail4] = zero;
+    return;
+  }
   if (b >= 130) {                                   // direction part: 16 blocks of 1 KiB, unchanged
     const int i = (b - 130) * 256 + threadIdx.x;    // float4 index, < 1024
     reinterpret_cast<f32x4*>(fold + kFoldOffDir)[i] = reinterpret_cast<const f32x4*>(pk + kOffViewsDir)[i];
@@ -1474,45 +1484,6 @@ static unsigned persistent_blocks(long long n_points, int wg_pts) {
   return (unsigned)(n_tiles < num_cus() ? n_tiles : num_cus());
 }
 
-// Fold buffers (nerf_layout.h kFold*, 156 672 bytes each): library-owned device memory, one per (device, stream) that has ever
-// made an fp32 forward launch with a colour branch.  A buffer is allocated on that stream's first such launch and kept until the
-// process ends (the runtime releases it; nothing is freed from a static destructor, where the runtime may already be gone).
-// In steady state a launch takes the lock, finds its buffer and enqueues: no allocation, no free, no host wait.  Stream order
-// alone protects a buffer: the fold kernel of launch n + 1 is enqueued behind the MLP kernel of launch n on the same stream,
-// and two streams never share one.  Nothing is cached across launches, so an in-place weight update or a packed buffer
-// re-used at the same address cannot meet a stale fold.  The lock is held across the fold launch AND the MLP launch, so two host
-// threads that launch on one stream cannot interleave as fold A, fold B, MLP A, MLP B.  (A handle that names a different stream
-// per thread -- hipStreamPerThread -- maps those streams onto one buffer: not supported, include/nerf_mi355x.h.)  Bound: kFoldPoolSlots buffers (10 MB) per process; a launch on a
-// further stream fails with NERF_ERR_UNSUPPORTED.  While a stream is capturing nothing is allocated: a capture on a stream
-// without a buffer fails, so a caller makes one eager call on that stream first.
-constexpr int kFoldPoolSlots = 64;
-struct FoldSlot { int device; hipStream_t stream; float* buf; };
-static FoldSlot g_fold_pool[kFoldPoolSlots];
-static int g_fold_pool_used = 0;
-static std::mutex g_fold_pool_lock;
-static int fold_buffer(hipStream_t st, const char* entry, float** out) {      // (the caller holds g_fold_pool_lock)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return fail(NERF_ERR_HIP, "%s: hipGetDevice failed", entry);
-  for (int i = 0; i < g_fold_pool_used; ++i)
-    if (g_fold_pool[i].device == dev && g_fold_pool[i].stream == st) { *out = g_fold_pool[i].buf; return NERF_OK; }
-  if (g_fold_pool_used == kFoldPoolSlots)
-    return fail(NERF_ERR_UNSUPPORTED, "%s: fp32 forward launches on more than 64 (device, stream) pairs in one process", entry);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return fail(NERF_ERR_HIP, "%s: hipStreamIsCapturing failed", entry); }
-  if (cap != hipStreamCaptureStatusNone)
-    return fail(NERF_ERR_UNSUPPORTED, "%s: first fp32 forward launch on a capturing stream: make one eager call on this stream before the capture", entry);
-  float* buf = nullptr;
-  // (the padding behind bvf and the ring slack are zeroed once, in this stream's own order: no arithmetic ever consumes them)
-  if (hipMalloc((void**)&buf, nerf::kFoldFloats * sizeof(float)) != hipSuccess || hipMemsetAsync(buf, 0, nerf::kFoldFloats * sizeof(float), st) != hipSuccess) {
-    (void)hipGetLastError();
-    if (buf) (void)hipFree(buf);
-    return fail(NERF_ERR_HIP, "%s: allocating the fold buffer failed", entry);
-  }
-  g_fold_pool[g_fold_pool_used++] = FoldSlot{dev, st, buf};
-  *out = buf;
-  return NERF_OK;
-}
-
 // every MLP forward launch: the family from (precision, save), the instance from (ray_mode, density_only, skip_dead_colour).
 // `entry`: the public function that was called (error texts)
 static int launch_mlp(const MlpArgs& a_in, bool ray_mode, bool save, int precision, hipStream_t st, const char* entry) {
@@ -1524,16 +1495,7 @@ static int launch_mlp(const MlpArgs& a_in, bool ray_mode, bool save, int precisi
   if (!f) return fail(NERF_ERR_UNSUPPORTED, "%s: f32 or f32x only", entry);
   // density_only (ray mode): every precision has an instance that stops after the sigma head
   const MlpKernel k = f->inst[!ray_mode ? 3 : a.density_only ? 0 : a.skip_dead_colour ? 1 : 2];
-  std::unique_lock<std::mutex> hold(g_fold_pool_lock, std::defer_lock);
-  if (precision == NERF_PREC_F32 && !(ray_mode && a.density_only)) {
-    // fp32 with a colour branch: fold feature_linear into the views layer for THIS launch's weights, on this launch's stream;
-    // the pool lock is kept until the MLP kernel is enqueued behind it
-    hold.lock();
-    float* fold = nullptr;
-    if (const int rc = fold_buffer(st, entry, &fold)) return rc;
-    if (const int rc = NERF_LAUNCH(nerf_fold_f32_kernel, dim3(kFoldBlocks), dim3(256), st, a.packed, fold)) return rc;
-    a.fold = fold;
-  }
+  if (precision == NERF_PREC_F32) a.fold = a.packed + nerf::kOffFold;
   if (f->persistent) return launch(f->name, k, dim3(persistent_blocks(a.n_points, f->wg_pts)), dim3(f->threads), st, a);
   const long long blocks = (a.n_points + f->wg_pts - 1) / f->wg_pts;
   if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s: too many points for one launch", entry);
@@ -1614,8 +1576,9 @@ int32_t nerf_pack_model(const float* const params[24], void* packed, int32_t pre
     return NERF_LAUNCH(nerf_pack_f16_kernel<true>, grid, dim3(threads), st, ax);
   }
   if (precision != NERF_PREC_F32) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_pack_model: unknown precision");
-  const unsigned blocks = (unsigned)((nerf::kPackedFloats + threads - 1) / threads);
-  return NERF_LAUNCH(nerf_pack_kernel, dim3(blocks), dim3(threads), (hipStream_t)stream, a);
+  const unsigned blocks = (unsigned)((nerf::kUnfoldedFloats + threads - 1) / threads);
+  if (const int rc = NERF_LAUNCH(nerf_pack_kernel, dim3(blocks), dim3(threads), (hipStream_t)stream, a)) return rc;
+  return NERF_LAUNCH(nerf_fold_f32_kernel, dim3(kFoldBlocks), dim3(256), (hipStream_t)stream, (const float*)a.out, a.out + nerf::kOffFold);
 }
 
 int32_t nerf_positional_encoding(const float* x, int64_t n, int32_t n_freqs, float* out, void* stream) {

@@ -70,19 +70,23 @@ constexpr int64_t kOffBiasViews = kOffBias + 9 * 256;          // [2][64]
 constexpr int64_t kOffWAlpha = kOffBiasViews + 128;            // [2][128]
 constexpr int64_t kOffWRgb = kOffWAlpha + 256;                 // [3][2][64]
 constexpr int64_t kOffHeadBias = kOffWRgb + 384;               // b_rgb[3], b_alpha
-constexpr int64_t kPackedFloats = kOffHeadBias + 4;
+constexpr int64_t kUnfoldedFloats = kOffHeadBias + 4;          // the stream nerf_pack_kernel permutes out of the parameters
 
-// ---- fold buffer (nerf_fold_f32_kernel, library-owned: NOT part of the packed model) ------------
+// ---- fold region (nerf_fold_f32_kernel): part of the packed fp32 model, written by nerf_pack_model behind the stream above ----
 // feature_linear has no activation behind it (network.py:62), so the views layer's feature part folds into it:
 //   Wvf = Wv[:, :256] . Wf   (128 x 256),   bvf = Wv[:, :256] . bf + bv,
 // both accumulated in float64 from the packed stream and rounded once to fp32.  One linear weight stream covers the whole
 // colour branch of the fp32 kernels: the 32 x 4 blocks of Wvf in the block order of the views layer's feature part, a copy
 // of its 4 x 4 direction-part blocks, then bvf in the [2][64] layout of kOffBiasViews (padded to one 1-KiB LDS-DMA block).
+// `packed` must be 256-byte aligned (a torch allocation is); the region starts at the next multiple of 256 bytes, so its 1-KiB
+// blocks keep that alignment.  The alignment gap, the padding behind bvf and the ring slack are written as zeros.
+constexpr int64_t kOffFold = (kUnfoldedFloats + 63) / 64 * 64;
 constexpr int64_t kFoldOffWvf = 0;
 constexpr int64_t kFoldOffDir = kFoldOffWvf + wsize(128, 4);
 constexpr int64_t kFoldOffBias = kFoldOffDir + wsize(16, 4);
 constexpr int64_t kFoldFloats = kFoldOffBias + 256 + 8 * 256;  // + what a compiler-scheduled ring (kPF blocks ahead) reads past the
                                                                // direction part: 156 672 bytes
+constexpr int64_t kPackedFloats = kOffFold + kFoldFloats;      // nerf_packed_model_bytes(NERF_PREC_F32)
 constexpr int64_t kOffViewsDir = kOffViews + wsize(128, 4);    // the direction-part blocks inside the packed stream
 
 // ---- fp16-activation path (nerf_mlp_f16.hip.inc): v_mfma_f32_32x32x16_f16 ---------------------

@@ -76,8 +76,8 @@ struct MlpArgs {
   int skip_dead_colour;    // ray mode, fp32 inference kernel: tiles without a single sigma > 0 stop after the sigma head (DSKIP)
   int density_only;        // ray mode, fp32 kernel: stop after the sigma head (raw = (0,0,0,sigma)): the coarse pass of a
                            // hierarchical render / training step, whose colour is never read (volume_renderer.py:335 / SURVEY F6)
-  const float* fold;       // fp32 kernel with a colour branch: the fold buffer of `packed` (nerf_layout.h kFold*), filled by
-                           // nerf_fold_f32_kernel on the same stream right before this launch (launch_mlp)
+  const float* fold;       // fp32 kernels: packed + kOffFold, the fold region of `packed` (nerf_layout.h kFold*), written by
+                           // nerf_pack_model (launch_mlp)
 };
 
 // Training forward keeps what the backward pass needs, row-major per point (the layout the weight-
@@ -616,7 +616,7 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   }
 
   // Layer 7, peeled off the pair loop, and the sigma head on relu(h7) (network.py:61) on a drained ring.  The packed stream
-  // ends here for the inference instances: the colour branch reads the FOLD buffer (nerf_layout.h kFold*), so this GEMM is
+  // ends here for the inference instances: the colour branch reads the FOLD region (nerf_layout.h kFold*), so this GEMM is
   // the last of its stream and must not prefetch past it (the compiler reuses ring registers it believes dead, as in DENS).
   // The training forward still runs the feature layer from the packed stream -- the backward pass needs its row -- so
   // there layer 7 keeps prefetching and the feature GEMM is the last of the stream.

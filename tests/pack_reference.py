@@ -78,7 +78,55 @@ def pack_model(sd, prefix):
         parts.append(bias_block(Wr[c], 4))
     parts.append(g("rgb_linear.bias"))
     parts.append(g("alpha_linear.bias"))
+    assert sum(p.size for p in parts) == UNFOLDED_FLOATS
+    # the fold region (nerf_layout.h kFold*) at the next multiple of 256 bytes; gap, padding and ring slack are zeros
+    parts.append(np.zeros(OFF_FOLD - UNFOLDED_FLOATS, np.float32))
+    Wvf, bvf = fold(g("views_linears.0.weight"), g("views_linears.0.bias"), g("feature_linear.weight"), g("feature_linear.bias"))
+    parts.append(_stream(Wvf, 128, 4, hid))
+    parts.append(_stream(g("views_linears.0.weight"), 144, 4, views_col)[32 * 4 * 256:])      # the direction-part blocks (g >= 32) again
+    parts.append(bias_block(bvf, 4))
+    parts.append(np.zeros(128 + 8 * 256, np.float32))
+    assert sum(p.size for p in parts) == OFF_FOLD + FOLD_FLOATS
     return np.concatenate(parts)
+
+
+# offsets in floats (nerf_layout.h): the head biases b_rgb[3], b_alpha close the stream nerf_pack_kernel writes
+OFF_HEAD_BIAS = 2 * 64 * 256 + 8 * 256 * 256 + 288 * 128 + 9 * 256 + 128 + 256 + 384
+UNFOLDED_FLOATS = OFF_HEAD_BIAS + 4
+OFF_FOLD = (UNFOLDED_FLOATS + 63) // 64 * 64
+FOLD_OFF_WVF, FOLD_OFF_DIR, FOLD_OFF_BIAS = 0, 256 * 128, 256 * 128 + 32 * 128
+FOLD_FLOATS = FOLD_OFF_BIAS + 256 + 8 * 256
+
+
+def fold(Wv, bv, Wf, bf):
+    """Wvf = Wv[:, :256] . Wf [128, 256] and bvf = Wv[:, :256] . bf + bv [128] as nerf_fold_f32_kernel forms them: float64 (every
+    product of two floats is exact there), the 256 terms in natural order as four sequential 64-term partial sums combined as
+    (0 + 1) + (2 + 3), the views bias added last, one rounding to fp32."""
+    Wv, Wf, bv, bf = (np.asarray(x, np.float32).astype(np.float64) for x in (Wv, Wf, bv, bf))
+    part_w, part_b = np.zeros((4, 128, 256)), np.zeros((4, 128))
+    for m in range(256):
+        part_w[m // 64] += Wv[:, m:m + 1] * Wf[m:m + 1, :]
+        part_b[m // 64] += Wv[:, m] * bf[m]
+    Wvf = (part_w[0] + part_w[1]) + (part_w[2] + part_w[3])
+    bvf = ((part_b[0] + part_b[1]) + (part_b[2] + part_b[3])) + bv
+    return Wvf.astype(np.float32), bvf.astype(np.float32)
+
+
+def unfold(packed):
+    """(Wvf [128, 256], bvf [128]) in natural order, read back out of a packed fp32 model (the inverse of the two permutations)."""
+    region = np.asarray(packed)[OFF_FOLD:OFF_FOLD + FOLD_FLOATS]
+    blocks = region[FOLD_OFF_WVF:FOLD_OFF_DIR].reshape(32, 4, 64, 4)            # [g][j][lane][q]
+    Wvf, bvf = np.full((128, 256), np.nan, np.float32), np.full(128, np.nan, np.float32)
+    for s in range(128):
+        for h in range(2):
+            for j in range(4):
+                Wvf[32 * j:32 * j + 32, act_feat(s >> 4, s & 15, h)] = blocks[s // 4, j, 32 * h:32 * h + 32, s % 4]
+    bias = region[FOLD_OFF_BIAS:FOLD_OFF_BIAS + 128].reshape(2, 64)
+    for h in range(2):
+        for j in range(4):
+            for r in range(16):
+                bvf[act_feat(j, r, h)] = bias[h, j * 16 + r]
+    return Wvf, bvf
 
 
 # ------------------------------------------------------------------ fp16 stream (nerf_layout.h)

@@ -63,11 +63,17 @@ def test_library_builds_loads_and_exports():
     for name in _declared_symbols():
         assert hasattr(lib, name), name
     lib.nerf_abi_version.restype = ctypes.c_int32
-    assert lib.nerf_abi_version() == 2
+    assert lib.nerf_abi_version() == 3
     lib.nerf_packed_model_bytes.restype = ctypes.c_int64
     lib.nerf_packed_model_bytes.argtypes = [ctypes.c_int32]
     # f32: 2 x K=64 layers + 8 x K=256 layers + views (K=288 -> 128) + biases + heads
-    assert lib.nerf_packed_model_bytes(0) == 4 * (2 * 64 * 256 + 8 * 256 * 256 + 288 * 128 + 9 * 256 + 128 + 256 + 384 + 4)
+    stream = 2 * 64 * 256 + 8 * 256 * 256 + 288 * 128 + 9 * 256 + 128 + 256 + 384 + 4
+    assert stream == 596996
+    # + the fold region at the next multiple of 256 bytes: Wvf (256 x 128), the direction-part blocks (32 x 128), bvf padded to
+    # one 1-KiB block, 8 blocks of ring slack
+    fold = 256 * 128 + 32 * 128 + 256 + 8 * 256
+    assert fold == 39168
+    assert lib.nerf_packed_model_bytes(0) == 4 * ((stream + 63) // 64 * 64 + fold)
     # f16 (both MFMA shapes): 16 KiB const region + 1184 A fragments of 1 KiB (37 chunks of 32), + the split-fp16 stream of the same
     # model behind it (16 KiB + 2368 fragments: the far-plane guard of nerf_render_forward); f32x: that stream alone
     assert lib.nerf_packed_model_bytes(1) == lib.nerf_packed_model_bytes(3) == (16384 + 1184 * 1024) + (16384 + 2368 * 1024)

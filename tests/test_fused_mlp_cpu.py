@@ -76,7 +76,7 @@ def test_library_exports_the_nn_entries():
     lib = ctypes.CDLL(L.LIB_PATH)
     for name in L.NN_EXPORTS:
         assert hasattr(lib, name), name
-    assert L.load().nerf_nn_abi_version() == 1 and L.load().nerf_abi_version() == 2
+    assert L.load().nerf_nn_abi_version() == 1 and L.load().nerf_abi_version() == 3
     assert L.call("nerf_nn_abi_version") == 1     # call() finds the names of the second table
 
 

@@ -1,8 +1,11 @@
 """feature_linear folded into the views layer (csrc/nerf_layout.h kFold*, nerf_fold_f32_kernel): the fp32 kernels evaluate
     views = relu((Wv[:, :256] . Wf) . h7 + Wv[:, 256:] . dirs + (Wv[:, :256] . bf + bv))
-with the product and the bias formed in float64 from the packed stream before every launch.  Checked here: the orientation and
-exactness of the fold, that no launch meets a stale fold, that the training forward equals inference bit for bit, that two streams
-with two models do not share a buffer, and the distance of the folded chain to the float64 evaluation."""
+with the product and the bias formed in float64 from the packed stream by nerf_pack_model, which writes them behind that stream
+in the caller's buffer.  Checked here: the orientation and exactness of the fold, that the fold follows every repack, that the
+training forward equals inference bit for bit, that streams share nothing (two models on two streams, a capture on a stream that
+has never launched, more streams than any pool would hold, two models back to back on one stream), and the distance of the folded
+chain to the float64 evaluation."""
+import ctypes
 import json
 import os
 
@@ -94,7 +97,7 @@ def test_fold_orientation_and_exactness(amd, oracle, synthetic_sd):
 
 
 def test_no_stale_fold_after_in_place_updates(amd, oracle, synthetic_sd):
-    """The fold is formed per launch: after an in-place update of each tensor it depends on, a render and a points forward
+    """The fold follows the repack: after an in-place update of each tensor it depends on, a render and a points forward
     equal those of a freshly constructed network with the same state dict."""
     net = _network(amd, synthetic_sd)
     o, d = oracle.seeded_rays(64, 9)
@@ -147,7 +150,8 @@ def test_save_forward_equals_inference(amd, golden, family_sd, family):
 
 
 def test_two_streams_two_models(amd, oracle, family_sd):
-    """Fold buffers belong to a (device, stream) pair: two models rendering on two streams at once each get their own result."""
+    """Nothing is shared between streams (the fold lies in each model's own packed buffer): two models rendering on two streams
+    at once each get their own result."""
     nets = [_network(amd, family_sd(f)) for f in ("base", "sharp")]
     o, d = oracle.seeded_rays(2048, 13)
     batch = {"rays_o": o[None].cuda(), "rays_d": d[None].cuda()}
@@ -166,6 +170,84 @@ def test_two_streams_two_models(amd, oracle, family_sd):
         torch.cuda.synchronize()
     for i, (rgb, dep) in enumerate(got):
         assert torch.equal(_bits(rgb), _bits(want[i % 2][0])) and torch.equal(_bits(dep), _bits(want[i % 2][1])), i
+
+
+def _points_forward(amd, net, pts, vd, raw, stream):
+    """nerf_mlp_forward of the fine model, fp32, enqueued on the stream handle `stream`; everything preallocated."""
+    lib, L = amd._lib.load(), amd._lib
+    L.check(lib.nerf_mlp_forward(L.ptr(pts), L.ptr(vd), pts.shape[0], pts.shape[1], net.packed("fine").data_ptr(), L.ptr(raw), 0,
+                                 stream), "nerf_mlp_forward")
+
+
+def _eager(amd, net, pts, vd):
+    raw = torch.full((pts.shape[0], pts.shape[1], 4), float("nan"), device="cuda")
+    _points_forward(amd, net, pts, vd, raw, amd._lib.stream_of(pts.device))
+    torch.cuda.synchronize()
+    assert torch.isfinite(raw).all() and raw[..., :3].abs().max() > 0
+    return raw
+
+
+def test_capture_on_a_stream_that_never_launched(amd, synthetic_sd):
+    """A forward needs nothing but its arguments, so the first thing a new stream ever does can be a capture: one
+    nerf_mlp_forward of 35 points (a ragged tile), model packed and tensors allocated beforehand, captured as a one-node graph,
+    replayed, bit-equal to the eager call."""
+    net = _network(amd, synthetic_sd)
+    pts, vd = _points(35, 8)
+    pts, vd = pts.cuda(), vd.cuda()
+    want = _eager(amd, net, pts, vd)
+    raw = torch.full_like(want, float("nan"))
+    side, graph = torch.cuda.Stream(), torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        _points_forward(amd, net, pts, vd, raw, side.cuda_stream)
+    torch.cuda.synchronize()
+    assert torch.isnan(raw).all()                    # captured, not run
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(raw), _bits(want))
+
+
+def test_65_streams(amd, synthetic_sd):
+    """The same forward on 65 distinct streams, one after another: every call succeeds and gives the same bits (no per-stream
+    resource exists that could run out).  The streams come from the HIP runtime the library is linked against (torch hands out
+    32 pooled handles per priority)."""
+    lib = amd._lib.load()
+    create, destroy = lib.hipStreamCreate, lib.hipStreamDestroy
+    create.restype, create.argtypes = ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p)]
+    destroy.restype, destroy.argtypes = ctypes.c_int, [ctypes.c_void_p]
+    net = _network(amd, synthetic_sd)
+    pts, vd = _points(35, 8)
+    pts, vd = pts.cuda(), vd.cuda()
+    want = _eager(amd, net, pts, vd)
+    raws = torch.full((65,) + tuple(want.shape), float("nan"), device="cuda")
+    torch.cuda.synchronize()
+    streams = []
+    try:
+        for i in range(65):
+            h = ctypes.c_void_p()
+            assert create(ctypes.byref(h)) == 0 and h.value
+            streams.append(h)
+            _points_forward(amd, net, pts, vd, raws[i], h)
+        torch.cuda.synchronize()
+    finally:
+        for h in streams:
+            assert destroy(h) == 0
+    assert len({h.value for h in streams}) == 65
+    assert all(torch.equal(_bits(r), _bits(want)) for r in raws)
+
+
+def test_two_models_back_to_back_on_one_stream(amd, family_sd):
+    """"base" and "sharp" on one stream with no synchronisation in between: each returns its own eager result."""
+    nets = [_network(amd, family_sd(f)) for f in ("base", "sharp")]
+    pts, vd = _points(35, 8)
+    pts, vd = pts.cuda(), vd.cuda()
+    want = [_eager(amd, n, pts, vd) for n in nets]
+    assert not torch.equal(want[0], want[1])
+    raws = [torch.full_like(w, float("nan")) for w in want]
+    torch.cuda.synchronize()
+    for n, r in zip(nets, raws):
+        _points_forward(amd, n, pts, vd, r, amd._lib.stream_of(pts.device))
+    torch.cuda.synchronize()
+    assert all(torch.equal(_bits(r), _bits(w)) for r, w in zip(raws, want))
 
 
 def _chan_err(got, ref):

@@ -86,7 +86,7 @@ def _chan_err(got, ref):
 
 def test_library_loaded_from_tree(amd):
     assert os.path.dirname(amd._lib.LIB_PATH) == os.path.dirname(amd.__file__)
-    assert amd._lib.load().nerf_abi_version() == 2
+    assert amd._lib.load().nerf_abi_version() == 3
 
 
 def test_checkpoint_layout_loads(amd, synthetic_sd):
@@ -110,11 +110,14 @@ def test_repack_after_parameter_update(net):
     saved = net.model.rgb_linear.bias.detach().clone()
     with torch.no_grad():
         net.model.rgb_linear.bias.add_(1.0)
-    after = net.packed("").view(torch.float32)
-    assert not torch.equal(before, after)
-    assert torch.equal(after[-4:-1], saved + 1.0)       # head biases sit at the end of the stream
-    with torch.no_grad():
-        net.model.rgb_linear.bias.copy_(saved)
+    try:
+        after = net.packed("").view(torch.float32)
+        assert not torch.equal(before, after)
+        off = pack_reference.OFF_HEAD_BIAS              # head biases close the stream the fold region lies behind
+        assert torch.equal(after[off:off + 3], saved + 1.0)
+    finally:                                            # `net` is shared by the module: a failure here must not move its colours
+        with torch.no_grad():
+            net.model.rgb_linear.bias.copy_(saved)
     assert torch.equal(net.packed("").view(torch.float32), before)
 
 

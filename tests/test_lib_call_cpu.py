@@ -61,7 +61,7 @@ def test_size_queries_return_their_value(marked_library):
     assert L.call("nerf_train_save_floats", -1) == -1
     assert L.call("nerf_packed_model_bytes", 7) == -1
     assert L.call("nerf_packed_model_bytes", L.PREC_F32X) == lib.nerf_packed_model_bytes(L.PREC_F32X) > 0
-    assert L.call("nerf_abi_version") == 2
+    assert L.call("nerf_abi_version") == 3
     assert isinstance(L.call("nerf_last_error"), bytes)
 
 

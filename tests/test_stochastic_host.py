@@ -93,7 +93,7 @@ def test_new_symbols_in_header_binding_and_library():
         assert name in L._PROTOS, name
         assert hasattr(lib, name), name
     lib.nerf_abi_version.restype = ctypes.c_int32
-    assert lib.nerf_abi_version() == 2
+    assert lib.nerf_abi_version() == 3
     ws = lib.nerf_render_stochastic_workspace_bytes
     ws.restype, ws.argtypes = ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]
     det = lib.nerf_render_workspace_bytes

@@ -6,6 +6,7 @@ Public surface mirrors rkin100g/Nerf-Replication (paths relative to the referenc
     HashEncoder, TriPlane <- src/models/encoding/hashencoder/hashgrid.py  (constructor, `embeddings`, forward(xyz, wbounds, normalize))
     ImageFitNetwork <- src/models/img_fit/network.py              (state_dict keys, render(uv, batch), forward(batch)); FusedMLP and
                        fused_mlp are the small fused ReLU MLP it runs on (include/nerf_mi355x_nn.h)
+    HashField, HashRenderer: a hash-grid radiance field on those parts and its renderer (no counterpart that runs in the reference)
 The arithmetic runs in hand-written HIP kernels (csrc/) reached through the C ABI declared in
 include/nerf_mi355x.h; there is no CPU or eager-PyTorch fallback: without the built library or a
 GPU the product path raises.
@@ -31,13 +32,14 @@ _LAZY = {
     "OccupancyGrid": ".occupancy",
     "HashEncoder": ".hashgrid", "TriPlane": ".hashgrid",
     "fused_mlp": ".fused_mlp", "FusedMLP": ".fused_mlp", "ImageFitNetwork": ".fused_mlp",
+    "HashField": ".hashfield", "HashRenderer": ".hashfield",
 }
-_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy", "hashgrid", "modes")
+_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy", "hashgrid", "modes", "hashfield")
 
 __all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model",
            "density_grid", "isosurface", "write_ply", "extract_mesh", "density_gradient", "vertex_normals",
            "mesh_components", "filter_components", "vertex_colors", "write_ply_colors", "OccupancyGrid", "HashEncoder", "TriPlane",
-           "fused_mlp", "FusedMLP", "ImageFitNetwork"]
+           "fused_mlp", "FusedMLP", "ImageFitNetwork", "HashField", "HashRenderer"]
 
 
 def __getattr__(name):

@@ -143,6 +143,12 @@ nerf_fused_mlp_save_floats  i64 : i64 i32 i32
 nerf_fused_mlp_grad_floats  i64 : i64 i32 i32 i32
 nerf_fused_mlp_forward  status : f32* i64 i32 i32 i32 i32 i32 f32*[] f32*[] f32* f32* stream
 nerf_fused_mlp_backward  status : f32* f32* f32* i64 i32 i32 i32 i32 i32 f32*[] f32* f32* f32*[] f32*[] f32* stream
+nerf_sh4_encode  status : f32* i64 f32* stream
+nerf_field_points  status : f32* f32* f32* i64 i64 i32 i32* i64 f32[3] f32[3] f32 f32* stream
+nerf_field_color_inputs  status : f32* f32* i32* i64 i64 i32 f32* f32* stream
+nerf_field_color_inputs_backward  status : f32* f32* i64 f32* stream
+nerf_field_raw_scatter  status : f32* f32* i32* i64 i64 f32* stream
+nerf_field_raw_gather  status : f32* i32* i64 i64 f32* f32* stream
 """
 NN_SIGNATURES = _parse_table(_TABLE_NN)
 NN_EXPORTS = tuple(NN_SIGNATURES)

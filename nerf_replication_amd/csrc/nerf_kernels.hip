@@ -2472,3 +2472,5 @@ int32_t nerf_render_forward_stochastic(const float* rays_o, const float* rays_d,
 #include "nerf_hashgrid.hip.inc"
 // ---- small fused ReLU MLP (include/nerf_mi355x_nn.h): nerf_fused_mlp_forward / nerf_fused_mlp_backward
 #include "nerf_fused_mlp.hip.inc"
+// ---- hash-grid radiance field, the ray-side glue (include/nerf_mi355x_nn.h): nerf_sh4_encode, nerf_field_*
+#include "nerf_hashfield.hip.inc"

@@ -1,0 +1,313 @@
+"""Hash-grid radiance field (instant-NGP style) on the kernels this package already has, and its renderer.
+
+    HashField(bbox, encoder=None, geo_dim=16, width=64, sigma_hidden=1, color_hidden=2)      nn.Module
+        sigma, geo = sigma_net(encoder(x)),  rgb = color_net(geo, SH4(view direction));  density(xyz), occupancy_grid(N, level, dilate)
+    HashRenderer(field)            Renderer's call surface: render(batch) -> (rgb [B*N,3], depth [B*N])
+
+The encoder runs on hash_encode, the two networks on fused_mlp, the grid lookup on nerf_occupancy_mark / nerf_compact_valid and the
+image on nerf_composite, all as they are; what lies between them on the ray side (sample positions, the SH basis, the colour
+network's input rows, the scatter into `raw`) are the HIP kernels of csrc/nerf_hashfield.hip.inc (include/nerf_mi355x_nn.h has every
+formula).  No ATen op computes on the render path: torch allocates, zero-fills and slices.  fp32 only; CPU tensors raise
+NerfLibraryError: there is no eager fallback.
+
+One host synchronisation per chunk on the culled path (HashRenderer.occupancy set): the number of surviving samples is read back,
+because hash_encode and fused_mlp take their row count from the host.  Without a grid nothing synchronises.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from .fused_mlp import FusedMLP, fused_mlp
+from .hashgrid import EPS, HashEncoder, hash_encode
+
+GEO_DIM = 16                        # columns of the geometry feature: what the glue kernels move
+SH_DIM = 16                         # real spherical harmonics of degree 0..3
+MAX_SAMPLES = 192                   # nerf_composite's limit
+DENSITY_ROWS = 1 << 22              # rows of one launch chain in HashField.density
+
+
+def box_frame(wbounds):
+    """(box_min, box_max, extent) of the normalisation, from 6 fp32 numbers: extent = fp32(float64(largest fp32 axis extent) + 1e-6),
+    the divisor of hashgrid.normalize_to_bounds (the subtraction in fp32, the sum in float64, rounded once)."""
+    w = np.asarray(wbounds, dtype=np.float32).reshape(6)
+    lo, hi = w[:3], w[3:]
+    extent = np.float32(np.float64((hi - lo).max()) + EPS)
+    return lo, hi, extent
+
+
+class _ColorInputs(torch.autograd.Function):
+    """geo [M,16], sh [n,16] -> (cin [M,32], sigma_rows [M]); the backward writes g_geo from both incoming gradients."""
+
+    @staticmethod
+    def forward(ctx, geo, sh, index, M, n, S):
+        geo = geo.detach().contiguous()
+        cin = torch.empty(M, GEO_DIM + SH_DIM, dtype=torch.float32, device=geo.device)
+        sigma_rows = torch.empty(M, dtype=torch.float32, device=geo.device)
+        _lib.call("nerf_field_color_inputs", geo, sh, index, M, n, S, cin, sigma_rows)
+        ctx.M = M
+        return cin, sigma_rows
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cin, g_sigma_rows):
+        g_geo = torch.empty(ctx.M, GEO_DIM, dtype=torch.float32, device=g_cin.device)
+        _lib.call("nerf_field_color_inputs_backward", g_cin.contiguous(), g_sigma_rows.contiguous(), ctx.M, g_geo)
+        return g_geo, None, None, None, None, None
+
+
+class _RawScatter(torch.autograd.Function):
+    """rgb [M,3], sigma_rows [M] -> raw [n,S,4], zero at the points the list leaves out; the backward is the gather."""
+
+    @staticmethod
+    def forward(ctx, rgb, sigma_rows, index, M, n, S):
+        raw = torch.zeros(n, S, 4, dtype=torch.float32, device=rgb.device)
+        _lib.call("nerf_field_raw_scatter", rgb.detach().contiguous(), sigma_rows.detach().contiguous(), index, M, n * S, raw)
+        ctx.index, ctx.M = index, M
+        return raw
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_raw):
+        g_raw = g_raw.contiguous()
+        g_rgb = torch.empty(ctx.M, 3, dtype=torch.float32, device=g_raw.device)
+        g_sigma_rows = torch.empty(ctx.M, dtype=torch.float32, device=g_raw.device)
+        _lib.call("nerf_field_raw_gather", g_raw, ctx.index, ctx.M, g_raw.numel() // 4, g_rgb, g_sigma_rows)
+        return g_rgb, g_sigma_rows, None, None, None, None
+
+
+class _Composite(torch.autograd.Function):
+    """raw [n,S,4] -> (rgb [n,3], depth [n]) by nerf_composite; the backward is nerf_composite_backward with g_t = NULL (the depths
+    are constants)."""
+
+    @staticmethod
+    def forward(ctx, raw, tvals, white):
+        raw = raw.detach()
+        n, S = raw.shape[0], raw.shape[1]
+        rgb = torch.empty(n, 3, dtype=torch.float32, device=raw.device)
+        depth = torch.empty(n, dtype=torch.float32, device=raw.device)
+        _lib.call("nerf_composite", raw, tvals, 0, n, S, white, rgb, depth, None)
+        ctx.save_for_backward(raw, tvals)
+        ctx.white = white
+        ctx.set_materialize_grads(False)
+        return rgb, depth
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rgb, g_depth):
+        raw, tvals = ctx.saved_tensors
+        n, S = raw.shape[0], raw.shape[1]
+        g_rgb = torch.zeros(n, 3, dtype=torch.float32, device=raw.device) if g_rgb is None else g_rgb.contiguous()
+        g_depth = None if g_depth is None else g_depth.contiguous()
+        g_raw = torch.empty_like(raw)
+        _lib.call("nerf_composite_backward", raw, tvals, 0, n, S, ctx.white, g_rgb, g_depth, g_raw, None)
+        return g_raw, None, None
+
+
+class HashField(nn.Module):
+    """x in `bbox` -> hash encoding -> sigma_net -> 16 columns: column 0 is the raw (pre-ReLU) density, all 16 are the geometry
+    feature; (geometry feature, 16 SH coefficients of the view direction) -> color_net -> the pre-sigmoid rgb.
+
+    bbox: 6 numbers, min xyz then max xyz; kept as the persistent fp32 buffer `wbounds`, so a checkpoint carries it.  encoder: a 3-D
+    HashEncoder (default: L=16, C=2, H=16, T=19, desired_resolution=2048: 32 channels).  State-dict keys: encoder.embeddings,
+    sigma_net.layers.{i}.{weight,bias}, color_net.layers.{i}.{weight,bias}, wbounds -- 11 parameter tensors with the defaults, one
+    FusedAdam group."""
+
+    def __init__(self, bbox, encoder=None, geo_dim=GEO_DIM, width=64, sigma_hidden=1, color_hidden=2):
+        super().__init__()
+        if geo_dim != GEO_DIM:
+            raise ValueError(f"HashField: geo_dim = {GEO_DIM} is built (the glue kernels move 16-column rows), got {geo_dim!r}")
+        try:
+            b = np.asarray(bbox, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"bbox must hold 6 numbers (min xyz, max xyz), got {bbox!r}") from None
+        if b.shape != (6,) or not np.isfinite(b).all() or (b[3:] <= b[:3]).any():
+            raise ValueError(f"bbox must hold 6 finite numbers (min xyz, max xyz) with a positive extent on every axis, got {bbox!r}")
+        if encoder is None:
+            encoder = HashEncoder(input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=19,
+                                  desired_resolution=2048)
+        if not isinstance(encoder, HashEncoder) or encoder.input_dim != 3:
+            raise TypeError("HashField: encoder must be a HashEncoder with input_dim = 3")
+        self.encoder = encoder
+        self.sigma_net = FusedMLP(encoder.out_dim, GEO_DIM, width, sigma_hidden)
+        self.color_net = FusedMLP(GEO_DIM + SH_DIM, 3, width, color_hidden)
+        # Compositing takes relu(sigma): a field whose density starts negative everywhere renders the background, has a gradient of
+        # exactly zero and never trains.  With embeddings near zero the initial density is one constant of random sign, so the bias
+        # of the density column starts at 1 -- a uniform fog, whose gradient reaches every parameter.
+        with torch.no_grad():
+            self.sigma_net.layers[-1].bias[0] = 1.0
+        self.register_buffer("wbounds", torch.tensor(b, dtype=torch.float32), persistent=True)
+        self._frame = None
+
+    def frame(self):
+        """(box_min, box_max, extent) as the HOST arguments of nerf_field_points, re-read from `wbounds` when it was written (a
+        loaded checkpoint: one copy to the host)."""
+        key = (self.wbounds.data_ptr(), self.wbounds._version)
+        if self._frame is None or self._frame[0] != key:
+            lo, hi, extent = box_frame(self.wbounds.detach().cpu().numpy())
+            self._frame = (key, tuple(lo.tolist()), tuple(hi.tolist()), float(extent))
+        return self._frame[1:]
+
+    @property
+    def bbox(self):
+        """The box as 6 float64 numbers: the fp32 values of `wbounds`."""
+        lo, hi, _ = self.frame()
+        return np.array(list(lo) + list(hi), dtype=np.float64)
+
+    def _geo(self, x):
+        """x [M,3] in [0,1] -> the 16 columns of sigma_net."""
+        enc = self.encoder
+        feats = hash_encode(x, enc.embeddings, enc.offsets, enc.per_level_scale, enc.base_resolution)
+        return fused_mlp(feats, [l.weight for l in self.sigma_net.layers], [l.bias for l in self.sigma_net.layers])
+
+    def _rgb(self, cin):
+        return fused_mlp(cin, [l.weight for l in self.color_net.layers], [l.bias for l in self.color_net.layers])
+
+    def _check_fp32(self):
+        for name, p in self.named_parameters():
+            if p.dtype != torch.float32:
+                raise NotImplementedError(f"HashField: fp32 only (parameter {name} is {p.dtype})")
+
+    def density(self, xyz):
+        """World points xyz [n,3] on the GPU -> the raw density [n,1]: the queryfn protocol of extract_mesh.  The positions are
+        normalised by nerf_field_points in point mode; the parameters get gradients if they require them, xyz does not."""
+        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError("HashField.density: xyz must be a tensor [n, 3]")
+        if xyz.dtype != torch.float32:
+            raise NotImplementedError(f"HashField.density: fp32 only (xyz is {xyz.dtype})")
+        if xyz.requires_grad:
+            raise NotImplementedError("HashField.density: no gradient with respect to the positions is built")
+        self._check_fp32()
+        if not xyz.is_cuda:
+            raise _lib.NerfLibraryError("HashField.density needs xyz on a GPU (cuda) device; got a CPU tensor (there is no CPU fallback)")
+        xyz = xyz.contiguous()
+        if xyz.shape[0] == 0:
+            return xyz.new_zeros(0, 1)
+        lo, hi, extent = self.frame()
+        outs = []
+        for i in range(0, xyz.shape[0], DENSITY_ROWS):
+            pts = xyz[i:i + DENSITY_ROWS]
+            n = pts.shape[0]
+            x = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
+            _lib.call("nerf_field_points", pts, None, None, 0, n, 1, None, n, lo, hi, extent, x)
+            outs.append(self._geo(x)[:, :1].contiguous())       # a copy of one column: the [n,16] output is not kept alive
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    def occupancy_grid(self, N=128, level=0.0, dilate=1):
+        """OccupancyGrid.from_fields(bbox, fine=<the density on an N grid over the box>): where sigma can exceed `level` now.  Runs
+        under no_grad, the grid in x-slabs.  The grid carries no staleness key: rebuild it on your own schedule while training."""
+        from .mesh import _query_grid, grid_axes
+        from .occupancy import OccupancyGrid
+        bbox = self.bbox
+        axes, _, _ = grid_axes(bbox, N)
+        field = _query_grid(self.density, axes, self.wbounds.device)
+        return OccupancyGrid.from_fields(bbox, fine=field, level=level, dilate=dilate)
+
+
+class HashRenderer:
+    """Renderer's call surface over a HashField: render(batch) -> (rgb [B*N,3], depth [B*N]) with batch["rays_o"], batch["rays_d"]
+    [B,N,3] on the GPU.
+
+    N_samples (192; any int in [1, 192]) depths per ray, one shared table linspace(t_near, t_far, N_samples); no hierarchical pass
+    and no jitter.  white_bkgd (True).  occupancy: None, or an OccupancyGrid with a fine bitfield (HashField.occupancy_grid): the
+    samples in empty cells are not evaluated and keep raw = 0 -- at the price of ONE HOST SYNCHRONISATION PER CHUNK, the count of the
+    surviving samples.  stats: None, or a list that receives (evaluated, total) samples per chunk on the culled path.  chunk_rays
+    (16384): rays per launch chain; the result does not depend on it.
+
+    Under no_grad, or when no parameter requires grad, the result is detached.  Otherwise the same launches run through autograd
+    functions and every parameter that requires grad gets its gradient; rays that require grad are refused (no ray adjoint is built).
+    `net` is the field: training.train_step(renderer, optimizer, ...) works as with a Renderer."""
+
+    def __init__(self, field):
+        if not isinstance(field, HashField):
+            raise TypeError("HashRenderer needs a HashField")
+        self.field = field
+        self.N_samples = MAX_SAMPLES
+        self.t_near, self.t_far = 2.0, 6.0
+        self.white_bkgd = True
+        self.occupancy = None
+        self.chunk_rays = 16384
+        self.stats = None
+        self._tables = {}
+
+    @property
+    def net(self):
+        return self.field
+
+    def _get_table(self, dev):
+        key = (dev, float(self.t_near), float(self.t_far), int(self.N_samples))
+        t = self._tables.get(key)
+        if t is None:
+            self._tables.clear()
+            t = self._tables[key] = torch.linspace(self.t_near, self.t_far, self.N_samples).to(dev)
+        return t
+
+    def _check(self, rays_o, rays_d):
+        """Everything that is refused, before any launch or allocation -> the grid or None."""
+        S = self.N_samples
+        if isinstance(S, bool) or not isinstance(S, int) or not 1 <= S <= MAX_SAMPLES:
+            raise ValueError(f"HashRenderer.N_samples must be an int in [1, {MAX_SAMPLES}], got {S!r}")
+        if isinstance(self.chunk_rays, bool) or not isinstance(self.chunk_rays, int) or self.chunk_rays < 1:
+            raise ValueError(f"HashRenderer.chunk_rays must be an int >= 1 (rays), got {self.chunk_rays!r}")
+        grid = self.occupancy
+        if grid is not None:
+            from .occupancy import OccupancyGrid
+            if not isinstance(grid, OccupancyGrid):
+                raise TypeError("HashRenderer.occupancy must be an OccupancyGrid or None")
+            if grid.bits["fine"] is None:
+                raise ValueError("HashRenderer.occupancy needs a grid with a fine bitfield")
+        if rays_o.dim() != 3 or rays_o.shape[-1] != 3 or rays_d.shape != rays_o.shape:
+            raise ValueError("HashRenderer.render: rays_o and rays_d must both be [B, N, 3]")
+        if rays_o.requires_grad or rays_d.requires_grad:
+            raise NotImplementedError("HashRenderer: rays that require grad are not supported (the glue has no ray adjoint)")
+        self.field._check_fp32()
+        if not rays_o.is_cuda or not rays_d.is_cuda:
+            raise _lib.NerfLibraryError("HashRenderer needs rays on a GPU (cuda) device; got a CPU tensor (there is no CPU fallback)")
+        if grid is not None and grid.device != rays_o.device:
+            raise ValueError(f"the occupancy grid is on {grid.device}, the rays on {rays_o.device}")
+        return grid
+
+    def _chunk(self, o, d, t, S, grid, white):
+        """One chunk of n rays -> (rgb [n,3], depth [n]); every step is enqueued on the current stream."""
+        field, dev, n = self.field, o.device, o.shape[0]
+        P, M, index = n * S, n * S, None
+        if grid is not None:
+            valid = torch.empty(n, S, dtype=torch.uint8, device=dev)
+            _lib.call("nerf_occupancy_mark", o, d, t, 0, n, S, grid.bits["fine"], *grid.lookup_args(), 0, valid)
+            index = torch.empty(P, dtype=torch.int32, device=dev)
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+            ws = torch.empty(int(_lib.call("nerf_compact_valid_workspace_bytes", P)), dtype=torch.uint8, device=dev)
+            _lib.call("nerf_compact_valid", valid, P, index, count, ws)
+            M = int(count.item())                      # the host synchronisation of the culled path
+            if isinstance(self.stats, list):
+                self.stats.append((M, P))
+        if M == 0:
+            raw = torch.zeros(n, S, 4, dtype=torch.float32, device=dev)
+        else:
+            lo, hi, extent = field.frame()
+            x = torch.empty(M, 3, dtype=torch.float32, device=dev)
+            _lib.call("nerf_field_points", o, d, t, 0, n, S, index, M, lo, hi, extent, x)
+            geo = field._geo(x)
+            sh = torch.empty(n, SH_DIM, dtype=torch.float32, device=dev)
+            _lib.call("nerf_sh4_encode", d, n, sh)
+            cin, sigma_rows = _ColorInputs.apply(geo, sh, index, M, n, S)
+            raw = _RawScatter.apply(field._rgb(cin), sigma_rows, index, M, n, S)
+        return _Composite.apply(raw, t, white)
+
+    def render(self, batch):
+        rays_o, rays_d = batch["rays_o"], batch["rays_d"]
+        grid = self._check(rays_o, rays_d)
+        dev = rays_o.device
+        n = rays_o.shape[0] * rays_o.shape[1]
+        if n == 0:
+            return torch.empty(0, 3, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+        o = rays_o.reshape(-1, 3).to(torch.float32).contiguous()
+        d = rays_d.reshape(-1, 3).to(torch.float32).contiguous()
+        S, white = self.N_samples, int(bool(self.white_bkgd))
+        t = self._get_table(dev)
+        outs = [self._chunk(o[i:i + self.chunk_rays], d[i:i + self.chunk_rays], t, S, grid, white)
+                for i in range(0, n, self.chunk_rays)]
+        if len(outs) == 1:
+            return outs[0]
+        return torch.cat([r for r, _ in outs], 0), torch.cat([z for _, z in outs], 0)

@@ -8,6 +8,7 @@ reference's src/utils/mesh_utils.py extract_mesh is for).
     python examples/extract_mesh.py --normals                  # vertex normals (nx ny nz) from the density gradient: smooth shading
     python examples/extract_mesh.py --keep-largest 1 --colors  # the object alone, without floaters, coloured by the network
     python examples/extract_mesh.py --min-triangles 100        # everything bigger than a crumb
+    python examples/extract_mesh.py --hashfield field.pth --normals --colors --keep-largest 1      # a HashField (train_hashfield.py --out)
 
 Needs an MI355X and the built library (python -c "import __graft_entry__ as g; g.build()")."""
 import argparse
@@ -37,17 +38,33 @@ def main():
     ap.add_argument("--min-triangles", type=int, default=None, metavar="M", help="keep the connected components with at least M triangles")
     ap.add_argument("--colors", action="store_true",
                     help="write vertex colours (red green blue): the network's colour seen head-on from outside (nerf.vertex_colors; f32 / f32x)")
+    ap.add_argument("--hashfield", default=None, metavar="PTH",
+                    help="a HashField state dict (examples/train_hashfield.py --out) instead of --ckpt; the box is the field's own "
+                         "(--bbox and --precision are not used)")
+    ap.add_argument("--levels", type=int, default=16, help="with --hashfield: the encoder's levels, as the field was trained")
+    ap.add_argument("--log2-hashmap-size", type=int, default=19, help="with --hashfield: the encoder's table size, as the field was trained")
     ap.add_argument("--out", default="mesh.ply")
     args = ap.parse_args()
 
-    net = nerf.Network()
-    nerf.load_network(net, args.ckpt)
-    net = net.cuda().eval()
-    net.precision = args.precision
-    level = args.level
-    if level is None:
-        grid = nerf.density_grid(net, args.bbox, args.n)
-        level = 0.5 * (grid.median().item() + grid.max().item())
+    if args.hashfield:
+        sys.path.insert(0, os.path.join(REPO, "examples"))
+        from refine_hashfield_pose import load_field
+        net = load_field(args.hashfield, args.levels, args.log2_hashmap_size).cuda().eval().requires_grad_(False)
+        args.bbox, args.precision = None, "hash field"
+        level = args.level
+        if level is None:
+            from nerf_replication_amd.mesh import _query_grid, grid_axes
+            grid = _query_grid(net.density, grid_axes(net.bbox, args.n)[0], net.wbounds.device)
+            level = 0.5 * (grid.median().item() + grid.max().item())
+    else:
+        net = nerf.Network()
+        nerf.load_network(net, args.ckpt)
+        net = net.cuda().eval()
+        net.precision = args.precision
+        level = args.level
+        if level is None:
+            grid = nerf.density_grid(net, args.bbox, args.n)
+            level = 0.5 * (grid.median().item() + grid.max().item())
     torch.cuda.synchronize(); t0 = time.perf_counter()
     vertices, faces = nerf.extract_mesh(net, level, args.bbox, args.out, args.n, normals=True if args.normals else None,
                                         min_triangles=args.min_triangles, keep_largest=args.keep_largest,

@@ -154,6 +154,18 @@ NN_SIGNATURES = _parse_table(_TABLE_NN)
 NN_EXPORTS = tuple(NN_SIGNATURES)
 _NN_PROTOS = _protos(NN_SIGNATURES)
 
+# The spatial adjoint of the hash field's glue, one line per entry of include/nerf_mi355x_field.h (the third header of the same
+# library; the second table is pinned at its 11 entries).  tests/test_hashfield_grad_cpu.py compares this table with that header.
+_TABLE_FIELD = """
+nerf_field_density_seed  status : f32* i64 i64 i32 f32* stream
+nerf_field_points_backward  status : f32* f32* f32* i64 i64 i32 i32* i64 f32[3] f32[3] f32 f32* f32* i32 f32* f32* f32* stream
+nerf_field_sh_gradient  status : f32* i32* i64 i64 i32 f32* stream
+nerf_sh4_encode_backward  status : f32* f32* i64 f32* stream
+"""
+FIELD_SIGNATURES = _parse_table(_TABLE_FIELD)
+FIELD_EXPORTS = tuple(FIELD_SIGNATURES)
+_FIELD_PROTOS = _protos(FIELD_SIGNATURES)
+
 _lib = None
 
 
@@ -180,7 +192,7 @@ def load():
                 f"{LIB_PATH} is missing: build it with `make -C {CSRC}` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the render path")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOS.items()) + list(_NN_PROTOS.items()):
+        for name, (res, args) in list(_PROTOS.items()) + list(_NN_PROTOS.items()) + list(_FIELD_PROTOS.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.nerf_abi_version() != 3:
@@ -207,7 +219,7 @@ def call(name, *args):
     pointers, numbers for scalars, sequences or ctypes arrays for host arrays.  Every argument is checked against the entry's kinds
     in SIGNATURES (or NN_SIGNATURES, the small-network entries) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
     is checked (NerfLibraryError with nerf_last_error's text); any other return value comes back as it is."""
-    ret, kinds = SIGNATURES[name] if name in SIGNATURES else NN_SIGNATURES[name]
+    ret, kinds = SIGNATURES[name] if name in SIGNATURES else NN_SIGNATURES[name] if name in NN_SIGNATURES else FIELD_SIGNATURES[name]
     has_stream = kinds[-1:] == ("stream",)
     if len(args) != len(kinds) - has_stream:
         raise TypeError(f"{name} takes {len(kinds) - has_stream} arguments ({len(args)} given)")

@@ -1,31 +1,37 @@
 """Hash-grid radiance field (instant-NGP style) on the kernels this package already has, and its renderer.
 
     HashField(bbox, encoder=None, geo_dim=16, width=64, sigma_hidden=1, color_hidden=2)      nn.Module
-        sigma, geo = sigma_net(encoder(x)),  rgb = color_net(geo, SH4(view direction));  density(xyz), occupancy_grid(N, level, dilate)
-    HashRenderer(field)            Renderer's call surface: render(batch) -> (rgb [B*N,3], depth [B*N])
+        sigma, geo = sigma_net(encoder(x)),  rgb = color_net(geo, SH4(view direction));  density(xyz), occupancy_grid(N, level, dilate),
+        density_gradient(xyz), vertex_normals(vertices), vertex_colors(vertices, viewdirs)
+    HashRenderer(field)            Renderer's call surface: render(batch) -> (rgb [B*N,3], depth [B*N]); render_geometry(batch) -> (rgb,
+                                   depth, acc, normal); ray_gradients = True: rays that require grad get their gradient
 
 The encoder runs on hash_encode, the two networks on fused_mlp, the grid lookup on nerf_occupancy_mark / nerf_compact_valid and the
 image on nerf_composite, all as they are; what lies between them on the ray side (sample positions, the SH basis, the colour
 network's input rows, the scatter into `raw`) are the HIP kernels of csrc/nerf_hashfield.hip.inc (include/nerf_mi355x_nn.h has every
-formula).  No ATen op computes on the render path: torch allocates, zero-fills and slices.  fp32 only; CPU tensors raise
-NerfLibraryError: there is no eager fallback.
+formula).  The spatial adjoint of that glue -- the density gradient, the geometry outputs, gradients with respect to the rays --
+is DESIGN.md section 2.14.1, its formulas in include/nerf_mi355x_field.h.  No ATen op computes on the render path: torch allocates,
+zero-fills and slices.  fp32 only; CPU tensors raise NerfLibraryError: there is no eager fallback.
 
 One host synchronisation per chunk on the culled path (HashRenderer.occupancy set): the number of surviving samples is read back,
 because hash_encode and fused_mlp take their row count from the host.  Without a grid nothing synchronises.
 """
+import ctypes
+
 import numpy as np
 import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .fused_mlp import FusedMLP, fused_mlp
-from .hashgrid import EPS, HashEncoder, hash_encode
+from .fused_mlp import MAX_ROWS, FusedMLP, fused_mlp
+from .hashgrid import EPS, HashEncoder, _as_offsets, hash_encode, level_scales
 
 GEO_DIM = 16                        # columns of the geometry feature: what the glue kernels move
 SH_DIM = 16                         # real spherical harmonics of degree 0..3
 MAX_SAMPLES = 192                   # nerf_composite's limit
 DENSITY_ROWS = 1 << 22              # rows of one launch chain in HashField.density
+GRADIENT_ROWS = 1 << 20             # ... and in HashField.density_gradient, which keeps save, gsave, features and their gradient per row
 
 
 def box_frame(wbounds):
@@ -37,8 +43,65 @@ def box_frame(wbounds):
     return lo, hi, extent
 
 
+class _Points(torch.autograd.Function):
+    """World points [n,3] -> their normalised positions x [n,3] (nerf_field_points in point mode); the backward is
+    nerf_field_points_backward in point mode, the compact layout."""
+
+    @staticmethod
+    def forward(ctx, pts, frame):
+        pts = pts.detach().contiguous()
+        n = pts.shape[0]
+        x = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
+        _lib.call("nerf_field_points", pts, None, None, 0, n, 1, None, n, *frame, x)
+        ctx.save_for_backward(pts)
+        ctx.frame = frame
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x):
+        pts, = ctx.saved_tensors
+        n = pts.shape[0]
+        g_p = torch.empty_like(pts)
+        _lib.call("nerf_field_points_backward", pts, None, None, 0, n, 1, None, n, *ctx.frame, g_x.contiguous(), None, 0, g_p, None, None)
+        return g_p, None
+
+
+class _RayInputs(torch.autograd.Function):
+    """(o, d) [n,3] -> (x [M,3], sh [n,16]): nerf_field_points and nerf_sh4_encode, the two launches of the plain path.  The backward
+    takes (g_x, g_sh) and writes g_o and g_d once: nerf_sh4_encode_backward, then nerf_field_points_backward with its view term."""
+
+    @staticmethod
+    def forward(ctx, o, d, t, index, M, S, frame):
+        o, d = o.detach().contiguous(), d.detach().contiguous()
+        n = o.shape[0]
+        x = torch.empty(M, 3, dtype=torch.float32, device=o.device)
+        _lib.call("nerf_field_points", o, d, t, 0, n, S, index, M, *frame, x)
+        sh = torch.empty(n, SH_DIM, dtype=torch.float32, device=o.device)
+        _lib.call("nerf_sh4_encode", d, n, sh)
+        ctx.save_for_backward(o, d, t)
+        ctx.index, ctx.M, ctx.S, ctx.frame = index, M, S, frame
+        ctx.set_materialize_grads(False)
+        return x, sh
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x, g_sh):
+        o, d, t = ctx.saved_tensors
+        n, M = o.shape[0], ctx.M
+        g_view = None
+        if g_sh is not None:
+            g_view = torch.empty(n, 3, dtype=torch.float32, device=o.device)
+            _lib.call("nerf_sh4_encode_backward", d, g_sh.contiguous(), n, g_view)
+        g_x = torch.zeros(M, 3, dtype=torch.float32, device=o.device) if g_x is None else g_x.contiguous()
+        g_o, g_d = torch.empty_like(o), torch.empty_like(d)
+        _lib.call("nerf_field_points_backward", o, d, t, 0, n, ctx.S, ctx.index, M, *ctx.frame, g_x, g_view, 0, None, g_o, g_d)
+        return g_o, g_d, None, None, None, None, None
+
+
 class _ColorInputs(torch.autograd.Function):
-    """geo [M,16], sh [n,16] -> (cin [M,32], sigma_rows [M]); the backward writes g_geo from both incoming gradients."""
+    """geo [M,16], sh [n,16] -> (cin [M,32], sigma_rows [M]); the backward writes g_geo from both incoming gradients and, when sh
+    needs one (HashRenderer.ray_gradients), g_sh [n,16] by nerf_field_sh_gradient."""
 
     @staticmethod
     def forward(ctx, geo, sh, index, M, n, S):
@@ -46,15 +109,20 @@ class _ColorInputs(torch.autograd.Function):
         cin = torch.empty(M, GEO_DIM + SH_DIM, dtype=torch.float32, device=geo.device)
         sigma_rows = torch.empty(M, dtype=torch.float32, device=geo.device)
         _lib.call("nerf_field_color_inputs", geo, sh, index, M, n, S, cin, sigma_rows)
-        ctx.M = M
+        ctx.M, ctx.index, ctx.n, ctx.S = M, index, n, S
         return cin, sigma_rows
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cin, g_sigma_rows):
+        g_cin = g_cin.contiguous()
         g_geo = torch.empty(ctx.M, GEO_DIM, dtype=torch.float32, device=g_cin.device)
-        _lib.call("nerf_field_color_inputs_backward", g_cin.contiguous(), g_sigma_rows.contiguous(), ctx.M, g_geo)
-        return g_geo, None, None, None, None, None
+        _lib.call("nerf_field_color_inputs_backward", g_cin, g_sigma_rows.contiguous(), ctx.M, g_geo)
+        g_sh = None
+        if ctx.needs_input_grad[1]:
+            g_sh = torch.empty(ctx.n, SH_DIM, dtype=torch.float32, device=g_cin.device)
+            _lib.call("nerf_field_sh_gradient", g_cin, ctx.index, ctx.M, ctx.n, ctx.S, g_sh)
+        return g_geo, g_sh, None, None, None, None
 
 
 class _RawScatter(torch.autograd.Function):
@@ -169,30 +237,138 @@ class HashField(nn.Module):
             if p.dtype != torch.float32:
                 raise NotImplementedError(f"HashField: fp32 only (parameter {name} is {p.dtype})")
 
-    def density(self, xyz):
-        """World points xyz [n,3] on the GPU -> the raw density [n,1]: the queryfn protocol of extract_mesh.  The positions are
-        normalised by nerf_field_points in point mode; the parameters get gradients if they require them, xyz does not."""
+    def _check_points(self, xyz, what):
+        """The refusals of the entries that take world points, before any launch -> xyz, contiguous."""
         if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2 or xyz.shape[1] != 3:
-            raise ValueError("HashField.density: xyz must be a tensor [n, 3]")
+            raise ValueError(f"HashField.{what}: xyz must be a tensor [n, 3]")
         if xyz.dtype != torch.float32:
-            raise NotImplementedError(f"HashField.density: fp32 only (xyz is {xyz.dtype})")
-        if xyz.requires_grad:
-            raise NotImplementedError("HashField.density: no gradient with respect to the positions is built")
+            raise NotImplementedError(f"HashField.{what}: fp32 only (xyz is {xyz.dtype})")
         self._check_fp32()
         if not xyz.is_cuda:
-            raise _lib.NerfLibraryError("HashField.density needs xyz on a GPU (cuda) device; got a CPU tensor (there is no CPU fallback)")
-        xyz = xyz.contiguous()
+            raise _lib.NerfLibraryError(f"HashField.{what} needs xyz on a GPU (cuda) device; got a CPU tensor (there is no CPU fallback)")
+        return xyz.contiguous()
+
+    def density(self, xyz):
+        """World points xyz [n,3] on the GPU -> the raw density [n,1]: the queryfn protocol of extract_mesh.  The positions are
+        normalised by nerf_field_points in point mode; the parameters get gradients if they require them, and so does xyz (the
+        point-mode adjoint nerf_field_points_backward behind the encoder's and the network's input gradients)."""
+        xyz = self._check_points(xyz, "density")
         if xyz.shape[0] == 0:
             return xyz.new_zeros(0, 1)
-        lo, hi, extent = self.frame()
+        frame = self.frame()
+        with_grad = xyz.requires_grad and torch.is_grad_enabled()
         outs = []
         for i in range(0, xyz.shape[0], DENSITY_ROWS):
             pts = xyz[i:i + DENSITY_ROWS]
             n = pts.shape[0]
-            x = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
-            _lib.call("nerf_field_points", pts, None, None, 0, n, 1, None, n, lo, hi, extent, x)
+            if with_grad:
+                x = _Points.apply(pts, frame)
+            else:
+                x = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
+                _lib.call("nerf_field_points", pts, None, None, 0, n, 1, None, n, *frame, x)
             outs.append(self._geo(x)[:, :1].contiguous())       # a copy of one column: the [n,16] output is not kept alive
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    def _levels(self):
+        """(offsets, scales, L): the level tables as the host arrays nerf_hashgrid_* take (what hash_encode builds per call)."""
+        enc = self.encoder
+        offsets = _as_offsets(enc.offsets)
+        L = offsets.shape[0] - 1
+        scales = level_scales(L, enc.per_level_scale, enc.base_resolution)
+        return (ctypes.c_int32 * (L + 1))(*offsets.tolist()), (ctypes.c_float * L)(*scales.tolist()), L
+
+    def _sigma_gradient(self, x, positive_only):
+        """x [M,3] in [0,1] -> (geo [M,16], g_x [M,3]): the density network's output and the gradient of its column 0, the raw
+        density, with respect to x.  The launch chain of DESIGN.md section 2.14.1: nerf_hashgrid_forward, nerf_fused_mlp_forward with
+        `save`, nerf_field_density_seed, nerf_fused_mlp_backward (no parameter gradient, grad_x given), nerf_hashgrid_backward
+        (grad_emb = NULL).  Nothing is differentiated by autograd; M <= fused_mlp.MAX_ROWS."""
+        enc, net, dev, M = self.encoder, self.sigma_net, x.device, x.shape[0]
+        emb = enc.embeddings.detach().contiguous()
+        offsets, scales, L = self._levels()
+        C = emb.shape[1]
+        weights = [l.weight.detach().contiguous() for l in net.layers]
+        biases = [l.bias.detach().contiguous() for l in net.layers]
+        none = [None] * len(weights)
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        feats = new(M, L * C)
+        _lib.call("nerf_hashgrid_forward", x, emb, M, 3, C, L, offsets, scales, feats)
+        geo = new(M, GEO_DIM)
+        save = new(int(_lib.call("nerf_fused_mlp_save_floats", M, net.width, net.n_hidden)))
+        _lib.call("nerf_fused_mlp_forward", feats, M, L * C, net.width, net.n_hidden, GEO_DIM, 0, weights, biases, geo, save)
+        seed = new(M, GEO_DIM)
+        _lib.call("nerf_field_density_seed", geo, GEO_DIM, M, int(bool(positive_only)), seed)
+        gsave = new(int(_lib.call("nerf_fused_mlp_grad_floats", M, net.width, net.n_hidden, GEO_DIM)))
+        g_feats = new(M, L * C)
+        _lib.call("nerf_fused_mlp_backward", feats, None, seed, M, L * C, net.width, net.n_hidden, GEO_DIM, 0, weights, save, gsave,
+                  none, none, g_feats)
+        g_x = new(M, 3)
+        _lib.call("nerf_hashgrid_backward", x, emb, g_feats, M, 3, C, L, offsets, scales, None, g_x)
+        return geo, g_x
+
+    def density_gradient(self, xyz, positive_only=False):
+        """(sigma [n], grad [n,3]) at world points xyz [n,3] on the GPU: the raw density, bit-equal to density(xyz)[:, 0], and its
+        gradient with respect to the world position (exactly zero on an axis along which the point lies outside the box: the
+        normalisation clamps).  positive_only: grad is exactly zero wherever sigma <= 0.  Detached; no ATen op computes: the chain of
+        _sigma_gradient between nerf_field_points and nerf_field_points_backward in point mode, in chunks of GRADIENT_ROWS points."""
+        xyz = self._check_points(xyz, "density_gradient").detach()
+        n_all = xyz.shape[0]
+        sigma = torch.empty(n_all, dtype=torch.float32, device=xyz.device)
+        grad = torch.empty(n_all, 3, dtype=torch.float32, device=xyz.device)
+        frame = self.frame()
+        for i in range(0, n_all, GRADIENT_ROWS):
+            pts = xyz[i:i + GRADIENT_ROWS]
+            n = pts.shape[0]
+            x = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
+            _lib.call("nerf_field_points", pts, None, None, 0, n, 1, None, n, *frame, x)
+            geo, g_x = self._sigma_gradient(x, positive_only)
+            _lib.call("nerf_field_points_backward", pts, None, None, 0, n, 1, None, n, *frame, g_x, None, 0, grad[i:i + n], None, None)
+            sigma[i:i + n].copy_(geo[:, 0])                      # a copy of one column
+        return sigma, grad
+
+    def vertex_normals(self, vertices):
+        """Unit outward normals [V,3] of an iso-surface of the density at its vertices [V,3]: -grad sigma / |grad sigma|, the zero
+        vector where the gradient is zero or not finite -- mesh.vertex_normals' semantics on density_gradient (every point, whatever
+        the sign of sigma); the normalisation of the [V,3] result is three torch operations."""
+        _, g = self.density_gradient(self._as_points(vertices, "vertex_normals"), positive_only=False)
+        nrm = g.norm(dim=-1, keepdim=True)
+        ok = torch.isfinite(nrm) & (nrm > 0)
+        return torch.where(ok, -g / torch.where(ok, nrm, torch.ones_like(nrm)), torch.zeros_like(g))
+
+    def vertex_colors(self, vertices, viewdirs=None):
+        """Colours [V,3] fp32 in [0,1] at the vertices [V,3]: the sigmoid of the colour network's output for the view directions
+        `viewdirs` [V,3] (direction of travel; None: every vertex seen head-on from outside, -vertex_normals, (0, 0, 1) where the
+        normal is zero) -- mesh.vertex_colors' semantics.  The rows go through nerf_field_points (point mode), nerf_sh4_encode and
+        nerf_field_color_inputs with n_samples = 1; the sigmoid of the [V,3] result is one torch operation."""
+        from .mesh import _head_on
+        if isinstance(vertices, torch.Tensor) and viewdirs is not None and \
+                (not isinstance(viewdirs, torch.Tensor) or viewdirs.shape != vertices.shape):
+            raise ValueError(f"viewdirs must be a tensor of the vertices' shape {tuple(vertices.shape)}")
+        pts = self._as_points(vertices, "vertex_colors")
+        if pts.shape[0] == 0:
+            return torch.empty(0, 3, dtype=torch.float32, device=pts.device)
+        if viewdirs is None:
+            viewdirs = _head_on(self.vertex_normals(pts))
+        dirs = viewdirs.detach().to(device=pts.device, dtype=torch.float32).contiguous()
+        frame = self.frame()
+        out = torch.empty(pts.shape[0], 3, dtype=torch.float32, device=pts.device)
+        with torch.no_grad():
+            for i in range(0, pts.shape[0], DENSITY_ROWS):
+                p, d = pts[i:i + DENSITY_ROWS], dirs[i:i + DENSITY_ROWS]
+                n = p.shape[0]
+                x = torch.empty(n, 3, dtype=torch.float32, device=p.device)
+                _lib.call("nerf_field_points", p, None, None, 0, n, 1, None, n, *frame, x)
+                sh = torch.empty(n, SH_DIM, dtype=torch.float32, device=p.device)
+                _lib.call("nerf_sh4_encode", d, n, sh)
+                cin, _ = _ColorInputs.apply(self._geo(x), sh, None, n, n, 1)
+                out[i:i + n] = torch.sigmoid(self._rgb(cin))
+        return out
+
+    def _as_points(self, vertices, what):
+        if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
+            raise ValueError(f"HashField.{what}: vertices must be a tensor [V, 3]")
+        return self._check_points(vertices.detach().to(torch.float32), what)
 
     def occupancy_grid(self, N=128, level=0.0, dilate=1):
         """OccupancyGrid.from_fields(bbox, fine=<the density on an N grid over the box>): where sigma can exceed `level` now.  Runs
@@ -216,7 +392,10 @@ class HashRenderer:
     (16384): rays per launch chain; the result does not depend on it.
 
     Under no_grad, or when no parameter requires grad, the result is detached.  Otherwise the same launches run through autograd
-    functions and every parameter that requires grad gets its gradient; rays that require grad are refused (no ray adjoint is built).
+    functions and every parameter that requires grad gets its gradient.  ray_gradients (False): rays that require grad are refused;
+    True: they get their gradients too -- the same forward launches inside one autograd function whose backward writes g_rays_o and
+    g_rays_d once (nerf_sh4_encode_backward, nerf_field_points_backward), with or without a grid, with trainable or frozen parameters.
+    render_geometry(batch) adds the accumulated opacity and the composited analytic normal; geometry_chunk_rays (4096) is its chunk.
     `net` is the field: training.train_step(renderer, optimizer, ...) works as with a Renderer."""
 
     def __init__(self, field):
@@ -228,6 +407,8 @@ class HashRenderer:
         self.white_bkgd = True
         self.occupancy = None
         self.chunk_rays = 16384
+        self.geometry_chunk_rays = 4096
+        self.ray_gradients = False
         self.stats = None
         self._tables = {}
 
@@ -243,13 +424,19 @@ class HashRenderer:
             t = self._tables[key] = torch.linspace(self.t_near, self.t_far, self.N_samples).to(dev)
         return t
 
-    def _check(self, rays_o, rays_d):
+    def _check(self, rays_o, rays_d, geometry=False):
         """Everything that is refused, before any launch or allocation -> the grid or None."""
         S = self.N_samples
         if isinstance(S, bool) or not isinstance(S, int) or not 1 <= S <= MAX_SAMPLES:
             raise ValueError(f"HashRenderer.N_samples must be an int in [1, {MAX_SAMPLES}], got {S!r}")
         if isinstance(self.chunk_rays, bool) or not isinstance(self.chunk_rays, int) or self.chunk_rays < 1:
             raise ValueError(f"HashRenderer.chunk_rays must be an int >= 1 (rays), got {self.chunk_rays!r}")
+        if not isinstance(self.ray_gradients, bool):
+            raise ValueError(f"HashRenderer.ray_gradients must be a bool, got {self.ray_gradients!r}")
+        if geometry:
+            g = self.geometry_chunk_rays
+            if isinstance(g, bool) or not isinstance(g, int) or not 1 <= g <= MAX_ROWS // S:
+                raise ValueError(f"HashRenderer.geometry_chunk_rays must be an int in [1, {MAX_ROWS} // N_samples] (rays), got {g!r}")
         grid = self.occupancy
         if grid is not None:
             from .occupancy import OccupancyGrid
@@ -260,7 +447,11 @@ class HashRenderer:
         if rays_o.dim() != 3 or rays_o.shape[-1] != 3 or rays_d.shape != rays_o.shape:
             raise ValueError("HashRenderer.render: rays_o and rays_d must both be [B, N, 3]")
         if rays_o.requires_grad or rays_d.requires_grad:
-            raise NotImplementedError("HashRenderer: rays that require grad are not supported (the glue has no ray adjoint)")
+            if geometry:
+                raise NotImplementedError("HashRenderer.render_geometry: rays that require grad are not supported (inference only)")
+            if not self.ray_gradients:
+                raise NotImplementedError("HashRenderer: rays that require grad are not supported (the ray adjoint runs only with "
+                                          "HashRenderer.ray_gradients = True)")
         self.field._check_fp32()
         if not rays_o.is_cuda or not rays_d.is_cuda:
             raise _lib.NerfLibraryError("HashRenderer needs rays on a GPU (cuda) device; got a CPU tensor (there is no CPU fallback)")
@@ -268,32 +459,98 @@ class HashRenderer:
             raise ValueError(f"the occupancy grid is on {grid.device}, the rays on {rays_o.device}")
         return grid
 
+    def _survivors(self, o, d, t, S, grid):
+        """(index, M) of a chunk: the ascending list of the point ids in occupied cells and their number, (None, n * S) without a
+        grid.  With a grid this is the chunk's host synchronisation, and `stats` gets its (evaluated, total)."""
+        dev, n = o.device, o.shape[0]
+        P = n * S
+        if grid is None:
+            return None, P
+        valid = torch.empty(n, S, dtype=torch.uint8, device=dev)
+        _lib.call("nerf_occupancy_mark", o, d, t, 0, n, S, grid.bits["fine"], *grid.lookup_args(), 0, valid)
+        index = torch.empty(P, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(_lib.call("nerf_compact_valid_workspace_bytes", P)), dtype=torch.uint8, device=dev)
+        _lib.call("nerf_compact_valid", valid, P, index, count, ws)
+        M = int(count.item())                          # the host synchronisation of the culled path
+        if isinstance(self.stats, list):
+            self.stats.append((M, P))
+        return index, M
+
     def _chunk(self, o, d, t, S, grid, white):
         """One chunk of n rays -> (rgb [n,3], depth [n]); every step is enqueued on the current stream."""
         field, dev, n = self.field, o.device, o.shape[0]
-        P, M, index = n * S, n * S, None
-        if grid is not None:
-            valid = torch.empty(n, S, dtype=torch.uint8, device=dev)
-            _lib.call("nerf_occupancy_mark", o, d, t, 0, n, S, grid.bits["fine"], *grid.lookup_args(), 0, valid)
-            index = torch.empty(P, dtype=torch.int32, device=dev)
-            count = torch.empty(1, dtype=torch.int32, device=dev)
-            ws = torch.empty(int(_lib.call("nerf_compact_valid_workspace_bytes", P)), dtype=torch.uint8, device=dev)
-            _lib.call("nerf_compact_valid", valid, P, index, count, ws)
-            M = int(count.item())                      # the host synchronisation of the culled path
-            if isinstance(self.stats, list):
-                self.stats.append((M, P))
+        index, M = self._survivors(o.detach(), d.detach(), t, S, grid)
         if M == 0:
             raw = torch.zeros(n, S, 4, dtype=torch.float32, device=dev)
         else:
-            lo, hi, extent = field.frame()
-            x = torch.empty(M, 3, dtype=torch.float32, device=dev)
-            _lib.call("nerf_field_points", o, d, t, 0, n, S, index, M, lo, hi, extent, x)
+            if torch.is_grad_enabled() and (o.requires_grad or d.requires_grad):       # (only with ray_gradients: _check)
+                x, sh = _RayInputs.apply(o, d, t, index, M, S, field.frame())
+            else:
+                lo, hi, extent = field.frame()
+                x = torch.empty(M, 3, dtype=torch.float32, device=dev)
+                _lib.call("nerf_field_points", o, d, t, 0, n, S, index, M, lo, hi, extent, x)
+                sh = torch.empty(n, SH_DIM, dtype=torch.float32, device=dev)
+                _lib.call("nerf_sh4_encode", d, n, sh)
             geo = field._geo(x)
-            sh = torch.empty(n, SH_DIM, dtype=torch.float32, device=dev)
-            _lib.call("nerf_sh4_encode", d, n, sh)
             cin, sigma_rows = _ColorInputs.apply(geo, sh, index, M, n, S)
             raw = _RawScatter.apply(field._rgb(cin), sigma_rows, index, M, n, S)
         return _Composite.apply(raw, t, white)
+
+    def _geometry_chunk(self, o, d, t, S, grid, white):
+        """One chunk of n rays -> (rgb [n,3], depth [n], acc [n], normal [n,3]), detached: the launches of _chunk with the density
+        network's `save` kept, then the gradient chain with positive_only on the surviving rows, scattered by id, and
+        nerf_composite_normals."""
+        field, dev, n = self.field, o.device, o.shape[0]
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        index, M = self._survivors(o, d, t, S, grid)
+        grad = new(n, S, 3)                            # rows of culled samples stay unwritten: their raw sigma is 0, they are not used
+        if M == 0:
+            raw = torch.zeros(n, S, 4, dtype=torch.float32, device=dev)
+        else:
+            frame = field.frame()
+            x = new(M, 3)
+            _lib.call("nerf_field_points", o, d, t, 0, n, S, index, M, *frame, x)
+            geo, g_x = field._sigma_gradient(x, True)
+            sh = new(n, SH_DIM)
+            _lib.call("nerf_sh4_encode", d, n, sh)
+            cin, sigma_rows = new(M, GEO_DIM + SH_DIM), new(M)
+            _lib.call("nerf_field_color_inputs", geo, sh, index, M, n, S, cin, sigma_rows)
+            raw = torch.zeros(n, S, 4, dtype=torch.float32, device=dev)
+            _lib.call("nerf_field_raw_scatter", field._rgb(cin), sigma_rows, index, M, n * S, raw)
+            _lib.call("nerf_field_points_backward", o, d, t, 0, n, S, index, M, *frame, g_x, None, 1, grad, None, None)
+        rgb, depth, acc, normal = new(n, 3), new(n), new(n), new(n, 3)
+        _lib.call("nerf_composite", raw, t, 0, n, S, white, rgb, depth, None)
+        _lib.call("nerf_composite_normals", raw, t, 0, n, S, grad, normal, acc)
+        return rgb, depth, acc, normal
+
+    def render_geometry(self, batch):
+        """(rgb [B*N,3], depth [B*N], acc [B*N], normal [B*N,3]): rgb and depth as render(batch) returns them (bit-equal), acc =
+        sum_i w_i the accumulated opacity and normal = sum_i w_i n_i with n_i = -grad sigma / |grad sigma| at the samples with
+        sigma_i > 0, else 0 (nerf_composite_normals; not renormalised, |normal| <= acc) -- Renderer.render_geometry's outputs.  The
+        gradient is analytic, in world coordinates.  Honours occupancy and stats.  Inference only: rays
+        that require grad are refused, the result is detached under any grad mode.  geometry_chunk_rays (4096) rays per launch
+        chain (the chain keeps save, gsave, the features and their gradient per row); the result does not depend on it."""
+        rays_o, rays_d = batch["rays_o"], batch["rays_d"]
+        grid = self._check(rays_o, rays_d, geometry=True)
+        dev = rays_o.device
+        n = rays_o.shape[0] * rays_o.shape[1]
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        if n == 0:
+            return new(0, 3), new(0), new(0), new(0, 3)
+        o = rays_o.reshape(-1, 3).to(torch.float32).contiguous()
+        d = rays_d.reshape(-1, 3).to(torch.float32).contiguous()
+        S, white, step = self.N_samples, int(bool(self.white_bkgd)), self.geometry_chunk_rays
+        t = self._get_table(dev)
+        with torch.no_grad():
+            outs = [self._geometry_chunk(o[i:i + step], d[i:i + step], t, S, grid, white) for i in range(0, n, step)]
+        if len(outs) == 1:
+            return outs[0]
+        return tuple(torch.cat([out[k] for out in outs], 0) for k in range(4))
 
     def render(self, batch):
         rays_o, rays_d = batch["rays_o"], batch["rays_d"]

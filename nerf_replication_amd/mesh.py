@@ -437,27 +437,32 @@ def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None,
     passed through to write_ply_colors.  Arrays must match the vertices that are written.  With the defaults the result and the file are what
     they always were.
 
-    queryfn: a Network (the fast path: density_grid on its fine model), or a callable taking xyz [n,3] on the GPU whose
-    result's [..., 0] is the density (the reference's protocol; evaluated on explicit grid points in batches).  level and N
+    queryfn: a Network (the fast path: density_grid on its fine model), a HashField (its density on the grid points; normals=True /
+    colors=True are its vertex_normals / vertex_colors, and bbox=None is the field's own box), or a callable taking xyz [n,3] on
+    the GPU whose result's [..., 0] is the density (the reference's protocol; evaluated on explicit grid points in batches).  level and N
     default to cfg.level / cfg.resolution inside the reference, else 32.0 / 256.  Arguments are checked before any GPU work."""
     cfg = _reference_cfg()
     if level is None:
         level = getattr(cfg, "level", DEFAULT_LEVEL) if cfg is not None else DEFAULT_LEVEL
     if N is None:
         N = getattr(cfg, "resolution", DEFAULT_RESOLUTION) if cfg is not None else DEFAULT_RESOLUTION
+    from .hashfield import HashField
+    field = queryfn if isinstance(queryfn, HashField) else None
     if not isinstance(queryfn, Network) and not callable(queryfn):
         raise TypeError("queryfn must be a Network or a callable xyz [n,3] -> [..., 0] density")
     if isinstance(level, bool) or not isinstance(level, numbers.Real) or not np.isfinite(level):
         raise ValueError(f"level must be a finite number, got {level!r}")
+    if bbox is None and field is not None:
+        bbox = field.bbox
     if bbox is None:
         raise ValueError("bbox is required: 6 numbers (min xyz, max xyz)")
     if not isinstance(output_path, (str, bytes)) and not hasattr(output_path, "__fspath__"):
         raise TypeError(f"output_path must be a path, got {output_path!r}")
-    if normals is True and not isinstance(queryfn, Network):
+    if normals is True and not isinstance(queryfn, Network) and field is None:
         raise TypeError("normals=True needs a Network as queryfn (vertex_normals); pass an array [V,3] otherwise")
     if normals is False:
         normals = None
-    if colors is True and not isinstance(queryfn, Network):
+    if colors is True and not isinstance(queryfn, Network) and field is None:
         raise TypeError("colors=True needs a Network as queryfn (vertex_colors); pass an array [V,3] otherwise")
     if colors is False:
         colors = None
@@ -465,6 +470,8 @@ def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None,
     axes, origin, step = grid_axes(bbox, N)
     if isinstance(queryfn, Network):
         grid = density_grid(queryfn, bbox, N, model="fine")
+    elif field is not None:                            # a HashField: its density on explicit grid points, on the field's device
+        grid = _query_grid(field.density, axes, field.wbounds.device)
     else:
         if not torch.cuda.is_available():
             raise _lib.NerfLibraryError("extract_mesh needs a GPU; there is no CPU fallback")
@@ -474,8 +481,9 @@ def extract_mesh(queryfn, level=None, bbox=None, output_path="test.ply", N=None,
         vertices, faces, _ = filter_components(vertices, faces, min_triangles, keep_largest)
     made_normals = normals is True
     if made_normals:
-        normals = vertex_normals(queryfn, vertices, model="fine")
+        normals = field.vertex_normals(vertices) if field is not None else vertex_normals(queryfn, vertices, model="fine")
     if colors is True:                             # (the normals just computed are the ones vertex_colors would compute again)
-        colors = vertex_colors(queryfn, vertices, _head_on(normals) if made_normals else None, model="fine")
+        head_on = _head_on(normals) if made_normals else None
+        colors = field.vertex_colors(vertices, head_on) if field is not None else vertex_colors(queryfn, vertices, head_on, model="fine")
     _write_ply(output_path, vertices, faces, normals, colors)
     return vertices, faces

@@ -1,6 +1,9 @@
 // Weight-gradient GEMM of the 256 x 256 layers on the bf16 matrix cores with three-way split operands
 // (fp32-accurate: v = hi + mid + lo, 8 mantissa bits each, exact truncation splits; the six products down
-// to 2^-16 are kept, the dropped ones are below 2^-24).  (included by nerf_kernels.hip)
+// to 2^-16 are kept.  The three dropped ones, mid lo + lo mid + lo lo, are below 2^-24 of the term only for typical
+// operands (median 2^-25); they reach 2^-21 of it for significands 1.0000000 followed by ones, and are bounded by
+// (2^-20 + 2^-27) of it: |mid| < 2^-7 |v|, |lo| < 2^-14 |v|.  tests/test_wgrad_reference_cpu.py holds these figures.)
+// (included by nerf_kernels.hip)
 //
 //   dW[o][i] += sum_p dZ[p][o] * Hin[p][i]        (autograd of nn.Linear, network.py:22-47)
 //

@@ -140,6 +140,32 @@ def probe_points(seed, zero_axis, n):
     return pts, dirs
 
 
+def probe_rays(gen, zero_axis, n_rays, S, per_ray):
+    """Rays whose points and unit directions are exact: o on the 1/4 grid with o[zero_axis] = 0, d = +-e_j * {1, 2, 4} for an axis
+    j != zero_axis (d / ||d|| is exactly +-e_j), depths multiples of 1/4 in [0, 1] and |o_j| <= 4 - |d|, so o + d t stays in [-4, 4].
+    The other free coordinate takes four values, which keeps the distinct (point, direction) pairs of a network below 600.
+    -> o [n,3], d [n,3], t ([n,S] per ray, [S] shared), points [n,S,3], unit directions [n,3]."""
+    free = [a for a in range(3) if a != zero_axis]
+    pick = torch.randint(0, 2, (n_rays,), generator=gen)
+    j = torch.tensor(free)[pick]
+    k = torch.tensor(free)[1 - pick]
+    scale = 2.0 ** torch.randint(0, 3, (n_rays,), generator=gen).float()
+    sign = torch.randint(0, 2, (n_rays,), generator=gen).float() * 2 - 1
+    rows = torch.arange(n_rays)
+    d = torch.zeros(n_rays, 3)
+    d[rows, j] = sign * scale
+    o = torch.zeros(n_rays, 3)
+    span = (4 - scale) * 4                                            # |o_j| <= 4 - |d| in quarter steps
+    o[rows, j] = torch.floor((torch.rand(n_rays, generator=gen) * 2 - 1) * span).clamp(-span, span) / 4
+    o[rows, k] = torch.tensor([-2.75, -0.25, 1.5, 3.0])[torch.randint(0, 4, (n_rays,), generator=gen)]
+    t = torch.sort(torch.randint(0, 5, (n_rays if per_ray else 1, S), generator=gen).float() / 4, dim=-1).values
+    unit = torch.zeros(n_rays, 3)
+    unit[rows, j] = sign
+    pts = o[:, None, :] + d[:, None, :] * t[:, :, None]              # exact in fp32
+    assert pts.abs().max() <= 4 and torch.all(pts[..., zero_axis] == 0)
+    return o, d, (t if per_ray else t[0]).contiguous(), pts, unit
+
+
 def probe_network(seed, zero_axis):
     """A sub-model (24 tensors, keys without prefix) of +-1 weights and small integer biases: every row holds two +1 and two -1 (the
     two heads: four and four) at seeded columns; layer 0, the skip part of layer 5 and the direction part of the views layer use

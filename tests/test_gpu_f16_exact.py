@@ -27,31 +27,6 @@ def amd():
     return pkg
 
 
-def _probe_rays(gen, zero_axis, n_rays, S, per_ray):
-    """Rays whose points and unit directions are exact: o on the 1/4 grid with o[zero_axis] = 0, d = +-e_j * {1, 2, 4} for an axis
-    j != zero_axis (d / ||d|| is exactly +-e_j), depths multiples of 1/4 in [0, 1] and |o_j| <= 4 - |d|, so o + d t stays in [-4, 4].
-    The other free coordinate takes four values, which keeps the distinct (point, direction) pairs of a network below 600."""
-    free = [a for a in range(3) if a != zero_axis]
-    pick = torch.randint(0, 2, (n_rays,), generator=gen)
-    j = torch.tensor(free)[pick]
-    k = torch.tensor(free)[1 - pick]
-    scale = 2.0 ** torch.randint(0, 3, (n_rays,), generator=gen).float()
-    sign = torch.randint(0, 2, (n_rays,), generator=gen).float() * 2 - 1
-    rows = torch.arange(n_rays)
-    d = torch.zeros(n_rays, 3)
-    d[rows, j] = sign * scale
-    o = torch.zeros(n_rays, 3)
-    span = (4 - scale) * 4                                            # |o_j| <= 4 - |d| in quarter steps
-    o[rows, j] = torch.floor((torch.rand(n_rays, generator=gen) * 2 - 1) * span).clamp(-span, span) / 4
-    o[rows, k] = torch.tensor([-2.75, -0.25, 1.5, 3.0])[torch.randint(0, 4, (n_rays,), generator=gen)]
-    t = torch.sort(torch.randint(0, 5, (n_rays if per_ray else 1, S), generator=gen).float() / 4, dim=-1).values
-    unit = torch.zeros(n_rays, 3)
-    unit[rows, j] = sign
-    pts = o[:, None, :] + d[:, None, :] * t[:, :, None]              # exact in fp32
-    assert pts.abs().max() <= 4 and torch.all(pts[..., zero_axis] == 0)
-    return o, d, (t if per_ray else t[0]).contiguous(), pts, unit
-
-
 @functools.lru_cache(maxsize=None)
 def _case(seed, zero_axis):
     """Everything of one probe network that the CPU computes, once: the state dict, 1024 distinct points with their float64 results,
@@ -63,7 +38,7 @@ def _case(seed, zero_axis):
     gen = torch.Generator().manual_seed(31 * seed + zero_axis)
     rays = {}
     for name, n_rays, S, per_ray in (("shared", 3, 64, False), ("per_ray", 700, 192, True)):
-        o, d, t, rpts, unit = _probe_rays(gen, zero_axis, n_rays, S, per_ray)
+        o, d, t, rpts, unit = R.probe_rays(gen, zero_axis, n_rays, S, per_ray)
         rows = torch.cat([rpts, unit[:, None, :].expand(n_rays, S, 3)], -1).reshape(-1, 6)
         uniq, inverse = torch.unique(rows, dim=0, return_inverse=True)
         up, ud = uniq[:, :3].contiguous(), uniq[:, 3:].contiguous()

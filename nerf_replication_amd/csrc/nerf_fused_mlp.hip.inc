@@ -1,5 +1,5 @@
 // Generic small fused ReLU MLP on fp32 MFMA: forward (inference / SAVE), backward chain, weight and bias gradients (DESIGN.md section 2.13).
-// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH / mfma32 / wgrad_impl).  The C surface is
+// Needs nerf_train_backward.hip.inc ahead of it (wgrad_impl); mfma32 comes from nerf_mlp_common.h.  The C surface is
 // include/nerf_mi355x_nn.h.  fp32 throughout; the unit is compiled with -ffp-contract=off and every fused multiply-add here is an MFMA.
 //
 //     h_0 = relu(W_0 x + b_0),  h_i = relu(W_i h_{i-1} + b_i)  (i < n_hidden),  z = W_out h_last + b_out,  y = z or sigmoid(z)
@@ -22,6 +22,8 @@
 // the rows: only the staging differs.  dz and grad_x are written, never accumulated, in a fixed order: bit-reproducible.
 
 #include "../../include/nerf_mi355x_nn.h"
+#include "nerf_host.h"
+#include "nerf_mlp_common.h"
 
 namespace {
 

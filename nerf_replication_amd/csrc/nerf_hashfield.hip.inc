@@ -1,7 +1,6 @@
 // Ray-side glue of the hash-grid radiance field (DESIGN.md section 2.14): what sits between nerf_occupancy_mark / nerf_compact_valid,
-// nerf_hashgrid_forward, nerf_fused_mlp_forward and nerf_composite.  Included at the end of nerf_kernels.hip (uses its fail /
-// NERF_LAUNCH); the declarations and every formula are in include/nerf_mi355x_nn.h.  fp32 throughout; the unit is compiled with
-// -ffp-contract=off and every operation below is written with its own rounding, so each kernel is bit for bit the fp32 restatement in
+// nerf_hashgrid_forward, nerf_fused_mlp_forward and nerf_composite.  The declarations and every formula are in
+// include/nerf_mi355x_nn.h.  fp32 throughout; the unit is compiled with -ffp-contract=off and every operation below is written with its own rounding, so each kernel is bit for bit the fp32 restatement in
 // tests/hashfield_reference.py.  Memory-bound copies and a few flops per row: 256 threads, no LDS, no atomics; rows are indexed with
 // 32 bits (the entries refuse more than 2^31 - 1 point ids), addresses are formed in 64 bits.
 //
@@ -15,6 +14,7 @@
 //                           skipped (the scatter) or read as zero (the gather), so no index reaches outside `raw`
 
 #include "../../include/nerf_mi355x_nn.h"
+#include "nerf_host.h"
 #include "../../include/nerf_mi355x_field.h"      // the spatial adjoint of the same glue: the kernels behind "the spatial adjoint" below
 
 namespace {

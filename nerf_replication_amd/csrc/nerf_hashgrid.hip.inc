@@ -1,7 +1,6 @@
 // Multiresolution hash-grid encoding (instant-NGP): forward, embedding gradient, input gradient (DESIGN.md section 2.12).
-// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH).  fp32 throughout; the unit is compiled with
-// -ffp-contract=off, so every multiply and add below rounds on its own and the forward is bit for bit the fixed-order fp32
-// restatement in tests/hashgrid_reference.py.
+// fp32 throughout; the unit is compiled with -ffp-contract=off, so every multiply and add below rounds on its own and the forward
+// is bit for bit the fixed-order fp32 restatement in tests/hashgrid_reference.py.
 //
 // A level is a table of n = offsets[l+1] - offsets[l] rows of C floats.  A point x in [0,1]^D sits in the cell
 //     pos_d = x_d * scale + 0.5,  g_d = floor(pos_d),  f_d = pos_d - g_d                       (scale: host float, one per level)
@@ -21,6 +20,7 @@
 //                    contiguous rate.)  No-return global fp32 atomic adds into a buffer the caller zeroed: the entry accumulates.
 //   input grad       one thread per point, levels in a loop; the 2^D corner rows are loaded once per level and serve all D axes;
 //                    nothing is stored in the forward.  grad_x is written, not accumulated; no atomics.
+#include "nerf_host.h"
 
 namespace {
 

@@ -1,5 +1,4 @@
 // Iso-surface extraction: marching tetrahedra over the six-tetrahedra (Kuhn) split of every grid cell (DESIGN.md section 2.8).
-// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH / Carver).
 //
 // Grid point (i, j, k) has the linear id g = (i*ny + j)*nz + k and the value field[g * stride]; a cell is named by its lowest
 // corner.  Every edge of the split runs from a point p to p + e, e in {0,1}^3 \ 0: seven edge types t = 4 ex + 2 ey + ez, owned
@@ -12,6 +11,7 @@
 // whole topology from these words (the field gives only the interpolation values), so what it writes stays inside the counted
 // rows whatever the field holds by then.  Vertex ids ascend with (owner id, edge type), triangles with (cell id, tetrahedron,
 // triangle); nothing is atomic, so two runs write the same bytes.
+#include "nerf_host.h"
 #include "nerf_isosurface_table.inc"
 #include "nerf_scan.hip.inc"
 

@@ -18,10 +18,8 @@
 
 #include "../../include/nerf_mi355x.h"
 #include "nerf_layout.h"
-#include "nerf_mlp_f32.hip.inc"        // MlpArgs, TrainSave, shared device helpers
-#include "nerf_mlp_f16.hip.inc"        // ring constants
+#include "nerf_mlp_common.h"           // MlpArgs / BwdArgs, TrainSave / TrainGrad, types, ring and workgroup constants
 #include "nerf_mlp_f32x.hip.inc"
-#include "nerf_mlp_bwd_f32.hip.inc"    // BwdArgs, TrainGrad
 #include "nerf_mlp_bwd_f32x.hip.inc"
 #include "nerf_kernels_x.inst.inc"
 #include "nerf_timing_guard.h"         // after the kernel includes: refuses a build with a stray timing switch

@@ -1,6 +1,6 @@
 // Connected components of an indexed triangle mesh and the filter that keeps whole components (DESIGN.md section 2.11).
-// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH / Carver and the ordered compaction's
-// nerf_compact_scan_kernel; compact_block_rank comes from nerf_scan.hip.inc).
+// Needs nerf_sampling.hip.inc ahead of it (the ordered compaction's nerf_compact_scan_kernel); compact_block_rank comes from
+// nerf_scan.hip.inc.
 //
 // Union-find over parent[V] (int32), lock-free.  A root is always linked under a SMALLER root, so parent[x] <= x holds at every
 // moment, every chain strictly descends, and the root a tree ends up with is the smallest id in it whatever the order in which the
@@ -16,6 +16,7 @@
 //     under (< x) and the union goes on from there: a + b strictly falls with every failed CAS.  No loop waits for another thread.
 //   * labels are read only in later launches than the unions (the kernel boundary is the synchronisation).
 
+#include "nerf_host.h"
 #include "nerf_scan.hip.inc"
 
 namespace {

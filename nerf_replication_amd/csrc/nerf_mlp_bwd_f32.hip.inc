@@ -1,5 +1,5 @@
 // Backward (data-gradient) chain of the NeRF MLP, exact fp32 on v_mfma_f32_32x32x2_f32.
-// (included by nerf_kernels.hip)
+// (needs nerf_mlp_f32.hip.inc ahead of it: the weight ring, gemm_tiles and the taps)
 //
 // What autograd does for NeRF.forward (network.py:49-74) between grad(raw [P,4]) and
 // grad(z_l) of every layer, plus grad(points) through the positional encoding (freq.py:31-32):
@@ -10,40 +10,6 @@
 // accumulator layout and is fed unchanged as the next (previous) layer's B operand; only the weight
 // stream differs (transposed, nerf_pack_bwd_kernel).  ReLU masks come from the activations the
 // SAVE-mode forward stored; every g_z is stored row-major for the weight-gradient GEMMs.
-struct BwdArgs {
-  const float* rays_o; const float* rays_d; const float* tvals; long long t_ray_stride;
-  long long n_points; int n_samples;
-  const float* packed_bwd;   // transposed stream + head weights (nerf_layout.h kBwd*)
-  const float* draw;         // [P,4] gradient of raw (r,g,b,sigma)
-  const float* save;         // TrainSave of the forward
-  float* gsave;              // TrainGrad: g_zv [P,128], g_f [P,256], g_z7..g_z0 [P,256] each
-  float* g_t;                // optional [P]: d loss / d t through the points (= g_x . rays_d).  Ray mode, bit 0 set: the address
-                             // (bit cleared) of g_x [P,3] = d loss / d (o + d t) instead, written in place of g_t (the launcher's
-                             // encoding, mlp_backward_impl: ONE output pointer stays live across the chain, as before; a second
-                             // one cost the f32x density chain an SGPR spill to scratch)
-  // point mode (Network.forward under autograd, network.py:199-258: explicit points instead of o + d*t)
-  const float* pts;          // [P,3]
-  float* g_x;                // optional [P,3]: d loss / d points
-  int density_only;          // fp32 chain: d loss / d rgb is identically zero (coarse pass of a training step): the colour
-                             // branch (views, feature) is skipped, the chain starts at g_h7 = w_alpha * g_sigma
-  // live-tile list (fp32 chain, optional): workgroup slot i handles the 32-point tile live_tiles[i], slots >= *n_live exit.
-  // A tile is dead when d loss / d raw is zero at all of its points -- then every g_z of the tile is zero, so are its
-  // contributions to the weight gradients and to g_t / g_x, and nothing of it needs computing (see nerf_tile_flags_kernel)
-  const int* live_tiles;
-  const int* n_live;
-};
-
-struct TrainGrad {          // pad32(P) rows per region, like TrainSave
-  static constexpr long long off_gzv(long long P) { return 0; }
-  static constexpr long long off_gf(long long P) { return TrainSave::pad32(P) * 128; }
-  static constexpr long long off_gz(long long P, int l) { return TrainSave::pad32(P) * (384 + 256LL * (7 - l)); }   // l = 7..0
-  // behind the rows, as 32-bit integers: one flag per 32-point tile, the ascending list of live tiles, their count
-  static constexpr long long n_tiles(long long P) { return TrainSave::pad32(P) / 32; }
-  static constexpr long long off_flags(long long P) { return TrainSave::pad32(P) * (384 + 2048); }
-  static constexpr long long off_live(long long P) { return off_flags(P) + ((n_tiles(P) + 3) & ~3LL); }
-  static constexpr long long off_count(long long P) { return off_live(P) + ((n_tiles(P) + 3) & ~3LL); }
-  static constexpr long long floats(long long P) { return off_count(P) + 4; }
-};
 
 // acc *= (activation > 0) from the sign bits the SAVE forward collected (TrainSave::off_bits): bit 16*(t&1) + r of word
 // t>>1 belongs to register r of tile t.  v_bfe_i32 turns the bit into 0 / ~0, v_and applies it: two VALU per value,

@@ -1,7 +1,8 @@
 // Backward (data-gradient) chain of the NeRF MLP on the fp16 matrix cores with split (hi + 2^-11 lo)
 // operands: the f32x counterpart of nerf_mlp_bwd_f32.hip.inc (same math, same saved tensors, same
 // outputs), structured like nerf_mlp_f32x.hip.inc (LDS-DMA ring of (hi, lo) fragment pairs, m-outer
-// out-tiles, gradients as packed register-resident B fragments).  (included by nerf_kernels.hip)
+// out-tiles, gradients as packed register-resident B fragments).
+// (needs nerf_mlp_f32x.hip.inc ahead of it: XRing, the training layer skeleton, XRowStage)
 //
 // Stream (nerf_pack_f16_kernel<bwd>): transposed weights, A fragment of (in-feature tile m, k-step s over
 // the layer's OUTPUT features) = W[act16_feat(s, j, lane>>5)][32 m + (lane&31)], consumption order
@@ -68,7 +69,7 @@ __device__ __forceinline__ void xb_epilogue_chunk(XPending& t, h8* OUTh, h8* OUT
   f32x2 v;
   v.x = fmaf(t.al[2 * Q], kXLoInv, t.ah[2 * Q]); v.y = fmaf(t.al[2 * Q + 1], kXLoInv, t.ah[2 * Q + 1]);
   if constexpr (EXTRA) {
-    const f32x2 w = *reinterpret_cast<const __attribute__((address_space(3))) f32x2*>(extra_w + MM * 16 + 2 * Q);
+    const f32x2 w = *reinterpret_cast<lds_cf32x2*>(extra_w + MM * 16 + 2 * Q);
     v.x = fmaf(w.x, extra_g, v.x); v.y = fmaf(w.y, extra_g, v.y);
   }
   if constexpr (MASK) {

@@ -1,6 +1,5 @@
 // Fused positional-encoding + NeRF MLP with fp16 activations/weights and fp32 accumulation on
-// v_mfma_f32_32x32x16_f16 (BASELINE config 5).  Included by nerf_kernels.hip.
-//
+// v_mfma_f32_32x32x16_f16 (BASELINE config 5).//
 // Same replaced reference lines as nerf_mlp_f32.hip.inc (network.py:199-258, :49-74, freq.py:31-32;
 // in ray mode volume_renderer.py:63/:267/:314).  Not the parity path: tolerance is PSNR-based.
 //
@@ -20,25 +19,9 @@
 //  * sigma and rgb heads are 1-out-tile MFMA layers (rows 0 / 0..2), so (r,g,b,sigma) of point p end
 //    up in registers 0..2 / 0 of lane p: one float4 store, no cross-lane traffic.
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+#include "nerf_mlp_common.h"
 
-constexpr int kF16Waves = 8;
-constexpr int kF16Threads = kF16Waves * 64;
-constexpr int kF16TilePts = kF16Waves * 32;                 // points per workgroup tile
-constexpr int kF16RingSlots = 4;
-constexpr int kF16LdsBytes = nerf::kF16ConstBytes + kF16RingSlots * nerf::kF16ChunkBytes;   // 147456
 constexpr int kF16DmaPerWave = nerf::kF16ChunkFrags / kF16Waves;                            // 4
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef const __attribute__((address_space(3))) float lds_cfloat;
 
 // timing-only switches (tools/ab_bench.py builds variants with -D...)
 #ifndef NERF_F16_HACK_NOADV
@@ -108,9 +91,6 @@ __device__ __forceinline__ void ring_advance(FragRing& r) {
   r.cur_slot = (r.cur_slot + 1) & (kF16RingSlots - 1);
   ring_set_slots(r);
 }
-
-typedef const __attribute__((address_space(3))) f32x4 lds_cf32x4;
-typedef const __attribute__((address_space(3))) h8 lds_ch8;
 
 __device__ __forceinline__ h8 frag_read(const FragRing& r, int pfi) {   // pfi in [0, 64): static
   const lds_char* base = pfi < nerf::kF16ChunkFrags ? r.lcur : r.lnext;
@@ -195,8 +175,7 @@ __device__ __forceinline__ void gemm16_layer(FragRing& r, lds_cfloat* bias_lds_h
 #endif
     h8 o0, o1;
     if (NERF_F16_HACK_NOEPI) {          // keep the data dependence, drop the arithmetic
-      typedef float f4 __attribute__((ext_vector_type(4)));
-      f4 a0 = {acc[0], acc[1], acc[2], acc[3]}, a1 = {acc[8], acc[9], acc[10], acc[11]};
+      f32x4 a0 = {acc[0], acc[1], acc[2], acc[3]}, a1 = {acc[8], acc[9], acc[10], acc[11]};
       OUT[2 * m] = __builtin_bit_cast(h8, a0);
       OUT[2 * m + 1] = __builtin_bit_cast(h8, a1);
       continue;

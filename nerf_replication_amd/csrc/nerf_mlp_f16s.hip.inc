@@ -4,6 +4,7 @@
 // 1-KiB A fragment per 16 384 MACs -- so the two kernels are an A/B of the MFMA shape at equal output tile per wave and equal
 // LDS bytes per FLOP (round-2 VERDICT item 3; MI355X_MICROARCH.md "DVFS give-back" item 7: on random data the chip holds a
 // higher clock on the 16x16x32 loop).  Layout: nerf_layout.h "f16s".
+// Needs nerf_mlp_f16.hip.inc ahead of it (FragRing and its protocol).
 //
 // What changes with the shape:
 //  * a wave's 32 points are two column groups of 16 (points 16n + c, lane = (c, g)); every A fragment feeds two MFMAs;
@@ -13,7 +14,7 @@
 //    2g, 2g+1 by one exact sincos + one angle doubling, octaves 8, 9 and the raw coordinates as two per-lane-selected extras;
 //  * biases are read in natural order (16m + 4g), straight into both groups' accumulators.
 
-typedef const __attribute__((address_space(3))) f32x4 lds_cf32x4s;
+#include "nerf_mlp_common.h"
 
 __device__ __forceinline__ f32x4 mfma16s(h8 a, h8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
@@ -31,7 +32,7 @@ __device__ __forceinline__ void gemm16s_tile(FragRing& r, int m, const h8* B1a, 
   for (int s = 0; s < KS; ++s) {
     const int fi = (F0 + m * KS + s) & (nerf::kF16ChunkFrags - 1);
     r.pf[(fi + kPfDist) % kPfRing] = frag_read(r, fi + kPfDist);
-    if (s == kBiasAt && next_bias != nullptr) nxt = *reinterpret_cast<lds_cf32x4s*>(next_bias);
+    if (s == kBiasAt && next_bias != nullptr) nxt = *reinterpret_cast<lds_cf32x4*>(next_bias);
     __builtin_amdgcn_sched_barrier(0x406);     // VALU/SALU/TRANS may cross; LDS reads and MFMAs keep this order
     const h8 w = r.pf[fi % kPfRing];
     acc0 = mfma16s(w, s < KS1 ? B1a[s] : B2a[s - KS1], s == 0 ? cinit : acc0);
@@ -209,7 +210,7 @@ void nerf_mlp_f16s_kernel(MlpArgs a) {
   }
   for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     h8 X[2][8], Y[2][8];
-    f32x4 c = *reinterpret_cast<lds_cf32x4s*>(bias_g);                           // bias of (L0, out-tile 0): one exposed LDS round trip per tile
+    f32x4 c = *reinterpret_cast<lds_cf32x4*>(bias_g);                           // bias of (L0, out-tile 0): one exposed LDS round trip per tile
     gemm16s_layer<2, 0, 16, 0>(r, bias_g, PE[0], PE[1], PE[0], PE[1], X[0], X[1], true, c, bias_g + 256);   // L0
 #pragma unroll 1
     for (int it = 0; it < 2; ++it) {                                            // L1..L4

@@ -1,5 +1,4 @@
 // Fused positional-encoding + 8+1-layer NeRF MLP, exact fp32 on v_mfma_f32_32x32x2_f32.
-// (included by nerf_kernels.hip)
 //
 // Replaces, per 32-point tile, the reference's
 //   Network.forward   src/models/nerf/network.py:199-258   (PE + batchify(512) loop)
@@ -20,29 +19,7 @@
 //   8256 MFMAs x 64 cycles per tile vs ~1.5k VALU instructions (9280 before feature_linear was folded into the views
 //   layer, nerf_layout.h kFold*; the training forward still issues 9280: it keeps the feature GEMM for the backward pass).
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// Branch-free sin/cos for |x| < ~1e4: 3-term Cody-Waite reduction by pi/2 (FMA) + the classic
-// single-precision minimax polynomials on [-pi/4, pi/4]; abs error ~1e-7.  Small register
-// footprint and no slow path, so it can sit in the middle of the kernel (the ocml sincosf's
-// large-argument path forced ~50 spills when placed between layers).
-__device__ __forceinline__ void sincos_cw(float x, float& s, float& c) {
-  const float n = rintf(x * 0.636619772367581343f);            // x * 2/pi
-  float r = fmaf(n, -1.5703125f, x);
-  r = fmaf(n, -4.837512969970703125e-4f, r);
-  r = fmaf(n, -7.54978995489188216e-8f, r);
-  const float r2 = r * r;
-  const float sp = fmaf(r * r2, fmaf(r2, fmaf(r2, -1.9515295891e-4f, 8.3321608736e-3f), -1.6666654611e-1f), r);
-  const float cp = fmaf(r2 * r2, fmaf(r2, fmaf(r2, 2.443315711809948e-5f, -1.388731625493765e-3f), 4.166664568298827e-2f),
-                        fmaf(r2, -0.5f, 1.0f));
-  const int q = (int)n;
-  const float ss = (q & 1) ? cp : sp;
-  const float cc = (q & 1) ? sp : cp;
-  s = (q & 2) ? -ss : ss;
-  c = ((q + 1) & 2) ? -cc : cc;
-}
+#include "nerf_mlp_common.h"
 
 // timing-only diagnostics for tools/ab_bench.py (never set in the shipped build: they break numerics)
 #ifndef NERF_F32_WG_WAVES
@@ -59,99 +36,15 @@ __device__ __forceinline__ void sincos_cw(float x, float& s, float& c) {
 #define NERF_BWD_HACK_NOMASK 0
 #endif
 
-struct MlpArgs {
-  const float* pts;        // [P,3] explicit points, or nullptr -> o + d*t
-  const float* rays_o;     // [N,3]
-  const float* rays_d;     // [N,3]
-  const float* viewdirs;   // [N,3] or nullptr -> rays_d / ||rays_d||
-  const float* tvals;      // t of (ray, s) at tvals[ray*t_ray_stride + s]
-  long long t_ray_stride;  // 0: all rays share one t table
-  long long n_points;      // P = N*S
-  int n_samples;           // S
-  const float* packed;     // nerf_layout.h packed model
-  float* raw;              // [P,4] = (r,g,b,sigma) pre-activation
-  const int* index;        // optional (ray mode): compacted list of point ids to evaluate (masked fine pass)
-  const int* count;        // device count of entries in `index`
-  float* save;             // SAVE mode (training forward): activation store, see TrainSave
-  int skip_dead_colour;    // ray mode, fp32 inference kernel: tiles without a single sigma > 0 stop after the sigma head (DSKIP)
-  int density_only;        // ray mode, fp32 kernel: stop after the sigma head (raw = (0,0,0,sigma)): the coarse pass of a
-                           // hierarchical render / training step, whose colour is never read (volume_renderer.py:335 / SURVEY F6)
-  const float* fold;       // fp32 kernels: packed + kOffFold, the fold region of `packed` (nerf_layout.h kFold*), written by
-                           // nerf_pack_model (launch_mlp)
-};
-
-// Training forward keeps what the backward pass needs, row-major per point (the layout the weight-
-// gradient GEMMs read coalesced): P = n_points, offsets in floats.
-// Wave-uniform load of a word that no kernel of the same launch writes (live-tile list, its count), through the CONSTANT address
-// space: hipcc then emits s_load_dword.  As a plain global load it becomes a vector load + v_readfirstlane (it cannot prove the
-// list invariant next to the kernels' own stores and atomics) whose result it waits for with vmcnt(0) -- which, once per step of
-// a list-mode weight-gradient kernel, drained the whole LDS-DMA / asm-load pipeline (round 3, LAB_NOTEBOOK.md A11).
-__device__ __forceinline__ int uniform_load_i32(const int* p) {
-  return *(const __attribute__((address_space(4))) int*)p;
-}
-
-struct TrainSave {
-  static constexpr int kPe = 64, kDpe = 32;        // xyz / dir encodings in REFERENCE channel order, zero padded
-  // Every region holds pad32(P) rows: the fp32 kernels let the idle lanes of a ragged last tile store their
-  // (duplicate) rows into the padding instead of predicating ~300 stores per tile.
-  static constexpr long long pad32(long long P) { return (P + 31) & ~31LL; }
-  static constexpr long long off_pe(long long P) { return 0; }
-  static constexpr long long off_dpe(long long P) { return pad32(P) * 64; }
-  static constexpr long long off_h(long long P, int l) { return pad32(P) * (96 + 256LL * l); }      // h0..h7 (post-ReLU)
-  static constexpr long long off_f(long long P) { return pad32(P) * (96 + 2048); }                  // feature (no ReLU)
-  static constexpr long long off_hv(long long P) { return pad32(P) * (96 + 2304); }                 // views (post-ReLU) [P,128]
-  // ReLU sign bits for the fp32 backward chain: per 32-point tile and masked tensor (0..7 = h0..h7, 8 = views) one
-  // 1-KiB block = 64 lanes x 4 dwords in ACCUMULATOR layout (lane (p,h), bit 16*t + r of its 128 bits <-> feature
-  // act_feat(t, r, h) > 0): the backward kernel fetches a layer's mask with ONE coalesced 16-byte load per lane instead
-  // of re-reading the 1-KiB activation row of every point.  Written by the fp32 SAVE forward only.
-  static constexpr int kMasked = 9;
-  static constexpr long long off_bits(long long P) { return pad32(P) * (96 + 2304 + 128); }
-  static constexpr long long bits_block(long long tile, int which) { return ((tile * kMasked + which) * 64) * 4; }   // floats
-  // one word (+ padding) behind everything: what the forward that filled the buffer did with density-free tiles
-  // (0 = every row stored, != 0 = their h7 / feature / views rows and colour-branch bits are absent): dead_tile_list_available
-  static constexpr long long off_stamp(long long P) { return off_bits(P) + (pad32(P) / 32) * kMasked * 256; }
-  static constexpr long long floats(long long P) { return off_stamp(P) + 4; }
-};
-
-// store one activation set (NT tiles of 32 features) of this lane's point as row-major floats:
-// registers 4q..4q+3 of tile t are the 4 consecutive features 32t + 8q + 4h + (0..3)
-template <int NT>
-__device__ __forceinline__ void store_rows(const f32x16 (&A)[NT], float* __restrict__ dst_row, int h) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      f32x4 v;
-      v.x = A[t][4 * q + 0]; v.y = A[t][4 * q + 1]; v.z = A[t][4 * q + 2]; v.w = A[t][4 * q + 3];
-      *reinterpret_cast<f32x4*>(dst_row + 32 * t + 8 * q + 4 * h) = v;
-    }
-}
-template <int NT>
-__device__ __forceinline__ void load_rows(f32x16 (&A)[NT], const float* __restrict__ src_row, int h) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(src_row + 32 * t + 8 * q + 4 * h);
-      A[t][4 * q + 0] = v.x; A[t][4 * q + 1] = v.y; A[t][4 * q + 2] = v.z; A[t][4 * q + 3] = v.w;
-    }
-}
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 // The tail of the packed stream (9 layer biases, views bias, sigma / rgb head weights: 12 KiB) is staged in LDS by twelve
 // asynchronous LDS-DMAs issued before the positional encoding is computed, so the 32 bias reads at every layer boundary
 // and the head-weight reads are ds_read_b128 with ~100 cycles of latency instead of global loads with > 1000 -- with one
 // wave per SIMD that latency was exposed ten times per tile (round 1 measured the boundary bias loads at 1.7 %).
 constexpr int kTailFloats = 3072;                      // [kOffBias, kOffBias + 3072): everything but the 4 head biases
 static_assert(nerf::kOffHeadBias - nerf::kOffBias == kTailFloats, "LDS tail = biases + views bias + head weights");
-typedef const __attribute__((address_space(3))) float tail_float;
-typedef const __attribute__((address_space(3))) f32x4 tail_f32x4;
 template <int NT>
-__device__ __forceinline__ void load_bias(f32x16 (&acc)[NT], tail_float* bias_h) {
-  tail_f32x4* b = reinterpret_cast<tail_f32x4*>(bias_h);
+__device__ __forceinline__ void load_bias(f32x16 (&acc)[NT], lds_cfloat* bias_h) {
+  lds_cf32x4* b = reinterpret_cast<lds_cf32x4*>(bias_h);
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
 #pragma unroll
@@ -428,19 +321,18 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   // 12 KiB per wave of the workgroup, + 1 KiB behind it for the folded views bias (instances with a colour branch)
   constexpr int kTailLds = kTailFloats + (DENS ? 0 : 256);
   __shared__ __attribute__((aligned(16))) float tail_smem[NERF_F32_WG_WAVES * kTailLds];
-  typedef __attribute__((address_space(3))) char tail_lds_char;
-  tail_lds_char* const tail_w = (tail_lds_char*)tail_smem + wave * (kTailLds * 4);
+  lds_char* const tail_w = (lds_char*)tail_smem + wave * (kTailLds * 4);
   {
     const char* src = reinterpret_cast<const char*>(a.packed + kOffBias) + lane * 16;
 #pragma unroll
     for (int i = 0; i < kTailFloats * 4 / 1024; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024),
-                                       (__attribute__((address_space(3))) void*)(tail_w + i * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_void*)(src + i * 1024),
+                                       (lds_void*)(tail_w + i * 1024), 16, 0, 0);
     if constexpr (!DENS)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(a.fold + kFoldOffBias) + lane * 16),
-                                       (__attribute__((address_space(3))) void*)(tail_w + kTailFloats * 4), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_void*)(reinterpret_cast<const char*>(a.fold + kFoldOffBias) + lane * 16),
+                                       (lds_void*)(tail_w + kTailFloats * 4), 16, 0, 0);
   }
-  tail_float* const tail = reinterpret_cast<tail_float*>(tail_w);
+  lds_cfloat* const tail = reinterpret_cast<lds_cfloat*>(tail_w);
 
   // ---- point + view direction -----------------------------------------------------------
   float x[3], d[3];
@@ -531,7 +423,7 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   AStream ws;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // the tail DMAs (issued before the encodings) have landed
   wstream_start(ws, reinterpret_cast<const f32x4*>(pk), lane);
-  tail_float* bias = tail + h * 128;                                 // + 256 per layer
+  lds_cfloat* bias = tail + h * 128;                                 // + 256 per layer
 
   // SAVE: every activation row is stored by the GEMM that CONSUMES it (tap, one 16-byte store per 4-k-step group); the
   // ReLU sign bits of a layer are collected by its ReLU pass and stored at once (one coalesced 16-byte store per lane)
@@ -587,7 +479,7 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
     gemm_tiles<8, 8, true>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 6), &sb));
     tap_bits_done(6);
     relu8(Y, 7);
-    tail_f32x4* wa = reinterpret_cast<tail_f32x4*>(tail + (kOffWAlpha - kOffBias) + h * 128);
+    lds_cf32x4* wa = reinterpret_cast<lds_cf32x4*>(tail + (kOffWAlpha - kOffBias) + h * 128);
     float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
 #pragma unroll
     for (int t = 0; t < 8; ++t)
@@ -626,7 +518,7 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   relu8(Y, 7);
   stream_drain(ws);
   {
-    tail_f32x4* wa = reinterpret_cast<tail_f32x4*>(tail + (kOffWAlpha - kOffBias) + h * 128);
+    lds_cf32x4* wa = reinterpret_cast<lds_cf32x4*>(tail + (kOffWAlpha - kOffBias) + h * 128);
     float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
 #pragma unroll
     for (int t = 0; t < 8; ++t)
@@ -685,7 +577,7 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   // rgb head 128 -> 3 on the VALU (network.py:69)
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    tail_f32x4* wr = reinterpret_cast<tail_f32x4*>(tail + (kOffWRgb - kOffBias) + (c * 2 + h) * 64);
+    lds_cf32x4* wr = reinterpret_cast<lds_cf32x4*>(tail + (kOffWRgb - kOffBias) + (c * 2 + h) * 64);
     float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
 #pragma unroll
     for (int t = 0; t < 4; ++t)

@@ -1,5 +1,5 @@
 // "f32x": fp32-accurate fused NeRF MLP on the fp16 matrix cores by operand splitting.
-// (included by nerf_kernels.hip; same replaced reference lines as nerf_mlp_f32.hip.inc)
+// (same replaced reference lines as nerf_mlp_f32.hip.inc)
 //
 // Every fp32 operand a is carried as two fp16 numbers, a = a_h + 2^-11 a_l with a_h = fp16(a) and
 // a_l = fp16((a - a_h) * 2^11) (exactly representable residual, rescaled into fp16's normal range).
@@ -11,9 +11,8 @@
 // B fragments) with hi and lo copies of everything; 4 waves per workgroup, one per SIMD (the doubled
 // activation sets need the whole 512-entry register file), 32 points per wave.
 
-constexpr int kXWaves = 4;
-constexpr int kXThreads = kXWaves * 64;
-constexpr int kXTilePts = kXWaves * 32;
+#include "nerf_mlp_common.h"
+
 constexpr int kXStepsPerChunk = nerf::kF16ChunkFrags / 2;                 // 16 (hi, lo) fragment pairs per 32-KiB chunk
 constexpr int kXDmaPerWave = nerf::kF16ChunkFrags / kXWaves;              // 8
 constexpr int kXPf = 4, kXPfDist = 3;           // (hi, lo) pairs prefetched ahead
@@ -115,10 +114,6 @@ __device__ __forceinline__ void split16(float v, _Float16& hi, _Float16& lo) {
 // operations return in order, and the pair of k-step fi, issued kXPfDist steps earlier, has exactly 2 * kXPfDist younger reads
 // behind it (+ 4 when a tile's bias quads were issued in between).  As with the asm global-load rings, no instruction may touch a
 // destination register between an asm read and the wait that covers it: tools/check_asm_stream.py proves it on the ISA.
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 template <int PSTEP>
 __device__ __forceinline__ void xfrag_read_asm(const XRing& r, h8& hi, h8& lo) {     // PSTEP in [0, 32)
@@ -217,9 +212,6 @@ __device__ __forceinline__ f32x16 gemmx_tile(XRing& r, const h8* B1h, const h8* 
 // combined, biased, rectified and split into the next layer's B fragments (~120 VALU instructions, a quarter of a
 // tile's 48 MFMAs), so that epilogue is cut into eight 2-value chunks and issued behind the MFMAs of the NEXT
 // tile's first steps.  Only the last tile of a layer has its epilogue exposed.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 // (hi, lo) split of a pair, value by value with split16's roundings -- SCALAR fp32 instructions on purpose: beside MFMAs a packed
 // v_pk_{fma,add,mul}_f32 costs a lone wave ~17 cycles of issue against 2 x 4 for the two scalar ones (MI355X_MICROARCH.md, "price
@@ -351,14 +343,14 @@ __device__ __forceinline__ XRowStage xstage_init(lds_char* buf, int lane) {
 // the address are `q ^ ((p & 7) >> 1)` = the address of quad 0 with q xor-ed in)
 template <int Q4>
 __device__ __forceinline__ void xstage_put(const XRowStage& st, const f32x4& v) {
-  *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(st.w0 ^ (unsigned)(Q4 * 32)) = v;
+  *reinterpret_cast<lds_f32x4*>(st.w0 ^ (unsigned)(Q4 * 32)) = v;
 }
 // the transposed tile comes back in two halves (rows 0..15, 16..31: two 16-byte quads per lane each) to keep the registers few
 struct XStaged { f32x4 v[2]; };
 template <int HALF>
 __device__ __forceinline__ void xstage_get(const XRowStage& st, XStaged& g) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) g.v[i] = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(st.r0 + (2 * HALF + i) * 1024);
+  for (int i = 0; i < 2; ++i) g.v[i] = *reinterpret_cast<lds_cf32x4*>(st.r0 + (2 * HALF + i) * 1024);
 }
 // `tile_rows`: wave-uniform address of feature 0 of the tile's row 0 in a row-major region with ROWB-byte rows; m: out-tile
 template <int ROWB, int HALF>

@@ -1,11 +1,13 @@
 // Geometry outputs: the density gradient at points (nerf_density_gradient) and the composited surface normal / opacity of a ray
 // (nerf_composite_normals).  DESIGN.md section 2.10; the definitions are in include/nerf_mi355x.h.
-// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH / Carver / forward_rays / backward_rays, CompositeWeight,
-// lane_bcast and kCbMaxSamples).
+// Needs, ahead of it, nerf_sampling.hip.inc (lane_bcast), nerf_composite.hip.inc (CompositeWeight, kCbMaxSamples), nerf_mlp_launch.hip.inc
+// (forward_rays) and nerf_train_backward.hip.inc (backward_rays).
 //
 // No MLP kernel is added: a block of nerf_density_gradient is the density SAVE forward and the density chain (grads == NULL) of a
 // training step, through their launchers.  The two kernels here are memory-trivial next to them (20 and 32 bytes per point against
 // ~20 KB of saved / gradient rows).
+#include "nerf_host.h"
+#include "nerf_mlp_common.h"
 
 namespace {
 

@@ -1,6 +1,8 @@
 // Occupancy grid: a bitfield over the cells of a density grid, and the per-sample lookup that culls empty space from a render
 // (DESIGN.md section 2.9; the definitions are in include/nerf_mi355x.h, nerf_occupancy_*).
-// Included at the end of nerf_kernels.hip (uses its fail / NERF_LAUNCH / masked_sizes_ok / render_frame).
+// Needs, ahead of it, nerf_mlp_launch.hip.inc (masked_sizes_ok) and nerf_frame.hip.inc (render_frame, RenderOccupancy,
+// render_workspace_bytes; the tally of the points a pass evaluated lives there too, with its caller).
+#include "nerf_host.h"
 //
 // Both kernels are memory-trivial: the bitfield is (nx-1)(ny-1)(nz-1) / 8 bytes (2 MB at 256^3) and stays in L2; the build reads
 // the field (2r + 2)^3 times per cell out of the same cache, once per grid; the mark reads 4 bytes and writes 1 per sample.
@@ -95,12 +97,6 @@ void nerf_occupancy_mark_kernel(const float* __restrict__ rays_o, const float* _
   valid[e] = (unsigned char)((and_with_existing ? valid[e] != 0 : true) && keep);
 }
 
-// evaluated += the length of the list a pass just ran on (count), or `all` for a pass without a list.  One thread; the launches of
-// a frame are ordered by the stream, so nothing here is atomic.
-__global__ void nerf_occupancy_tally_kernel(const int* __restrict__ count, long long all, long long* __restrict__ evaluated) {
-  *evaluated += count ? (long long)*count : all;
-}
-
 // 0: sizes fine; the grid as OccGrid.  Every dimension >= 2, at most 2^31 - 1 points (cell ids are int32)
 int occ_sizes(const char* entry, const int32_t dims[3], OccGrid& G) {
   if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) return fail(NERF_ERR_INVALID_ARG, "%s: every grid dimension must be >= 2", entry);
@@ -128,11 +124,6 @@ int occ_lookup(const char* entry, const int32_t dims[3], const float box_min[3],
 }  // namespace
 
 extern "C" {
-
-// the hook of render_frame (declared in front of it)
-static int occupancy_tally(const int* count, long long all, long long* evaluated, hipStream_t st) {
-  return NERF_LAUNCH(nerf_occupancy_tally_kernel, dim3(1), dim3(1), st, count, all, evaluated);
-}
 
 int64_t nerf_occupancy_words(int32_t nx, int32_t ny, int32_t nz) {
   const int32_t dims[3] = {nx, ny, nz};

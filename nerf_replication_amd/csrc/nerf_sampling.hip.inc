@@ -1,0 +1,579 @@
+// Where the samples of a ray lie: the fine (hierarchical) sampler and its adjoint, the stratified coarse depths of a training step,
+// and the two stream compactions of valid sample ids (unordered for inference, ordered for the training forward), with their entries.
+#include "nerf_host.h"
+#include "nerf_mlp_common.h"
+#include "nerf_scan.hip.inc"
+
+namespace {
+
+// ------------------------------------------------------------------------------------ fine sampling
+// One thread per ray, sequential scans in the reference's CPU order (cumprod / cumsum are
+// sequential in torch CPU too).  A 64-ray block stages its I/O through LDS: the coarse sigmas are
+// loaded cooperatively, every lane then owns one padded 192-float LDS row (sigma -> fine depths in
+// [0,128) with the cdf in [128,191) -> the merged depths), and the 64 x 192 sorted depths are
+// written back coalesced.
+// Two instances of one body, which is what keeps them bit-compatible on the same tables:
+//  <false> one coarse table and one ascending u table for all rays (s_tab = t[64] | u[128]); t_fine comes out of the walk;
+//          optionally (fast_sampling) also the ESS/ERT validity of every merged sample (volume_renderer.py:116-123, :132-133,
+//          :158-193, :359-369), carried through the merge as the sign of the depth.
+//  <true>  a coarse table and a u table per ray (t of ray r at t_coarse + r * t_stride, u at u + r * u_stride; stride 0 shares one
+//          table): s_tab = one 65-float coarse row per ray.  t_sorted depends only on the MULTISET of fine depths, so each lane
+//          sorts its ray's 128 u ascending (registers, bitonic) and then runs the same monotone walk.  The row's slots [0,128)
+//          hold sigma, then the ray's u (staged coalesced), then the sorted u the walk overwrites in place with the fine depths
+//          (slot j <= k is written only after u[k] was read); t_fine is in the caller's u order, by bisection.  No masks.
+// LDS per 64-ray workgroup: the 64 x 193-float rows (49 408 B) + 768 B of shared tables, or + 16 640 B of coarse rows.
+constexpr int kSampleThreads = 64;
+constexpr int kBufPitch = 193;     // odd pitch: lanes walking their own rows never share a bank
+constexpr int kTcPitch = 65;       // odd pitch, as kBufPitch
+
+struct SampleArgs {
+  const float* raw_c;        // [n,64,4]
+  const float* t_coarse;     // [64] or [n,64]
+  long long t_stride;        // 0 or 64
+  const float* u;            // [128] or [n,128]
+  long long u_stride;        // 0 or 128
+  long long n_rays;
+  float* t_sorted;           // [n,192]
+  float* t_fine;             // optional [n,128], in the caller's u order
+  unsigned char* valid_sorted;   // optional [n,192], 1 = evaluate with the fine network (shared tables only)
+  int fast_sampling;
+  float weights_threshold, ert_threshold;
+};
+
+__device__ __forceinline__ float alpha_of(float sigma, float delta) {
+  return __fsub_rn(1.0f, expf(__fmul_rn(-sigma, delta)));       // 1 - exp(-sigma*delta)
+}
+
+// torch.sum(w, -1) of volume_renderer.py:138 on a 62-element fp32 row, in the CPU kernel's own order (ATen SumKernel.cpp,
+// vectorized_inner_sum / row_sum with 8-lane vectors and 4 accumulators -- verified bit for bit against torch.sum on the fixture
+// rows): the 56 leading elements as 7 vectors of 8, lane sums ((((((v0 + v4) + v5) + v6) + v1) + v2) + v3), then the 6 tail
+// elements and the 8 lane sums added one by one.  A plain left-to-right sum (rounds 1-2) is off by up to 3e-6 relative on rows of
+// many equal 1e-5 terms, i.e. cdf[62] = 1 + 3e-6: it moved every fine sample of a ray by ~3e-6 against the reference's and was
+// the "unexplained" part of the white-noise family's excess over the noise floor (round-2 VERDICT Weak 8).
+template <class Get>
+__device__ __forceinline__ float torch_sum62_of(Get x) {
+  float P[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float p = __fadd_rn(x(j), x(32 + j));
+    p = __fadd_rn(p, x(40 + j));
+    p = __fadd_rn(p, x(48 + j));
+    p = __fadd_rn(p, x(8 + j));
+    p = __fadd_rn(p, x(16 + j));
+    P[j] = __fadd_rn(p, x(24 + j));
+  }
+  float acc = x(56);
+#pragma unroll
+  for (int k = 57; k < 62; ++k) acc = __fadd_rn(acc, x(k));
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc = __fadd_rn(acc, P[j]);
+  return acc;
+}
+__device__ __forceinline__ float torch_sum62(const float* w) { return torch_sum62_of([&](int k) { return w[k]; }); }
+
+// Ascending bitonic network over one thread's 128 registers.  Fully unrolled (unroll(full): plain `#pragma unroll` left the
+// array in scratch, 528 B per lane), so every index is a constant and the array lives in VGPRs.
+__device__ __forceinline__ void sort128_ascending(float (&r)[NERF_N_IMPORTANCE]) {
+#pragma clang loop unroll(full)
+  for (int k = 2; k <= NERF_N_IMPORTANCE; k <<= 1) {
+#pragma clang loop unroll(full)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma clang loop unroll(full)
+      for (int i = 0; i < NERF_N_IMPORTANCE; ++i) {
+        const int l = i ^ j;
+        if (l > i) {
+          const float x = r[i], y = r[l];
+          const bool up = (i & k) == 0;
+          r[i] = up ? fminf(x, y) : fmaxf(x, y);
+          r[l] = up ? fmaxf(x, y) : fminf(x, y);
+        }
+      }
+    }
+  }
+}
+
+// Inverse CDF of one u given its searchsorted(right) index; also the two bins it interpolates between.
+__device__ __forceinline__ float inv_cdf_at(const float* cdf, const float* tc, float u, int ind, int& below, int& above) {
+  constexpr int S = NERF_N_SAMPLES;
+  below = min(max(ind - 1, 0), S - 3);
+  above = min(ind, S - 3);                             // clamp to 61: tail collapse (SURVEY F7)
+  const float cb = cdf[below], ca = cdf[above];
+  const float bb = __fmul_rn(0.5f, __fadd_rn(tc[below + 1], tc[below]));
+  const float ba = __fmul_rn(0.5f, __fadd_rn(tc[above + 1], tc[above]));
+  float denom = __fsub_rn(ca, cb);
+  if (denom < 1e-5f) denom = 1.0f;
+  const float frac = __fdiv_rn(__fsub_rn(u, cb), denom);
+  return __fadd_rn(bb, __fmul_rn(frac, __fsub_rn(ba, bb)));
+}
+
+template <bool RAYS>
+__global__ __launch_bounds__(kSampleThreads)
+void nerf_sample_fine_kernel(SampleArgs a) {
+  constexpr int S = NERF_N_SAMPLES, F = NERF_N_IMPORTANCE, NB = S - 1;   // 63 cdf entries / bins
+  __shared__ float s_tab[RAYS ? kSampleThreads * kTcPitch : S + F];
+  __shared__ float s_buf[kSampleThreads * kBufPitch];
+  const int lane = threadIdx.x;
+  const long long ray0 = (long long)blockIdx.x * kSampleThreads;
+  if (!RAYS) {
+    s_tab[lane] = a.t_coarse[lane];
+    s_tab[S + lane] = a.u[lane];
+    s_tab[S + lane + 64] = a.u[lane + 64];
+  }
+  for (int r = 0; r < kSampleThreads; ++r) {          // lane = coarse sample index
+    long long rg = ray0 + r;
+    if (rg >= a.n_rays) rg = a.n_rays - 1;
+    s_buf[r * kBufPitch + lane] = a.raw_c[rg * (S * 4) + lane * 4 + 3];
+    if (RAYS) s_tab[r * kTcPitch + lane] = a.t_coarse[rg * a.t_stride + lane];
+  }
+  __syncthreads();
+  float* buf = s_buf + lane * kBufPitch;
+  float* cdf = buf + F;        // slots 128..190: free until the merge, which no longer needs the cdf
+  const float* tc = RAYS ? s_tab + lane * kTcPitch : s_tab;
+  const float* us = RAYS ? buf : s_tab + S;            // the ascending u the walk reads
+  auto depth_of = [](float v) { return RAYS ? v : fabsf(v); };      // shared tables: the sign carries "masked out"
+
+  // weights of the coarse pass (volume_renderer.py:67-96), inner 62 + eps, running sum
+  float T = 1.0f, dsum = 0.0f, dmax = 0.0f;
+  unsigned long long empty_bits = 0, ert_bits = 0;
+  bool ert_seen = false;
+  for (int i = 0; i < S; ++i) {
+    const float sigma = fmaxf(buf[i], 0.0f);
+    const float delta = (i < S - 1) ? __fsub_rn(tc[i + 1], tc[i]) : 1e10f;
+    const float alpha = alpha_of(sigma, delta);
+    const float w = __fmul_rn(T, alpha);
+    if (i >= 1 && i <= S - 2) cdf[i - 1] = __fadd_rn(w, 1e-5f);     // stash w+eps in cdf slots 0..61 (summed below, in torch's order)
+    if (!RAYS) {
+      dsum = __fadd_rn(dsum, sigma);
+      dmax = fmaxf(dmax, sigma);
+      if (i >= 1 && i <= S - 2) {
+        if (w < a.weights_threshold) empty_bits |= 1ull << (i - 1);
+        ert_seen = ert_seen || (T < a.ert_threshold);     // cummax of (T < thr) over the inner bins
+        if (ert_seen) ert_bits |= 1ull << (i - 1);
+      }
+    }
+    T = __fmul_rn(T, fminf(fmaxf(__fsub_rn(1.0f, alpha), 1e-10f), 1.0f));
+  }
+  const float wsum = torch_sum62(cdf);
+  const bool empty_ray = dsum < 1e-3f;
+  const bool object_ray = dmax > 0.5f;
+  // cdf = [0, cumsum(pdf)]  (63 entries)
+  {
+    float run = 0.0f, prev = cdf[0];
+    cdf[0] = 0.0f;
+    for (int m = 1; m < NB; ++m) {
+      run = __fadd_rn(run, __fdiv_rn(prev, wsum));
+      prev = cdf[m];
+      cdf[m] = run;
+    }
+  }
+  const long long ray = ray0 + lane;
+  const bool ray_ok = ray < a.n_rays;
+  int below, above;
+  if (RAYS) {
+    __syncthreads();                                   // every lane has read its sigmas: slots [0,128) take the rays' u
+    for (int r = 0; r < kSampleThreads; ++r) {
+      long long rg = ray0 + r;
+      if (rg >= a.n_rays) rg = a.n_rays - 1;
+      s_buf[r * kBufPitch + lane] = a.u[rg * a.u_stride + lane];
+      s_buf[r * kBufPitch + 64 + lane] = a.u[rg * a.u_stride + 64 + lane];
+    }
+    __syncthreads();
+    if (a.t_fine && ray_ok) {                          // in the caller's order: searchsorted(right) by bisection
+      for (int k = 0; k < F; ++k) {
+        const float u = buf[k];
+        int lo = 0, hi = NB;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] <= u) lo = mid + 1; else hi = mid; }
+        a.t_fine[ray * F + k] = inv_cdf_at(cdf, tc, u, lo, below, above);
+      }
+    }
+    float r[F];
+#pragma clang loop unroll(full)
+    for (int k = 0; k < F; ++k) r[k] = buf[k];
+    sort128_ascending(r);
+#pragma clang loop unroll(full)
+    for (int k = 0; k < F; ++k) buf[k] = r[k];
+  }
+  // inverse CDF at the ascending u; u ascending -> the searchsorted(right=True) index only grows
+  int ind = 0;
+  for (int k = 0; k < F; ++k) {
+    const float u = us[k];
+    while (ind < NB && cdf[ind] <= u) ++ind;
+    float v = inv_cdf_at(cdf, tc, u, ind, below, above);
+    if (!RAYS) {
+      if (a.t_fine && ray_ok) a.t_fine[ray * F + k] = v;
+      if (a.fast_sampling) {
+        const bool be = (empty_bits >> below) & 1, ae = (empty_bits >> above) & 1, ert = (ert_bits >> below) & 1;
+        const bool ess_nv = object_ray ? (be && ae) : (be || ae);
+        if (ess_nv || ert || empty_ray) v = -v;           // depths are > 0: the sign carries "masked out"
+      }
+    }
+    // keep the fine depths sorted even if rounding ever produced a 1-ulp inversion (torch.sort would fix it too)
+    int j = k;
+    while (j > 0 && depth_of(buf[j - 1]) > depth_of(v)) { buf[j] = buf[j - 1]; --j; }
+    buf[j] = v;
+  }
+  // in-place two-way merge from the back of (sorted coarse table, sorted fine depths) = cat + torch.sort;
+  // on ties the coarse sample comes first
+  {
+    int ic = S - 1, jf = F - 1;
+    for (int k = S + F - 1; k >= 0; --k) {
+      const bool take_f = (ic < 0) || (jf >= 0 && depth_of(buf[jf]) >= tc[ic]);
+      if (take_f) { buf[k] = buf[jf]; --jf; }
+      else { buf[k] = tc[ic]; --ic; }
+    }
+  }
+  __syncthreads();
+  for (int i = 0; i < S + F; ++i) {                    // 64 rays x 192 depths, coalesced
+    const int e = lane + 64 * i, r = e / (S + F), k = e - r * (S + F);
+    const long long rg = ray0 + r;
+    if (rg < a.n_rays) {
+      const float v = s_buf[r * kBufPitch + k];
+      a.t_sorted[rg * (S + F) + k] = depth_of(v);
+      if (!RAYS && a.valid_sorted) a.valid_sorted[rg * (S + F) + k] = v > 0.0f;
+    }
+  }
+}
+
+// Stream compaction of the valid (ray, sample) ids for the masked fine pass (replaces the boolean
+// indexing of network.py:207-214): order inside `index` is arbitrary, results are scattered back by id.
+__global__ __launch_bounds__(256)
+void nerf_compact_kernel(const unsigned char* __restrict__ valid, long long n, int* __restrict__ index,
+                         int* __restrict__ count) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool v = i < n && valid[i] != 0;
+  const unsigned long long m = __ballot(v);
+  const int lane = threadIdx.x & 63;
+  int base = 0;
+  if (lane == 0 && m) base = atomicAdd(count, (int)__popcll(m));
+  base = __shfl(base, 0);
+  if (v) index[base + (int)__popcll(m & ((1ull << lane) - 1ull))] = (int)i;
+}
+
+// Point ids of the LAST sample of every ray (the fp16 paths' far-plane guard, nerf_render_forward): index[r] = r * S + S - 1.
+__global__ __launch_bounds__(256)
+void nerf_last_sample_index_kernel(int* __restrict__ index, int* __restrict__ count, long long n_rays, int S) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n_rays) index[r] = (int)(r * S + S - 1);
+  if (r == 0) *count = (int)n_rays;
+}
+
+// Inclusive scan over the 64 lanes of a wave: UP: lane l gets op over lanes 0..l (prefix), else over lanes l..63 (suffix)
+template <bool UP, class T, class Op>
+__device__ __forceinline__ T wave_scan(T x, int lane, Op op) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T o = UP ? __shfl_up(x, d) : __shfl_down(x, d);
+    if (UP ? lane >= d : lane + d < 64) x = op(x, o);
+  }
+  return x;
+}
+// The value of the neighbouring lane (UP: lane - 1, else lane + 1); the lane at the end of the wave gets `edge`: turns an
+// inclusive scan into the exclusive one
+template <bool UP, class T>
+__device__ __forceinline__ T wave_shift(T x, int lane, T edge) {
+  const T o = UP ? __shfl_up(x, 1) : __shfl_down(x, 1);
+  return lane == (UP ? 0 : 63) ? edge : o;
+}
+constexpr auto op_sum = [](auto x, auto y) { return x + y; };
+constexpr auto op_prod = [](auto x, auto y) { return x * y; };
+constexpr auto op_max = [](auto x, auto y) { return max(x, y); };
+
+// Backward of hierarchical sampling (volume_renderer.py:126-154, :247-264 under autograd): gradient of the
+// merged depths w.r.t. the coarse densities (the coarse table and u are constants).  Recomputes the
+// forward quantities, then: g_t_fine -> g_cdf[below/above] -> g_pdf (reverse cumsum) -> g_(w+eps) ->
+// g_w (inner 62) -> g_sigma through T/alpha -> g_raw_coarse[..., 3] (relu mask).
+// One WAVE per ray, lane i = coarse sample i (S = 64), two fine samples per lane.  What decides where a fine sample falls --
+// transmittance, the running sum of the weights and the cdf -- is recomputed in the forward's own SEQUENTIAL order (a
+// v_readlane walk over the lanes with the forward's rounding intrinsics: bit-identical bins); everything downstream of the
+// decisions is a gradient and uses wave scans / LDS atomics.  (One thread per ray took 131 us for the 4096 rays of a step:
+// 64 lonely waves whose data-dependent while-loops also ran in lockstep.)
+// The two instances are those of nerf_sample_fine_kernel: <false> one coarse table and one ascending u table (s_tab = t[64] |
+// u[128]), <true> tables per ray with the forward's strides (s_tab = one coarse row per wave), where each wave first sorts its
+// ray's u: the merged-slot logic (k + ic with the running maximum, ties coarse first) needs the fine samples in ascending order.
+__device__ __forceinline__ float lane_bcast(float v, int lane_const) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_const));
+}
+// Ascending bitonic sort of 128 values across a wave: lane l holds elements l and l + 64
+__device__ __forceinline__ void wave_sort128_ascending(float (&us)[2], int lane) {
+#pragma unroll
+  for (int k = 2; k <= 128; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (j == 64) {                                   // k == 128: partners share the lane
+        const float x = us[0], y = us[1];
+        us[0] = fminf(x, y); us[1] = fmaxf(x, y);
+      } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int idx = lane + 64 * h;
+          const float p = __shfl_xor(us[h], j);
+          const bool up = (idx & k) == 0, low = (idx & j) == 0;
+          us[h] = (low == up) ? fminf(us[h], p) : fmaxf(us[h], p);
+        }
+      }
+    }
+  }
+}
+template <bool RAYS>
+__global__ __launch_bounds__(256)
+void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __restrict__ t_coarse, long long t_stride,
+                            const float* __restrict__ u_in, long long u_stride, long long n_rays,
+                            const float* __restrict__ g_tsorted, float* __restrict__ g_raw_c) {
+  constexpr int S = NERF_N_SAMPLES, F = NERF_N_IMPORTANCE, NB = S - 1;
+  static_assert(S == 64 && F == 128, "lane = coarse sample, two fine samples per lane");
+  __shared__ float s_tab[RAYS ? 4 * S : S + F];
+  __shared__ float s_cdf[4][S];
+  __shared__ double s_gcdf[4][S];          // adjoint of the cdf, accumulated in float64 (see below)
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long ray_slot = (long long)blockIdx.x * 4 + wv;
+  const bool ray_ok = ray_slot < n_rays;                       // a wave past the end recomputes the last ray and stores nothing
+  const long long ray = ray_ok ? ray_slot : n_rays - 1;        // (it has to reach the workgroup barriers below)
+  float us[2];
+  if (RAYS) {
+    s_tab[wv * S + lane] = t_coarse[ray * t_stride + lane];
+    us[0] = u_in[ray * u_stride + lane];
+    us[1] = u_in[ray * u_stride + 64 + lane];
+    wave_sort128_ascending(us, lane);
+  } else {
+    if (threadIdx.x < S) s_tab[threadIdx.x] = t_coarse[threadIdx.x];
+    if (threadIdx.x < F) s_tab[S + threadIdx.x] = u_in[threadIdx.x];
+  }
+  s_gcdf[wv][lane] = 0.0;
+  __syncthreads();
+  const float* tc = RAYS ? s_tab + wv * S : s_tab;
+  const int i = lane;
+  // ---- forward recompute, in the forward's order and rounding (nerf_sample_fine_kernel)
+  const float s_raw = raw_c[ray * (S * 4) + i * 4 + 3];
+  const float sigma = fmaxf(s_raw, 0.0f);
+  const float delta = (i < S - 1) ? __fsub_rn(tc[i + 1], tc[i]) : 1e10f;
+  const float e = expf(__fmul_rn(-sigma, delta));
+  const float alpha = __fsub_rn(1.0f, e);                      // = alpha_of(sigma, delta)
+  const float om = __fsub_rn(1.0f, alpha);
+  const float q = fminf(fmaxf(om, 1e-10f), 1.0f);
+  float Ti = 1.0f;
+  {
+    float T = 1.0f;
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+      if (lane == j) Ti = T;
+      T = __fmul_rn(T, lane_bcast(q, j));
+    }
+  }
+  const bool inner = i >= 1 && i <= S - 2;
+  const float we = __fadd_rn(__fmul_rn(Ti, alpha), 1e-5f);     // w + eps (used for the inner 62 only)
+  const float wsum = torch_sum62_of([&](int k) { return lane_bcast(we, k + 1); });     // bin k <-> lane k + 1; the forward's order
+  const float pdf = __fdiv_rn(we, wsum);                       // lane i: pdf of bin i - 1
+  float cdf_m = 0.0f;                                          // lane m: cdf[m], m = 0..62
+  {
+    float run = 0.0f;
+#pragma unroll
+    for (int m = 1; m < NB; ++m) {
+      run = __fadd_rn(run, lane_bcast(pdf, m));
+      if (lane == m) cdf_m = run;
+    }
+  }
+  s_cdf[wv][lane] = cdf_m;                                     // (lane 63: unused slot)
+  __syncthreads();
+  // ---- the two fine samples of this lane: bin, merged slot, adjoint into g_cdf
+  const float* gts = g_tsorted + ray * (S + F);
+  float* cdf = s_cdf[wv];
+  // Everything downstream of the (fp32, forward-identical) decisions is accumulated in float64: the terms num / denom^2 of an
+  // ill-conditioned ray (denom ~ 1e-5) are 1e5 x the result of the sums they enter, and the fp32 version of these sums (LDS float
+  // atomics + wave scans) was 10-20 x further from a float64 evaluation of the adjoint than torch's fp32 autograd on the same
+  // inputs (tests/test_gpu_train_steps.py, round 3).  The kernel is 20 us of a training step either way.
+  double* gcdf = s_gcdf[wv];
+  int ic_carry = 0;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int k = lane + 64 * half;                             // rank of this fine sample among the ray's (ascending) fine samples
+    const float u = RAYS ? us[half] : s_tab[S + k];
+    int ind = 0;
+    for (int m = 0; m < NB; ++m) ind += cdf[m] <= u;            // cdf is non-decreasing: = the forward's searchsorted(right)
+    const int below = min(max(ind - 1, 0), S - 3), above = min(ind, S - 3);
+    const float cb = cdf[below], ca = cdf[above];
+    const float bb = __fmul_rn(0.5f, __fadd_rn(tc[below + 1], tc[below]));
+    const float ba = __fmul_rn(0.5f, __fadd_rn(tc[above + 1], tc[above]));
+    const float draw_ = __fsub_rn(ca, cb);
+    const bool live = !(draw_ < 1e-5f);
+    const float denom = live ? draw_ : 1.0f;
+    const float num = __fsub_rn(u, cb);
+    const float v = __fadd_rn(bb, __fmul_rn(__fdiv_rn(num, denom), __fsub_rn(ba, bb)));
+    int ic = 0;                                                 // coarse entries sorted before this fine sample (ties: coarse first)
+    for (int j = 0; j < S; ++j) ic += tc[j] <= v;
+    // the forward's merge pointer never moves back: running maximum over the fine samples in order
+    ic = max(wave_scan<true>(ic, lane, op_max), ic_carry);
+    ic_carry = __shfl(ic, 63);
+    const double g = (double)gts[k + ic];                       // its slot in the merged array
+    const double g_frac = g * (double)__fsub_rn(ba, bb);
+    double g_cb = -g_frac / (double)denom, g_ca = 0.0;          // frac = (u - cb) / denom, denom = ca - cb when live
+    if (live) { const double gden = -g_frac * (double)num / ((double)denom * (double)denom); g_ca += gden; g_cb -= gden; }
+    atomicAdd(&gcdf[below], g_cb);
+    atomicAdd(&gcdf[above], g_ca);
+  }
+  __syncthreads();
+  // ---- cdf[m] = sum_{j<m} pdf_j  ->  g_pdf_j = sum_{m>j} g_cdf[m];  pdf = we / W
+  const double sfx = wave_scan<false>(lane < NB ? gcdf[lane] : 0.0, lane, op_sum);
+  const double gpdf_excl = wave_shift<false>(sfx, lane, 0.0);   // lane j: g_pdf_j = sum_{m>j} g_cdf[m]
+  double gpdf_i = __shfl_up(gpdf_excl, 1);                      // lane i: g_pdf of bin i - 1 (the bin of sample i)
+  if (!inner) gpdf_i = 0.0;
+  double dot = inner ? gpdf_i * (double)we : 0.0;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) dot += __shfl_xor(dot, d);
+  const double g_w = inner ? (gpdf_i / (double)wsum - dot / ((double)wsum * (double)wsum)) : 0.0;
+  const double sf2 = wave_scan<false>(g_w * (double)alpha * (double)Ti, lane, op_sum);     // suf_i = sum_{m>i} g_w_m a_m T_m
+  const double suf = wave_shift<false>(sf2, lane, 0.0);
+  double g_alpha = g_w * (double)Ti;
+  if (om >= 1e-10f && om <= 1.0f) g_alpha -= suf / (double)q;
+  f32x4 go = {0.f, 0.f, 0.f, 0.f};
+  go.w = s_raw > 0.0f ? (float)(g_alpha * (double)delta * (double)e) : 0.0f;
+  if (ray_ok) reinterpret_cast<f32x4*>(g_raw_c)[ray * S + i] = go;
+}
+
+// ------------------------------------------------------------------------------------ stochastic sampling (task == "train")
+// Coarse jitter (volume_renderer.py:48-60): mids = 0.5 (t[1:] + t[:-1]), lower = [t0, mids], upper = [mids, t63],
+// t = lower + (upper - lower) * jitter, every operation rounded on its own as the CPU torch expression is.
+__global__ __launch_bounds__(256)
+void nerf_stratified_kernel(const float* __restrict__ t_lin, const float* __restrict__ jitter, long long n, float* __restrict__ t_out) {
+  constexpr int S = NERF_N_SAMPLES;
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n * S) return;
+  const int s = (int)(e % S);
+  const float lower = s == 0 ? t_lin[0] : __fmul_rn(0.5f, __fadd_rn(t_lin[s], t_lin[s - 1]));
+  const float upper = s == S - 1 ? t_lin[S - 1] : __fmul_rn(0.5f, __fadd_rn(t_lin[s + 1], t_lin[s]));
+  t_out[e] = __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), jitter[e]));
+}
+
+// ------------------------------------------------------------------------------------ training: the masked (fast_sampling) fine pass
+// Ordered stream compaction of the valid (ray, sample) ids: index[0..M) = the ids with valid != 0 in ASCENDING order, *count = M.
+// Unlike nerf_compact_kernel (one atomic per wave, arbitrary order: fine for inference, where results are scattered back by id)
+// the order here is fixed, because the training forward stores the activations of index[j] at row j of the save buffer: a
+// repeatable layout gives repeatable tiles, live-tile lists and gradient sums.  Three launches: per-block counts (256 ids per
+// block), one-workgroup exclusive scan of the block counts, ordered scatter.  No atomics.
+constexpr int kCompactBlock = kRankBlock;       // compact_block_rank (nerf_scan.hip.inc)
+__global__ __launch_bounds__(kCompactBlock)
+void nerf_compact_count_kernel(const unsigned char* __restrict__ valid, long long n, int* __restrict__ block_count) {
+  __shared__ int s_wave[kCompactBlock / 64];
+  const long long i = (long long)blockIdx.x * kCompactBlock + threadIdx.x;
+  int total;
+  compact_block_rank(i < n && valid[i] != 0, s_wave, total);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+// block counts -> exclusive offsets in place, *count = their sum; one workgroup (3072 blocks for a 4096-ray step)
+__global__ __launch_bounds__(kScanThreads)
+void nerf_compact_scan_kernel(int* __restrict__ block_count, long long n_blocks, int* __restrict__ count) {
+  __shared__ int s_cnt[kScanThreads];
+  const int total = workgroup_scan(n_blocks, s_cnt, [&](long long b) { return block_count[b]; },
+                                   [&](long long b, int pos) { block_count[b] = pos; });
+  if (threadIdx.x == 0) *count = total;
+}
+__global__ __launch_bounds__(kCompactBlock)
+void nerf_compact_scatter_kernel(const unsigned char* __restrict__ valid, long long n, const int* __restrict__ block_offset,
+                                 int* __restrict__ index) {
+  __shared__ int s_wave[kCompactBlock / 64];
+  const long long i = (long long)blockIdx.x * kCompactBlock + threadIdx.x;
+  const bool v = i < n && valid[i] != 0;
+  int total;
+  const int rank = compact_block_rank(v, s_wave, total);
+  if (v) index[block_offset[blockIdx.x] + rank] = (int)i;       // offset + rank <= number of valid ids before i <= i < n
+}
+
+}  // namespace
+
+extern "C" {
+
+static bool bad_strides(int64_t t_ray_stride, int64_t u_ray_stride) {
+  return (t_ray_stride != 0 && t_ray_stride != NERF_N_SAMPLES) || (u_ray_stride != 0 && u_ray_stride != NERF_N_IMPORTANCE);
+}
+// nerf_sample_fine (shared tables: both strides 0) and nerf_sample_fine_rays behind their own size checks.  Shared tables take
+// the <false> instance, a table per ray of either kind the <true> one.
+static int32_t sample_fine(const char* entry, const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                           int64_t u_ray_stride, int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
+                           float weights_threshold, float ert_threshold, void* stream) {
+  const bool per_ray = t_ray_stride != 0 || u_ray_stride != 0;
+  if (per_ray && valid_sorted) return fail(NERF_ERR_INVALID_ARG, "%s: fast_sampling needs the shared tables", entry);
+  if (n_rays == 0) return NERF_OK;
+  if (!raw_coarse || !t_coarse || !u || !t_sorted) return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
+  SampleArgs a;
+  a.raw_c = raw_coarse; a.t_coarse = t_coarse; a.t_stride = t_ray_stride; a.u = u; a.u_stride = u_ray_stride; a.n_rays = n_rays;
+  a.t_sorted = t_sorted; a.t_fine = t_fine; a.valid_sorted = valid_sorted; a.fast_sampling = valid_sorted != nullptr;
+  a.weights_threshold = per_ray ? 0.0f : weights_threshold; a.ert_threshold = per_ray ? 0.0f : ert_threshold;
+  const dim3 blocks((unsigned)((n_rays + kSampleThreads - 1) / kSampleThreads));
+  return per_ray ? NERF_LAUNCH(nerf_sample_fine_kernel<true>, blocks, dim3(kSampleThreads), (hipStream_t)stream, a)
+                 : NERF_LAUNCH(nerf_sample_fine_kernel<false>, blocks, dim3(kSampleThreads), (hipStream_t)stream, a);
+}
+int32_t nerf_sample_fine(const float* raw_coarse, const float* t_coarse, const float* u,
+                         int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
+                         float weights_threshold, float ert_threshold, void* stream) {
+  if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine: bad size");
+  return sample_fine("nerf_sample_fine", raw_coarse, t_coarse, 0, u, 0, n_rays, t_sorted, t_fine, valid_sorted, weights_threshold,
+                     ert_threshold, stream);
+}
+int32_t nerf_sample_fine_rays(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                              int64_t u_ray_stride, int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
+                              float weights_threshold, float ert_threshold, void* stream) {
+  if (n_rays < 0 || bad_strides(t_ray_stride, u_ray_stride))
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays: bad size or stride (t: 0 or 64, u: 0 or 128)");
+  return sample_fine("nerf_sample_fine_rays", raw_coarse, t_coarse, t_ray_stride, u, u_ray_stride, n_rays, t_sorted, t_fine, valid_sorted,
+                     weights_threshold, ert_threshold, stream);
+}
+
+// the same pair for the backward: nerf_sample_fine_backward and nerf_sample_fine_rays_backward
+static int32_t sample_fine_backward(const char* entry, const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride,
+                                    const float* u, int64_t u_ray_stride, int64_t n_rays, const float* t_sorted,
+                                    const float* g_t_sorted, float* g_raw_coarse, void* stream) {
+  if (n_rays == 0) return NERF_OK;
+  if (!raw_coarse || !t_coarse || !u || !t_sorted || !g_t_sorted || !g_raw_coarse) return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
+  const dim3 blocks((unsigned)((n_rays + 3) / 4));
+  const long long ts = t_ray_stride, us = u_ray_stride, n = n_rays;
+  return ts != 0 || us != 0
+             ? NERF_LAUNCH(nerf_sample_bwd_kernel<true>, blocks, dim3(256), (hipStream_t)stream, raw_coarse, t_coarse, ts, u, us, n,
+                           g_t_sorted, g_raw_coarse)
+             : NERF_LAUNCH(nerf_sample_bwd_kernel<false>, blocks, dim3(256), (hipStream_t)stream, raw_coarse, t_coarse, ts, u, us, n,
+                           g_t_sorted, g_raw_coarse);
+}
+int32_t nerf_sample_fine_backward(const float* raw_coarse, const float* t_coarse, const float* u, int64_t n_rays,
+                                  const float* t_sorted, const float* g_t_sorted, float* g_raw_coarse, void* stream) {
+  if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_backward: bad size");
+  return sample_fine_backward("nerf_sample_fine_backward", raw_coarse, t_coarse, 0, u, 0, n_rays, t_sorted, g_t_sorted, g_raw_coarse, stream);
+}
+int32_t nerf_sample_fine_rays_backward(const float* raw_coarse, const float* t_coarse, int64_t t_ray_stride, const float* u,
+                                       int64_t u_ray_stride, int64_t n_rays, const float* t_sorted, const float* g_t_sorted,
+                                       float* g_raw_coarse, void* stream) {
+  if (n_rays < 0 || bad_strides(t_ray_stride, u_ray_stride))
+    return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_sample_fine_rays_backward: bad size or stride (t: 0 or 64, u: 0 or 128)");
+  return sample_fine_backward("nerf_sample_fine_rays_backward", raw_coarse, t_coarse, t_ray_stride, u, u_ray_stride, n_rays, t_sorted,
+                              g_t_sorted, g_raw_coarse, stream);
+}
+
+int32_t nerf_stratified_samples(const float* t_linear, const float* jitter, int64_t n_rays, float* t_coarse, void* stream) {
+  if (n_rays < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_stratified_samples: bad size");
+  if (n_rays == 0) return NERF_OK;
+  if (!t_linear || !jitter || !t_coarse) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_stratified_samples: null argument");
+  const long long ne = (long long)n_rays * NERF_N_SAMPLES;
+  return NERF_LAUNCH(nerf_stratified_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), (hipStream_t)stream, t_linear, jitter,
+                     (long long)n_rays, t_coarse);
+}
+
+int64_t nerf_compact_valid_workspace_bytes(int64_t n_points) {
+  if (n_points < 0 || n_points > 0x7fffffffLL) return -1;
+  return align256(((n_points + kCompactBlock - 1) / kCompactBlock) * (int64_t)sizeof(int));
+}
+int32_t nerf_compact_valid(const uint8_t* valid, int64_t n_points, int32_t* index, int32_t* count, void* workspace, void* stream) {
+  if (n_points < 0 || n_points > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_compact_valid: point ids are int32");
+  if (!count) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_compact_valid: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_points == 0) {
+    if (hipMemsetAsync(count, 0, sizeof(int), st) != hipSuccess) return fail(NERF_ERR_HIP, "%s", "nerf_compact_valid: memset failed");
+    return NERF_OK;
+  }
+  if (!valid || !index || !workspace) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_compact_valid: null argument");
+  const long long n_blocks = (n_points + kCompactBlock - 1) / kCompactBlock;
+  int* block = (int*)workspace;
+  int rc = NERF_LAUNCH(nerf_compact_count_kernel, dim3((unsigned)n_blocks), dim3(kCompactBlock), st, valid, (long long)n_points, block);
+  if (rc) return rc;
+  if ((rc = NERF_LAUNCH(nerf_compact_scan_kernel, dim3(1), dim3(kScanThreads), st, block, n_blocks, count))) return rc;
+  return NERF_LAUNCH(nerf_compact_scatter_kernel, dim3((unsigned)n_blocks), dim3(kCompactBlock), st, valid, (long long)n_points, block,
+                     index);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // Ordered lists without atomics: the rank of a thread inside its 256-thread block, and the one-workgroup scan that turns the
-// block totals into offsets.  Used by the live-tile list and the ordered compaction (nerf_kernels.hip), the iso-surface
-// (nerf_isosurface.hip.inc) and the mesh clean-up (nerf_mesh_components.hip.inc).
+// block totals into offsets.  Used by the live-tile list (nerf_train_backward.hip.inc), the ordered compaction
+// (nerf_sampling.hip.inc), the iso-surface (nerf_isosurface.hip.inc) and the mesh clean-up (nerf_mesh_components.hip.inc).
 #pragma once
 
 namespace {

@@ -9,7 +9,8 @@
                               NERF_F16_HACK_NOADV || NERF_F16_HACK_NOBARRIER || NERF_WG_HACK_NOATOMIC || NERF_F16_HACK_NOEPI || \
                               NERF_F16_HACK_NORELU || NERF_F32X_HACK_NOADV || NERF_F32X_HACK_NOPE || NERF_F32X_HACK_NOEPI || \
                               NERF_F32X_HACK_SAVE_NOSTORE || NERF_XB_HACK_NOSTORE)
-// (a structural knob of the SAVE forward also breaks results when switched off: no rows stored)
-#if (NERF_ANY_TIMING_HACK || NERF_SAVE_TAPS == 0) && !defined(NERF_TIMING_BUILD)
+// (a structural knob of the SAVE forward also breaks results when switched off: no rows stored.  Its default is 1, so in a unit
+// without nerf_mlp_f32.hip.inc, which owns it, the name counts only where the command line set it)
+#if (NERF_ANY_TIMING_HACK || (defined(NERF_SAVE_TAPS) && NERF_SAVE_TAPS == 0)) && !defined(NERF_TIMING_BUILD)
 #error "a NERF_*_HACK_* / NERF_F32_ASM_OVERRUN timing switch is set: such a library computes wrong results; build it with -DNERF_TIMING_BUILD (tools/ab_bench.py does) so that nerf_build_flags() reports it"
 #endif

@@ -3,7 +3,6 @@
 // to 2^-16 are kept.  The three dropped ones, mid lo + lo mid + lo lo, are below 2^-24 of the term only for typical
 // operands (median 2^-25); they reach 2^-21 of it for significands 1.0000000 followed by ones, and are bounded by
 // (2^-20 + 2^-27) of it: |mid| < 2^-7 |v|, |lo| < 2^-14 |v|.  tests/test_wgrad_reference_cpu.py holds these figures.)
-// (included by nerf_kernels.hip)
 //
 //   dW[o][i] += sum_p dZ[p][o] * Hin[p][i]        (autograd of nn.Linear, network.py:22-47)
 //
@@ -14,6 +13,8 @@
 // nerf_wgrad256_f32_asm_kernel.  All 256 x 256 layers of one sub-network are one launch ("jobs": blockIdx % n_jobs),
 // so a workgroup integrates 8x more points before its 65536 atomic adds and concurrently running workgroups
 // add to different matrices.
+#include "nerf_mlp_common.h"
+
 struct WgradXJob {
   const float* dz; const float* hin; float* dw; float* db;
   int ldz, zc0, ldh, hc0, ldw, wc0;

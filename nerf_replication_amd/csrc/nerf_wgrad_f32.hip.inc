@@ -2,7 +2,7 @@
 #define NERF_WG_HACK_NOATOMIC 0
 #endif
 // Weight-gradient GEMM for the training path (fp32 MFMA): dW[o][i] += sum_p dZ[p][o] * Hin[p][i].
-// (included by nerf_kernels.hip; csrc/nerf_wgrad_table.h says which instance serves which shape)
+// (csrc/nerf_wgrad_table.h says which instance serves which shape)
 //
 // This is what autograd computes for every nn.Linear of network.py:22-47 (grad_weight = grad_out^T @
 // input, grad_bias = grad_out.sum(0)).  The reduction index is the POINT, so both MFMA operands want
@@ -11,6 +11,8 @@
 // contiguous point ranges, each wave keeps OT x IT 32x32 output tiles in registers (4x4 = 256
 // accumulators for a 256x256 layer split over the 4 waves) and adds them to dW with float atomics
 // at the end (256-B row segments per wave-instruction, the full-rate shape).
+#include "nerf_mlp_common.h"
+
 struct WgradArgs {
   const float* dz; long long ldz; int zc0; int n_out;
   const float* hin; long long ldh; int hc0; int n_in;

@@ -1,5 +1,5 @@
 // Which fp32 weight-gradient kernel serves a layer shape: one ordered table and one pure function, no HIP in it (a host
-// compiler alone builds it: tests/test_wgrad_choice.py).  nerf_kernels.hip instantiates the kernels from the same rows.
+// compiler alone builds it: tests/test_wgrad_choice.py).  nerf_train_backward.hip.inc instantiates the kernels from the same rows.
 //
 // Every kernel gives each of its 4 waves `wo` x `wi` 32x32 output tiles and splits the waves osplit x isplit, so a row
 // covers 32*wo*osplit outputs and 32*wi*isplit inputs.  A row that does not cover the shape is never eligible; the first

@@ -34,7 +34,7 @@ HARD_MAX = {"base": (8e-4, 3e-3), "sharp": (1e-4, 1e-3), "white": (6e-2, 2.5e-1)
 # the reference against its own fp64-MLP self: 19 of 3072, tests/test_noise_floor.py)
 # "trained" (a network trained by the build, tests/golden/trained_ckpt.pth): SURVEY 8c's flat per-ray tolerance holds on EVERY ray
 # (measured max 8.2e-5 / 4.5e-4 over 4096 + 1024 rays) -- its smooth coarse pdf has no empty bins, so no sample flips
-# round 3: with the sampler summing its 62 weights in torch.sum's own order (nerf_kernels.hip torch_sum62) the white-noise family went
+# round 3: with the sampler summing its 62 weights in torch.sum's own order (nerf_sampling.hip.inc torch_sum62) the white-noise family went
 # from 53 to 33 rays of 4096 outside the tolerance (the reference against its fp64-MLP self: 19 of 3072 = 25 per 4096) -> 2 %
 MAX_OVER_FRAC = {"base": 0.01, "sharp": 0.01, "white": 0.02, "trained": 0.0}
 

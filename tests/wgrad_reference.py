@@ -37,7 +37,7 @@ def pad32(P):
 
 
 class Save:
-    """TrainSave of csrc/nerf_mlp_f32.hip.inc: every region holds pad32(P) rows."""
+    """TrainSave of csrc/nerf_mlp_common.h: every region holds pad32(P) rows."""
     @staticmethod
     def off_pe(P): return 0
     @staticmethod
@@ -57,7 +57,7 @@ class Save:
 
 
 class Grad:
-    """TrainGrad of csrc/nerf_mlp_bwd_f32.hip.inc: the rows, then int32 flags, live list and count."""
+    """TrainGrad of csrc/nerf_mlp_common.h: the rows, then int32 flags, live list and count."""
     @staticmethod
     def off_gzv(P): return 0
     @staticmethod

@@ -270,7 +270,8 @@ def call(name, *args):
 
 
 # The helpers below are the direct path to the C ABI: load() plus check / ptr / ptr_array / stream_of at the call site.  The package
-# itself goes through call(); bench.py, tests/ and tools/ call entries directly through these, so they stay.
+# itself and the tests go through call(); bench.py, tools/ and the tests' refusal probes (which need the raw status of deliberately
+# malformed arguments) call entries directly through these, so they stay.
 def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().nerf_last_error().decode("utf-8", "replace")

@@ -14,17 +14,11 @@ import pytest
 import torch
 
 import f16_reference as R
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 N_DISTINCT = 1024
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 @functools.lru_cache(maxsize=None)
@@ -66,7 +60,7 @@ def _same(got, want, what, tally):
 @pytest.mark.parametrize("seed,zero_axis", R.PROBES)
 def test_exact_probe(amd, seed, zero_axis, precision):
     c = _case(seed, zero_axis)
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     net = amd.Network()
     net.load_state_dict(c["sd"], strict=True)
     net = net.cuda().eval()
@@ -90,8 +84,7 @@ def test_exact_probe(amd, seed, zero_axis, precision):
         n_rays, S = rwant.shape[:2]
         o, d, t = o.cuda(), d.cuda(), t.cuda()
         out = torch.full((n_rays, S, 4), float("nan"), device="cuda")
-        L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(t), S if t.dim() == 2 else 0, n_rays, S, net.packed(model).data_ptr(),
-                                          L.ptr(out), prec, L.stream_of(o.device)))
+        L.call("nerf_mlp_forward_rays", o, d, t, S if t.dim() == 2 else 0, n_rays, S, net.packed(model), out, prec)
         torch.cuda.synchronize()
         _same(out, rwant, f"{tag} nerf_mlp_forward_rays[{name}]", tally)
     R.parity_record("gpu_exact_probes", f"seed{seed}/axis{zero_axis}/{precision}", dict(points=tally["points"], mismatching_points=tally["mismatching_points"],

@@ -14,15 +14,9 @@ import pytest
 import torch
 
 import f16_reference as R
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 @functools.lru_cache(maxsize=None)

@@ -12,24 +12,13 @@ import os
 import pytest
 import torch
 
+from gpu_common import amd, network  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FOLD_JSON = os.path.join(REPO, "profiles", "parity_fold.json")
 MODELS = (("", "model"), ("fine", "model_fine"))
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
-
-
-def _network(amd, sd):
-    n = amd.Network()
-    n.load_state_dict(sd, strict=True)
-    return n.cuda().eval()
 
 
 def _points(n, seed):
@@ -45,14 +34,13 @@ def _bits(x):
 
 def _forward_rays(amd, fn, net, o, d, t, save=False):
     """One of the ray-mode C-ABI forwards of the fine model on [n] rays x t.shape[1] depths -> raw [n, S, 4]."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     n, S = o.shape[0], t.shape[1]
     raw = torch.full((n, S, 4), float("nan"), device="cuda")
-    args = [L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, net.packed("fine").data_ptr(), L.ptr(raw)]
+    args = [o, d, t, S, n, S, net.packed("fine"), raw]
     if save:
-        buf = torch.zeros(int(lib.nerf_train_save_floats(n * S)), device="cuda")
-        args.append(L.ptr(buf))
-    L.check(getattr(lib, fn)(*args, 0, L.stream_of(o.device)), fn)
+        args.append(torch.zeros(int(L.call("nerf_train_save_floats", n * S)), device="cuda"))
+    L.call(fn, *args, 0)
     torch.cuda.synchronize()
     return raw
 
@@ -82,7 +70,7 @@ def test_fold_orientation_and_exactness(amd, oracle, synthetic_sd):
         sd_b[f"{m}.feature_linear.weight"], sd_b[f"{m}.feature_linear.bias"] = torch.eye(256), torch.zeros(256)
         sd_b[f"{m}.views_linears.0.weight"] = wv_b
         sd_b[f"{m}.views_linears.0.bias"] = (bv.double() + wv[:, :256].double() @ bf.double()).float()
-    net_a, net_b = _network(amd, sd_a), _network(amd, sd_b)
+    net_a, net_b = network(amd, sd_a, "f32", train=False), network(amd, sd_b, "f32", train=False)
     pts, vd = _points(35, 3)                                                                   # a ragged tile
     with torch.no_grad():
         for model, _ in MODELS:
@@ -99,7 +87,7 @@ def test_fold_orientation_and_exactness(amd, oracle, synthetic_sd):
 def test_no_stale_fold_after_in_place_updates(amd, oracle, synthetic_sd):
     """The fold follows the repack: after an in-place update of each tensor it depends on, a render and a points forward
     equal those of a freshly constructed network with the same state dict."""
-    net = _network(amd, synthetic_sd)
+    net = network(amd, synthetic_sd, "f32", train=False)
     o, d = oracle.seeded_rays(64, 9)
     batch = {"rays_o": o[None].cuda(), "rays_d": d[None].cuda()}
     pts, vd = _points(35, 4)
@@ -111,7 +99,7 @@ def test_no_stale_fold_after_in_place_updates(amd, oracle, synthetic_sd):
             for sub in (net.model, net.model_fine):
                 p = dict(sub.named_parameters())[name]
                 p.add_((torch.randn(p.shape, generator=g) * 0.05).cuda())
-            fresh = _network(amd, {k: v.detach().cpu().clone() for k, v in net.state_dict().items()})
+            fresh = network(amd, {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, "f32", train=False)
             rgb, dep = amd.Renderer(net).render(batch)
             rgb_f, dep_f = amd.Renderer(fresh).render(batch)
             assert torch.equal(_bits(rgb), _bits(rgb_f)) and torch.equal(_bits(dep), _bits(dep_f)), name
@@ -126,7 +114,7 @@ def test_save_forward_equals_inference(amd, golden, family_sd, family):
     """The training (SAVE) forward forms the views layer with the instructions of the inference kernels: raw bit-equal at the
     C ABI (tiles with and without density) and through Network.forward in .train() and .eval()."""
     g = golden(f"render_family_{family}.npz")
-    net = _network(amd, family_sd(family))
+    net = network(amd, family_sd(family), "f32", train=False)
     n = 67
     o, d = g["pin_rays_o"][:n].cuda().contiguous(), g["pin_rays_d"][:n].cuda().contiguous()
     t = g["pin_t_sorted"][:n].cuda().contiguous()
@@ -152,7 +140,7 @@ def test_save_forward_equals_inference(amd, golden, family_sd, family):
 def test_two_streams_two_models(amd, oracle, family_sd):
     """Nothing is shared between streams (the fold lies in each model's own packed buffer): two models rendering on two streams
     at once each get their own result."""
-    nets = [_network(amd, family_sd(f)) for f in ("base", "sharp")]
+    nets = [network(amd, family_sd(f), "f32", train=False) for f in ("base", "sharp")]
     o, d = oracle.seeded_rays(2048, 13)
     batch = {"rays_o": o[None].cuda(), "rays_d": d[None].cuda()}
     with torch.no_grad():
@@ -172,16 +160,14 @@ def test_two_streams_two_models(amd, oracle, family_sd):
         assert torch.equal(_bits(rgb), _bits(want[i % 2][0])) and torch.equal(_bits(dep), _bits(want[i % 2][1])), i
 
 
-def _points_forward(amd, net, pts, vd, raw, stream):
-    """nerf_mlp_forward of the fine model, fp32, enqueued on the stream handle `stream`; everything preallocated."""
-    lib, L = amd._lib.load(), amd._lib
-    L.check(lib.nerf_mlp_forward(L.ptr(pts), L.ptr(vd), pts.shape[0], pts.shape[1], net.packed("fine").data_ptr(), L.ptr(raw), 0,
-                                 stream), "nerf_mlp_forward")
+def _points_forward(amd, net, pts, vd, raw):
+    """nerf_mlp_forward of the fine model, fp32, enqueued on the current stream; everything preallocated."""
+    amd._lib.call("nerf_mlp_forward", pts, vd, pts.shape[0], pts.shape[1], net.packed("fine"), raw, 0)
 
 
 def _eager(amd, net, pts, vd):
     raw = torch.full((pts.shape[0], pts.shape[1], 4), float("nan"), device="cuda")
-    _points_forward(amd, net, pts, vd, raw, amd._lib.stream_of(pts.device))
+    _points_forward(amd, net, pts, vd, raw)
     torch.cuda.synchronize()
     assert torch.isfinite(raw).all() and raw[..., :3].abs().max() > 0
     return raw
@@ -191,14 +177,14 @@ def test_capture_on_a_stream_that_never_launched(amd, synthetic_sd):
     """A forward needs nothing but its arguments, so the first thing a new stream ever does can be a capture: one
     nerf_mlp_forward of 35 points (a ragged tile), model packed and tensors allocated beforehand, captured as a one-node graph,
     replayed, bit-equal to the eager call."""
-    net = _network(amd, synthetic_sd)
+    net = network(amd, synthetic_sd, "f32", train=False)
     pts, vd = _points(35, 8)
     pts, vd = pts.cuda(), vd.cuda()
     want = _eager(amd, net, pts, vd)
     raw = torch.full_like(want, float("nan"))
     side, graph = torch.cuda.Stream(), torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph, stream=side):
-        _points_forward(amd, net, pts, vd, raw, side.cuda_stream)
+        _points_forward(amd, net, pts, vd, raw)                    # the current stream is `side` here
     torch.cuda.synchronize()
     assert torch.isnan(raw).all()                    # captured, not run
     graph.replay()
@@ -210,11 +196,11 @@ def test_65_streams(amd, synthetic_sd):
     """The same forward on 65 distinct streams, one after another: every call succeeds and gives the same bits (no per-stream
     resource exists that could run out).  The streams come from the HIP runtime the library is linked against (torch hands out
     32 pooled handles per priority)."""
-    lib = amd._lib.load()
+    lib, L = amd._lib.load(), amd._lib
     create, destroy = lib.hipStreamCreate, lib.hipStreamDestroy
     create.restype, create.argtypes = ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p)]
     destroy.restype, destroy.argtypes = ctypes.c_int, [ctypes.c_void_p]
-    net = _network(amd, synthetic_sd)
+    net = network(amd, synthetic_sd, "f32", train=False)
     pts, vd = _points(35, 8)
     pts, vd = pts.cuda(), vd.cuda()
     want = _eager(amd, net, pts, vd)
@@ -226,7 +212,9 @@ def test_65_streams(amd, synthetic_sd):
             h = ctypes.c_void_p()
             assert create(ctypes.byref(h)) == 0 and h.value
             streams.append(h)
-            _points_forward(amd, net, pts, vd, raws[i], h)
+            # a raw stream handle, which call() cannot take: the direct path
+            L.check(lib.nerf_mlp_forward(L.ptr(pts), L.ptr(vd), pts.shape[0], pts.shape[1], net.packed("fine").data_ptr(), L.ptr(raws[i]), 0, h),
+                    "nerf_mlp_forward")
         torch.cuda.synchronize()
     finally:
         for h in streams:
@@ -237,7 +225,7 @@ def test_65_streams(amd, synthetic_sd):
 
 def test_two_models_back_to_back_on_one_stream(amd, family_sd):
     """"base" and "sharp" on one stream with no synchronisation in between: each returns its own eager result."""
-    nets = [_network(amd, family_sd(f)) for f in ("base", "sharp")]
+    nets = [network(amd, family_sd(f), "f32", train=False) for f in ("base", "sharp")]
     pts, vd = _points(35, 8)
     pts, vd = pts.cuda(), vd.cuda()
     want = [_eager(amd, n, pts, vd) for n in nets]
@@ -245,7 +233,7 @@ def test_two_models_back_to_back_on_one_stream(amd, family_sd):
     raws = [torch.full_like(w, float("nan")) for w in want]
     torch.cuda.synchronize()
     for n, r in zip(nets, raws):
-        _points_forward(amd, n, pts, vd, r, amd._lib.stream_of(pts.device))
+        _points_forward(amd, n, pts, vd, r)
     torch.cuda.synchronize()
     assert all(torch.equal(_bits(r), _bits(w)) for r, w in zip(raws, want))
 
@@ -265,7 +253,7 @@ def test_folded_colours_are_as_close_to_float64_as_the_reference(amd, oracle, fa
     fp32 instead of float64 would add about sqrt(256) x 2^-24 = 1e-6 to the views layer and miss this.  Measured ratios are
     recorded in profiles/parity_fold.json (CPU model of the folded chain: 1.0 in every family; MI355X: 0.78 .. 1.25)."""
     sd = family_sd(family)
-    net = _network(amd, sd)
+    net = network(amd, sd, "f32", train=False)
     pts, vd = _points(4096, 21)
     ratios = {}
     for model, prefix in MODELS:

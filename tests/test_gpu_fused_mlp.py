@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import fused_mlp_reference as R
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -33,13 +34,6 @@ CONFIGS = [(1, 64, 1, 1, False), (2, 64, 2, 3, True), (31, 64, 2, 16, False), (3
            (256, 128, 1, 4, False), (32, 64, 8, 3, False)]
 _IDS = ["%dx%dx%d-%d%s" % (c[0], c[1], c[2], c[3], "-sigmoid" if c[4] else "") for c in CONFIGS]
 _worst = {}
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -95,8 +89,7 @@ def _forward(amd, net, x, sigmoid, save=True):
     whole_o, out = _padded(B * net.out_dim)
     n_save = net.n_hidden * B * net.width
     whole_s, sv = _padded(n_save) if save else (None, None)
-    L.check(L.load().nerf_fused_mlp_forward(x.data_ptr(), *net.dims(B), int(sigmoid), _ptrs(net.w), _ptrs(net.b), out.data_ptr(),
-                                            sv.data_ptr() if save else None, L.stream_of(x.device)), "nerf_fused_mlp_forward")
+    L.call("nerf_fused_mlp_forward", x, *net.dims(B), int(sigmoid), net.w, net.b, out, sv if save else None)
     assert _intact(whole_o, B * net.out_dim) and (not save or _intact(whole_s, n_save))
     assert not (out == SENTINEL).any() and (not save or not (sv == SENTINEL).any())          # everything was written
     return out.view(B, net.out_dim), (sv.view(net.n_hidden, B, net.width) if save else None)
@@ -121,10 +114,8 @@ class Grads:
         L, net = amd._lib, self.net
         gw = [None if i in self.skip else t[1] for i, t in enumerate(self.w)]
         gb = [None if i in self.skip else t[1] for i, t in enumerate(self.b)]
-        L.check(L.load().nerf_fused_mlp_backward(x.data_ptr(), out.data_ptr(), go.data_ptr(), *net.dims(self.B), int(sigmoid),
-                                                 _ptrs(net.w), sv.data_ptr(), self.gsave.data_ptr(), _ptrs(gw), _ptrs(gb),
-                                                 self.gx.data_ptr() if self.want_x else None, L.stream_of(x.device)),
-                "nerf_fused_mlp_backward")
+        L.call("nerf_fused_mlp_backward", x, out, go, *net.dims(self.B), int(sigmoid), net.w, sv, self.gsave, gw, gb,
+               self.gx if self.want_x else None)
         assert _intact(self.whole_g, self.n_gsave) and _intact(self.whole_x, self.B * net.in_dim)
         for i in range(net.n_hidden + 1):
             n_out, n_in = net.layer_shape(i)

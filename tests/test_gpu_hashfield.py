@@ -13,19 +13,13 @@ import torch
 
 import hashfield_reference as R
 import occupancy_reference as O
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 U = R.U
 SENTINEL = -12345.5
 PAD = 64                   # elements in front of and behind every guarded output (256 bytes: the views stay 16-byte aligned)
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 class Guarded:

@@ -19,17 +19,11 @@ import hashfield_reference as R
 import occupancy_reference as O
 from test_gpu_hashfield import (GRID_N, PARAM_KEYS, Guarded, _allowed, batch_of, half_field, half_grid_words, hand_grid, hip_field,
                                 hip_renderer, same)
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 U = R.U
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 def decided(pres64, pres32, what):

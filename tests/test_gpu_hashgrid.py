@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import hashgrid_reference as R
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -34,13 +35,6 @@ CONFIGS = {
     "c4": (3, 3, 4, 1.5, 3, 6),                # C = 4
     "c8": (3, 2, 8, 2, 5, 9),                  # C = 8: a dense level of 6^3 = 216 rows and a hashed one of 512
 }
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 class Case:
@@ -86,8 +80,7 @@ def _forward(amd, cs, x, emb=None):
     emb = cs.emb if emb is None else emb
     B = x.shape[0]
     whole, out = _padded(B * cs.L * cs.C)
-    L.check(L.load().nerf_hashgrid_forward(x.data_ptr(), emb.data_ptr(), B, cs.D, cs.C, cs.L, cs.off_c, cs.sc_c, out.data_ptr(),
-                                           L.stream_of(x.device)), "nerf_hashgrid_forward")
+    L.call("nerf_hashgrid_forward", x, emb, B, cs.D, cs.C, cs.L, cs.off_c, cs.sc_c, out)
     torch.cuda.synchronize()
     assert _intact(whole, B * cs.L * cs.C)
     return out.view(B, cs.L * cs.C)
@@ -100,9 +93,7 @@ def _backward(amd, cs, x, go, want_emb=True, want_x=True, into=None):
     ne, nx = cs.emb.numel(), B * cs.D
     we, ge = into[0] if into else _padded(ne, zero=True)
     wx, gx = _padded(nx)
-    L.check(L.load().nerf_hashgrid_backward(x.data_ptr(), cs.emb.data_ptr(), go.data_ptr(), B, cs.D, cs.C, cs.L, cs.off_c, cs.sc_c,
-                                            ge.data_ptr() if want_emb else None, gx.data_ptr() if want_x else None,
-                                            L.stream_of(x.device)), "nerf_hashgrid_backward")
+    L.call("nerf_hashgrid_backward", x, cs.emb, go, B, cs.D, cs.C, cs.L, cs.off_c, cs.sc_c, ge if want_emb else None, gx if want_x else None)
     torch.cuda.synchronize()
     assert _intact(we, ne) and _intact(wx, nx)
     if not want_x:

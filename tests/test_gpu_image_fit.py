@@ -10,18 +10,12 @@ import torch
 import torch.nn as nn
 
 import fused_mlp_reference as R
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 U = R.U
 SEED = 27           # picked on the CPU and checked below: with this seed no hidden pre-activation of the float64 twin is within 1e-4 of zero
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 def _twin(linears, dtype, device, sigmoid=True):

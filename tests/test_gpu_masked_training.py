@@ -1,12 +1,12 @@
 """-m gpu: training with fast_sampling (the ESS / ERT masked fine pass on compacted points) and with N_importance = 0
 (coarse only), against the reference's own autograd (tests/golden/masked_train.npz, tools/gen_masked_train_golden.py) and
 against the unmasked entries of the C ABI."""
-import ctypes
-
 import pytest
 import torch
 
 from conftest import parity_record
+from gpu_common import amd, assert_grads_equal, network  # noqa: F401
+from train_steps_common import subsample
 
 pytestmark = pytest.mark.gpu
 
@@ -14,34 +14,10 @@ MASKED_CASES = (("trained_t002", "trained", 0.02), ("sharp_t025", "sharp", 0.25)
 GRAD_STRIDE = 53
 
 
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
-
-
-def _rel(got, ref):
-    return ((got.double().cpu() - ref.double().cpu()).abs().max() / ref.double().cpu().abs().max().clamp_min(1e-9)).item()
-
-
-def _subsample(t):
-    f = t.detach().reshape(-1)
-    return f.clone() if f.numel() <= 4096 else f[::GRAD_STRIDE].clone()
-
-
 def _case(golden, tag):
     g = golden("masked_train.npz")
     assert int(g["grad_stride"]) == GRAD_STRIDE
     return {k[len(tag) + 1:]: v for k, v in g.items() if k.startswith(tag + "/")}
-
-
-def _net(amd, sd, precision):
-    net = amd.Network()
-    net.load_state_dict(sd, strict=True)
-    net = net.cuda().train()
-    net.precision = precision
-    return net
 
 
 def _grad_rows(net, c, prefixes=("model.", "model_fine.")):
@@ -51,7 +27,7 @@ def _grad_rows(net, c, prefixes=("model.", "model_fine.")):
             continue
         ref = c["grad/" + k]
         assert p.grad is not None, k
-        got = _subsample(p.grad.cpu())
+        got = subsample(p.grad.cpu(), GRAD_STRIDE)
         assert got.shape == ref.shape, k
         denom = ref.abs().max().item()
         err = (got - ref).abs().max().item()
@@ -71,7 +47,7 @@ def test_masked_step_matches_reference_autograd(amd, family_sd, golden, tag, fam
     gradients go through the inverse-CDF sampler's own discontinuities).  masked_stats reports M = 64 n + valid_fine.sum()."""
     c = _case(golden, tag)
     assert float(c["weights_threshold"]) == pytest.approx(thr)
-    net = _net(amd, family_sd(family), precision)
+    net = network(amd, family_sd(family), precision, train=True)
     ren = amd.Renderer(net)
     ren.fast_sampling, ren.weights_threshold = True, thr
     ren.masked_stats, ren.capture_adjoints = [], {}
@@ -118,7 +94,7 @@ def test_masked_forward_under_autograd_equals_the_no_grad_render(amd, family_sd,
     pair is bit-equal in both precisions (measured on the MI355X; asserted here, so a change of that relation shows up)."""
     c = _case(golden, tag)
     batch = {"rays_o": c["rays_o"][None].cuda(), "rays_d": c["rays_d"][None].cuda()}
-    net = _net(amd, family_sd(family), precision)
+    net = network(amd, family_sd(family), precision, train=True)
     out = {}
     for mode in ("unmasked", "masked"):
         ren = amd.Renderer(net)
@@ -142,11 +118,7 @@ SENTINEL = 12345.0
 
 def _abi_setup(amd, synthetic_sd, precision, n, S, seed):
     L = amd._lib
-    lib = L.load()
-    net = amd.Network()
-    net.load_state_dict(synthetic_sd, strict=True)
-    net = net.cuda().eval()
-    net.precision = precision
+    net = network(amd, synthetic_sd, precision, train=False)
     prec = L.PRECISIONS[precision]
     gen = torch.Generator().manual_seed(seed)
     o = torch.tensor([0.0, 0.0, 4.0]).expand(n, 3).contiguous().cuda()
@@ -154,66 +126,46 @@ def _abi_setup(amd, synthetic_sd, precision, n, S, seed):
     d = (d / d.norm(dim=-1, keepdim=True)).contiguous().cuda()
     t = torch.sort(torch.rand(n, S, generator=gen) * 4 + 2, dim=-1).values.cuda().contiguous()
     params = [p.detach().contiguous() for p in net.model_fine.ordered_params()]
-    arr = (ctypes.c_void_p * 24)(*[p.data_ptr() for p in params])
-    st = L.stream_of(o.device)
-    pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device="cuda")
-    L.check(lib.nerf_pack_model_bwd(arr, pk_b.data_ptr(), prec, st))
-    return dict(L=L, lib=lib, net=net, prec=prec, gen=gen, o=o, d=d, t=t, params=params, st=st, pk_b=pk_b, n=n, S=S, P=n * S,
-                pk=net.packed("fine"))
+    pk_b = torch.empty(int(L.call("nerf_packed_bwd_bytes", prec)), dtype=torch.uint8, device="cuda")
+    L.call("nerf_pack_model_bwd", params, pk_b, prec)
+    return dict(net=net, prec=prec, gen=gen, o=o, d=d, t=t, params=params, pk_b=pk_b, n=n, S=S, P=n * S, pk=net.packed("fine"))
 
 
-def _grad_ptrs(grads):
-    return (ctypes.c_void_p * 24)(*[g.data_ptr() for g in grads])
-
-
-def _forward(s, entry, index=None, count=None, raw_fill=0.0):
-    L, lib, P = s["L"], s["lib"], s["P"]
+def _forward(amd, s, entry, index=None, count=None, raw_fill=0.0):
+    L, P = amd._lib, s["P"]
     raw = torch.full((s["n"], s["S"], 4), raw_fill, device="cuda")
-    save = torch.full((int(lib.nerf_train_save_floats(P)),), SENTINEL, device="cuda")
-    a = (L.ptr(s["o"]), L.ptr(s["d"]), L.ptr(s["t"]), s["S"], s["n"], s["S"])
+    save = torch.full((int(L.call("nerf_train_save_floats", P)),), SENTINEL, device="cuda")
+    a = (s["o"], s["d"], s["t"], s["S"], s["n"], s["S"])
     if index is None:
-        L.check(entry(*a, s["pk"].data_ptr(), L.ptr(raw), L.ptr(save), s["prec"], s["st"]))
+        L.call(entry, *a, s["pk"], raw, save, s["prec"])
     else:
-        L.check(entry(*a, L.ptr(index, torch.int32), L.ptr(count, torch.int32), s["pk"].data_ptr(), L.ptr(raw), L.ptr(save),
-                      s["prec"], s["st"]))
+        L.call(entry, *a, index, count, s["pk"], raw, save, s["prec"])
     return raw, save
 
 
-def _backward(s, save, G, index=None, count=None):
-    L, lib, P = s["L"], s["lib"], s["P"]
-    gsave = torch.full((int(lib.nerf_train_grad_floats(P)),), float("nan"), device="cuda")       # rows of dead tiles stay NaN: never read
+def _backward(amd, s, save, G, index=None, count=None):
+    L, P = amd._lib, s["P"]
+    gsave = torch.full((int(L.call("nerf_train_grad_floats", P)),), float("nan"), device="cuda")       # rows of dead tiles stay NaN: never read
     g_t = torch.full((s["n"], s["S"]), float("nan"), device="cuda")
     grads = [torch.zeros_like(p) for p in s["params"]]
-    a = (L.ptr(s["o"]), L.ptr(s["d"]), L.ptr(s["t"]), s["S"], s["n"], s["S"])
+    a = (s["o"], s["d"], s["t"], s["S"], s["n"], s["S"])
     if index is None:
-        L.check(lib.nerf_mlp_backward(*a, s["pk_b"].data_ptr(), L.ptr(G), L.ptr(save), L.ptr(gsave), L.ptr(g_t), _grad_ptrs(grads),
-                                      s["prec"], s["st"]))
+        L.call("nerf_mlp_backward", *a, s["pk_b"], G, save, gsave, g_t, grads, s["prec"])
     else:
-        ws = torch.empty(int(lib.nerf_mlp_backward_masked_workspace_bytes(P)), dtype=torch.uint8, device="cuda")
-        L.check(lib.nerf_mlp_backward_masked(*a, L.ptr(index, torch.int32), L.ptr(count, torch.int32), s["pk_b"].data_ptr(), L.ptr(G),
-                                             L.ptr(save), L.ptr(gsave), L.ptr(g_t), _grad_ptrs(grads), s["prec"], ws.data_ptr(), s["st"]))
+        ws = torch.empty(int(L.call("nerf_mlp_backward_masked_workspace_bytes", P)), dtype=torch.uint8, device="cuda")
+        L.call("nerf_mlp_backward_masked", *a, index, count, s["pk_b"], G, save, gsave, g_t, grads, s["prec"], ws)
     torch.cuda.synchronize()
     return g_t, grads
 
 
-def _compact(s, valid):
-    L, lib, P = s["L"], s["lib"], s["P"]
+def _compact(amd, s, valid):
+    L, P = amd._lib, s["P"]
     index = torch.full((P,), -7, dtype=torch.int32, device="cuda")
     count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
-    ws = torch.empty(int(lib.nerf_compact_valid_workspace_bytes(P)), dtype=torch.uint8, device="cuda")
-    L.check(lib.nerf_compact_valid(L.ptr(valid, torch.uint8), P, L.ptr(index, torch.int32), L.ptr(count, torch.int32), ws.data_ptr(), s["st"]))
+    ws = torch.empty(int(L.call("nerf_compact_valid_workspace_bytes", P)), dtype=torch.uint8, device="cuda")
+    L.call("nerf_compact_valid", valid, P, index, count, ws)
     torch.cuda.synchronize()
     return index, count
-
-
-def _assert_grads_equal(got, ref, bound=1e-4):
-    """Form and bound of test_training_step_same_with_and_without_dead_tile_skipping: atomic accumulation order."""
-    for i, (a, b) in enumerate(zip(got, ref)):
-        assert torch.isfinite(a).all(), i
-        if b.abs().max() == 0:
-            assert torch.all(a == 0), i
-        else:
-            assert _rel(a, b) <= bound, (i, _rel(a, b))
 
 
 @pytest.mark.parametrize("n", [96, 4096])
@@ -224,21 +176,21 @@ def test_masked_entries_with_every_point_listed_equal_the_unmasked_entries(amd, 
     nerf_mlp_forward_rays_save_for_compositing / nerf_mlp_backward; the parameter gradients equal to the rounding of their
     atomic accumulation order."""
     s = _abi_setup(amd, synthetic_sd, precision, n, 192, seed=41)
-    lib, P = s["lib"], s["P"]
-    index, count = _compact(s, torch.ones(P, dtype=torch.uint8, device="cuda"))
+    P = s["P"]
+    index, count = _compact(amd, s, torch.ones(P, dtype=torch.uint8, device="cuda"))
     assert int(count.item()) == P and torch.equal(index.cpu(), torch.arange(P, dtype=torch.int32))
-    raw_u, save_u = _forward(s, lib.nerf_mlp_forward_rays_save_for_compositing)
-    raw_m, save_m = _forward(s, lib.nerf_mlp_forward_rays_save_masked, index, count)
+    raw_u, save_u = _forward(amd, s, "nerf_mlp_forward_rays_save_for_compositing")
+    raw_m, save_m = _forward(amd, s, "nerf_mlp_forward_rays_save_masked", index, count)
     torch.cuda.synchronize()
     assert torch.equal(raw_u.view(torch.int32), raw_m.view(torch.int32))
     assert torch.equal(save_u.view(torch.int32), save_m.view(torch.int32))
     G = torch.randn(n, 192, 4, generator=s["gen"]).cuda() * 1e-3 * (raw_u[..., 3:] > 0)     # zero wherever sigma <= 0 (the entries' contract)
     G = G.contiguous()
-    gt_u, grads_u = _backward(s, save_u, G)
-    gt_m, grads_m = _backward(s, save_m, G, index, count)
+    gt_u, grads_u = _backward(amd, s, save_u, G)
+    gt_m, grads_m = _backward(amd, s, save_m, G, index, count)
     assert torch.isfinite(gt_u).all() and torch.equal(gt_u.view(torch.int32), gt_m.view(torch.int32))
     assert any(g.abs().max() > 0 for g in grads_u)
-    _assert_grads_equal(grads_m, grads_u)
+    assert_grads_equal(grads_m, grads_u)
 
 
 @pytest.mark.parametrize("n", [96, 4096])
@@ -250,7 +202,7 @@ def test_masked_entries_on_a_random_half_of_the_points(amd, synthetic_sd, monkey
     at unlisted ids and bit-equal at listed ones, the parameter gradients equal those of nerf_mlp_backward fed the same draw
     with the unlisted rows zeroed.  The same with NERF_DEAD_TILE_SKIP=0 (every occupied compact tile computed)."""
     s = _abi_setup(amd, synthetic_sd, precision, n, 192, seed=43)
-    lib, P = s["lib"], s["P"]
+    P = s["P"]
     valid = (torch.rand(P, generator=s["gen"]) < 0.5)
     if int(valid.sum()) % 32 == 0:
         valid[int(valid.nonzero()[0])] = False
@@ -258,16 +210,16 @@ def test_masked_entries_on_a_random_half_of_the_points(amd, synthetic_sd, monkey
     assert M % 32 != 0
     ids = valid.nonzero()[:, 0].to(torch.int32)
     valid_d = valid.to(torch.uint8).cuda()
-    index, count = _compact(s, valid_d)
+    index, count = _compact(amd, s, valid_d)
     assert int(count.item()) == M and torch.equal(index[:M].cpu(), ids) and torch.all(index[M:] == -7)
-    raw_u, save_u = _forward(s, lib.nerf_mlp_forward_rays_save)
+    raw_u, save_u = _forward(amd, s, "nerf_mlp_forward_rays_save")
     listed = valid.cuda().view(n, 192)
     G = torch.randn(n, 192, 4, generator=s["gen"]).cuda() * 1e-3 * (raw_u[..., 3:] > 0) * listed[..., None]
     G = G.contiguous()
-    gt_u, grads_u = _backward(s, save_u, G)
+    gt_u, grads_u = _backward(amd, s, save_u, G)
     for env in ("1", "0"):
         monkeypatch.setenv("NERF_DEAD_TILE_SKIP", env)
-        raw_m, save_m = _forward(s, lib.nerf_mlp_forward_rays_save_masked, index, count, raw_fill=777.0)
+        raw_m, save_m = _forward(amd, s, "nerf_mlp_forward_rays_save_masked", index, count, raw_fill=777.0)
         torch.cuda.synchronize()
         assert torch.all(raw_m[~listed] == 777.0)
         ru, rm = raw_u[listed], raw_m[listed]
@@ -277,11 +229,11 @@ def test_masked_entries_on_a_random_half_of_the_points(amd, synthetic_sd, monkey
         assert torch.all(same | skipped)
         if env == "0":
             assert torch.all(same)
-        gt_m, grads_m = _backward(s, save_m, G, index, count)
+        gt_m, grads_m = _backward(amd, s, save_m, G, index, count)
         assert torch.all(gt_m[~listed] == 0)
         assert torch.equal(gt_u[listed].view(torch.int32), gt_m[listed].view(torch.int32))
         assert any(g.abs().max() > 0 for g in grads_u)
-        _assert_grads_equal(grads_m, grads_u)
+        assert_grads_equal(grads_m, grads_u)
     monkeypatch.delenv("NERF_DEAD_TILE_SKIP")
 
 
@@ -290,35 +242,34 @@ def test_masked_entries_with_nothing_listed(amd, synthetic_sd, precision):
     """M = 0: success, `raw` and g_t (zero) aside nothing is written, every gradient stays zero.  n_rays = 0: success, nothing
     touched at all.  More than 2^31 - 1 points: refused (point ids are int32)."""
     s = _abi_setup(amd, synthetic_sd, precision, 96, 192, seed=47)
-    L, lib, P = s["L"], s["lib"], s["P"]
-    index, count = _compact(s, torch.zeros(P, dtype=torch.uint8, device="cuda"))
+    L, P = amd._lib, s["P"]
+    lib, st = L.load(), L.stream_of(s["o"].device)
+    index, count = _compact(amd, s, torch.zeros(P, dtype=torch.uint8, device="cuda"))
     assert int(count.item()) == 0 and torch.all(index == -7)
-    raw, save = _forward(s, lib.nerf_mlp_forward_rays_save_masked, index, count, raw_fill=777.0)
+    raw, save = _forward(amd, s, "nerf_mlp_forward_rays_save_masked", index, count, raw_fill=777.0)
     torch.cuda.synchronize()
     assert torch.all(raw == 777.0)
-    stamp = int(lib.nerf_train_save_floats(P)) - 4
+    stamp = int(L.call("nerf_train_save_floats", P)) - 4
     assert torch.all(save[:stamp] == SENTINEL)
     G = torch.randn(96, 192, 4, generator=s["gen"]).cuda().contiguous()
-    g_t, grads = _backward(s, save, G, index, count)
+    g_t, grads = _backward(amd, s, save, G, index, count)
     assert torch.all(g_t == 0) and all(torch.all(g == 0) for g in grads)
     # n_rays = 0
-    a0 = (L.ptr(s["o"]), L.ptr(s["d"]), L.ptr(s["t"]), 192, 0, 192)
-    assert lib.nerf_mlp_forward_rays_save_masked(*a0, L.ptr(index, torch.int32), L.ptr(count, torch.int32), s["pk"].data_ptr(), L.ptr(raw),
-                                                 L.ptr(save), s["prec"], s["st"]) == 0
+    a0 = (s["o"], s["d"], s["t"], 192, 0, 192)
+    assert L.call("nerf_mlp_forward_rays_save_masked", *a0, index, count, s["pk"], raw, save, s["prec"]) == 0
     g0 = [torch.zeros_like(p) for p in s["params"]]
-    assert lib.nerf_mlp_backward_masked(*a0, L.ptr(index, torch.int32), L.ptr(count, torch.int32), s["pk_b"].data_ptr(), L.ptr(G), L.ptr(save),
-                                        None, None, _grad_ptrs(g0), s["prec"], None, s["st"]) == 0
-    assert lib.nerf_compact_valid(None, 0, None, L.ptr(count, torch.int32), None, s["st"]) == 0
+    assert L.call("nerf_mlp_backward_masked", *a0, index, count, s["pk_b"], G, save, None, None, g0, s["prec"], None) == 0
+    assert lib.nerf_compact_valid(None, 0, None, L.ptr(count, torch.int32), None, st) == 0
     torch.cuda.synchronize()
     assert int(count.item()) == 0 and torch.all(raw == 777.0)
     # int32 point ids
     big = (L.ptr(s["o"]), L.ptr(s["d"]), L.ptr(s["t"]), 192, (1 << 31) // 192 + 1, 192)
     assert lib.nerf_mlp_forward_rays_save_masked(*big, L.ptr(index, torch.int32), L.ptr(count, torch.int32), s["pk"].data_ptr(), L.ptr(raw),
-                                                 L.ptr(save), s["prec"], s["st"]) == -1
+                                                 L.ptr(save), s["prec"], st) == -1
     assert lib.nerf_mlp_backward_masked(*big, L.ptr(index, torch.int32), L.ptr(count, torch.int32), s["pk_b"].data_ptr(), L.ptr(G), L.ptr(save),
-                                        L.ptr(save), None, _grad_ptrs(g0), s["prec"], L.ptr(save), s["st"]) == -1
+                                        L.ptr(save), None, L.ptr_array(g0), s["prec"], L.ptr(save), st) == -1
     assert lib.nerf_compact_valid(L.ptr(index, torch.int32), 1 << 31, L.ptr(index, torch.int32), L.ptr(count, torch.int32),
-                                  L.ptr(index, torch.int32), s["st"]) == -1
+                                  L.ptr(index, torch.int32), st) == -1
     assert lib.nerf_compact_valid_workspace_bytes(1 << 31) == -1 and lib.nerf_mlp_backward_masked_workspace_bytes(1 << 31) == -1
 
 
@@ -330,10 +281,9 @@ def test_compact_valid_lists_the_set_ids_in_ascending_order(amd, n_points):
     """nerf_compact_valid against numpy.flatnonzero for an empty, a half-set and a full mask: the count, the ids in ascending
     order, and nothing written behind them -- neither in the rest of `index` nor behind the buffer."""
     import numpy as np
-    L, lib = amd._lib, amd._lib.load()
-    st = L.stream_of(torch.device("cuda"))
+    L = amd._lib
     rng = np.random.default_rng(n_points)
-    ws_bytes = int(lib.nerf_compact_valid_workspace_bytes(n_points))
+    ws_bytes = int(L.call("nerf_compact_valid_workspace_bytes", n_points))
     for density in (0.0, 0.5, 1.0):
         mask = (rng.random(n_points) < density).astype(np.uint8) * rng.integers(1, 256, n_points, dtype=np.uint8)     # any non-zero byte is set
         ref = np.flatnonzero(mask)
@@ -341,8 +291,7 @@ def test_compact_valid_lists_the_set_ids_in_ascending_order(amd, n_points):
         index = torch.full((n_points + 64,), -7, dtype=torch.int32, device="cuda")      # 64 ids of room behind the buffer the entry knows
         count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
         ws = torch.full((ws_bytes + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-        L.check(lib.nerf_compact_valid(L.ptr(valid, torch.uint8), n_points, L.ptr(index, torch.int32), L.ptr(count, torch.int32),
-                                       ws.data_ptr(), st))
+        L.call("nerf_compact_valid", valid, n_points, index, count, ws)
         torch.cuda.synchronize()
         print(n_points, density, int(count.item()), int(mask.astype(bool).sum()))
         assert int(count.item()) == int((mask != 0).sum()) == ref.size
@@ -363,7 +312,7 @@ def test_masked_step_same_with_and_without_dead_tile_skipping(amd, family_sd, go
     out = {}
     for env in ("1", "0"):
         monkeypatch.setenv("NERF_DEAD_TILE_SKIP", env)
-        net = _net(amd, family_sd(family), precision)
+        net = network(amd, family_sd(family), precision, train=True)
         ren = amd.Renderer(net)
         ren.fast_sampling, ren.weights_threshold = True, thr
         ren.live_tile_stats, ren.masked_stats = [], []
@@ -379,7 +328,7 @@ def test_masked_step_same_with_and_without_dead_tile_skipping(amd, family_sd, go
     m = out["1"][5]
     assert out["0"][5] == m and out["0"][4] == (m + 31) // 32 and 0 <= out["1"][4] <= out["0"][4]
     print(f"masked step [{tag}/{precision}]: {out['1'][4]} live of {out['0'][4]} occupied compact tiles ({96 * 192 // 32} tiles unmasked)")
-    _assert_grads_equal(out["1"][3], out["0"][3])
+    assert_grads_equal(out["1"][3], out["0"][3])
 
 
 # ================================================================================ 6: it trains
@@ -389,7 +338,7 @@ def test_short_masked_training_run_reduces_loss(amd, oracle, family_sd, precisio
     rendered by the same masked renderer: the fine colour head is knocked off and trained back; same pass condition."""
     from nerf_replication_amd.training import train_step
     torch.manual_seed(0)
-    net = _net(amd, family_sd("trained"), precision)
+    net = network(amd, family_sd("trained"), precision, train=True)
     ren = amd.Renderer(net)
     ren.fast_sampling, ren.weights_threshold = True, 0.02
     ids = torch.randperm(800 * 800, generator=torch.Generator().manual_seed(9))[:1024]
@@ -419,7 +368,7 @@ def test_coarse_only_step_matches_reference_autograd(amd, family_sd, golden, pre
     bound of test_training_step_matches_reference_autograd (5e-4 of the tensor's largest entry); depth, which that test does not
     bound, to the 2e-3 that test_render_masked_golden allows the no-grad render."""
     c = _case(golden, "coarse_only")
-    net = _net(amd, family_sd("trained"), precision)
+    net = network(amd, family_sd("trained"), precision, train=True)
     ren = amd.Renderer(net)
     ren.N_importance = 0
     rgb, dep = ren.render({"rays_o": c["rays_o"][None].cuda(), "rays_d": c["rays_d"][None].cuda()})
@@ -447,7 +396,7 @@ def test_coarse_only_step_matches_reference_autograd(amd, family_sd, golden, pre
 @pytest.mark.parametrize("mode", ["fast_sampling", "no_importance"])
 @pytest.mark.parametrize("precision", ["f16", "f16m32"])
 def test_fp16_training_still_refused(amd, synthetic_sd, oracle, precision, mode):
-    net = _net(amd, synthetic_sd, precision)
+    net = network(amd, synthetic_sd, precision, train=True)
     ren = amd.Renderer(net)
     if mode == "fast_sampling":
         ren.fast_sampling = True

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import isosurface_reference as R
+from gpu_common import amd, network  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,13 +21,6 @@ BIG = (67, 63, 66)
 SHAPES = [(2, 2, 2), (9, 12, 17), (33, 33, 33), BIG]
 FIELDS = ["sphere", "two_spheres", "torus", "sinusoids", "random"]
 V_SENTINEL, T_SENTINEL, PAD = 12345.0, -7, 5
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 @functools.lru_cache(maxsize=None)
@@ -48,20 +42,16 @@ def _device_field(f, stride):
 
 def _run_abi(amd, field, level, origin, step):
     """count + emit through the C ABI into oversized, sentinel-filled buffers -> (V, T, vertices buffer, triangles buffer)."""
-    import ctypes
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     nx, ny, nz = field.shape
     stride = field.stride(2)
-    st = L.stream_of(field.device)
-    ws = torch.empty(int(lib.nerf_isosurface_workspace_bytes(nx, ny, nz)), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(int(L.call("nerf_isosurface_workspace_bytes", nx, ny, nz)), dtype=torch.uint8, device="cuda")
     counts = torch.full((2,), -99, dtype=torch.int32, device="cuda")
-    L.check(lib.nerf_isosurface_count(field.data_ptr(), stride, nx, ny, nz, level, ws.data_ptr(), counts.data_ptr(), st))
+    L.call("nerf_isosurface_count", L.strided(field), stride, nx, ny, nz, level, ws, counts)
     n_v, n_t = counts.tolist()
     vbuf = torch.full((n_v + PAD, 3), V_SENTINEL, device="cuda")
     tbuf = torch.full((n_t + PAD, 3), T_SENTINEL, dtype=torch.int32, device="cuda")
-    c3 = ctypes.c_double * 3
-    L.check(lib.nerf_isosurface_emit(field.data_ptr(), stride, nx, ny, nz, level, c3(*origin), c3(*step), ws.data_ptr(),
-                                     vbuf.data_ptr(), tbuf.data_ptr(), st))
+    L.call("nerf_isosurface_emit", L.strided(field), stride, nx, ny, nz, level, origin, step, ws, vbuf, tbuf)
     torch.cuda.synchronize()
     return n_v, n_t, vbuf, tbuf
 
@@ -107,15 +97,15 @@ def test_isosurface_raw_buffer_argument(amd):
 
 
 def test_isosurface_empty_results(amd):
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     f = torch.from_numpy(np.array(_case("sphere", (9, 12, 17))[0])).cuda()
     for field, level in ((f, 10.0), (f, -10.0), (f[:1].contiguous(), 0.0), (f[:, :1].contiguous(), 0.0), (f[:, :, :1].contiguous(), 0.0)):
         v, t = amd.isosurface(field, level, R.BOX_ORIGIN, (0.1, 0.1, 0.1))
         assert v.shape == (0, 3) and t.shape == (0, 3) and v.dtype == torch.float32 and t.dtype == torch.int32
         nx, ny, nz = field.shape
         counts = torch.full((2,), -99, dtype=torch.int32, device="cuda")
-        ws = torch.empty(max(1, int(lib.nerf_isosurface_workspace_bytes(nx, ny, nz))), dtype=torch.uint8, device="cuda")
-        L.check(lib.nerf_isosurface_count(field.data_ptr(), 1, nx, ny, nz, level, ws.data_ptr(), counts.data_ptr(), L.stream_of(f.device)))
+        ws = torch.empty(max(1, int(L.call("nerf_isosurface_workspace_bytes", nx, ny, nz))), dtype=torch.uint8, device="cuda")
+        L.call("nerf_isosurface_count", field, 1, nx, ny, nz, level, ws, counts)
         assert counts.tolist() == [0, 0]
 
 
@@ -158,14 +148,6 @@ BOX = [-1.2, -0.8, -1.5, 1.1, 0.9, 1.4]
 DIMS = (8, 6, 10)
 
 
-def _network(amd, sd, precision="f32"):
-    net = amd.Network()
-    net.load_state_dict(sd, strict=True)
-    net = net.cuda().eval()
-    net.precision = precision
-    return net
-
-
 def _grid_points():
     from nerf_replication_amd.mesh import grid_axes
     axes, _, _ = grid_axes(BOX, DIMS)
@@ -176,7 +158,7 @@ def _grid_points():
 
 
 def test_density_grid_f32_is_the_point_mode_sigma(amd, oracle, synthetic_sd):
-    net = _network(amd, synthetic_sd)
+    net = network(amd, synthetic_sd, "f32", train=False)
     pts, vd, _ = _grid_points()
     grid = amd.density_grid(net, BOX, DIMS)
     assert grid.shape == DIMS and grid.dtype == torch.float32 and grid.is_cuda and grid.is_contiguous()
@@ -193,15 +175,14 @@ def test_density_grid_f32_is_the_point_mode_sigma(amd, oracle, synthetic_sd):
 
 @pytest.mark.parametrize("precision", ["f16", "f32x", "f16m32"])
 def test_density_grid_other_precisions_are_the_ray_mode_sigma(amd, synthetic_sd, precision):
-    lib, L = amd._lib.load(), amd._lib
-    net = _network(amd, synthetic_sd, precision)
+    L = amd._lib
+    net = network(amd, synthetic_sd, precision, train=False)
     pts, vd, z = _grid_points()
     o = pts[:, 0, :].clone()
     o[:, 2] = 0.0
     o, d, t = o.cuda(), vd.cuda(), z.cuda()
     full = torch.empty(pts.shape[0], DIMS[2], 4, device="cuda")
-    L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(t), 0, pts.shape[0], DIMS[2], net.packed("fine").data_ptr(),
-                                      L.ptr(full), L.PRECISIONS[precision], L.stream_of(o.device)))
+    L.call("nerf_mlp_forward_rays", o, d, t, 0, pts.shape[0], DIMS[2], net.packed("fine"), full, L.PRECISIONS[precision])
     grid = amd.density_grid(net, BOX, DIMS)
     assert torch.equal(grid.reshape(-1, DIMS[2]), full[..., 3])
     assert torch.equal(amd.density_grid(net, BOX, DIMS, chunk_lines=7), grid)
@@ -223,7 +204,7 @@ def _read_ply(path):
 
 
 def test_extract_mesh_end_to_end(amd, family_sd, tmp_path):
-    net = _network(amd, family_sd("trained"))
+    net = network(amd, family_sd("trained"), "f32", train=False)
     box, n = [-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], 48
     grid = amd.density_grid(net, box, n)
     level = 0.5 * (grid.median().item() + grid.max().item())            # from the grid itself: the surface is not empty

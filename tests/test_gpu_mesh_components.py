@@ -11,20 +11,14 @@ import torch
 
 import isosurface_reference as R
 import mesh_components_reference as M
-from test_gpu_mesh import FIELDS, SHAPES, _bits, _case, _network
+from gpu_common import amd, network  # noqa: F401
+from test_gpu_mesh import FIELDS, SHAPES, _bits, _case
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL, PAD = -77, 5
 WS_PAD = 512                       # bytes of sentinel on both sides of the workspace
 WS_BYTE = 0xA5
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 @functools.lru_cache(maxsize=None)
@@ -49,10 +43,10 @@ def _intact(whole, n, fill=SENTINEL):
 def _run_components(amd, faces, V):
     """nerf_mesh_components through the C ABI.  faces: numpy [T,3].  The label buffers and the workspace (which holds parent[]) are
     interior slices of sentinel-filled tensors, the table has PAD spare rows -> dict of device tensors; the sentinels are checked."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     f = torch.from_numpy(np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)).cuda()
     T = f.shape[0]
-    nbytes = int(lib.nerf_mesh_components_workspace_bytes(V, T))
+    nbytes = int(L.call("nerf_mesh_components_workspace_bytes", V, T))
     assert nbytes >= 0
     ws_whole = torch.full((nbytes + 2 * WS_PAD,), WS_BYTE, dtype=torch.uint8, device="cuda")
     ws = ws_whole[WS_PAD:WS_PAD + nbytes]
@@ -60,9 +54,7 @@ def _run_components(amd, faces, V):
     fl_whole, fl = _padded(T)
     table = torch.full((3, V + PAD), SENTINEL, dtype=torch.int32, device="cuda")
     n_comp = torch.full((1,), SENTINEL, dtype=torch.int32, device="cuda")
-    L.check(lib.nerf_mesh_components(f.data_ptr(), T, V, ws.data_ptr(), vl.data_ptr(), fl.data_ptr(), table[0].data_ptr(),
-                                     table[1].data_ptr(), table[2].data_ptr(), n_comp.data_ptr(), L.stream_of(f.device)),
-            "nerf_mesh_components")
+    L.call("nerf_mesh_components", f, T, V, ws, vl, fl, table[0], table[1], table[2], n_comp)
     torch.cuda.synchronize()
     C = int(n_comp.item())
     assert 0 <= C <= V
@@ -192,20 +184,17 @@ def test_components_out_of_range_faces_join_nothing(amd):
 def _run_filter(amd, comp, vertices, keep_labels):
     """nerf_mesh_filter_count / _emit through the C ABI on the labels of `comp`, keeping the components in keep_labels; outputs
     oversized and sentinel-filled -> (V', T', vertices buffer, faces buffer, vertex_index buffer)."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     V, T = comp["V"], comp["T"]
     keep = torch.zeros(V, dtype=torch.uint8, device="cuda")
     keep[torch.tensor(sorted(keep_labels), dtype=torch.int64, device="cuda")] = 1
     counts = torch.full((2,), SENTINEL, dtype=torch.int32, device="cuda")
-    st = L.stream_of(keep.device)
-    L.check(lib.nerf_mesh_filter_count(comp["vertex_label"].data_ptr(), comp["face_label"].data_ptr(), keep.data_ptr(), V, T,
-                                       comp["workspace"].data_ptr(), counts.data_ptr(), st), "nerf_mesh_filter_count")
+    L.call("nerf_mesh_filter_count", comp["vertex_label"], comp["face_label"], keep, V, T, comp["workspace"], counts)
     n_v, n_t = counts.tolist()
     vbuf = torch.full((n_v + PAD, 3), 12345.0, device="cuda")
     fbuf = torch.full((n_t + PAD, 3), SENTINEL, dtype=torch.int32, device="cuda")
     ibuf = torch.full((n_v + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
-    L.check(lib.nerf_mesh_filter_emit(vertices.data_ptr(), comp["faces"].data_ptr(), V, T, comp["workspace"].data_ptr(), vbuf.data_ptr(),
-                                      fbuf.data_ptr(), ibuf.data_ptr(), st), "nerf_mesh_filter_emit")
+    L.call("nerf_mesh_filter_emit", vertices, comp["faces"], V, T, comp["workspace"], vbuf, fbuf, ibuf)
     torch.cuda.synchronize()
     assert bool((vbuf[n_v:] == 12345.0).all() and (fbuf[n_t:] == SENTINEL).all() and (ibuf[n_v:] == SENTINEL).all())
     return n_v, n_t, vbuf, fbuf, ibuf
@@ -305,7 +294,7 @@ def _points_and_dirs(n=200, seed=7):
 def test_vertex_colors_f32_against_the_oracle(amd, oracle, synthetic_sd):
     """bound: max|d c| <= 1/4 * 2e-5 * max|raw_ref| over the colour channels -- DESIGN 3.1's fp32 raw tolerance times the sigmoid's
     largest slope."""
-    net = _network(amd, synthetic_sd)
+    net = network(amd, synthetic_sd, "f32", train=False)
     pts, dirs = _points_and_dirs()
     col = amd.vertex_colors(net, pts.cuda(), dirs.cuda())
     assert col.shape == (200, 3) and col.dtype == torch.float32 and col.is_cuda
@@ -321,7 +310,7 @@ def test_vertex_colors_f32_against_the_oracle(amd, oracle, synthetic_sd):
 
 
 def test_vertex_colors_default_direction_is_against_the_normal(amd, synthetic_sd):
-    net = _network(amd, synthetic_sd)
+    net = network(amd, synthetic_sd, "f32", train=False)
     pts, _ = _points_and_dirs(96, seed=8)
     pts = pts.cuda()
     n = amd.vertex_normals(net, pts)
@@ -332,13 +321,12 @@ def test_vertex_colors_default_direction_is_against_the_normal(amd, synthetic_sd
 
 @pytest.mark.parametrize("precision", ["f16", "f32x"])
 def test_vertex_colors_other_precisions_are_the_mlp_forward(amd, synthetic_sd, precision):
-    lib, L = amd._lib.load(), amd._lib
-    net = _network(amd, synthetic_sd, precision)
+    L = amd._lib
+    net = network(amd, synthetic_sd, precision, train=False)
     pts, dirs = _points_and_dirs()
     pts, dirs = pts.cuda(), dirs.cuda()
     raw = torch.empty(200, 1, 4, device="cuda")
-    L.check(lib.nerf_mlp_forward(L.ptr(pts), L.ptr(dirs), 200, 1, net.packed("fine").data_ptr(), L.ptr(raw), L.PRECISIONS[precision],
-                                 L.stream_of(pts.device)), "nerf_mlp_forward")
+    L.call("nerf_mlp_forward", pts, dirs, 200, 1, net.packed("fine"), raw, L.PRECISIONS[precision])
     assert torch.equal(amd.vertex_colors(net, pts, dirs), torch.sigmoid(raw[:, 0, :3]))
 
 
@@ -362,7 +350,7 @@ def _read_ply(path):
 
 def test_extract_mesh_filtered_with_normals_and_colours(amd, family_sd, tmp_path):
     from nerf_replication_amd.mesh import grid_axes
-    net = _network(amd, family_sd("trained"))
+    net = network(amd, family_sd("trained"), "f32", train=False)
     box, n = [-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], 48
     grid = amd.density_grid(net, box, n)
     level = 0.5 * (grid.median().item() + grid.max().item())            # the level rule of test_extract_mesh_end_to_end

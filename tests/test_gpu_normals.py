@@ -11,6 +11,7 @@ import torch
 import normals_reference as NR
 from conftest import parity_record
 from test_gpu_ray_grad import BARS          # f32 (3.0, 1e-3), f32x (4.0, 1e-3): the same chain, the project's bars
+from gpu_common import amd, network  # noqa: F401
 
 # Measured on the MI355X (profiles/parity_r03.json "gradients"): density_gradient/*, HIP q99 over torch-fp32 q99 of the per-point
 # error: f32 1.40 (synthetic) / 1.09 (trained), f32x 0.94 / 1.05 -- q99 1.4e-6 .. 2.0e-6, every point within the bar;
@@ -20,22 +21,6 @@ from test_gpu_ray_grad import BARS          # f32 (3.0, 1e-3), f32x (4.0, 1e-3):
 pytestmark = pytest.mark.gpu
 
 ERR_WORKSPACE = -2
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
-
-
-def _net(amd, sd, precision="f32"):
-    net = amd.Network()
-    net.load_state_dict(sd, strict=True)
-    net = net.cuda().eval()
-    net.requires_grad_(False)
-    net.precision = precision
-    return net
 
 
 def _sd(scene, synthetic_sd, family_sd):
@@ -57,10 +42,10 @@ def _density_gradient(amd, net, model, o, d, t, positive_only, block_points, str
     n, S = o.shape[0], t.shape[-1]
     sigma = torch.full((n, S), 7.0, device="cuda") if want_sigma else None
     grad = torch.full((n, S, 3), 7.0, device="cuda")
-    ws = torch.empty(max(1, int(lib.nerf_density_gradient_point_bytes()) * block_points), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(max(1, int(L.call("nerf_density_gradient_point_bytes")) * block_points), dtype=torch.uint8, device="cuda")
     rc = lib.nerf_density_gradient(L.ptr(o), L.ptr(d), L.ptr(t), S if stride is None else stride, n, S, net.packed(model).data_ptr(),
                                    net.packed_bwd(model).data_ptr(), int(positive_only), L.ptr(sigma), L.ptr(grad),
-                                   L.PRECISIONS[net.precision], ws.data_ptr(), int(lib.nerf_density_gradient_point_bytes()) * block_points,
+                                   L.PRECISIONS[net.precision], ws.data_ptr(), int(L.call("nerf_density_gradient_point_bytes")) * block_points,
                                    L.stream_of(o.device))
     torch.cuda.synchronize()
     return rc, sigma, grad
@@ -88,16 +73,15 @@ def test_density_gradient_matches_float64(amd, oracle, synthetic_sd, family_sd, 
     """5 rays x 37 samples = 185 points (a ragged last tile).  Per-point error |g - g64| / max(|g64|, 1e-3 max |g64|); at least 98 %
     of the points within FACTOR x torch-fp32's q99 + ABS (test_gpu_ray_grad._judge's rule and bars).  sigma is bit for bit the
     density-only forward's."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     sd = _sd(scene, synthetic_sd, family_sd)
     o, d, t, (_, g32), (s64, g64) = _point_refs(oracle, scene, sd)
-    net = _net(amd, sd, precision)
+    net = network(amd, sd, precision, train=False, frozen=True)
     oc, dc, tc = o.cuda(), d.cuda(), t.cuda()
     rc, sigma, grad = _density_gradient(amd, net, "fine", oc, dc, tc, 0, 192)       # 185 points, rounded up to whole tiles
     assert rc == 0
     raw = torch.empty(5, 37, 4, device="cuda")
-    L.check(lib.nerf_mlp_forward_rays_density(L.ptr(oc), L.ptr(dc), L.ptr(tc), 37, 5, 37, net.packed("fine").data_ptr(), L.ptr(raw),
-                                              L.PRECISIONS[precision], L.stream_of(oc.device)))
+    L.call("nerf_mlp_forward_rays_density", oc, dc, tc, 37, 5, 37, net.packed("fine"), raw, L.PRECISIONS[precision])
     assert torch.equal(sigma, raw[..., 3])
     assert (sigma.cpu().reshape(-1).double() - s64).abs().max() <= 1e-3 * max(1.0, s64.abs().max().item())
     assert (s64 > 0).any() and g64.abs().max() > 0
@@ -127,7 +111,7 @@ MIXED_PIXELS = (160400, 320200, 192400, 320400, 320640, 320680)
 def test_density_gradient_is_the_composed_calls_whatever_the_blocking(amd, oracle, family_sd, precision):
     lib, L = amd._lib.load(), amd._lib
     prec = L.PRECISIONS[precision]
-    net = _net(amd, family_sd("trained"), precision)
+    net = network(amd, family_sd("trained"), precision, train=False, frozen=True)
     o, d = (x.cuda() for x in _camera_rays(oracle, MIXED_PIXELS))
     n, S = 6, 64
     P = n * S
@@ -138,18 +122,16 @@ def test_density_gradient_is_the_composed_calls_whatever_the_blocking(amd, oracl
 
     # 2. by hand: the density SAVE forward, the seed, the chain alone
     raw = torch.empty(P, 4, device="cuda")
-    save = torch.empty(int(lib.nerf_train_save_floats(P)), device="cuda")
-    L.check(lib.nerf_mlp_forward_rays_save_density(L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, net.packed("fine").data_ptr(), L.ptr(raw),
-                                                   L.ptr(save), prec, st))
+    save = torch.empty(int(L.call("nerf_train_save_floats", P)), device="cuda")
+    L.call("nerf_mlp_forward_rays_save_density", o, d, t, S, n, S, net.packed("fine"), raw, save, prec)
     assert torch.equal(sigma.reshape(-1), raw[:, 3])
 
     def by_hand(seed):
         draw = torch.zeros(P, 4, device="cuda")
         draw[:, 3] = seed
-        gsave = torch.empty(int(lib.nerf_train_grad_floats(P)), device="cuda")
+        gsave = torch.empty(int(L.call("nerf_train_grad_floats", P)), device="cuda")
         g_x = torch.full((P, 3), 7.0, device="cuda")
-        L.check(lib.nerf_mlp_backward_rays_x(L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, net.packed_bwd("fine").data_ptr(), L.ptr(draw),
-                                             L.ptr(save), L.ptr(gsave), None, L.ptr(g_x), None, 1, prec, st))
+        L.call("nerf_mlp_backward_rays_x", o, d, t, S, n, S, net.packed_bwd("fine"), draw, save, gsave, None, g_x, None, 1, prec)
         torch.cuda.synchronize()
         return g_x.view(n, S, 3)
     assert torch.equal(grad, by_hand(1.0))
@@ -173,7 +155,7 @@ def test_density_gradient_is_the_composed_calls_whatever_the_blocking(amd, oracl
     # sigma is optional; fp16 is refused; no rays is a no-op
     rc, _, g_b = _density_gradient(amd, net, "fine", o, d, t, 0, P, want_sigma=False)
     assert rc == 0 and torch.equal(g_b, grad)
-    ws = torch.empty(int(lib.nerf_density_gradient_point_bytes()) * P, dtype=torch.uint8, device="cuda")
+    ws = torch.empty(int(L.call("nerf_density_gradient_point_bytes")) * P, dtype=torch.uint8, device="cuda")
     args = lambda n_rays, p: (L.ptr(o), L.ptr(d), L.ptr(t), S, n_rays, S, net.packed("fine").data_ptr(), net.packed_bwd("fine").data_ptr(),
                               0, None, L.ptr(g_b), p, ws.data_ptr(), ws.numel(), st)
     assert lib.nerf_density_gradient(*args(n, L.PREC_F16)) == -4 and lib.nerf_density_gradient(*args(0, prec)) == 0
@@ -203,14 +185,14 @@ def test_composite_normals_against_float64(amd, S):
     def run():
         normal = torch.full((n, 3), 7.0, device="cuda")
         acc = torch.full((n,), 7.0, device="cuda")
-        L.check(lib.nerf_composite_normals(L.ptr(rawc), L.ptr(tc), S, n, S, L.ptr(gc), L.ptr(normal), L.ptr(acc), st))
+        L.call("nerf_composite_normals", rawc, tc, S, n, S, gc, normal, acc)
         torch.cuda.synchronize()
         return normal, acc
     normal, acc = run()
     again = run()
     assert torch.equal(normal.view(torch.int32), again[0].view(torch.int32)) and torch.equal(acc.view(torch.int32), again[1].view(torch.int32))
     rgb, depth, weights = torch.empty(n, 3, device="cuda"), torch.empty(n, device="cuda"), torch.empty(n, S, device="cuda")
-    L.check(lib.nerf_composite(L.ptr(rawc), L.ptr(tc), S, n, S, 1, L.ptr(rgb), L.ptr(depth), L.ptr(weights), st))
+    L.call("nerf_composite", rawc, tc, S, n, S, 1, rgb, depth, weights)
     w = weights.cpu()
     acc_seq = torch.zeros(n)
     for k in range(S):
@@ -228,8 +210,8 @@ def test_composite_normals_against_float64(amd, S):
     t0 = tc[0].contiguous()
     g_nan = torch.where((rawc[..., 3] <= 0)[..., None], torch.full_like(gc, float("nan")), gc)
     out = [torch.empty(n, 3, device="cuda"), torch.empty(n, device="cuda"), torch.empty(n, 3, device="cuda"), torch.empty(n, device="cuda")]
-    L.check(lib.nerf_composite_normals(L.ptr(rawc), L.ptr(t0), 0, n, S, L.ptr(gc), L.ptr(out[0]), L.ptr(out[1]), st))
-    L.check(lib.nerf_composite_normals(L.ptr(rawc), L.ptr(t0), 0, n, S, L.ptr(g_nan), L.ptr(out[2]), L.ptr(out[3]), st))
+    L.call("nerf_composite_normals", rawc, t0, 0, n, S, gc, out[0], out[1])
+    L.call("nerf_composite_normals", rawc, t0, 0, n, S, g_nan, out[2], out[3])
     assert torch.equal(out[0], out[2]) and torch.equal(out[1], out[3]) and torch.equal(out[0][0], normal[0])
     assert lib.nerf_composite_normals(L.ptr(rawc), L.ptr(tc), 193, n, 193, L.ptr(gc), L.ptr(normal), L.ptr(acc), st) == -1
 
@@ -250,7 +232,7 @@ def test_planar_density_through_the_renderer(amd, oracle, synthetic_sd, precisio
     s_near, s_far = (o + 2.0 * d).double() @ a + PLANE_C, (o + 6.0 * d).double() @ a + PLANE_C
     inside, never = s_far > 1e-3, (s_near < -1e-3) & (s_far < -1e-3)        # sigma is linear along a ray: its maximum is at an end
     assert inside.sum() >= 8 and never.sum() >= 8
-    ren = amd.Renderer(_net(amd, sd, precision))
+    ren = amd.Renderer(network(amd, sd, precision, train=False, frozen=True))
     ren.N_importance = n_importance
     out = ren.render_geometry({"rays_o": o[None].cuda(), "rays_d": d[None].cuda()})
     normal, acc = out["normal"].cpu().double(), out["acc"].cpu().double()
@@ -287,7 +269,7 @@ def test_render_geometry_contract(amd, oracle, family_sd, monkeypatch, precision
     sd = family_sd("trained")
     ref = _frame_refs(oracle, sd)
     batch = {"rays_o": ref["o"][None].cuda(), "rays_d": ref["d"][None].cuda()}
-    ren = amd.Renderer(_net(amd, sd, precision))
+    ren = amd.Renderer(network(amd, sd, precision, train=False, frozen=True))
     rgb, depth = ren.render(batch)
     ren.geometry_block_rays = 40
     with torch.enable_grad():
@@ -330,7 +312,7 @@ def test_render_geometry_contract(amd, oracle, family_sd, monkeypatch, precision
 
 @pytest.mark.parametrize("case", ["f16", "f16m32", "fast_sampling", "occupancy", "train_perturb", "rays_require_grad"])
 def test_render_geometry_refuses_what_is_not_built(amd, oracle, synthetic_sd, case):
-    net = _net(amd, synthetic_sd, case if case.startswith("f16") else "f32")
+    net = network(amd, synthetic_sd, case if case.startswith("f16") else "f32", train=False, frozen=True)
     ren = amd.Renderer(net)
     o, d = (x.cuda() for x in _camera_rays(oracle, OBJECT_PIXELS["synthetic_sd"]))
     words = {"f16": "f16", "f16m32": "f16m32", "fast_sampling": "fast_sampling", "occupancy": "occupancy", "train_perturb": "perturb",
@@ -338,7 +320,7 @@ def test_render_geometry_refuses_what_is_not_built(amd, oracle, synthetic_sd, ca
     if case == "fast_sampling":
         ren.fast_sampling = True
     if case == "occupancy":
-        ren.occupancy = amd.OccupancyGrid.from_network(_net(amd, synthetic_sd, "f32"), [-2, -2, -2, 2, 2, 2], 8)
+        ren.occupancy = amd.OccupancyGrid.from_network(network(amd, synthetic_sd, "f32", train=False, frozen=True), [-2, -2, -2, 2, 2, 2], 8)
     if case == "train_perturb":
         ren.task, ren.perturb = "train", True
     if case == "rays_require_grad":
@@ -355,7 +337,7 @@ def test_render_geometry_refuses_what_is_not_built(amd, oracle, synthetic_sd, ca
 @pytest.mark.parametrize("precision", ["f32", "f32x"])
 def test_vertex_normals_of_an_extracted_mesh(amd, synthetic_sd, tmp_path, precision):
     from nerf_replication_amd.mesh import grid_axes
-    net = _net(amd, synthetic_sd, precision)
+    net = network(amd, synthetic_sd, precision, train=False, frozen=True)
     box, N = [-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], 24
     grid = amd.density_grid(net, box, N)
     level = 0.5 * (grid.median().item() + grid.max().item())

@@ -1,7 +1,6 @@
 """GPU tests of the occupancy grid (nerf_replication_amd/occupancy.py): the nerf_occupancy_* kernels against
 the NumPy restatement tests/occupancy_reference.py (byte for byte), and the culled render against the plain render: bit-equal on
 every ray none of whose culled samples has a positive density, which the staged entries decide."""
-import ctypes
 import functools
 
 import numpy as np
@@ -11,6 +10,7 @@ import torch
 import isosurface_reference as R
 import occupancy_reference as O
 from conftest import parity_record
+from gpu_common import amd, network  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -18,13 +18,6 @@ SENTINEL, PAD = -1412567297, 6            # 0xABCDEEFF as int32
 BOX = [-2.0, -2.0, -2.0, 2.0, 2.0, 2.0]
 BIG_BOX = [-8.0, -8.0, -8.0, 8.0, 8.0, 8.0]          # contains every sample: |o| = 4.03, t <= 6 (t_sorted <= 6 too)
 N_PROBE = 512
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 # ---- 1. build ---------------------------------------------------------------------------------------------------------------------
@@ -37,11 +30,11 @@ def _device_field(f, stride):
 
 
 def _build_abi(amd, field, level, dilate):
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     nx, ny, nz = field.shape
-    n_words = int(lib.nerf_occupancy_words(nx, ny, nz))
+    n_words = int(L.call("nerf_occupancy_words", nx, ny, nz))
     buf = torch.full((n_words + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
-    L.check(lib.nerf_occupancy_build(field.data_ptr(), field.stride(2), nx, ny, nz, level, dilate, buf.data_ptr(), L.stream_of(field.device)))
+    L.call("nerf_occupancy_build", L.strided(field), field.stride(2), nx, ny, nz, level, dilate, buf)
     torch.cuda.synchronize()
     assert (buf[n_words:] == SENTINEL).all()
     return buf[:n_words].cpu().numpy().view(np.uint32)
@@ -87,10 +80,7 @@ def _probe_rays():
 
 
 def _mark_abi(amd, o, d, t, stride, S, bits, dims, lo, inv, and_with_existing, valid):
-    lib, L = amd._lib.load(), amd._lib
-    i3, f3 = ctypes.c_int32 * 3, ctypes.c_float * 3
-    L.check(lib.nerf_occupancy_mark(L.ptr(o), L.ptr(d), L.ptr(t), stride, o.shape[0], S, bits.data_ptr(), i3(*dims), f3(*lo.tolist()),
-                                    f3(*inv.tolist()), and_with_existing, valid.data_ptr(), L.stream_of(o.device)))
+    amd._lib.call("nerf_occupancy_mark", o, d, t, stride, o.shape[0], S, bits, dims, lo.tolist(), inv.tolist(), and_with_existing, valid)
     torch.cuda.synchronize()
     return valid
 
@@ -126,14 +116,6 @@ def test_mark_equals_the_restatement(amd, S):
 
 
 # ---- 3. render exactness ------------------------------------------------------------------------------------------------------------
-def _network(amd, sd, precision):
-    net = amd.Network()
-    net.load_state_dict(sd, strict=True)
-    net = net.cuda().eval()
-    net.precision = precision
-    return net
-
-
 def _render(amd, net, o, d, grid=None, n_importance=128, fast=False, threshold=0.25):
     """-> rgb, depth, evaluated (a list of two ints, None without a grid)"""
     r = amd.Renderer(net)
@@ -165,20 +147,20 @@ def scene(amd, family_sd):
     def get(family, precision):
         key = (family, precision)
         if key not in _SCENES:
-            lib, L = amd._lib.load(), amd._lib
-            net = _network(amd, family_sd(family), precision)
+            L = amd._lib
+            net = network(amd, family_sd(family), precision, train=False)
             o, d = _probe_rays()
-            n, st, prec = o.shape[0], L.stream_of(o.device), L.PRECISIONS[precision]
+            n, prec = o.shape[0], L.PRECISIONS[precision]
             grid = amd.OccupancyGrid.from_network(net, BOX, 64, dilate=1)
             assert grid.dims == (64, 64, 64) and grid.bits[""] is not None and grid.bits["fine"] is not None
             # the plain stages, one by one
             t_c, u = torch.linspace(2.0, 6.0, 64).cuda(), torch.linspace(0.0, 1.0, 128).cuda()
             raw_c = torch.empty(n, 64, 4, device="cuda")
-            L.check(lib.nerf_mlp_forward_rays_density(L.ptr(o), L.ptr(d), L.ptr(t_c), 0, n, 64, net.packed("").data_ptr(), L.ptr(raw_c), prec, st))
+            L.call("nerf_mlp_forward_rays_density", o, d, t_c, 0, n, 64, net.packed(""), raw_c, prec)
             t_sorted = torch.empty(n, 192, device="cuda")
-            L.check(lib.nerf_sample_fine(L.ptr(raw_c), L.ptr(t_c), L.ptr(u), n, L.ptr(t_sorted), None, None, 0.0, 0.0, st))
+            L.call("nerf_sample_fine", raw_c, t_c, u, n, t_sorted, None, None, 0.0, 0.0)
             raw_f = torch.empty(n, 192, 4, device="cuda")
-            L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(t_sorted), 192, n, 192, net.packed("fine").data_ptr(), L.ptr(raw_f), prec, st))
+            L.call("nerf_mlp_forward_rays", o, d, t_sorted, 192, n, 192, net.packed("fine"), raw_f, prec)
             # the two marks
             lo, inv = O.lookup_frame(BOX, grid.dims)
             assert np.array_equal(lo, grid.box_min) and np.array_equal(inv, grid.inv_step)
@@ -288,7 +270,7 @@ def test_ray_blocks_change_nothing(amd, scene, monkeypatch):
 # ---- 7. refusals --------------------------------------------------------------------------------------------------------------------
 def test_refusals(amd, family_sd):
     o, d = (x[:64].contiguous() for x in _probe_rays())
-    net = _network(amd, family_sd("sharp"), "f32")
+    net = network(amd, family_sd("sharp"), "f32", train=False)
     grid = amd.OccupancyGrid.from_network(net, BOX, (9, 12, 17))
     r = amd.Renderer(net)
     r.occupancy = grid

@@ -12,6 +12,7 @@ import isosurface_reference as R
 import occupancy_reference as O
 import occupancy_train_reference as A
 from conftest import parity_record
+from gpu_common import Replay, amd, assert_grads_equal, network, rel  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,22 +22,14 @@ N_PROBE = 512
 SENTINEL_F, SENTINEL_B, PAD = 12345.0, 77, 6
 
 
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
-
-
 def _same_bits(a, b):
     return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # ---- 1. the age kernel --------------------------------------------------------------------------------------------------------------
 def _age_abi(amd, field, stride, n, level, hold, age_buf, on_buf):
-    lib, L = amd._lib.load(), amd._lib
-    L.check(lib.nerf_occupancy_age(field.data_ptr(), stride, n, level, hold, age_buf.data_ptr(), on_buf.data_ptr(), L.stream_of(field.device)),
-            "nerf_occupancy_age")
+    L = amd._lib
+    L.call("nerf_occupancy_age", L.strided(field), stride, n, level, hold, age_buf, on_buf)
     torch.cuda.synchronize()
 
 
@@ -48,7 +41,7 @@ def test_age_equals_the_restatement(amd, shape, hold):
     that must not be read), the bytes behind both buffers stay untouched, and `on` aliased to the field gives the same bytes.
     1836 points are no multiple of the 256-thread block, 35 937 take more than one block.  The bitfield built from `on` is the union
     of the direct builds of the last `hold` fields."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     n = shape[0] * shape[1] * shape[2]
     steps = [("torus", 0.0), ("sphere", 0.0), ("torus", -0.25)]
     ref_age = {s: A.new_age(n) for s in (1, 4)}
@@ -84,9 +77,9 @@ def test_age_equals_the_restatement(amd, shape, hold):
         assert np.array_equal(field[:n].cpu().numpy().view(np.uint32), ref_on.view(np.uint32))
         assert np.array_equal(age_buf["alias"][:n].cpu().numpy(), ref_age[1])
         # the bitfield of `on`: the OR of the direct builds of the last `hold` fields
-        n_words = int(lib.nerf_occupancy_words(*shape))
+        n_words = int(L.call("nerf_occupancy_words", *shape))
         bits = torch.empty(n_words, dtype=torch.int32, device="cuda")
-        L.check(lib.nerf_occupancy_build(field.data_ptr(), 1, *shape, 0.0, 1, bits.data_ptr(), L.stream_of(field.device)))
+        L.call("nerf_occupancy_build", field, 1, *shape, 0.0, 1, bits)
         torch.cuda.synchronize()
         union = functools.reduce(np.bitwise_or, direct[max(0, i - hold + 1):i + 1])
         assert np.array_equal(bits.cpu().numpy().view(np.uint32), union), (name, hold)
@@ -103,45 +96,21 @@ def _probe_rays():
     return o.cuda(), d.cuda()
 
 
-def _network(amd, sd, precision, train=True):
-    net = amd.Network()
-    net.load_state_dict(sd, strict=True)
-    net = net.cuda()
-    net.train() if train else net.eval()
-    net.precision = precision
-    return net
-
-
 def _mark(amd, grid, o, d, t_sorted):
-    lib, L = amd._lib.load(), amd._lib
     n = o.shape[0]
     valid = torch.empty(n, 192, dtype=torch.uint8, device="cuda")
-    L.check(lib.nerf_occupancy_mark(L.ptr(o), L.ptr(d), L.ptr(t_sorted), 192, n, 192, grid.bits["fine"].data_ptr(), *grid.lookup_args(), 0,
-                                    valid.data_ptr(), L.stream_of(o.device)), "nerf_occupancy_mark")
+    amd._lib.call("nerf_occupancy_mark", o, d, t_sorted, 192, n, 192, grid.bits["fine"], *grid.lookup_args(), 0, valid)
     torch.cuda.synchronize()
     return valid.bool()
 
 
 def _fine_raw(amd, net, o, d, t_sorted):
     """The plain fine pass of the staged entries on given merged depths -> raw [n,192,4]."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     n = o.shape[0]
     raw_f = torch.empty(n, 192, 4, device="cuda")
-    L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(t_sorted), 192, n, 192, net.packed("fine").data_ptr(), L.ptr(raw_f),
-                                      L.PRECISIONS[net.precision], L.stream_of(o.device)), "nerf_mlp_forward_rays")
+    L.call("nerf_mlp_forward_rays", o, d, t_sorted, 192, n, 192, net.packed("fine"), raw_f, L.PRECISIONS[net.precision])
     return raw_f
-
-
-class Replay:
-    """Renderer._rand replacement that hands out recorded draws in order."""
-
-    def __init__(self, draws):
-        self.draws = list(draws)
-
-    def __call__(self, shape, device):
-        t = self.draws.pop(0)
-        assert tuple(t.shape) == tuple(shape)
-        return t.to(device)
 
 
 def _step(amd, net, o, d, target, grid=None, fast=None, draws=None, every=16):
@@ -175,24 +144,6 @@ def _step(amd, net, o, d, target, grid=None, fast=None, draws=None, every=16):
                 cap=ren.capture_adjoints, tiles=ren.live_tile_stats)
 
 
-def _rel(got, ref):
-    return ((got.double() - ref.double()).abs().max() / ref.double().abs().max().clamp_min(1e-9)).item()
-
-
-def _assert_grads_equal(got, ref, bound=1e-4):
-    """The project's form and bound for regrouped atomic accumulation of identical terms (tests/test_gpu_masked_training.py):
-    relative 1e-4 of the tensor's maximum, exact zeros where the reference step has zeros.  -> the largest relative deviation."""
-    worst = 0.0
-    for i, (a, b) in enumerate(zip(got, ref)):
-        assert torch.isfinite(a).all(), i
-        if b.abs().max() == 0:
-            assert torch.all(a == 0), i
-        else:
-            worst = max(worst, _rel(a, b))
-            assert _rel(a, b) <= bound, (i, _rel(a, b))
-    return worst
-
-
 def _target(n, seed):
     return torch.rand(n, 3, generator=torch.Generator().manual_seed(seed)).cuda()
 
@@ -209,7 +160,7 @@ def _perturb_fine(net, seed):
 
 def test_refresh(amd, family_sd):
     dims = (9, 12, 17)
-    net = _network(amd, family_sd("sharp"), "f32", train=False)
+    net = network(amd, family_sd("sharp"), "f32", train=False)
     grid = amd.OccupancyGrid.from_network(net, BOX, dims, dilate=0)
     assert grid.hold == 1 and grid.uses == 0 and not grid.stale(net, "fine")
     coarse, ptr, words = grid.bits[""].clone(), grid.bits["fine"].data_ptr(), grid.bits["fine"].numel()
@@ -256,16 +207,16 @@ def test_culled_step_is_the_plain_step(amd, family_sd, family, precision):
     3 / 512 on trained, 0 / 512 on sharp; the margin is for last-bit differences between the GPU grid and the oracle's).  On the
     others: rgb, depth and the loss bit-equal, the list is the mark of the selected rays and at most half of the points (probe: 0.21
     and 0.335), all 48 gradients within 1e-4 of the tensor's maximum, exact zeros where the plain step has zeros."""
-    lib, L = amd._lib.load(), amd._lib
-    net = _network(amd, family_sd(family), precision)
+    L = amd._lib
+    net = network(amd, family_sd(family), precision, train=True)
     o, d = _probe_rays()
-    n, st, prec = N_PROBE, L.stream_of(o.device), L.PRECISIONS[precision]
+    n, prec = N_PROBE, L.PRECISIONS[precision]
     grid = amd.OccupancyGrid.from_network(net, BOX, 64, dilate=1, models=("fine",))
     t_c, u = torch.linspace(2.0, 6.0, 64).cuda(), torch.linspace(0.0, 1.0, 128).cuda()
     raw_c = torch.empty(n, 64, 4, device="cuda")
-    L.check(lib.nerf_mlp_forward_rays_density(L.ptr(o), L.ptr(d), L.ptr(t_c), 0, n, 64, net.packed("").data_ptr(), L.ptr(raw_c), prec, st))
+    L.call("nerf_mlp_forward_rays_density", o, d, t_c, 0, n, 64, net.packed(""), raw_c, prec)
     t_sorted = torch.empty(n, 192, device="cuda")
-    L.check(lib.nerf_sample_fine(L.ptr(raw_c), L.ptr(t_c), L.ptr(u), n, L.ptr(t_sorted), None, None, 0.0, 0.0, st))
+    L.call("nerf_sample_fine", raw_c, t_c, u, n, t_sorted, None, None, 0.0, 0.0)
     raw_f = _fine_raw(amd, net, o, d, t_sorted)
     keep_f = _mark(amd, grid, o, d, t_sorted)
     excluded = (~keep_f & (raw_f[..., 3] > 0)).any(1)
@@ -282,7 +233,7 @@ def test_culled_step_is_the_plain_step(amd, family_sd, family, precision):
     assert torch.equal(culled["cap"]["valid_sorted"].bool(), keep_f[sel])
     d_rgb = (culled["rgb"] - plain["rgb"]).abs().max().item()
     d_dep = (culled["depth"] - plain["depth"]).abs().max().item()
-    rels = [(_rel(a, b) if b.abs().max() > 0 else float(a.abs().max())) for a, b in zip(culled["grads"], plain["grads"])]
+    rels = [(rel(a, b) if b.abs().max() > 0 else float(a.abs().max())) for a, b in zip(culled["grads"], plain["grads"])]
     stats = dict(excluded_rays=n_ex, n_rays=n, selected_rays=m, share_evaluated=culled["count"] / (192 * m), rgb_max_diff=d_rgb,
                  depth_max_diff=d_dep, loss_plain=plain["loss"].item(), loss_culled=culled["loss"].item(),
                  worst_rel_gradient_diff=max(rels), per_tensor_rel_diff=rels,
@@ -294,7 +245,7 @@ def test_culled_step_is_the_plain_step(amd, family_sd, family, precision):
     assert culled["count"] == int(keep_f[sel].sum())
     assert culled["count"] <= 0.5 * 192 * m
     assert any(g.abs().max() > 0 for g in plain["grads"][24:])
-    _assert_grads_equal(culled["grads"], plain["grads"])
+    assert_grads_equal(culled["grads"], plain["grads"])
 
 
 # ---- 4. degenerate grids ------------------------------------------------------------------------------------------------------------
@@ -306,7 +257,7 @@ def _draws(n, seed):
 @pytest.mark.parametrize("precision", ["f32", "f32x"])
 def test_all_occupied_and_all_empty_grids(amd, family_sd, precision):
     n = 96
-    net = _network(amd, family_sd("sharp"), precision)
+    net = network(amd, family_sd("sharp"), precision, train=True)
     o, d = (x[:n].contiguous() for x in _probe_rays())
     target = _target(n, 19)
     ones = torch.ones(5, 6, 7, device="cuda")
@@ -317,7 +268,7 @@ def test_all_occupied_and_all_empty_grids(amd, family_sd, precision):
     def same(got, ref):
         assert _same_bits(got["rgb"], ref["rgb"]) and _same_bits(got["depth"], ref["depth"])
         assert _same_bits(got["loss"].reshape(1), ref["loss"].reshape(1))
-        _assert_grads_equal(got["grads"], ref["grads"])
+        assert_grads_equal(got["grads"], ref["grads"])
 
     # every cell occupied: the plain step on a list of all the points
     got = _step(amd, net, o, d, target, grid=full)
@@ -351,7 +302,7 @@ def test_stochastic_step_with_a_grid(amd, family_sd):
     the list is the mark of the step's own depths; rays the grid keeps whole, and rays none of whose culled samples has a positive
     density (decided by the plain fine pass of the staged entries on the step's depths), have the plain step's rgb bit for bit."""
     n = 96
-    net = _network(amd, family_sd("trained"), "f32")
+    net = network(amd, family_sd("trained"), "f32", train=True)
     o, d = (x[:n].contiguous() for x in _probe_rays())
     target = _target(n, 29)
     grid = amd.OccupancyGrid.from_network(net, BOX, 64, dilate=1, models=("fine",))
@@ -382,7 +333,7 @@ def test_short_culled_training_run_reduces_loss(amd, oracle, family_sd, precisio
     one build per 4 steps: refreshes before steps 5, 9, 13, 17, 21 and 25."""
     from nerf_replication_amd.training import train_step
     torch.manual_seed(0)
-    net = _network(amd, family_sd("trained"), precision)
+    net = network(amd, family_sd("trained"), precision, train=True)
     ren = amd.Renderer(net)
     ids = torch.randperm(800 * 800, generator=torch.Generator().manual_seed(9))[:1024]
     o, d = oracle.pinhole_rays(800, 800, oracle.camera_pose(20.0), pixel_ids=ids)
@@ -421,7 +372,7 @@ def test_short_culled_training_run_reduces_loss(amd, oracle, family_sd, precisio
 # ---- 7. refusals --------------------------------------------------------------------------------------------------------------------
 def test_refusals(amd, family_sd):
     o, d = (x[:64].contiguous() for x in _probe_rays())
-    net = _network(amd, family_sd("sharp"), "f32")
+    net = network(amd, family_sd("sharp"), "f32", train=True)
     grid = amd.OccupancyGrid.from_network(net, BOX, (9, 12, 17), models=("fine",))
     r = amd.Renderer(net)
     r.train_occupancy = grid

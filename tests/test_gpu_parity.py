@@ -23,6 +23,7 @@ import torch
 
 from conftest import GOLDEN, parity_record
 import pack_reference
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -62,13 +63,6 @@ def assert_image_close(oracle, rgb, dep, ref_rgb, ref_dep, max_rgb=None, max_dep
     assert st["rgb_q99"] <= EPS_RGB and st["depth_q99"] <= EPS_DEP, st
     assert st["rgb_max"] <= max_rgb and st["depth_max"] <= max_dep, st
     return st
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()            # fail loudly if the HIP extension is not there
-    return pkg
 
 
 @pytest.fixture(scope="module")
@@ -171,11 +165,10 @@ def test_mlp_rays_mode_points_bit_exact(amd, net, golden):
     (sigma depends on xyz only -> bit-equal); d/||d|| may differ from torch.norm by an ulp (reduction
     order inside norm), which only reaches the colour channels through the 4-octave direction PE."""
     g = golden("sampling.npz")
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     o, d, t = g["rays_o"].cuda(), g["rays_d"].cuda(), g["t_sorted"].cuda().contiguous()
     raw_rays = torch.empty(256, 192, 4, device="cuda")
-    L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(t), 192, 256, 192, net.packed("fine").data_ptr(),
-                                      L.ptr(raw_rays), 0, L.stream_of(o.device)))
+    L.call("nerf_mlp_forward_rays", o, d, t, 192, 256, 192, net.packed("fine"), raw_rays, 0)
     pts = (g["rays_o"][:, None, :] + g["rays_d"][:, None, :] * g["t_sorted"][:, :, None]).cuda()
     vd = (g["rays_d"] / torch.norm(g["rays_d"], dim=-1, keepdim=True)).cuda()
     raw_pts = net.forward(pts, vd, None, model="fine")
@@ -190,7 +183,7 @@ def test_density_only_forward_is_the_full_forwards_sigma(amd, synthetic_sd, gold
     """nerf_mlp_forward_rays_density (the coarse pass of nerf_render_forward when N_importance > 0: the reference reads only
     outputs[..., 3] of the coarse network, volume_renderer.py:335) must write BIT FOR BIT the sigma nerf_mlp_forward_rays
     writes, in every precision; the colour columns are zero (the network stops after the sigma head)."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     net = amd.Network(); net.load_state_dict(synthetic_sd); net = net.cuda().eval(); net.precision = precision
     prec = L.PRECISIONS[precision]
     gen = torch.Generator().manual_seed(n_rays)
@@ -202,10 +195,9 @@ def test_density_only_forward_is_the_full_forwards_sigma(amd, synthetic_sd, gold
         t = torch.linspace(2.0, 6.0, S).cuda()
     full = torch.full((n_rays, S, 4), float("nan"), device="cuda")
     dens = torch.full((n_rays, S, 4), float("nan"), device="cuda")
-    st = L.stream_of(o.device)
-    pk = net.packed("").data_ptr()
-    L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(t), stride, n_rays, S, pk, L.ptr(full), prec, st))
-    L.check(lib.nerf_mlp_forward_rays_density(L.ptr(o), L.ptr(d), L.ptr(t), stride, n_rays, S, pk, L.ptr(dens), prec, st))
+    pk = net.packed("")
+    L.call("nerf_mlp_forward_rays", o, d, t, stride, n_rays, S, pk, full, prec)
+    L.call("nerf_mlp_forward_rays_density", o, d, t, stride, n_rays, S, pk, dens, prec)
     torch.cuda.synchronize()
     assert torch.isfinite(full).all() and torch.isfinite(dens).all()
     assert torch.equal(dens[..., 3], full[..., 3])
@@ -218,19 +210,18 @@ def test_compositing_forward_drops_only_colours_that_are_multiplied_by_zero(amd,
     """nerf_mlp_forward_rays_for_compositing (the fine pass of nerf_render_forward) vs nerf_mlp_forward_rays on the reference's
     own merged depths of every scene family: sigma bit-identical everywhere; rgb bit-identical wherever it is not zeroed; a
     zeroed colour only at points with sigma <= 0 (weight exactly 0), exactly in the 32-sample tiles without a single sigma > 0; nerf_composite of the two raw buffers bit-identical.  The families cover 0 % ... 86 % dead tiles."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     g = golden(f"render_family_{family}.npz")
     net = amd.Network(); net.load_state_dict(family_sd(family)); net = net.cuda().eval(); net.precision = precision
     prec = L.PRECISIONS[precision]
     n = 509                                                        # ragged last tile pair
     o, d = g["pin_rays_o"][:n].cuda().contiguous(), g["pin_rays_d"][:n].cuda().contiguous()
     t = g["pin_t_sorted"][:n].cuda().contiguous()
-    st = L.stream_of(o.device)
-    pk = net.packed("fine").data_ptr()
+    pk = net.packed("fine")
     full = torch.full((n, 192, 4), float("nan"), device="cuda")
     comp = torch.full((n, 192, 4), float("nan"), device="cuda")
-    L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(t), 192, n, 192, pk, L.ptr(full), prec, st))
-    L.check(lib.nerf_mlp_forward_rays_for_compositing(L.ptr(o), L.ptr(d), L.ptr(t), 192, n, 192, pk, L.ptr(comp), prec, st))
+    L.call("nerf_mlp_forward_rays", o, d, t, 192, n, 192, pk, full, prec)
+    L.call("nerf_mlp_forward_rays_for_compositing", o, d, t, 192, n, 192, pk, comp, prec)
     torch.cuda.synchronize()
     assert torch.isfinite(comp).all()
     assert torch.equal(comp[..., 3], full[..., 3])
@@ -248,22 +239,21 @@ def test_compositing_forward_drops_only_colours_that_are_multiplied_by_zero(amd,
     outs = []
     for raw in (full, comp):
         rgb, dep = torch.empty(n, 3, device="cuda"), torch.empty(n, device="cuda")
-        L.check(lib.nerf_composite(L.ptr(raw), L.ptr(t), 192, n, 192, 1, L.ptr(rgb), L.ptr(dep), None, st))
+        L.call("nerf_composite", raw, t, 192, n, 192, 1, rgb, dep, None)
         outs.append((rgb, dep))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
 
 def test_fine_sampling_stage(amd, golden):
     g = golden("sampling.npz")
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     raw_c = g["raw_coarse"].cuda().contiguous()
     t_c = torch.linspace(2.0, 6.0, 64).cuda()
     u = torch.linspace(0.0, 1.0, 128).cuda()
     assert torch.equal(t_c.cpu(), g["t_coarse"][0])
     t_sorted = torch.empty(256, 192, device="cuda")
     t_fine = torch.empty(256, 128, device="cuda")
-    L.check(lib.nerf_sample_fine(L.ptr(raw_c), L.ptr(t_c), L.ptr(u), 256, L.ptr(t_sorted), L.ptr(t_fine), None, 0.0, 0.0,
-                                 L.stream_of(raw_c.device)))
+    L.call("nerf_sample_fine", raw_c, t_c, u, 256, t_sorted, t_fine, None, 0.0, 0.0)
     tf, ts = t_fine.cpu(), t_sorted.cpu()
     d = (tf - g["t_fine"]).abs()
     # continuous in the inputs; only the sum order of the 62 weights differs from torch (1-ulp pdf changes,
@@ -286,11 +276,10 @@ def test_fine_sampling_stage(amd, golden):
 
 def test_composite_stage(amd, oracle, golden):
     g = golden("sampling.npz")
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     raw, t = g["raw_fine"].cuda().contiguous(), g["t_sorted"].cuda().contiguous()
     rgb, dep, w = torch.empty(256, 3, device="cuda"), torch.empty(256, device="cuda"), torch.empty(256, 192, device="cuda")
-    L.check(lib.nerf_composite(L.ptr(raw), L.ptr(t), 192, 256, 192, 1, L.ptr(rgb), L.ptr(dep), L.ptr(w),
-                               L.stream_of(raw.device)))
+    L.call("nerf_composite", raw, t, 192, 256, 192, 1, rgb, dep, w)
     ref_rgb, ref_dep = oracle.composite(g["raw_fine"], g["t_sorted"], True)
     assert (w.cpu() - g["w192"]).abs().max() <= 2e-6
     assert (rgb.cpu() - ref_rgb).abs().max() <= 5e-6
@@ -301,20 +290,17 @@ def test_composite_stage(amd, oracle, golden):
     t_off.copy_(t)
     assert t_off.data_ptr() % 16 == 4
     rgb_b, dep_b, w_b = torch.empty_like(rgb), torch.empty_like(dep), torch.empty_like(w)
-    L.check(lib.nerf_composite(L.ptr(raw), t_off.data_ptr(), 192, 256, 192, 1, L.ptr(rgb_b), L.ptr(dep_b), L.ptr(w_b),
-                               L.stream_of(raw.device)))
+    L.call("nerf_composite", raw, t_off, 192, 256, 192, 1, rgb_b, dep_b, w_b)
     assert torch.equal(rgb, rgb_b) and torch.equal(dep, dep_b) and torch.equal(w, w_b)
     # ragged ray count (not a multiple of the 64-ray block)
     rgb_c, dep_c = torch.empty(101, 3, device="cuda"), torch.empty(101, device="cuda")
-    L.check(lib.nerf_composite(L.ptr(raw), L.ptr(t), 192, 101, 192, 1, L.ptr(rgb_c), L.ptr(dep_c), None,
-                               L.stream_of(raw.device)))
+    L.call("nerf_composite", raw, t, 192, 101, 192, 1, rgb_c, dep_c, None)
     assert torch.equal(rgb_c, rgb[:101]) and torch.equal(dep_c, dep[:101])
     # no white background, coarse table shared by all rays (stride 0)
     t64 = torch.linspace(2.0, 6.0, 64).cuda()
     rawc = g["raw_coarse"].cuda().contiguous()
     rgb0, dep0 = torch.empty(256, 3, device="cuda"), torch.empty(256, device="cuda")
-    L.check(lib.nerf_composite(L.ptr(rawc), L.ptr(t64), 0, 256, 64, 0, L.ptr(rgb0), L.ptr(dep0), None,
-                               L.stream_of(rawc.device)))
+    L.call("nerf_composite", rawc, t64, 0, 256, 64, 0, rgb0, dep0, None)
     r0, d0 = oracle.composite(g["raw_coarse"], g["t_coarse"], False)
     assert (rgb0.cpu() - r0).abs().max() <= 5e-6 and (dep0.cpu() - d0).abs().max() <= 2e-5
 
@@ -343,19 +329,18 @@ def _hip_stages(amd, net, o, d, t_sorted_override=None):
     """The four launches of a frame, one by one through the C ABI, returning every intermediate.  With
     `t_sorted_override` the fine pass + compositing run on THOSE merged depths (the reference's) instead of the
     sampler's: the attribution leg."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     n = o.shape[0]
-    st = L.stream_of(o.device)
     t_c, u = torch.linspace(2.0, 6.0, 64).cuda(), torch.linspace(0.0, 1.0, 128).cuda()
     raw_c = torch.empty(n, 64, 4, device="cuda")
-    L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(t_c), 0, n, 64, net.packed("").data_ptr(), L.ptr(raw_c), 0, st))
+    L.call("nerf_mlp_forward_rays", o, d, t_c, 0, n, 64, net.packed(""), raw_c, 0)
     t_sorted = torch.empty(n, 192, device="cuda")
-    L.check(lib.nerf_sample_fine(L.ptr(raw_c), L.ptr(t_c), L.ptr(u), n, L.ptr(t_sorted), None, None, 0.0, 0.0, st))
+    L.call("nerf_sample_fine", raw_c, t_c, u, n, t_sorted, None, None, 0.0, 0.0)
     t_use = t_sorted if t_sorted_override is None else t_sorted_override.cuda().contiguous()
     raw_f = torch.empty(n, 192, 4, device="cuda")
-    L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(t_use), 192, n, 192, net.packed("fine").data_ptr(), L.ptr(raw_f), 0, st))
+    L.call("nerf_mlp_forward_rays", o, d, t_use, 192, n, 192, net.packed("fine"), raw_f, 0)
     rgb, dep = torch.empty(n, 3, device="cuda"), torch.empty(n, device="cuda")
-    L.check(lib.nerf_composite(L.ptr(raw_f), L.ptr(t_use), 192, n, 192, 1, L.ptr(rgb), L.ptr(dep), None, st))
+    L.call("nerf_composite", raw_f, t_use, 192, n, 192, 1, rgb, dep, None)
     return dict(raw_coarse=raw_c, t_sorted=t_sorted, raw_fine=raw_f, rgb=rgb, depth=dep)
 
 
@@ -447,7 +432,7 @@ def test_render_rejects_cpu_and_bad_args(amd, net):
     # masked fine pass: (ray, sample) ids are int32 -> more than 2^31 / 192 rays per call is refused, not wrapped
     # (the check precedes every launch; the dummy non-null pointers are never dereferenced)
     big = (2 ** 31) // 192 + 1
-    need = lib.nerf_render_workspace_bytes(big, 128, 1)
+    need = amd._lib.call("nerf_render_workspace_bytes", big, 128, 1)
     assert lib.nerf_render_forward(8, 8, big, 8, 8, 8, 8, 128, 1, 0, 1, 0.25, 8, need, 8, 8, None) == -1
     assert b"int32" in lib.nerf_last_error()
     assert lib.nerf_build_flags() == 0            # product build: no timing switch compiled in
@@ -476,9 +461,9 @@ def test_ray_blocks_change_nothing(amd, synthetic_sd, oracle, monkeypatch, preci
     monkeypatch.delenv("NERF_RENDER_BLOCK_RAYS")
     for (ra, da), (rb, db) in zip(out["one"], out["blocks"]):
         assert torch.isfinite(rb).all() and torch.equal(ra, rb) and torch.equal(da, db)
-    lib = amd._lib.load()
+    L = amd._lib
     monkeypatch.setenv("NERF_RENDER_BLOCK_RAYS", "1024")
-    assert lib.nerf_render_workspace_bytes(10 ** 7, 128, 0) == lib.nerf_render_workspace_bytes(1024, 128, 0)      # bounded by the block
+    assert L.call("nerf_render_workspace_bytes", 10 ** 7, 128, 0) == L.call("nerf_render_workspace_bytes", 1024, 128, 0)      # bounded by the block
     monkeypatch.delenv("NERF_RENDER_BLOCK_RAYS")
 
 
@@ -622,15 +607,14 @@ def test_ess_ert_mask_stage(amd, golden):
     """fast_sampling branch of fine_sample_points: validity of the 128 fine samples, recovered from the
     merged [n,192] mask (coarse samples are always valid), for the default threshold and a useful one."""
     g = golden("render_masked.npz")
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     raw_c = g["raw_coarse"].cuda().contiguous()
     t_c, u = torch.linspace(2.0, 6.0, 64).cuda(), torch.linspace(0.0, 1.0, 128).cuda()
     for thr, key in ((0.25, "valid_fine"), (0.02, "valid_fine_thr002")):
         t_sorted = torch.empty(256, 192, device="cuda")
         t_fine = torch.empty(256, 128, device="cuda")
         valid = torch.empty(256, 192, dtype=torch.uint8, device="cuda")
-        L.check(lib.nerf_sample_fine(L.ptr(raw_c), L.ptr(t_c), L.ptr(u), 256, L.ptr(t_sorted), L.ptr(t_fine),
-                                     valid.data_ptr(), thr, 0.45, L.stream_of(raw_c.device)))
+        L.call("nerf_sample_fine", raw_c, t_c, u, 256, t_sorted, t_fine, valid, thr, 0.45)
         valid, ts, tf = valid.cpu().bool(), t_sorted.cpu(), t_fine.cpu()
         want = g[key].bool()
         # every ray keeps its 64 coarse samples; the number of surviving fine samples matches the reference

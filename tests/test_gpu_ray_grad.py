@@ -14,26 +14,9 @@ import torch
 
 import ray_grad_common as RG
 from conftest import REPO, parity_record
+from gpu_common import amd, network  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
-
-
-def _net(amd, sd, precision="f32", train=False, frozen=False):
-    net = amd.Network()
-    net.load_state_dict(sd, strict=True)
-    net = net.cuda()
-    net.train() if train else net.eval()
-    if frozen:
-        net.requires_grad_(False)
-    net.precision = precision
-    return net
 
 
 def _batch(oracle, seed, n=128):
@@ -85,7 +68,7 @@ def test_ray_gradients_match_float64(amd, oracle, synthetic_sd, family_sd, scene
     """Test 1: d (mse(rgb, target) + 0.1 depth.mean()) / d (rays_o, rays_d), frozen network, deterministic sampling."""
     sd = synthetic_sd if scene == "synthetic_sd" else family_sd("trained")
     o, d, target = _batch(oracle, 3)
-    g_hip = _hip_ray_grads(amd.Renderer(_net(amd, sd, precision, frozen=True)), o, d, target)
+    g_hip = _hip_ray_grads(amd.Renderer(network(amd, sd, precision, train=False, frozen=True)), o, d, target)
     g32 = RG.ray_grads_fp32(sd, o, d, target)
     g64 = RG.ray_grads_fp64(sd, o, d, target)
     _judge(scene, precision, g_hip, g32, g64)
@@ -98,7 +81,7 @@ def test_ray_gradients_with_stochastic_sampling(amd, oracle, family_sd, precisio
     o, d, target = _batch(oracle, 4)
     gen = torch.Generator().manual_seed(44)
     jitter, u = torch.rand(o.shape[0], 64, generator=gen), torch.rand(o.shape[0], 128, generator=gen)
-    ren = amd.Renderer(_net(amd, sd, precision, frozen=True))
+    ren = amd.Renderer(network(amd, sd, precision, train=False, frozen=True))
     ren.task, ren.perturb = "train", True
     draws = [jitter, u]
     ren._rand = lambda shape, device: draws.pop(0).to(device)
@@ -115,7 +98,7 @@ def test_frozen_network_gets_ray_gradients_only(amd, oracle, family_sd, precisio
     bit-identical to the same call with the parameters requiring grad (the chains are the same launches either way)."""
     sd = family_sd("trained")
     o, d, target = _batch(oracle, 5)
-    net = _net(amd, sd, precision, frozen=True)
+    net = network(amd, sd, precision, train=False, frozen=True)
     ren = amd.Renderer(net)
     g_frozen = _hip_ray_grads(ren, o, d, target)
     assert all(p.grad is None for p in net.parameters())
@@ -133,11 +116,6 @@ def test_frozen_network_gets_ray_gradients_only(amd, oracle, family_sd, precisio
     assert dd.grad is None and torch.equal(og.grad.cpu(), g_frozen[0])
 
 
-def _ptrs(ts):
-    import ctypes
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
 @pytest.mark.parametrize("precision", ["f32", "f32x"])
 @pytest.mark.parametrize("density_only", [0, 1])
 def test_chain_only_backward_at_the_abi(amd, synthetic_sd, precision, density_only):
@@ -145,10 +123,9 @@ def test_chain_only_backward_at_the_abi(amd, synthetic_sd, precision, density_on
     the call with gradient arrays, and touches no gradient array (a sentinel-filled set stays as it was); g_t and gsave are
     also bit-identical to nerf_mlp_backward(_density), which has no g_x.  Some 32-point tiles have a zero incoming gradient
     (dropped by the live-tile list: their g_x must read zero)."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     prec = L.PRECISIONS[precision]
-    st = torch.cuda.current_stream().cuda_stream
-    net = _net(amd, synthetic_sd, precision)
+    net = network(amd, synthetic_sd, precision, train=False, frozen=False)
     params = list(net.model.ordered_params())
     n, S = 48, 64
     P = n * S
@@ -158,29 +135,27 @@ def test_chain_only_backward_at_the_abi(amd, synthetic_sd, precision, density_on
     o = torch.tensor([0.1, -0.2, 4.0]).expand(n, 3).contiguous().cuda()
     t = (torch.linspace(2.0, 6.0, S)[None] + 0.01 * torch.rand(n, S, generator=gen)).cuda().contiguous()
     raw = torch.empty(P, 4, device="cuda")
-    save = torch.empty(int(lib.nerf_train_save_floats(P)), device="cuda")
-    fwd = lib.nerf_mlp_forward_rays_save_density if density_only else lib.nerf_mlp_forward_rays_save
-    L.check(fwd(L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, net.packed("").data_ptr(), L.ptr(raw), L.ptr(save), prec, st))
+    save = torch.empty(int(L.call("nerf_train_save_floats", P)), device="cuda")
+    fwd = "nerf_mlp_forward_rays_save_density" if density_only else "nerf_mlp_forward_rays_save"
+    L.call(fwd, o, d, t, S, n, S, net.packed(""), raw, save, prec)
     draw = (torch.randn(P, 4, generator=gen) * 1e-3)
     draw.view(P // 32, 32, 4)[::3] = 0.0                     # every third tile dead
     draw = draw.cuda().contiguous()
-    pk = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device="cuda")
-    L.check(lib.nerf_pack_model_bwd(_ptrs([p.detach().contiguous() for p in params]), pk.data_ptr(), prec, st))
-    G = int(lib.nerf_train_grad_floats(P))
+    pk = torch.empty(int(L.call("nerf_packed_bwd_bytes", prec)), dtype=torch.uint8, device="cuda")
+    L.call("nerf_pack_model_bwd", [p.detach().contiguous() for p in params], pk, prec)
+    G = int(L.call("nerf_train_grad_floats", P))
 
     def run(with_grads, with_gx, entry="rays_x"):
         gsave = torch.full((G,), 7.0, device="cuda")
         g_t = torch.full((P,), 7.0, device="cuda")
         g_x = torch.full((P, 3), 7.0, device="cuda") if with_gx else None
         grads = [torch.zeros(p.shape, device="cuda") if with_grads else torch.full(p.shape, 3.0, device="cuda") for p in params]
-        gp = _ptrs(grads) if with_grads else None
+        gp = grads if with_grads else None
         if entry == "rays_x":
-            L.check(lib.nerf_mlp_backward_rays_x(L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, pk.data_ptr(), L.ptr(draw), L.ptr(save),
-                                                 L.ptr(gsave), L.ptr(g_t), L.ptr(g_x), gp, density_only, prec, st))
+            L.call("nerf_mlp_backward_rays_x", o, d, t, S, n, S, pk, draw, save, gsave, g_t, g_x, gp, density_only, prec)
         else:
-            old = lib.nerf_mlp_backward_density if density_only else lib.nerf_mlp_backward
-            L.check(old(L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, pk.data_ptr(), L.ptr(draw), L.ptr(save), L.ptr(gsave), L.ptr(g_t),
-                        gp, prec, st))
+            old = "nerf_mlp_backward_density" if density_only else "nerf_mlp_backward"
+            L.call(old, o, d, t, S, n, S, pk, draw, save, gsave, g_t, gp, prec)
         torch.cuda.synchronize()
         return gsave, g_t, g_x, grads
 
@@ -211,7 +186,7 @@ def test_training_step_unchanged_by_ray_gradients(amd, oracle, family_sd, monkey
     out = {}
     for tag, env, rays_grad in (("plain", "1", False), ("rays", "1", True), ("rays_dense", "0", True)):
         monkeypatch.setenv("NERF_DEAD_TILE_SKIP", env)
-        net = _net(amd, sd, precision, train=True)
+        net = network(amd, sd, precision, train=True, frozen=False)
         ren = amd.Renderer(net)
         og, dg = o.cuda().requires_grad_(rays_grad), d.cuda().requires_grad_(rays_grad)
         rgb, dep = ren.render({"rays_o": og[None], "rays_d": dg[None]})
@@ -236,7 +211,7 @@ def test_training_step_unchanged_by_ray_gradients(amd, oracle, family_sd, monkey
 def test_unbuilt_modes_refuse_rays_that_require_grad(amd, oracle, synthetic_sd, case):
     """Test 5: no detached result for rays that require grad: NotImplementedError; the same call under no_grad renders."""
     o, d, _ = _batch(oracle, 7, n=64)
-    net = _net(amd, synthetic_sd, case if case.startswith("f16") else "f32", frozen=True)
+    net = network(amd, synthetic_sd, case if case.startswith("f16") else "f32", train=False, frozen=True)
     ren = amd.Renderer(net)
     if case == "fast_sampling":
         ren.fast_sampling = True

@@ -11,28 +11,9 @@ import pytest
 import torch
 
 import stochastic_common as SC
+from gpu_common import Replay, amd, network  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _net(amd, sd, precision="f32", train=False):
-    net = amd.Network()
-    net.load_state_dict(sd, strict=True)
-    net = net.cuda()
-    net.train() if train else net.eval()
-    net.precision = precision
-    return net
 
 
 def _train_renderer(amd, net, perturb=True):
@@ -41,21 +22,7 @@ def _train_renderer(amd, net, perturb=True):
     return ren
 
 
-class Replay:
-    """Renderer._rand replacement that hands out recorded draws in order (and records the shapes asked for)."""
-
-    def __init__(self, draws):
-        self.draws, self.shapes = [t for t in draws if t is not None], []
-
-    def __call__(self, shape, device):
-        self.shapes.append(tuple(shape))
-        t = self.draws.pop(0)
-        assert tuple(t.shape) == tuple(shape)
-        return t.to(device)
-
-
 def test_stratified_samples_bit_equal_to_torch(amd):
-    lib, L = amd._lib.load(), amd._lib
     gen = torch.Generator().manual_seed(21)
     j = torch.rand(300, 64, generator=gen)
     j[0] = 0.0
@@ -63,16 +30,14 @@ def test_stratified_samples_bit_equal_to_torch(amd):
     t_lin = torch.linspace(2.0, 6.0, 64).cuda()
     jd = j.cuda()
     out = torch.full((300, 64), float("nan"), device="cuda")
-    L.check(lib.nerf_stratified_samples(L.ptr(t_lin), L.ptr(jd), 300, L.ptr(out), _stream()))
+    amd._lib.call("nerf_stratified_samples", t_lin, jd, 300, out)
     assert torch.equal(out.cpu(), SC.stratified_t(j))
 
 
 def _sample(amd, raw_c, t_c, t_stride, u, u_stride, n, t_fine=False):
-    lib, L = amd._lib.load(), amd._lib
     ts = torch.full((n, 192), float("nan"), device="cuda")
     tf = torch.full((n, 128), float("nan"), device="cuda") if t_fine else None
-    L.check(lib.nerf_sample_fine_rays(L.ptr(raw_c), L.ptr(t_c), t_stride, L.ptr(u), u_stride, n, L.ptr(ts), L.ptr(tf), None,
-                                      0.0, 0.0, _stream()), "nerf_sample_fine_rays")
+    amd._lib.call("nerf_sample_fine_rays", raw_c, t_c, t_stride, u, u_stride, n, ts, tf, None, 0.0, 0.0)
     return ts, tf
 
 
@@ -84,7 +49,7 @@ def test_sample_fine_rays_shared_tables_identical(amd, golden):
     t_c, u = torch.linspace(2.0, 6.0, 64).cuda(), torch.linspace(0.0, 1.0, 128).cuda()
     ts0 = torch.empty(n, 192, device="cuda")
     tf0 = torch.empty(n, 128, device="cuda")
-    L.check(lib.nerf_sample_fine(L.ptr(raw_c), L.ptr(t_c), L.ptr(u), n, L.ptr(ts0), L.ptr(tf0), None, 0.0, 0.0, _stream()))
+    L.call("nerf_sample_fine", raw_c, t_c, u, n, ts0, tf0, None, 0.0, 0.0)
     ts, tf = _sample(amd, raw_c, t_c, 0, u, 0, n, t_fine=True)
     assert torch.equal(ts, ts0) and torch.equal(tf, tf0)
     # the per-ray kernel itself on per-ray copies of the shared tables: same bits
@@ -93,7 +58,7 @@ def test_sample_fine_rays_shared_tables_identical(amd, golden):
     # fast_sampling needs the shared tables
     valid = torch.empty(n, 192, dtype=torch.uint8, device="cuda")
     rc = lib.nerf_sample_fine_rays(L.ptr(raw_c), L.ptr(t_c), 0, L.ptr(u), 128, n, L.ptr(ts), None, valid.data_ptr(),
-                                   0.25, 0.45, _stream())
+                                   0.25, 0.45, L.stream_of(raw_c.device))
     assert rc == -1
 
 
@@ -129,15 +94,14 @@ def _render(ren, o, d):
 
 def _fine_pass_on(amd, net, o, d, t_sorted):
     """The HIP fine pass + compositing on given merged depths [n,192] (attribution)."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     n = o.shape[0]
     prec = L.PRECISIONS[net.precision]
     raw = torch.empty(n, 192, 4, device="cuda")
     rgb, dep = torch.empty(n, 3, device="cuda"), torch.empty(n, device="cuda")
     ts = t_sorted.cuda().contiguous()
-    L.check(lib.nerf_mlp_forward_rays(L.ptr(o), L.ptr(d), L.ptr(ts), 192, n, 192, net.packed("fine").data_ptr(), L.ptr(raw), prec,
-                                      _stream()))
-    L.check(lib.nerf_composite(L.ptr(raw), L.ptr(ts), 192, n, 192, 1, L.ptr(rgb), L.ptr(dep), None, _stream()))
+    L.call("nerf_mlp_forward_rays", o, d, ts, 192, n, 192, net.packed("fine"), raw, prec)
+    L.call("nerf_composite", raw, ts, 192, n, 192, 1, rgb, dep, None)
     return rgb.cpu(), dep.cpu()
 
 
@@ -146,7 +110,7 @@ def test_render_with_replayed_draws_matches_reference(amd, oracle, golden, synth
     g = golden("stochastic_render.npz")
     o, d = g["rays_o"].cuda().contiguous(), g["rays_d"].cuda().contiguous()
     for tag, fam, jitter, u in SC.fixture_runs(g):
-        net = _net(amd, SC.family_sd(oracle, synthetic_sd, fam), precision)
+        net = network(amd, SC.family_sd(oracle, synthetic_sd, fam), precision, train=False)
         ren = _train_renderer(amd, net, perturb=jitter is not None)
         ren._rand = rp = Replay([jitter, u])
         rgb, dep = _render(ren, o, d)
@@ -172,8 +136,8 @@ def test_render_with_replayed_draws_matches_reference(amd, oracle, golden, synth
 @pytest.mark.parametrize("precision", ["f32", "f32x"])
 @pytest.mark.parametrize("n_importance", [0, 128])
 def test_linspace_draws_reproduce_the_deterministic_render(amd, synthetic_sd, oracle, precision, n_importance):
-    lib, L = amd._lib.load(), amd._lib
-    net = _net(amd, synthetic_sd, precision)
+    L = amd._lib
+    net = network(amd, synthetic_sd, precision, train=False)
     ren = amd.Renderer(net)
     ren.N_importance = n_importance
     ids = torch.randperm(800 * 800, generator=torch.Generator().manual_seed(4))[:333]
@@ -183,18 +147,17 @@ def test_linspace_draws_reproduce_the_deterministic_render(amd, synthetic_sd, or
     n = o.shape[0]
     t_c, u = ren._get_tables(o.device)
     u_rays = u.expand(n, 128).contiguous()
-    ws = torch.empty(int(lib.nerf_render_stochastic_workspace_bytes(n, n_importance)), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(int(L.call("nerf_render_stochastic_workspace_bytes", n, n_importance)), dtype=torch.uint8, device="cuda")
     rgb, dep = torch.empty(n, 3, device="cuda"), torch.empty(n, device="cuda")
-    pk_f = net.packed("fine").data_ptr() if n_importance else None
+    pk_f = net.packed("fine") if n_importance else None
     for draws in ((None, u_rays), (None, None)):
-        L.check(lib.nerf_render_forward_stochastic(L.ptr(o), L.ptr(d), n, net.packed("").data_ptr(), pk_f, L.ptr(t_c), L.ptr(u),
-                                                   L.ptr(draws[0]), L.ptr(draws[1]), n_importance, 1, L.PRECISIONS[precision], 0,
-                                                   0.25, ws.data_ptr(), ws.numel(), L.ptr(rgb), L.ptr(dep), _stream()))
+        L.call("nerf_render_forward_stochastic", o, d, n, net.packed(""), pk_f, t_c, u, draws[0], draws[1], n_importance, 1,
+               L.PRECISIONS[precision], 0, 0.25, ws, ws.numel(), rgb, dep)
         assert torch.equal(rgb, rgb0) and torch.equal(dep, dep0)
 
 
 def test_render_is_invariant_to_the_ray_block(amd, synthetic_sd, oracle, monkeypatch):
-    net = _net(amd, synthetic_sd)
+    net = network(amd, synthetic_sd, "f32", train=False)
     o, d = oracle.seeded_rays(300, 8)
     o, d = o.reshape(-1, 3).cuda().contiguous(), d.reshape(-1, 3).cuda().contiguous()
     outs = []
@@ -209,7 +172,7 @@ def test_render_is_invariant_to_the_ray_block(amd, synthetic_sd, oracle, monkeyp
 
 
 def test_seed_controls_the_samples(amd, synthetic_sd, oracle):
-    net = _net(amd, synthetic_sd)
+    net = network(amd, synthetic_sd, "f32", train=False)
     o, d = oracle.seeded_rays(256, 9)
     o, d = o.reshape(-1, 3).cuda().contiguous(), d.reshape(-1, 3).cuda().contiguous()
     ren = _train_renderer(amd, net)
@@ -234,7 +197,6 @@ def test_seed_controls_the_samples(amd, synthetic_sd, oracle):
 
 
 def test_sample_fine_rays_backward_matches_float64_autograd(amd, golden):
-    lib, L = amd._lib.load(), amd._lib
     g = golden("sampling.npz")
     n = 256
     gen = torch.Generator().manual_seed(23)
@@ -250,8 +212,7 @@ def test_sample_fine_rays_backward_matches_float64_autograd(amd, golden):
     ts, _ = _sample(amd, rawd, tcd, 64, ud, 128, n)
     g_raw = torch.full((n, 64, 4), float("nan"), device="cuda")
     Gd = G.cuda().contiguous()
-    L.check(lib.nerf_sample_fine_rays_backward(L.ptr(rawd), L.ptr(tcd), 64, L.ptr(ud), 128, n, L.ptr(ts), L.ptr(Gd), L.ptr(g_raw),
-                                               _stream()), "nerf_sample_fine_rays_backward")
+    amd._lib.call("nerf_sample_fine_rays_backward", rawd, tcd, 64, ud, 128, n, ts, Gd, g_raw)
     got, ref = g_raw.cpu().double(), raw_r.grad
     assert torch.all(got[..., :3] == 0)
     scale = ref[..., 3].abs().amax(dim=1).clamp_min(1e-6)
@@ -266,7 +227,7 @@ def test_sample_fine_rays_backward_matches_float64_autograd(amd, golden):
 def test_training_steps_with_replayed_draws_match_reference(amd, oracle, golden, synthetic_sd, precision):
     g = golden("stochastic_train_steps.npz")
     K = int(g["K"])
-    net = _net(amd, SC.family_sd(oracle, synthetic_sd, "trained"), precision, train=True)
+    net = network(amd, SC.family_sd(oracle, synthetic_sd, "trained"), precision, train=True)
     ren = _train_renderer(amd, net)
     ren._rand = Replay([t for s in range(K) for t in (g["jitter"][s], g["u"][s])])
     opt = torch.optim.Adam([{"params": [p], "lr": 5e-4, "weight_decay": 0.0, "eps": 1e-8} for p in net.parameters()],
@@ -317,7 +278,7 @@ def test_training_steps_with_replayed_draws_match_reference(amd, oracle, golden,
 def test_short_stochastic_training_run_reduces_loss(amd, oracle, synthetic_sd, precision):
     from nerf_replication_amd.training import train_step
     torch.manual_seed(0)
-    net = _net(amd, synthetic_sd, precision, train=True)
+    net = network(amd, synthetic_sd, precision, train=True)
     ids = torch.randperm(800 * 800, generator=torch.Generator().manual_seed(9))[:1024]
     o, d = oracle.pinhole_rays(800, 800, oracle.camera_pose(20.0), pixel_ids=ids)
     o, d = o.cuda(), d.cuda()
@@ -336,7 +297,7 @@ def test_short_stochastic_training_run_reduces_loss(amd, oracle, synthetic_sd, p
 
 @pytest.mark.parametrize("what", ["f16", "f16m32", "fast_sampling"])
 def test_unsupported_combinations_raise(amd, synthetic_sd, what):
-    net = _net(amd, synthetic_sd, "f32" if what == "fast_sampling" else what)
+    net = network(amd, synthetic_sd, "f32" if what == "fast_sampling" else what, train=False)
     ren = _train_renderer(amd, net)
     ren.fast_sampling = what == "fast_sampling"
     o = torch.zeros(8, 3, device="cuda")

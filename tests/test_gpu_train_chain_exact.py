@@ -25,6 +25,7 @@ import torch
 import f16_reference as R
 import train_chain_reference as T
 from train_chain_reference import Grad, Save, pad32
+from gpu_common import amd, network  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -44,13 +45,6 @@ TRUNK_GRAD = tuple(f"gz{l}" for l in range(8))
 
 _record = {}
 _t0 = [None]
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 @pytest.fixture(scope="module")
@@ -87,11 +81,7 @@ def _network(precision, many):
     import nerf_replication_amd as pkg
     sd = R.both_models(_sub(MANY_PROBE)) if many else \
         {f"{m}.{k}": v.clone() for m, key in (("model", ""), ("model_fine", "fine")) for k, v in _sub(PROBE_OF[key]).items()}
-    net = pkg.Network()
-    net.load_state_dict(sd, strict=True)
-    net = net.cuda().eval()
-    net.precision = precision
-    return net
+    return network(pkg, sd, precision, train=False)
 
 
 # ================================================================================ buffers and comparisons

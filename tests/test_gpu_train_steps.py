@@ -26,16 +26,10 @@ import torch
 
 import train_steps_common as T
 from conftest import GOLDEN, parity_record
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 K = 5
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 def _ckpt(oracle, tag):

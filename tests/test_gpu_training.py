@@ -4,15 +4,9 @@ import pytest
 import torch
 
 from conftest import parity_record
+from gpu_common import amd, rel  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 @pytest.fixture(scope="module")
@@ -22,16 +16,12 @@ def net(amd, synthetic_sd):
     return n.cuda().eval()
 
 
-def _rel(got, ref):
-    return ((got.double().cpu() - ref.double()).abs().max() / ref.double().abs().max().clamp_min(1e-9)).item()
-
-
 @pytest.mark.parametrize("precision", ["f32", "f32x"])
 def test_forward_save_matches_reference_activations(amd, net, golden, precision):
     """SAVE-mode forward: every tensor autograd would keep for NeRF.forward (network.py:49-74) equals
     the reference's own per-layer activations (forward hooks in oracle/gen_golden.py)."""
     g = golden("mlp_layers.npz")
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     P = 128
     net.precision = precision
     prec = L.PRECISIONS[precision]
@@ -39,9 +29,8 @@ def test_forward_save_matches_reference_activations(amd, net, golden, precision)
     t = torch.zeros(P, 1, device="cuda")
     for model, tag in (("", "coarse"), ("fine", "fine")):
         raw = torch.empty(P, 1, 4, device="cuda")
-        save = torch.full((int(lib.nerf_train_save_floats(P)),), float("nan"), device="cuda")
-        L.check(lib.nerf_mlp_forward_rays_save(L.ptr(o), L.ptr(d), L.ptr(t), 1, P, 1, net.packed(model).data_ptr(),
-                                               L.ptr(raw), L.ptr(save), prec, L.stream_of(o.device)))
+        save = torch.full((int(L.call("nerf_train_save_floats", P)),), float("nan"), device="cuda")
+        L.call("nerf_mlp_forward_rays_save", o, d, t, 1, P, 1, net.packed(model), raw, save, prec)
         sv = save.cpu()
         rows = P * (96 + 2304 + 128)                   # (P is a multiple of 32: no padding rows)
         assert torch.isfinite(sv[:rows]).all()
@@ -51,11 +40,11 @@ def test_forward_save_matches_reference_activations(amd, net, golden, precision)
         assert (dpe[:, :27] - g["emb"][:, 63:]).abs().max() <= 2e-6 and torch.all(dpe[:, 27:] == 0)
         for l in range(8):
             h = sv[P * (96 + 256 * l):P * (96 + 256 * (l + 1))].view(P, 256)
-            assert _rel(h, g[f"{tag}_h{l}"]) <= 2e-5, l
+            assert rel(h, g[f"{tag}_h{l}"]) <= 2e-5, l
         f = sv[P * (96 + 2048):P * (96 + 2304)].view(P, 256)
         hv = sv[P * (96 + 2304):rows].view(P, 128)
-        assert _rel(f, g[f"{tag}_feature"]) <= 2e-5 and _rel(hv, g[f"{tag}_views"]) <= 2e-5
-        assert _rel(raw[:, 0], g[f"{tag}_out"]) <= 2e-5
+        assert rel(f, g[f"{tag}_feature"]) <= 2e-5 and rel(hv, g[f"{tag}_views"]) <= 2e-5
+        assert rel(raw[:, 0], g[f"{tag}_out"]) <= 2e-5
         if precision in ("f32", "f32x"):
             # behind the rows (both SAVE forwards, same layout): ReLU sign bits in accumulator layout, one 1-KiB block per
             # 32-point tile and masked tensor (h0..h7, views)
@@ -91,7 +80,7 @@ _WGRAD_ROW_CASES = [(n_out, n_in, P) for n_out, n_in in _WGRAD_ROW_SHAPES for P 
 def test_wgrad_gemm(amd, n_out, n_in, P, aligned):
     """grad_weight = grad_out^T @ input and grad_bias = grad_out.sum(0), written into a column block of an
     nn.Linear-shaped [out, in_total] gradient (the skip / view concatenations are column blocks)."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     gen = torch.Generator().manual_seed(n_out * 1000 + n_in)
     # aligned: leading dimensions / offsets that allow the float4 fast path of the 256x256 layers
     ldz, zc0, ldh, hc0, ldw, wc0 = (n_out + 8, 4, n_in + 12, 8, n_in + 11, 7) if aligned else (n_out + 5, 2, n_in + 9, 4, n_in + 11, 7)
@@ -100,8 +89,7 @@ def test_wgrad_gemm(amd, n_out, n_in, P, aligned):
     dw = torch.zeros(n_out, ldw, device="cuda")
     db = torch.zeros(n_out, device="cuda")
     dz_d, hin_d = dz.cuda(), hin.cuda()            # keep the device copies alive across the call
-    L.check(lib.nerf_wgrad(L.ptr(dz_d), ldz, zc0, n_out, L.ptr(hin_d), ldh, hc0, n_in, L.ptr(dw), ldw, wc0,
-                           L.ptr(db), P, L.stream_of(dw.device)))
+    L.call("nerf_wgrad", dz_d, ldz, zc0, n_out, hin_d, ldh, hc0, n_in, dw, ldw, wc0, db, P)
     ref = dz[:, zc0:zc0 + n_out].double().T @ hin[:, hc0:hc0 + n_in].double()
     got = dw.cpu()
     assert torch.all(got[:, :wc0] == 0) and torch.all(got[:, wc0 + n_in:] == 0)          # only the column block
@@ -125,7 +113,7 @@ def test_wgrad_small_layers_in_training_layout(amd, layer, P):
     """The small-layer weight gradients in exactly the row pitches / column offsets of a training step.  Columns that
     exist in memory but not in the layer (float 63 of a PE row, 27..31 of a direction row, the colour columns next to
     sigma) hold NaN here: they may be loaded but must not reach any output."""
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     (ldz, zc0, n_out), (ldh, hc0, n_in), (ldw, wc0), bias = _SMALL_LAYOUTS[layer]
     gen = torch.Generator().manual_seed(P + n_out)
     dz = torch.randn(P, ldz, generator=gen)
@@ -135,8 +123,7 @@ def test_wgrad_small_layers_in_training_layout(amd, layer, P):
     dw = torch.zeros(n_out, ldw, device="cuda")
     db = torch.zeros(n_out, device="cuda")
     dz_d, hin_d = dz.cuda(), hin_d.cuda()
-    L.check(lib.nerf_wgrad(L.ptr(dz_d), ldz, zc0, n_out, L.ptr(hin_d), ldh, hc0, n_in, L.ptr(dw), ldw, wc0,
-                           L.ptr(db) if bias else None, P, L.stream_of(dw.device)))
+    L.call("nerf_wgrad", dz_d, ldz, zc0, n_out, hin_d, ldh, hc0, n_in, dw, ldw, wc0, db if bias else None, P)
     ref = dz[:, zc0:zc0 + n_out].double().T @ hin[:, hc0:hc0 + n_in].double()
     got = dw.cpu()
     assert torch.all(got[:, :wc0] == 0) and torch.all(got[:, wc0 + n_in:] == 0)
@@ -148,19 +135,13 @@ def test_wgrad_small_layers_in_training_layout(amd, layer, P):
         assert torch.all(db == 0)
 
 
-def _grad_ptrs(amd, grads):
-    import ctypes
-    return (ctypes.c_void_p * 24)(*[g.data_ptr() for g in grads])
-
-
 @pytest.mark.parametrize("gscale", [1.0, 1e-7])          # mean-reduced losses hand over gradients around 1e-6 .. 1e-8
 @pytest.mark.parametrize("precision", ["f32", "f32x"])
 @pytest.mark.parametrize("model,prefix", [("fine", "model_fine"), ("", "model")])
 def test_mlp_backward_matches_autograd(amd, net, oracle, synthetic_sd, model, prefix, precision, gscale):
     """loss = sum(raw * G): all 24 parameter gradients of one NeRF MLP and d loss / d t through the
     points (positional encoding included) against the CPU oracle under torch autograd."""
-    import ctypes
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     gen = torch.Generator().manual_seed(7)
     n, S = 37, 5                                              # 185 points: ragged last tile
     o = torch.tensor([0.0, 0.0, 4.0]).expand(n, 3).contiguous()
@@ -178,32 +159,28 @@ def test_mlp_backward_matches_autograd(amd, net, oracle, synthetic_sd, model, pr
     # ---- HIP
     sub = net.model_fine if model == "fine" else net.model
     params = [p.detach().contiguous() for p in sub.ordered_params()]
-    arr = (ctypes.c_void_p * 24)(*[p.data_ptr() for p in params])
-    st = L.stream_of(params[0].device)
     prec = L.PRECISIONS[precision]
-    pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device="cuda")
-    L.check(lib.nerf_pack_model_bwd(arr, pk_b.data_ptr(), prec, st))
+    pk_b = torch.empty(int(L.call("nerf_packed_bwd_bytes", prec)), dtype=torch.uint8, device="cuda")
+    L.call("nerf_pack_model_bwd", params, pk_b, prec)
     P = n * S
     od, dd, td, Gd = o.cuda(), d.cuda(), t.cuda(), G.cuda().contiguous()
     raw = torch.empty(n, S, 4, device="cuda")
-    save = torch.empty(int(lib.nerf_train_save_floats(P)), device="cuda")
-    gsave = torch.empty(int(lib.nerf_train_grad_floats(P)), device="cuda")
+    save = torch.empty(int(L.call("nerf_train_save_floats", P)), device="cuda")
+    gsave = torch.empty(int(L.call("nerf_train_grad_floats", P)), device="cuda")
     g_t = torch.empty(n, S, device="cuda")
-    L.check(lib.nerf_mlp_forward_rays_save(L.ptr(od), L.ptr(dd), L.ptr(td), S, n, S, net.packed(model).data_ptr(),
-                                           L.ptr(raw), L.ptr(save), 0, st))
+    L.call("nerf_mlp_forward_rays_save", od, dd, td, S, n, S, net.packed(model), raw, save, 0)
     grads = [torch.zeros_like(p) for p in params]
-    L.check(lib.nerf_mlp_backward(L.ptr(od), L.ptr(dd), L.ptr(td), S, n, S, pk_b.data_ptr(), L.ptr(Gd), L.ptr(save),
-                                  L.ptr(gsave), L.ptr(g_t), _grad_ptrs(amd, grads), prec, st))
+    L.call("nerf_mlp_backward", od, dd, td, S, n, S, pk_b, Gd, save, gsave, g_t, grads, prec)
     torch.cuda.synchronize()
-    assert _rel(raw, raw_ref.detach()) <= 2e-5
+    assert rel(raw, raw_ref.detach()) <= 2e-5
     names = [f"{prefix}.{k}" for k in oracle.SUBMODEL_KEYS]
     worst = 0.0
     for name, got in zip(names, grads):
         ref = sd[name].grad
-        err = _rel(got, ref)
+        err = rel(got, ref)
         worst = max(worst, err)
         assert err <= 1e-5, (name, err)          # measured <= 1.2e-6 (profiles/parity_r03.json)
-    e_t = _rel(g_t, t_ref.grad)
+    e_t = rel(g_t, t_ref.grad)
     print(f"{prefix} [{precision}, |G|~{gscale:g}]: worst parameter-gradient error {worst:.2e}, d/dt error {e_t:.2e}")
     parity_record("gradients", f"mlp_backward_vs_autograd/{prefix}/{precision}/G{gscale:g}",
                   {"worst_param_rel_err": worst, "dt_rel_err": e_t})
@@ -212,7 +189,7 @@ def test_mlp_backward_matches_autograd(amd, net, oracle, synthetic_sd, model, pr
 
 def test_composite_backward_matches_autograd(amd, oracle, golden):
     g = golden("sampling.npz")
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     gen = torch.Generator().manual_seed(11)
     n, S = 200, 192
     raw = g["raw_fine"][:n].clone()
@@ -225,9 +202,8 @@ def test_composite_backward_matches_autograd(amd, oracle, golden):
     rawd, td = raw.cuda().contiguous(), t.cuda().contiguous()
     Gr, Gd = G_rgb.cuda().contiguous(), G_dep.cuda().contiguous()
     g_raw, g_t = torch.empty(n, S, 4, device="cuda"), torch.empty(n, S, device="cuda")
-    L.check(lib.nerf_composite_backward(L.ptr(rawd), L.ptr(td), S, n, S, 1, L.ptr(Gr), L.ptr(Gd), L.ptr(g_raw), L.ptr(g_t),
-                                        L.stream_of(rawd.device)))
-    e_raw, e_t = _rel(g_raw, raw_r.grad), _rel(g_t, t_r.grad)
+    L.call("nerf_composite_backward", rawd, td, S, n, S, 1, Gr, Gd, g_raw, g_t)
+    e_raw, e_t = rel(g_raw, raw_r.grad), rel(g_t, t_r.grad)
     print(f"composite backward: g_raw {e_raw:.2e}, g_t {e_t:.2e}")
     parity_record("gradients", "composite_backward_vs_autograd", {"g_raw_rel_err": e_raw, "g_t_rel_err": e_t})
     assert e_raw <= 1e-5 and e_t <= 1e-5          # measured 1.1e-6 / 2.0e-6
@@ -235,7 +211,7 @@ def test_composite_backward_matches_autograd(amd, oracle, golden):
 
 def test_sample_backward_matches_autograd(amd, oracle, golden):
     g = golden("sampling.npz")
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     gen = torch.Generator().manual_seed(12)
     n = 256
     raw_c = g["raw_coarse"][:n].clone()
@@ -248,11 +224,10 @@ def test_sample_backward_matches_autograd(amd, oracle, golden):
     rawd = raw_c.cuda().contiguous()
     tcd, ud = torch.linspace(2.0, 6.0, 64).cuda(), torch.linspace(0.0, 1.0, 128).cuda()
     ts = torch.empty(n, 192, device="cuda")
-    L.check(lib.nerf_sample_fine(L.ptr(rawd), L.ptr(tcd), L.ptr(ud), n, L.ptr(ts), None, None, 0.0, 0.0, L.stream_of(rawd.device)))
+    L.call("nerf_sample_fine", rawd, tcd, ud, n, ts, None, None, 0.0, 0.0)
     Gd = G.cuda().contiguous()
     g_raw = torch.full((n, 64, 4), float("nan"), device="cuda")
-    L.check(lib.nerf_sample_fine_backward(L.ptr(rawd), L.ptr(tcd), L.ptr(ud), n, L.ptr(ts), L.ptr(Gd), L.ptr(g_raw),
-                                          L.stream_of(rawd.device)))
+    L.call("nerf_sample_fine_backward", rawd, tcd, ud, n, ts, Gd, g_raw)
     got, ref = g_raw.cpu(), raw_r.grad
     assert torch.all(got[..., :3] == 0)
     # per-ray comparison: a searchsorted / denom<1e-5 flip (module docstring of test_gpu_parity) changes a ray's
@@ -443,15 +418,15 @@ def test_network_forward_is_differentiable(amd, oracle, synthetic_sd, model, pre
         raw = net(p_hip, vd_hip, None if msk is None else msk.cuda(), model)
         assert raw.requires_grad and raw.shape == (n, S, 4)
         (raw * G.cuda()).sum().backward()
-        assert _rel(raw.detach(), raw_ref.detach()) <= 2e-5
+        assert rel(raw.detach(), raw_ref.detach()) <= 2e-5
         worst = 0.0
         for name, p in zip(names, sub.ordered_params()):
-            err = _rel(p.grad, sd[name].grad)
+            err = rel(p.grad, sd[name].grad)
             worst = max(worst, err)
             assert err <= 1e-5, (tag, name, err)         # measured <= 1.3e-6
-        e_x = _rel(p_hip.grad, p_ref.grad)
+        e_x = rel(p_hip.grad, p_ref.grad)
         assert e_x <= 1e-5, (tag, e_x)
-        e_d = _rel(vd_hip.grad, vd_ref.grad)                                  # d / d viewdirs (nerf_viewdirs_backward)
+        e_d = rel(vd_hip.grad, vd_ref.grad)                                  # d / d viewdirs (nerf_viewdirs_backward)
         assert vd_hip.grad.shape == (n, 3) and e_d <= 1e-5, (tag, e_d)
         assert all(p.grad is None for p in other.parameters())               # the other sub-model is not touched
         if msk is not None:
@@ -473,8 +448,7 @@ def test_density_only_pair_equals_full_pair_with_zero_colour_gradient(amd, net, 
     branch is computed by the reference but never used: SURVEY F6/F10).  Against the full pair fed a d loss / d raw with
     zero rgb columns: sigma bit-identical, the 18 trunk / alpha gradients and d loss / d t equal to rounding (the
     weight-gradient kernels accumulate with atomics), the colour-branch gradients EXACTLY zero in both."""
-    import ctypes
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     gen = torch.Generator().manual_seed(23)
     n, S = 41, 64
     o = torch.tensor([0.0, 0.0, 4.0]).expand(n, 3).contiguous().cuda()
@@ -485,35 +459,32 @@ def test_density_only_pair_equals_full_pair_with_zero_colour_gradient(amd, net, 
     G[..., :3] = 0.0
     G = G.cuda().contiguous()
     params = [p.detach().contiguous() for p in net.model.ordered_params()]
-    arr = (ctypes.c_void_p * 24)(*[p.data_ptr() for p in params])
-    st = L.stream_of(o.device)
     prec = L.PRECISIONS[precision]                           # (f32x: both instances since round 3)
     net.precision = precision
-    pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device="cuda")
-    L.check(lib.nerf_pack_model_bwd(arr, pk_b.data_ptr(), prec, st))
+    pk_b = torch.empty(int(L.call("nerf_packed_bwd_bytes", prec)), dtype=torch.uint8, device="cuda")
+    L.call("nerf_pack_model_bwd", params, pk_b, prec)
     P = n * S
     out = {}
-    for tag, fwd, bwd in (("full", lib.nerf_mlp_forward_rays_save, lib.nerf_mlp_backward),
-                          ("density", lib.nerf_mlp_forward_rays_save_density, lib.nerf_mlp_backward_density)):
+    for tag, fwd, bwd in (("full", "nerf_mlp_forward_rays_save", "nerf_mlp_backward"),
+                          ("density", "nerf_mlp_forward_rays_save_density", "nerf_mlp_backward_density")):
         raw = torch.full((n, S, 4), float("nan"), device="cuda")
-        save = torch.empty(int(lib.nerf_train_save_floats(P)), device="cuda")
-        gsave = torch.empty(int(lib.nerf_train_grad_floats(P)), device="cuda")
+        save = torch.empty(int(L.call("nerf_train_save_floats", P)), device="cuda")
+        gsave = torch.empty(int(L.call("nerf_train_grad_floats", P)), device="cuda")
         g_t = torch.empty(n, S, device="cuda")
         grads = [torch.zeros_like(p) for p in params]
-        L.check(fwd(L.ptr(o), L.ptr(d), L.ptr(t_c), 0, n, S, net.packed("").data_ptr(), L.ptr(raw), L.ptr(save), prec, st))
-        L.check(bwd(L.ptr(o), L.ptr(d), L.ptr(t_c), 0, n, S, pk_b.data_ptr(), L.ptr(G), L.ptr(save), L.ptr(gsave), L.ptr(g_t),
-                    _grad_ptrs(amd, grads), prec, st))
+        L.call(fwd, o, d, t_c, 0, n, S, net.packed(""), raw, save, prec)
+        L.call(bwd, o, d, t_c, 0, n, S, pk_b, G, save, gsave, g_t, grads, prec)
         torch.cuda.synchronize()
         out[tag] = (raw, g_t, grads)
     assert torch.equal(out["full"][0][..., 3], out["density"][0][..., 3])
     assert torch.all(out["density"][0][..., :3] == 0)
-    assert _rel(out["density"][1], out["full"][1].cpu()) <= 1e-6
+    assert rel(out["density"][1], out["full"][1].cpu()) <= 1e-6
     names = list(__import__("nerf_oracle").SUBMODEL_KEYS)
     for name, gf, gd in zip(names, out["full"][2], out["density"][2]):
         if name.startswith(("views_linears", "feature_linear", "rgb_linear")):
             assert torch.all(gf == 0) and torch.all(gd == 0), name
         else:
-            assert gf.abs().max() > 0 and _rel(gd, gf.cpu()) <= 2e-6, name
+            assert gf.abs().max() > 0 and rel(gd, gf.cpu()) <= 2e-6, name
     net.precision = "f32"
 
 
@@ -528,8 +499,7 @@ def test_dead_tile_skip_changes_nothing(amd, net, synthetic_sd, monkeypatch, dea
     d loss / d t equal as numbers everywhere (bit-identical code on live tiles, 0 on dead ones), all 24 parameter gradients
     equal to the rounding of their atomic accumulation -- for no dead tile, a scene-like 60 %, and all of them (gradients
     exactly zero).  Zeros include -0.0; a tile with ONE live point is live."""
-    import ctypes
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     net.precision = precision
     prec = L.PRECISIONS[precision]
     gen = torch.Generator().manual_seed(31)
@@ -551,24 +521,21 @@ def test_dead_tile_skip_changes_nothing(amd, net, synthetic_sd, monkeypatch, dea
         tiles[..., :3] = 0.0
     G = G.cuda().contiguous()
     params = [p.detach().contiguous() for p in net.model.ordered_params()]
-    arr = (ctypes.c_void_p * 24)(*[p.data_ptr() for p in params])
-    st = L.stream_of(o.device)
-    pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device="cuda")
-    L.check(lib.nerf_pack_model_bwd(arr, pk_b.data_ptr(), prec, st))
+    pk_b = torch.empty(int(L.call("nerf_packed_bwd_bytes", prec)), dtype=torch.uint8, device="cuda")
+    L.call("nerf_pack_model_bwd", params, pk_b, prec)
     P = n * S
-    fwd = lib.nerf_mlp_forward_rays_save_density if density_only else lib.nerf_mlp_forward_rays_save
-    bwd = lib.nerf_mlp_backward_density if density_only else lib.nerf_mlp_backward
+    fwd = "nerf_mlp_forward_rays_save_density" if density_only else "nerf_mlp_forward_rays_save"
+    bwd = "nerf_mlp_backward_density" if density_only else "nerf_mlp_backward"
     raw = torch.empty((n, S, 4), device="cuda")
-    save = torch.empty(int(lib.nerf_train_save_floats(P)), device="cuda")
-    L.check(fwd(L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, net.packed(model).data_ptr(), L.ptr(raw), L.ptr(save), prec, st))
+    save = torch.empty(int(L.call("nerf_train_save_floats", P)), device="cuda")
+    L.call(fwd, o, d, t, S, n, S, net.packed(model), raw, save, prec)
     out = {}
     for tag, env in (("skip", "1"), ("dense", "0")):
         monkeypatch.setenv("NERF_DEAD_TILE_SKIP", env)
-        gsave = torch.full((int(lib.nerf_train_grad_floats(P)),), float("nan"), device="cuda")     # dead rows stay NaN: never read
+        gsave = torch.full((int(L.call("nerf_train_grad_floats", P)),), float("nan"), device="cuda")     # dead rows stay NaN: never read
         g_t = torch.full((n, S), float("nan"), device="cuda")
         grads = [torch.zeros_like(p) for p in params]
-        L.check(bwd(L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, pk_b.data_ptr(), L.ptr(G), L.ptr(save), L.ptr(gsave), L.ptr(g_t),
-                    _grad_ptrs(amd, grads), prec, st))
+        L.call(bwd, o, d, t, S, n, S, pk_b, G, save, gsave, g_t, grads, prec)
         torch.cuda.synchronize()
         out[tag] = (g_t, grads)
     monkeypatch.delenv("NERF_DEAD_TILE_SKIP")
@@ -583,7 +550,7 @@ def test_dead_tile_skip_changes_nothing(amd, net, synthetic_sd, monkeypatch, dea
         elif density_only and name.startswith(("views_linears", "feature_linear", "rgb_linear")):
             assert torch.all(gs == 0) and torch.all(gd == 0), name
         else:
-            assert gd.abs().max() > 0 and _rel(gs, gd.cpu()) <= 1e-5, name      # (sums of ~10^4 signed terms, accumulated by atomics in a different order)
+            assert gd.abs().max() > 0 and rel(gs, gd.cpu()) <= 1e-5, name      # (sums of ~10^4 signed terms, accumulated by atomics in a different order)
 
 
 @pytest.mark.parametrize("precision", ["f32", "f32x"])
@@ -622,7 +589,7 @@ def test_training_step_same_with_and_without_dead_tile_skipping(amd, family_sd, 
         if gd.abs().max() == 0:
             assert torch.all(gs == 0)
         else:
-            assert _rel(gs, gd.cpu()) <= 1e-4            # (atomic accumulation order; scalar sums with cancellation reach 5e-5)
+            assert rel(gs, gd.cpu()) <= 1e-4            # (atomic accumulation order; scalar sums with cancellation reach 5e-5)
 
 
 @pytest.mark.parametrize("n_sub", [1, 5, 63])
@@ -646,7 +613,7 @@ def test_per_ray_adjoints_are_independent_of_the_ray_count(amd, golden, n_sub):
         for n in (n_all, n_sub):
             g_raw = torch.full((n_all, S, 4), float("nan"), device="cuda")
             g_t = torch.full((n_all, S), float("nan"), device="cuda")
-            L.check(lib.nerf_composite_backward(L.ptr(raw), L.ptr(t_all), stride, n, S, 1, L.ptr(Gr), L.ptr(Gd), L.ptr(g_raw), L.ptr(g_t), st))
+            L.call("nerf_composite_backward", raw, t_all, stride, n, S, 1, Gr, Gd, g_raw, g_t)
             torch.cuda.synchronize()
             outs.append((g_raw, g_t))
         assert torch.equal(outs[0][0][:n_sub], outs[1][0][:n_sub]) and torch.equal(outs[0][1][:n_sub], outs[1][1][:n_sub])
@@ -655,12 +622,12 @@ def test_per_ray_adjoints_are_independent_of_the_ray_count(amd, golden, n_sub):
     raw_c = g["raw_coarse"][:n_all].cuda().contiguous()
     tcd, ud = torch.linspace(2.0, 6.0, 64).cuda(), torch.linspace(0.0, 1.0, 128).cuda()
     ts = torch.empty(n_all, 192, device="cuda")
-    L.check(lib.nerf_sample_fine(L.ptr(raw_c), L.ptr(tcd), L.ptr(ud), n_all, L.ptr(ts), None, None, 0.0, 0.0, st))
+    L.call("nerf_sample_fine", raw_c, tcd, ud, n_all, ts, None, None, 0.0, 0.0)
     G = torch.randn(n_all, 192, generator=gen).cuda().contiguous()
     outs = []
     for n in (n_all, n_sub):
         g_raw = torch.full((n_all, 64, 4), float("nan"), device="cuda")
-        L.check(lib.nerf_sample_fine_backward(L.ptr(raw_c), L.ptr(tcd), L.ptr(ud), n, L.ptr(ts), L.ptr(G), L.ptr(g_raw), st))
+        L.call("nerf_sample_fine_backward", raw_c, tcd, ud, n, ts, G, g_raw)
         torch.cuda.synchronize()
         outs.append(g_raw)
     # (LDS float atomics accumulate the few contributions per cdf entry in arbitrary order: equal to rounding, not bit for bit)
@@ -705,14 +672,14 @@ def test_network_forward_viewdirs_gradient_with_dead_tiles(amd, oracle, syntheti
         assert raw.requires_grad                              # eval(): viewdirs alone switches the autograd path on
         (raw * G.cuda()).sum().backward()
         assert torch.isfinite(vd_hip.grad).all()
-        e_d = _rel(vd_hip.grad, vd_ref.grad)
+        e_d = rel(vd_hip.grad, vd_ref.grad)
         assert e_d <= 1e-5, (mode, e_d)
         assert torch.all(vd_hip.grad[5] == 0) and vd_ref.grad[5].abs().max() == 0
         if mode == "train":
-            assert _rel(p_hip.grad, p_ref.grad) <= 1e-5
+            assert rel(p_hip.grad, p_ref.grad) <= 1e-5
             assert torch.all(p_hip.grad.view(-1, 32, 3)[[0, 3, 4, 7, 10, 11]] == 0)
             for name, p in zip([f"model_fine.{k}" for k in oracle.SUBMODEL_KEYS], net.model_fine.ordered_params()):
-                assert _rel(p.grad, sd[name].grad) <= 1e-5, name
+                assert rel(p.grad, sd[name].grad) <= 1e-5, name
     parity_record("gradients", f"network_forward_viewdirs_dead_tiles/{precision}", {"d_viewdirs_rel_err": e_d})
 
 
@@ -739,8 +706,7 @@ def test_point_mode_backward_in_list_mode(amd, net, monkeypatch, dead_frac, prec
     memset with dead tiles, nerf_mlp_bwd_f32x_kernel<true> taking four list entries per workgroup, nerf_mlp_bwd_f32_kernel<true>
     with live_tiles) against NERF_DEAD_TILE_SKIP=0: g_pts equal as numbers, the 24 gradients to the rounding of their atomics,
     and the g_zv region (what nerf_viewdirs_backward reads) zero on dead tiles."""
-    import ctypes
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     prec = L.PRECISIONS[precision]
     net.precision = precision
     gen = torch.Generator().manual_seed(53)
@@ -755,21 +721,18 @@ def test_point_mode_backward_in_list_mode(amd, net, monkeypatch, dead_frac, prec
     tiles[dead] = 0.0
     G = G.cuda().contiguous()
     params = [p.detach().contiguous() for p in net.model_fine.ordered_params()]
-    arr = (ctypes.c_void_p * 24)(*[p.data_ptr() for p in params])
-    st = L.stream_of(pts.device)
-    pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(prec)), dtype=torch.uint8, device="cuda")
-    L.check(lib.nerf_pack_model_bwd(arr, pk_b.data_ptr(), prec, st))
+    pk_b = torch.empty(int(L.call("nerf_packed_bwd_bytes", prec)), dtype=torch.uint8, device="cuda")
+    L.call("nerf_pack_model_bwd", params, pk_b, prec)
     raw = torch.empty((n, S, 4), device="cuda")
-    save = torch.empty(int(lib.nerf_train_save_floats(P)), device="cuda")
-    L.check(lib.nerf_mlp_forward_points_save(L.ptr(pts), L.ptr(vd), n, S, net.packed("fine").data_ptr(), L.ptr(raw), L.ptr(save), prec, st))
+    save = torch.empty(int(L.call("nerf_train_save_floats", P)), device="cuda")
+    L.call("nerf_mlp_forward_points_save", pts, vd, n, S, net.packed("fine"), raw, save, prec)
     out = {}
     for tag, env in (("skip", "1"), ("dense", "0")):
         monkeypatch.setenv("NERF_DEAD_TILE_SKIP", env)
-        gsave = torch.full((int(lib.nerf_train_grad_floats(P)),), float("nan"), device="cuda")
+        gsave = torch.full((int(L.call("nerf_train_grad_floats", P)),), float("nan"), device="cuda")
         g_x = torch.full((n, S, 3), float("nan"), device="cuda")
         grads = [torch.zeros_like(p) for p in params]
-        L.check(lib.nerf_mlp_backward_points(L.ptr(pts), n, S, pk_b.data_ptr(), L.ptr(G), L.ptr(save), L.ptr(gsave), L.ptr(g_x),
-                                             _grad_ptrs(amd, grads), prec, st))
+        L.call("nerf_mlp_backward_points", pts, n, S, pk_b, G, save, gsave, g_x, grads, prec)
         torch.cuda.synchronize()
         out[tag] = (g_x, grads, gsave[:P * 128].view(-1, 32, 128).clone())
     monkeypatch.delenv("NERF_DEAD_TILE_SKIP")
@@ -781,15 +744,14 @@ def test_point_mode_backward_in_list_mode(amd, net, monkeypatch, dead_frac, prec
         if bool(dead.all()):
             assert torch.all(gs == 0) and torch.all(gd == 0)
         else:
-            assert gd.abs().max() > 0 and _rel(gs, gd.cpu()) <= 1e-5
+            assert gd.abs().max() > 0 and rel(gs, gd.cpu()) <= 1e-5
 
 
 def test_dense_backward_refuses_a_forward_that_skipped_rows(amd, net, family_sd, monkeypatch):
     """One helper decides about dead-tile skipping for the SAVE forward and for the backward pass, and the forward stamps the save
     buffer.  If the two are forced apart anyway (environment toggled between the passes), the dense backward does not read the
     rows that were never written in silence: grads[alpha_linear.bias] comes back NaN."""
-    import ctypes
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     n, S = 32, 192
     P = n * S
     sharp = amd.Network(); sharp.load_state_dict(family_sd("sharp")); sharp = sharp.cuda().eval()
@@ -799,25 +761,21 @@ def test_dense_backward_refuses_a_forward_that_skipped_rows(amd, net, family_sd,
     d = (d / d.norm(dim=-1, keepdim=True)).contiguous().cuda()
     t = torch.sort(torch.rand(n, S, generator=gen) * 4 + 2, dim=-1).values.cuda().contiguous()
     params = [p.detach().contiguous() for p in sharp.model_fine.ordered_params()]
-    arr = (ctypes.c_void_p * 24)(*[p.data_ptr() for p in params])
-    st = L.stream_of(o.device)
-    pk_b = torch.empty(int(lib.nerf_packed_bwd_bytes(0)), dtype=torch.uint8, device="cuda")
-    L.check(lib.nerf_pack_model_bwd(arr, pk_b.data_ptr(), 0, st))
+    pk_b = torch.empty(int(L.call("nerf_packed_bwd_bytes", 0)), dtype=torch.uint8, device="cuda")
+    L.call("nerf_pack_model_bwd", params, pk_b, 0)
     raw = torch.empty((n, S, 4), device="cuda")
-    save = torch.zeros(int(lib.nerf_train_save_floats(P)), device="cuda")
+    save = torch.zeros(int(L.call("nerf_train_save_floats", P)), device="cuda")
     monkeypatch.setenv("NERF_DEAD_TILE_SKIP", "1")
-    L.check(lib.nerf_mlp_forward_rays_save_for_compositing(L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, sharp.packed("fine").data_ptr(),
-                                                           L.ptr(raw), L.ptr(save), 0, st))
+    L.call("nerf_mlp_forward_rays_save_for_compositing", o, d, t, S, n, S, sharp.packed("fine"), raw, save, 0)
     G = torch.zeros(n, S, 4, device="cuda")
     G[..., 3] = (raw[..., 3] > 0).float() * 1e-3               # the contract: zero wherever sigma <= 0
     res = {}
     for env in ("1", "0"):
         monkeypatch.setenv("NERF_DEAD_TILE_SKIP", env)
-        gsave = torch.zeros(int(lib.nerf_train_grad_floats(P)), device="cuda")
+        gsave = torch.zeros(int(L.call("nerf_train_grad_floats", P)), device="cuda")
         g_t = torch.zeros(n, S, device="cuda")
         grads = [torch.zeros_like(p) for p in params]
-        L.check(lib.nerf_mlp_backward(L.ptr(o), L.ptr(d), L.ptr(t), S, n, S, pk_b.data_ptr(), L.ptr(G), L.ptr(save), L.ptr(gsave),
-                                      L.ptr(g_t), _grad_ptrs(amd, grads), 0, st))
+        L.call("nerf_mlp_backward", o, d, t, S, n, S, pk_b, G, save, gsave, g_t, grads, 0)
         torch.cuda.synchronize()
         res[env] = grads[21]                                  # alpha_linear.bias
     monkeypatch.delenv("NERF_DEAD_TILE_SKIP")

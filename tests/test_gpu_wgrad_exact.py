@@ -16,13 +16,13 @@ The worst error / bound ratio per kernel family and the run time of this file go
 
 Measured on the MI355X (profiles/wgrad_bounds.json): every integer probe bit-equal; worst error / bound 0.32 for the bf16x3 dW, 0.45 - 0.52
 for the fp32 families, 0.33 - 0.44 for db; the file runs in about 3 s."""
-import ctypes
 import time
 
 import pytest
 import torch
 
 import wgrad_reference as R
+from gpu_common import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -30,13 +30,6 @@ SENTINEL, PAD = -77.0, 8
 _worst = {}
 _probes = {"calls_bit_equal": 0}
 _t0 = [None]
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import nerf_replication_amd as pkg
-    pkg._lib.load()
-    return pkg
 
 
 @pytest.fixture(scope="module")
@@ -79,11 +72,11 @@ def _intact(whole, n):
 
 # ================================================================================ 1: layout and coverage, with the device's own numbers
 def test_layout_mirror_matches_the_library(amd):
-    lib = amd._lib.load()
+    L = amd._lib
     for P in (1, 31, 32, 33, 185, 533, 2048, 2592, 16385):
-        assert int(lib.nerf_train_save_floats(P)) == R.Save.floats(P)
-        assert int(lib.nerf_train_grad_floats(P)) == R.Grad.floats(P)
-        assert int(lib.nerf_train_live_count_offset(P)) == R.Grad.off_count(P)
+        assert int(L.call("nerf_train_save_floats", P)) == R.Save.floats(P)
+        assert int(L.call("nerf_train_grad_floats", P)) == R.Grad.floats(P)
+        assert int(L.call("nerf_train_live_count_offset", P)) == R.Grad.off_count(P)
 
 
 def test_cases_visit_every_regime_on_this_device(cus):
@@ -94,7 +87,7 @@ def test_cases_visit_every_regime_on_this_device(cus):
 
 # ================================================================================ 2: integer probes of nerf_wgrad
 def _probe(amd, layout, P, scale, seed):
-    lib, L = amd._lib.load(), amd._lib
+    L = amd._lib
     (ldz, zc0, n_out), (ldh, hc0, n_in), (ldw, wc0), bias = layout
     gen = torch.Generator(device="cuda").manual_seed(seed)
     dz_i = torch.randint(-R.PROBE_MAX, R.PROBE_MAX + 1, (P, n_out), device="cuda", generator=gen).double()
@@ -109,8 +102,7 @@ def _probe(amd, layout, P, scale, seed):
     whole_w, dw = _padded(n_out * ldw)
     whole_b, db = _padded(n_out)
     for call in (1, 2):                                       # the second call adds into the same buffers: exactly twice
-        L.check(lib.nerf_wgrad(L.ptr(dz), ldz, zc0, n_out, L.ptr(hin), ldh, hc0, n_in, L.ptr(dw), ldw, wc0, L.ptr(db) if bias else None,
-                               P, L.stream_of(dw.device)), "nerf_wgrad")
+        L.call("nerf_wgrad", dz, ldz, zc0, n_out, hin, ldh, hc0, n_in, dw, ldw, wc0, db if bias else None, P)
         torch.cuda.synchronize()
         got = dw.view(n_out, ldw)
         block = got[:, wc0:wc0 + n_in]
@@ -171,39 +163,34 @@ class Run:
     """One forward + backward through the C ABI; keeps every buffer the weight-gradient kernels read and wrote."""
 
     def __init__(self, amd, net, precision, density_only, P, G, seed, masked_valid=None, save_fill=float("nan")):
-        lib, L = amd._lib.load(), amd._lib
+        L = amd._lib
         self.P, self.precision, self.dens = P, precision, density_only
         net.precision = precision
         prec = L.PRECISIONS[precision]
         o, d, t = _rays(P, seed)
-        st = L.stream_of(o.device)
         self.params = [p.detach().contiguous() for p in net.model.ordered_params()]
         assert [tuple(p.shape) for p in self.params] == R.PARAM_SHAPES
         pk, pk_b = net.packed(""), net.packed_bwd("")
         raw = torch.empty(P, 1, 4, device="cuda")
-        self.save = torch.full((int(lib.nerf_train_save_floats(P)),), save_fill, device="cuda")
-        self.gsave = torch.full((int(lib.nerf_train_grad_floats(P)),), float("nan"), device="cuda")    # a read of a row nobody wrote shows
+        self.save = torch.full((int(L.call("nerf_train_save_floats", P)),), save_fill, device="cuda")
+        self.gsave = torch.full((int(L.call("nerf_train_grad_floats", P)),), float("nan"), device="cuda")    # a read of a row nobody wrote shows
         g_t = torch.empty(P, 1, device="cuda")
         self.grads = [torch.zeros_like(p) for p in self.params]
-        gp = (ctypes.c_void_p * 24)(*[g.data_ptr() for g in self.grads])
-        rays = (L.ptr(o), L.ptr(d), L.ptr(t), 1, P, 1)
+        rays = (o, d, t, 1, P, 1)
         self.draw = G.view(-1)
         if masked_valid is None:
-            fwd = lib.nerf_mlp_forward_rays_save_density if density_only else lib.nerf_mlp_forward_rays_save
-            bwd = lib.nerf_mlp_backward_density if density_only else lib.nerf_mlp_backward
-            L.check(fwd(*rays, pk.data_ptr(), L.ptr(raw), L.ptr(self.save), prec, st), "forward")
-            L.check(bwd(*rays, pk_b.data_ptr(), L.ptr(G), L.ptr(self.save), L.ptr(self.gsave), L.ptr(g_t), gp, prec, st), "backward")
+            fwd = "nerf_mlp_forward_rays_save_density" if density_only else "nerf_mlp_forward_rays_save"
+            bwd = "nerf_mlp_backward_density" if density_only else "nerf_mlp_backward"
+            L.call(fwd, *rays, pk, raw, self.save, prec)
+            L.call(bwd, *rays, pk_b, G, self.save, self.gsave, g_t, self.grads, prec)
         else:
             index = torch.full((P,), -7, dtype=torch.int32, device="cuda")
             count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
-            ws_c = torch.empty(int(lib.nerf_compact_valid_workspace_bytes(P)), dtype=torch.uint8, device="cuda")
-            L.check(lib.nerf_compact_valid(L.ptr(masked_valid, torch.uint8), P, L.ptr(index, torch.int32), L.ptr(count, torch.int32),
-                                           ws_c.data_ptr(), st), "compact")
-            ws = torch.zeros(int(lib.nerf_mlp_backward_masked_workspace_bytes(P)), dtype=torch.uint8, device="cuda")
-            ids = (L.ptr(index, torch.int32), L.ptr(count, torch.int32))
-            L.check(lib.nerf_mlp_forward_rays_save_masked(*rays, *ids, pk.data_ptr(), L.ptr(raw), L.ptr(self.save), prec, st), "forward")
-            L.check(lib.nerf_mlp_backward_masked(*rays, *ids, pk_b.data_ptr(), L.ptr(G), L.ptr(self.save), L.ptr(self.gsave), L.ptr(g_t),
-                                                 gp, prec, ws.data_ptr(), st), "backward")
+            ws_c = torch.empty(int(L.call("nerf_compact_valid_workspace_bytes", P)), dtype=torch.uint8, device="cuda")
+            L.call("nerf_compact_valid", masked_valid, P, index, count, ws_c)
+            ws = torch.zeros(int(L.call("nerf_mlp_backward_masked_workspace_bytes", P)), dtype=torch.uint8, device="cuda")
+            L.call("nerf_mlp_forward_rays_save_masked", *rays, index, count, pk, raw, self.save, prec)
+            L.call("nerf_mlp_backward_masked", *rays, index, count, pk_b, G, self.save, self.gsave, g_t, self.grads, prec, ws)
             self.draw = ws[:P * 16].view(torch.float32)       # the compact incoming gradient: the first piece of the workspace
             self.count = int(count.item())
         torch.cuda.synchronize()

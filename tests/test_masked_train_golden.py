@@ -4,6 +4,8 @@ tests/test_gpu_masked_training.py are judged by; it does not touch the HIP path.
 import pytest
 import torch
 
+from train_steps_common import subsample
+
 GRAD_STRIDE = 53
 MASKED_CASES = (("trained_t002", "trained", 0.02), ("sharp_t025", "sharp", 0.25), ("trained_t025", "trained", 0.25))
 
@@ -12,11 +14,6 @@ def _case(golden, tag):
     g = golden("masked_train.npz")
     assert int(g["grad_stride"]) == GRAD_STRIDE
     return g, {k[len(tag) + 1:]: v for k, v in g.items() if k.startswith(tag + "/")}
-
-
-def _subsample(t):
-    f = t.detach().reshape(-1)
-    return f.clone() if f.numel() <= 4096 else f[::GRAD_STRIDE].clone()
 
 
 def _check_grads(sd, c, prefixes):
@@ -29,7 +26,7 @@ def _check_grads(sd, c, prefixes):
             assert v.grad is None, k
             continue
         ref = c["grad/" + k]
-        got = _subsample(v.grad)
+        got = subsample(v.grad, GRAD_STRIDE)
         assert got.shape == ref.shape, k
         assert torch.allclose(got, ref, rtol=1e-4, atol=1e-6 + 1e-5 * ref.abs().max().item()), (k, (got - ref).abs().max().item(), ref.abs().max().item())
         n += 1

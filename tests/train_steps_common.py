@@ -12,11 +12,11 @@ on the CPU oracle, with two extras the tests need:
 import torch
 
 
-def subsample(t):
+def subsample(t, stride=7):
     """The fixture's view of a parameter-shaped tensor (oracle/gen_golden.py::_subsample): small tensors in full, weight
-    matrices as their flat stride-7 subsample."""
+    matrices as their flat subsample of the fixture's stride (7 in train_steps_*.npz)."""
     f = t.detach().reshape(-1)
-    return f.clone() if f.numel() <= 4096 else f[::7].clone()
+    return f.clone() if f.numel() <= 4096 else f[::stride].clone()
 
 
 def sampler_conditioning(oracle, sigma_c_raw, eps=1e-5):

@@ -8,7 +8,9 @@ teacher setup of examples/train_synthetic.py (renders of tests/golden/synthetic_
 
 --occupancy N rebuilds an N^3 occupancy grid from the field itself (HashField.occupancy_grid) every --refresh-every steps; a grid made
 from fields carries no staleness key, so this loop owns the schedule; the first --occupancy-from steps run unculled.  Prints ms per
-step and the held-out PSNR.
+step and the held-out PSNR.  --deterministic-table sums the hash table's gradient exactly and order-independently
+(HashEncoder(deterministic=True)); the two networks' weight gradients keep their fp32 atomics, so a whole step is not yet
+bit-reproducible.
 """
 import argparse
 import math
@@ -47,6 +49,8 @@ def main():
                     help="first step that is culled: a fresh field has no density to speak of, and a grid built from it would cull "
                          "every sample (no sample, no gradient)")
     ap.add_argument("--out", default=None, help="write the trained field's state dict here")
+    ap.add_argument("--deterministic-table", action="store_true",
+                    help="sum the hash table's gradient exactly, in an order-independent way (HashEncoder(deterministic=True))")
     args = ap.parse_args()
     if args.occupancy and args.occupancy < 2:
         ap.error("--occupancy needs at least 2 grid points per axis")
@@ -68,7 +72,8 @@ def main():
 
     torch.manual_seed(0)
     encoder = nerf.HashEncoder(input_dim=3, num_levels=args.levels, level_dim=2, base_resolution=16,
-                               log2_hashmap_size=args.log2_hashmap_size, desired_resolution=2048)
+                               log2_hashmap_size=args.log2_hashmap_size, desired_resolution=2048,
+                               deterministic=args.deterministic_table)
     half = float(args.half_extent)
     field = nerf.HashField((-half, -half, -half, half, half, half), encoder=encoder).cuda()
     ren = nerf.HashRenderer(field)                             # the held-out evaluation: never culled

@@ -166,6 +166,18 @@ FIELD_SIGNATURES = _parse_table(_TABLE_FIELD)
 FIELD_EXPORTS = tuple(FIELD_SIGNATURES)
 _FIELD_PROTOS = _protos(FIELD_SIGNATURES)
 
+# The deterministic table gradient of the hash-grid encoding, one line per entry of include/nerf_mi355x_hashgrid.h (the fourth header
+# of the same library; the three tables above are pinned at their sizes).  tests/test_hashgrid_deterministic_cpu.py compares this
+# table with that header.
+_TABLE_HASHGRID = """
+nerf_hashgrid_deterministic_workspace_bytes  i64 : i64 i32
+nerf_hashgrid_deterministic_guard_bits  i32 : i64 i32
+nerf_hashgrid_backward_deterministic  status : f32* f32* i64 i32 i32 i32 i32[] f32[] f32* void* i64 stream
+"""
+HASHGRID_SIGNATURES = _parse_table(_TABLE_HASHGRID)
+HASHGRID_EXPORTS = tuple(HASHGRID_SIGNATURES)
+_HASHGRID_PROTOS = _protos(HASHGRID_SIGNATURES)
+
 _lib = None
 
 
@@ -192,7 +204,8 @@ def load():
                 f"{LIB_PATH} is missing: build it with `make -C {CSRC}` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the render path")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOS.items()) + list(_NN_PROTOS.items()) + list(_FIELD_PROTOS.items()):
+        for name, (res, args) in (list(_PROTOS.items()) + list(_NN_PROTOS.items()) + list(_FIELD_PROTOS.items()) +
+                                  list(_HASHGRID_PROTOS.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.nerf_abi_version() != 3:
@@ -217,9 +230,12 @@ class strided:
 def call(name, *args):
     """Call entry `name` of the library with `args` as its header lists them, minus the stream: tensors (None: NULL) for device
     pointers, numbers for scalars, sequences or ctypes arrays for host arrays.  Every argument is checked against the entry's kinds
-    in SIGNATURES (or NN_SIGNATURES, the small-network entries) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
+    in SIGNATURES (or, looked up in this order, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
     is checked (NerfLibraryError with nerf_last_error's text); any other return value comes back as it is."""
-    ret, kinds = SIGNATURES[name] if name in SIGNATURES else NN_SIGNATURES[name] if name in NN_SIGNATURES else FIELD_SIGNATURES[name]
+    for table in (SIGNATURES, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES):
+        if name in table:
+            break
+    ret, kinds = table[name]
     has_stream = kinds[-1:] == ("stream",)
     if len(args) != len(kinds) - has_stream:
         raise TypeError(f"{name} takes {len(kinds) - has_stream} arguments ({len(args)} given)")

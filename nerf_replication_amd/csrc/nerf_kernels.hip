@@ -46,6 +46,8 @@
 #include "nerf_mesh_components.hip.inc"
 // ---- multiresolution hash-grid encoding: nerf_hashgrid_forward / nerf_hashgrid_backward
 #include "nerf_hashgrid.hip.inc"
+// ---- its deterministic table gradient (include/nerf_mi355x_hashgrid.h): nerf_hashgrid_backward_deterministic
+#include "nerf_hashgrid_det.hip.inc"
 // ---- small fused ReLU MLP (include/nerf_mi355x_nn.h): nerf_fused_mlp_forward / nerf_fused_mlp_backward
 #include "nerf_fused_mlp.hip.inc"
 // ---- hash-grid radiance field, the ray-side glue (include/nerf_mi355x_nn.h): nerf_sh4_encode, nerf_field_*

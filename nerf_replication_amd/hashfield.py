@@ -226,7 +226,7 @@ class HashField(nn.Module):
     def _geo(self, x):
         """x [M,3] in [0,1] -> the 16 columns of sigma_net."""
         enc = self.encoder
-        feats = hash_encode(x, enc.embeddings, enc.offsets, enc.per_level_scale, enc.base_resolution)
+        feats = hash_encode(x, enc.embeddings, enc.offsets, enc.per_level_scale, enc.base_resolution, enc.deterministic)
         return fused_mlp(feats, [l.weight for l in self.sigma_net.layers], [l.bias for l in self.sigma_net.layers])
 
     def _rgb(self, cin):

@@ -6,6 +6,10 @@ then alternating rounds (HIP, torch, HIP, torch, ...); the record keeps every sa
 an MI355X and the built library.
 
     python tools/time_hashgrid.py [--log2-batch 20] [--rounds 7] [--inner 10] [--out profiles/hashgrid_timing.json]
+    python tools/time_hashgrid.py --deterministic      # the table gradient alone: fp32 atomics against the exact sum
+
+--deterministic times nerf_hashgrid_backward (table gradient only) and nerf_hashgrid_backward_deterministic alternately in one
+process under the same protocol and writes profiles/hashgrid_deterministic_timing.json; the other record is left alone.
 
 Bytes are counted from the shapes: every (point, level, corner) gathers one row of C floats (forward, and again for the input
 gradient) and adds one row of C floats (table gradient).  The rates are those bytes over the call's time -- whole calls, not
@@ -50,8 +54,12 @@ def main():
     ap.add_argument("--log2-batch", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--inner", type=int, default=10, help="HIP calls per timed window (the torch baseline is timed one call at a time)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "hashgrid_timing.json"))
+    ap.add_argument("--deterministic", action="store_true", help="time the deterministic table gradient against the atomic one")
+    ap.add_argument("--out", default=None, help="default: profiles/hashgrid_timing.json (--deterministic: "
+                                                "profiles/hashgrid_deterministic_timing.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "hashgrid_deterministic_timing.json" if args.deterministic else "hashgrid_timing.json")
     assert torch.cuda.is_available(), "time_hashgrid.py needs a GPU"
     assert args.rounds >= 5
     dev = torch.device("cuda")
@@ -76,6 +84,9 @@ def main():
         _lib.check(lib.nerf_hashgrid_backward(x.data_ptr(), emb.data_ptr(), go.data_ptr(), B, D, C, L, off_c, sc_c, grad_emb.data_ptr(),
                                               grad_x.data_ptr() if want_x else None, st))
 
+    if args.deterministic:
+        return time_deterministic(args, lib, st, hip_backward, dict(x=x, go=go, grad_emb=grad_emb, B=B, D=D, L=L, C=C, s=s, H=H, T=T,
+                                                                     off=off, off_c=off_c, sc_c=sc_c))
     cases = {
         "forward": (hip_forward, lambda: R.forward_f32(x, emb, off, sc)),
         "backward_embeddings": (lambda: hip_backward(False), lambda: R.backward_f32(x, emb, off, sc, go, want_x=False)),
@@ -122,6 +133,54 @@ def main():
             "hip_atomic_TBps": atomic[name] / (hip_ms * 1e-3) / 1e12,
         }
         print(name, json.dumps(rec["cases"][name]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+    print("wrote", args.out)
+
+
+def time_deterministic(args, lib, st, hip_backward, a):
+    """The table gradient alone: the fp32-atomics entry and the deterministic entry, each call with its zero-fill of grad_emb,
+    alternating windows in one process."""
+    x, go, grad_emb, B, D, L, C = a["x"], a["go"], a["grad_emb"], a["B"], a["D"], a["L"], a["C"]
+    rows = a["off"][-1] - a["off"][0]
+    nbytes = int(lib.nerf_hashgrid_deterministic_workspace_bytes(rows, C))
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+
+    def atomic():
+        hip_backward(False)
+
+    def exact():
+        grad_emb.zero_()
+        _lib.check(lib.nerf_hashgrid_backward_deterministic(x.data_ptr(), go.data_ptr(), B, D, C, L, a["off_c"], a["sc_c"],
+                                                            grad_emb.data_ptr(), workspace.data_ptr(), nbytes, st))
+    # agreement (and the warm-up): the exact sum twice gives the same bytes, and the atomic sum lies within its own error of it
+    exact()
+    first = grad_emb.clone()
+    exact()
+    assert torch.equal(first.view(torch.int32), grad_emb.view(torch.int32)), "two deterministic calls differ"
+    atomic()
+    rel = float((grad_emb - first).abs().max() / first.abs().max())
+    assert rel < 1e-4, rel
+    del first
+    for fn in (atomic, exact):
+        fn()
+    torch.cuda.synchronize()
+    ms = {"atomic": [], "deterministic": []}
+    for _ in range(args.rounds):
+        ms["atomic"].append(timed(atomic, args.inner))
+        ms["deterministic"].append(timed(exact, args.inner))
+    ratio = statistics.median(ms["deterministic"]) / statistics.median(ms["atomic"])
+    rec = {"device": torch.cuda.get_device_name(0),
+           "config": {"D": D, "L": L, "C": C, "per_level_scale": a["s"], "base_resolution": a["H"], "log2_hashmap_size": a["T"],
+                      "table_rows": a["off"][-1]},
+           "B": B, "rounds": args.rounds, "calls_per_window": args.inner,
+           "timer": "device events around whole calls (each includes zeroing the table gradient; the deterministic entry also "
+                    "zero-fills its workspace); windows alternate atomic, deterministic",
+           "guard_bits": int(lib.nerf_hashgrid_deterministic_guard_bits(B, D)), "workspace_bytes": nbytes,
+           "agreement": {"deterministic_run_to_run": "bit-equal", "atomic_vs_deterministic_max_rel": rel},
+           "atomic_ms": stats(ms["atomic"]), "deterministic_ms": stats(ms["deterministic"]), "ratio_of_medians": ratio}
+    print(json.dumps({k: rec[k] for k in ("atomic_ms", "deterministic_ms", "ratio_of_medians")}), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(rec, f, indent=1, sort_keys=True)

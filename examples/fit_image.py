@@ -5,12 +5,16 @@ after, and the time per step.  The MLP is eager PyTorch by default (a dozen ATen
 sigmoid included, through nerf.FusedMLP: one HIP kernel forward, one for the gradient chain.
 
     python examples/fit_image.py [--size 512] [--steps 1000] [--batch 65536] [--fused] [--width 64] [--hidden 2] [--out fit.ppm]
-                                 [--deterministic-table]
+                                 [--deterministic-table] [--deterministic] [--digest]
 
 --deterministic-table sums the table gradient exactly (HashEncoder(deterministic=True)): the same bytes whatever order the pixels
 arrive in, at 1.7 times the time of that kernel.  The MLP's weight gradients keep their fp32 atomics (--fused) or rocBLAS's order.
+--deterministic (with --fused) turns on the table and the network together (FusedMLP(deterministic=True)): every gradient of the
+step is an exact, order-independent sum, and two runs end with the same parameters, byte for byte -- the last line printed is then a
+digest of them (--digest prints it for any run).
 """
 import argparse
+import hashlib
 import math
 import os
 import sys
@@ -57,7 +61,12 @@ def main():
     ap.add_argument("--out", default="", help="write the fitted image as a binary PPM")
     ap.add_argument("--deterministic-table", action="store_true",
                     help="sum the hash table's gradient exactly, in an order-independent way (HashEncoder(deterministic=True))")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="with --fused: exact, order-independent sums for the table AND the network's weight and bias gradients")
+    ap.add_argument("--digest", action="store_true", help="print a SHA-256 of the final parameters (--deterministic does it anyway)")
     args = ap.parse_args()
+    if args.deterministic and not args.fused:
+        ap.error("--deterministic needs --fused (the eager MLP's weight gradients are rocBLAS's; --deterministic-table alone works with both)")
     assert torch.cuda.is_available(), "fit_image.py needs a GPU"
     dev = torch.device("cuda")
     torch.manual_seed(0)
@@ -66,9 +75,10 @@ def main():
     coords = (torch.stack([u, v], dim=-1).float() + 0.5) / args.size              # pixel centres in [0, 1]^2
     enc = nerf.HashEncoder(input_dim=2, num_levels=args.levels, level_dim=2, base_resolution=16,
                            log2_hashmap_size=args.log2_hashmap_size, desired_resolution=args.size,
-                           deterministic=args.deterministic_table).to(dev)
+                           deterministic=args.deterministic_table or args.deterministic).to(dev)
     if args.fused:
-        mlp = nerf.FusedMLP(enc.out_dim, 3, width=args.width, n_hidden=args.hidden, output_activation="sigmoid").to(dev)
+        mlp = nerf.FusedMLP(enc.out_dim, 3, width=args.width, n_hidden=args.hidden, output_activation="sigmoid",
+                            deterministic=args.deterministic).to(dev)
         network = mlp
     else:
         dims = [enc.out_dim] + [args.width] * args.hidden
@@ -108,6 +118,11 @@ def main():
             f.write(f"P6 {args.size} {args.size} 255\n".encode())
             f.write((out.clamp(0, 1) * 255 + 0.5).to(torch.uint8).cpu().numpy().tobytes())
         print("wrote", args.out)
+    if args.deterministic or args.digest:
+        digest = hashlib.sha256()
+        for p in list(enc.parameters()) + list(mlp.parameters()):
+            digest.update(p.detach().cpu().numpy().tobytes())
+        print("parameters sha256:", digest.hexdigest())
 
 
 if __name__ == "__main__":

@@ -9,10 +9,12 @@ teacher setup of examples/train_synthetic.py (renders of tests/golden/synthetic_
 --occupancy N rebuilds an N^3 occupancy grid from the field itself (HashField.occupancy_grid) every --refresh-every steps; a grid made
 from fields carries no staleness key, so this loop owns the schedule; the first --occupancy-from steps run unculled.  Prints ms per
 step and the held-out PSNR.  --deterministic-table sums the hash table's gradient exactly and order-independently
-(HashEncoder(deterministic=True)); the two networks' weight gradients keep their fp32 atomics, so a whole step is not yet
-bit-reproducible.
+(HashEncoder(deterministic=True)); the two networks' weight and bias gradients then keep their fp32 atomics.  --deterministic turns
+on the table and both networks together (HashField(deterministic=True)): every sum of the step is exact and order-independent, and
+two runs from one seed end with the same parameters, byte for byte -- the last line printed is then a digest of them.
 """
 import argparse
+import hashlib
 import math
 import os
 import sys
@@ -51,6 +53,9 @@ def main():
     ap.add_argument("--out", default=None, help="write the trained field's state dict here")
     ap.add_argument("--deterministic-table", action="store_true",
                     help="sum the hash table's gradient exactly, in an order-independent way (HashEncoder(deterministic=True))")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="exact, order-independent sums for the table and for both networks' weight and bias gradients "
+                         "(HashField(deterministic=True))")
     args = ap.parse_args()
     if args.occupancy and args.occupancy < 2:
         ap.error("--occupancy needs at least 2 grid points per axis")
@@ -73,9 +78,9 @@ def main():
     torch.manual_seed(0)
     encoder = nerf.HashEncoder(input_dim=3, num_levels=args.levels, level_dim=2, base_resolution=16,
                                log2_hashmap_size=args.log2_hashmap_size, desired_resolution=2048,
-                               deterministic=args.deterministic_table)
+                               deterministic=args.deterministic_table or args.deterministic)
     half = float(args.half_extent)
-    field = nerf.HashField((-half, -half, -half, half, half, half), encoder=encoder).cuda()
+    field = nerf.HashField((-half, -half, -half, half, half, half), encoder=encoder, deterministic=args.deterministic).cuda()
     ren = nerf.HashRenderer(field)                             # the held-out evaluation: never culled
     ren.N_samples = args.samples
     train_ren = nerf.HashRenderer(field)
@@ -116,6 +121,11 @@ def main():
     if args.out:
         torch.save(field.state_dict(), args.out)
         print("saved", args.out)
+    if args.deterministic:
+        digest = hashlib.sha256()
+        for p in field.parameters():
+            digest.update(p.detach().cpu().numpy().tobytes())
+        print("parameters sha256:", digest.hexdigest())
 
 
 if __name__ == "__main__":

@@ -178,6 +178,18 @@ HASHGRID_SIGNATURES = _parse_table(_TABLE_HASHGRID)
 HASHGRID_EXPORTS = tuple(HASHGRID_SIGNATURES)
 _HASHGRID_PROTOS = _protos(HASHGRID_SIGNATURES)
 
+# The exact weight and bias gradients of the fused MLP, one line per entry of include/nerf_mi355x_nn_exact.h (the fifth header of the
+# same library; the four tables above are pinned at their sizes).  tests/test_fused_mlp_exact_cpu.py compares this table with that
+# header.
+_TABLE_NN_EXACT = """
+nerf_fused_mlp_exact_workspace_bytes  i64 : i32 i32 i32 i32
+nerf_fused_mlp_exact_guard_bits  i32 : i64
+nerf_fused_mlp_backward_exact  status : f32* f32* f32* i64 i32 i32 i32 i32 i32 f32*[] f32* f32* f32*[] f32*[] f32* void* i64 stream
+"""
+NN_EXACT_SIGNATURES = _parse_table(_TABLE_NN_EXACT)
+NN_EXACT_EXPORTS = tuple(NN_EXACT_SIGNATURES)
+_NN_EXACT_PROTOS = _protos(NN_EXACT_SIGNATURES)
+
 _lib = None
 
 
@@ -205,7 +217,7 @@ def load():
                 "there is no CPU fallback for the render path")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_PROTOS.items()) + list(_NN_PROTOS.items()) + list(_FIELD_PROTOS.items()) +
-                                  list(_HASHGRID_PROTOS.items())):
+                                  list(_HASHGRID_PROTOS.items()) + list(_NN_EXACT_PROTOS.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.nerf_abi_version() != 3:
@@ -230,9 +242,9 @@ class strided:
 def call(name, *args):
     """Call entry `name` of the library with `args` as its header lists them, minus the stream: tensors (None: NULL) for device
     pointers, numbers for scalars, sequences or ctypes arrays for host arrays.  Every argument is checked against the entry's kinds
-    in SIGNATURES (or, looked up in this order, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
+    in SIGNATURES (or, looked up in this order, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
     is checked (NerfLibraryError with nerf_last_error's text); any other return value comes back as it is."""
-    for table in (SIGNATURES, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES):
+    for table in (SIGNATURES, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES):
         if name in table:
             break
     ret, kinds = table[name]

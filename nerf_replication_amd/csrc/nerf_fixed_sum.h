@@ -3,7 +3,9 @@
 // a signed 64-bit accumulator in units of 2^(emax - 150 - K), K guard bits.  A term joins as the integer fx_quantize() makes of it;
 // integer addition is associative, so the sum is a function of the multiset of terms.  fx_finish() turns the accumulator back into
 // one fp32 value, rounded once.  Nothing here knows about hash grids: any scatter-add of fp32 terms can run the same three passes
-// (exponent max, quantised add, finish).  Plain C++ when compiled without HIP, so a host program can call every function.
+// (exponent max, quantised add, finish).  The fused MLP's exact weight gradients (section 2.13.1, include/nerf_mi355x_nn_exact.h) do,
+// with an emax that bounds the terms' exponents from the column maxima of their two factors (fx_product_exponent) instead of being
+// their maximum.  Plain C++ when compiled without HIP, so a host program can call every function.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -19,6 +21,20 @@ constexpr uint32_t kFxPoison = 255u;           // the exponent field of Inf and 
 
 // the biased exponent field of a term: 0 = zero or subnormal (a null term), 255 = Inf or NaN (a poison term)
 NERF_FX_INLINE uint32_t fx_exponent(uint32_t bits) { return (bits >> 23) & 0xffu; }
+
+// The biased exponent field of fmul(|a|, |b|), a and b given as bit patterns with the sign cleared: the emax of a sum whose every
+// term is a product fmul(u, v) with |u| <= |a| and |v| <= |b| (the fused MLP's weight gradient, DESIGN.md section 2.13.1, where a
+// and b are column maxima).  Rounding is monotonic, so no term's exponent exceeds it.  255 when either is a NaN, when the product
+// overflows, and for Inf * 0; 0 when the product is zero or subnormal (then every term is a null term).
+NERF_FX_INLINE uint32_t fx_product_exponent(uint32_t a_bits, uint32_t b_bits) {
+  float a, b;
+  __builtin_memcpy(&a, &a_bits, sizeof a);
+  __builtin_memcpy(&b, &b_bits, sizeof b);
+  const float p = a * b;                                      // one fp32 multiplication, nothing to contract it into
+  uint32_t bits;
+  __builtin_memcpy(&bits, &p, sizeof bits);
+  return fx_exponent(bits);
+}
 
 // Guard bits for at most `terms` (>= 1, <= 2^35) terms per element: K = min(30, 39 - ceil(log2(terms))).  Every |q| is at most
 // (2^24 - 1) * 2^K, so |sum q| < 2^24 * 2^K * 2^ceil(log2(terms)) <= 2^63: the accumulator cannot overflow.

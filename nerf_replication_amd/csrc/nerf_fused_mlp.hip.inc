@@ -359,6 +359,37 @@ int fm_check(const char* entry, int64_t B, int32_t in_dim, int32_t width, int32_
 
 bool fm_aligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
+// everything nerf_fused_mlp_backward checks before a launch (nerf_fused_mlp_backward_exact checks the same); fills the chain
+// kernel's arguments
+int fm_bwd_check(const char* entry, const float* x, const float* out, const float* grad_out, int64_t B, int32_t in_dim, int32_t width,
+                 int32_t n_hidden, int32_t out_dim, int32_t activation, const float* const weights[], const float* save, float* gsave,
+                 float* const grad_weights[], float* const grad_biases[], float* grad_x, FmBwdArgs& a) {
+  int rc = fm_check(entry, B, in_dim, width, n_hidden, out_dim, activation);
+  if (rc) return rc;
+  if (!x || !grad_out || !weights || !save || !gsave || !grad_weights || !grad_biases || (activation && !out))
+    return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
+  if (!fm_aligned(x, 4) || !fm_aligned(out, 4) || !fm_aligned(grad_out, 4) || !fm_aligned(grad_x, 4) || !fm_aligned(save, 16) ||
+      !fm_aligned(gsave, 16))
+    return fail(NERF_ERR_INVALID_ARG, "%s: x, out, grad_out and grad_x must be aligned to 4 bytes, save and gsave to 16", entry);
+  a = {};
+  for (int i = 0; i <= n_hidden; ++i) {
+    if (!weights[i]) return fail(NERF_ERR_INVALID_ARG, "%s: null parameter pointer", entry);
+    if (!fm_aligned(weights[i], 4) || !fm_aligned(grad_weights[i], 4) || !fm_aligned(grad_biases[i], 4))
+      return fail(NERF_ERR_INVALID_ARG, "%s: misaligned parameter or gradient pointer", entry);
+    a.w[i] = weights[i];
+  }
+  a.out = out; a.grad_out = grad_out; a.save = save; a.gsave = gsave; a.grad_x = grad_x; a.B = B;
+  a.in_dim = in_dim; a.n_hidden = n_hidden; a.out_dim = out_dim; a.activation = activation;
+  return NERF_OK;
+}
+
+// the gradient chain: gsave and grad_x
+int fm_bwd_chain(const FmBwdArgs& a, int32_t width, void* stream) {
+  const dim3 grid((unsigned)((a.B + kFmWgPts - 1) / kFmWgPts)), blk(kFmBlock);
+  hipStream_t st = (hipStream_t)stream;
+  return width == 64 ? NERF_LAUNCH(nerf_fused_mlp_bwd_kernel<64>, grid, blk, st, a) : NERF_LAUNCH(nerf_fused_mlp_bwd_kernel<128>, grid, blk, st, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -405,27 +436,14 @@ int32_t nerf_fused_mlp_forward(const float* x, int64_t B, int32_t in_dim, int32_
 int32_t nerf_fused_mlp_backward(const float* x, const float* out, const float* grad_out, int64_t B, int32_t in_dim, int32_t width,
                                 int32_t n_hidden, int32_t out_dim, int32_t activation, const float* const weights[], const float* save,
                                 float* gsave, float* const grad_weights[], float* const grad_biases[], float* grad_x, void* stream) {
-  const char* entry = "nerf_fused_mlp_backward";
-  int rc = fm_check(entry, B, in_dim, width, n_hidden, out_dim, activation);
+  FmBwdArgs a;
+  int rc = fm_bwd_check("nerf_fused_mlp_backward", x, out, grad_out, B, in_dim, width, n_hidden, out_dim, activation, weights, save, gsave,
+                        grad_weights, grad_biases, grad_x, a);
   if (rc) return rc;
-  if (!x || !grad_out || !weights || !save || !gsave || !grad_weights || !grad_biases || (activation && !out))
-    return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
-  if (!fm_aligned(x, 4) || !fm_aligned(out, 4) || !fm_aligned(grad_out, 4) || !fm_aligned(grad_x, 4) || !fm_aligned(save, 16) ||
-      !fm_aligned(gsave, 16))
-    return fail(NERF_ERR_INVALID_ARG, "%s: x, out, grad_out and grad_x must be aligned to 4 bytes, save and gsave to 16", entry);
-  FmBwdArgs a = {};
-  for (int i = 0; i <= n_hidden; ++i) {
-    if (!weights[i]) return fail(NERF_ERR_INVALID_ARG, "%s: null parameter pointer", entry);
-    if (!fm_aligned(weights[i], 4) || !fm_aligned(grad_weights[i], 4) || !fm_aligned(grad_biases[i], 4))
-      return fail(NERF_ERR_INVALID_ARG, "%s: misaligned parameter or gradient pointer", entry);
-    a.w[i] = weights[i];
-  }
-  a.out = out; a.grad_out = grad_out; a.save = save; a.gsave = gsave; a.grad_x = grad_x; a.B = B;
-  a.in_dim = in_dim; a.n_hidden = n_hidden; a.out_dim = out_dim; a.activation = activation;
-  const dim3 grid((unsigned)((B + kFmWgPts - 1) / kFmWgPts)), blk(kFmBlock);
+  rc = fm_bwd_chain(a, width, stream);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  rc = width == 64 ? NERF_LAUNCH(nerf_fused_mlp_bwd_kernel<64>, grid, blk, st, a) : NERF_LAUNCH(nerf_fused_mlp_bwd_kernel<128>, grid, blk, st, a);
-  if (rc) return rc;
+  const dim3 blk(kFmBlock);
   // weight gradients: dW_i += dz_i^T in_i, one nerf_wgrad launch per layer that wants them; bias gradients: db_i += sum_p dz_i, one
   // launch for all layers
   const int64_t plane = B * width;

@@ -50,6 +50,8 @@
 #include "nerf_hashgrid_det.hip.inc"
 // ---- small fused ReLU MLP (include/nerf_mi355x_nn.h): nerf_fused_mlp_forward / nerf_fused_mlp_backward
 #include "nerf_fused_mlp.hip.inc"
+// ---- its exact weight and bias gradients (include/nerf_mi355x_nn_exact.h): nerf_fused_mlp_backward_exact
+#include "nerf_fused_mlp_exact.hip.inc"
 // ---- hash-grid radiance field, the ray-side glue (include/nerf_mi355x_nn.h): nerf_sh4_encode, nerf_field_*
 #include "nerf_hashfield.hip.inc"
 

@@ -1,12 +1,17 @@
 """Small fused ReLU MLP on the HIP kernels of csrc/nerf_fused_mlp.hip.inc (include/nerf_mi355x_nn.h).
 
-    fused_mlp(x, weights, biases, output_activation=None)      autograd function over nn.Linear-shaped parameter lists
-    FusedMLP(in_dim, out_dim, width=64, n_hidden=2, output_activation=None)
-    ImageFitNetwork(D=4, W=128, uv_encoder=None, chunk_size=16384)  <- the reference's src/models/img_fit/network.py Network
+    fused_mlp(x, weights, biases, output_activation=None, deterministic=False)   autograd function over nn.Linear-shaped lists
+    FusedMLP(in_dim, out_dim, width=64, n_hidden=2, output_activation=None, deterministic=False)
+    ImageFitNetwork(D=4, W=128, uv_encoder=None, chunk_size=16384, deterministic=False)
+                                                               <- the reference's src/models/img_fit/network.py Network
 
 One kernel runs the whole network, one more the gradient chain, and one weight-gradient launch per layer follows.  fp32 only (other
 dtypes raise NotImplementedError); CPU tensors raise NerfLibraryError: there is no eager fallback.  The kernels read the parameter
 tensors themselves at every call, so an in-place optimizer step is seen by the next call.  Double backward is not supported and raises.
+
+deterministic=True sums the weight and bias gradients exactly in 64-bit fixed point (nerf_fused_mlp_backward_exact,
+include/nerf_mi355x_nn_exact.h) instead of with fp32 atomics: the same bytes from run to run and under any
+permutation of the rows.  The forward, the gradient chain and the input gradient are the same kernels either way.
 """
 import sys
 import types
@@ -16,6 +21,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from .hashgrid import _flag
 
 WIDTHS = (64, 128)
 MAX_IN_DIM = 256
@@ -59,8 +65,9 @@ def _check(x, weights, biases, output_activation):
 
 class _FusedMLP(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, activation, n_layers, want_grad, *params):
-        # x [B, in_dim] (1 <= B <= MAX_ROWS), params = the weights then the biases; everything validated by fused_mlp()
+    def forward(ctx, x, activation, n_layers, want_grad, deterministic, *params):
+        # x [B, in_dim] (1 <= B <= MAX_ROWS), params = the weights then the biases; everything validated by fused_mlp().
+        # deterministic: which entry sums the parameter gradients
         weights = [w.detach().contiguous() for w in params[:n_layers]]
         biases = [b.detach().contiguous() for b in params[n_layers:]]
         x = x.detach().contiguous()
@@ -74,6 +81,7 @@ class _FusedMLP(torch.autograd.Function):
         if save is not None:
             ctx.save_for_backward(x, out, save, *weights)
             ctx.activation = activation
+            ctx.deterministic = deterministic
         return out
 
     @staticmethod
@@ -87,23 +95,33 @@ class _FusedMLP(torch.autograd.Function):
             raise NotImplementedError(f"fused_mlp: fp32 only (the output gradient is {grad.dtype})")
         grad = grad.contiguous()
         need = ctx.needs_input_grad
-        need_w, need_b = need[4:4 + n_layers], need[4 + n_layers:]
+        need_w, need_b = need[5:5 + n_layers], need[5 + n_layers:]
         # the entry accumulates into zeroed buffers
         grad_w = [torch.zeros_like(w) if need_w[i] else None for i, w in enumerate(weights)]
         grad_b = [torch.zeros(w.shape[0], dtype=torch.float32, device=x.device) if need_b[i] else None for i, w in enumerate(weights)]
         grad_x = torch.empty_like(x) if need[0] else None
         gsave = torch.empty(_lib.call("nerf_fused_mlp_grad_floats", B, width, n_hidden, out_dim), dtype=torch.float32, device=x.device)
-        _lib.call("nerf_fused_mlp_backward", x, out, grad, B, in_dim, width, n_hidden, out_dim, ctx.activation, weights, save, gsave,
-                  grad_w, grad_b, grad_x)
-        return (grad_x, None, None, None, *grad_w, *grad_b)
+        if ctx.deterministic and (any(need_w) or any(need_b)):
+            nbytes = _lib.call("nerf_fused_mlp_exact_workspace_bytes", in_dim, width, n_hidden, out_dim)
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=x.device)      # the entry zero-fills it
+            _lib.call("nerf_fused_mlp_backward_exact", x, out, grad, B, in_dim, width, n_hidden, out_dim, ctx.activation, weights, save,
+                      gsave, grad_w, grad_b, grad_x, workspace, nbytes)
+        else:
+            _lib.call("nerf_fused_mlp_backward", x, out, grad, B, in_dim, width, n_hidden, out_dim, ctx.activation, weights, save, gsave,
+                      grad_w, grad_b, grad_x)
+        return (grad_x, None, None, None, None, *grad_w, *grad_b)
 
 
-def fused_mlp(x, weights, biases, output_activation=None):
+def fused_mlp(x, weights, biases, output_activation=None, deterministic=False):
     """x [..., in_dim] through relu(W_i . + b_i) for the hidden layers and act(W_out . + b_out) -> [..., out_dim].  `weights` and
     `biases` list the hidden layers in order, then the output layer, as nn.Linear holds them ([out, in] and [out]); the hidden width
     (64 or 128), the number of hidden layers (1..8) and out_dim (1..16) are inferred from the shapes.  output_activation: None or
     "sigmoid".  Gradients are computed for exactly those of x, weights and biases that require them (the one of x so that an
-    encoder in front gets its own)."""
+    encoder in front gets its own).
+    deterministic=True: the gradients with respect to `weights` and `biases` are the exact, order-independent sums (the module's
+    docstring).  A batch above MAX_ROWS still runs in chunks: each chunk's sum is exact, and autograd adds the chunks' gradients in
+    fp32, in a fixed order -- reproducible from run to run, but no longer independent of how the rows fall into chunks."""
+    _flag(deterministic, "fused_mlp")
     weights, biases = list(weights), list(biases)
     in_dim, width, n_hidden, out_dim, activation = _check(x, weights, biases, output_activation)
     prefix = list(x.shape[:-1])
@@ -112,16 +130,17 @@ def fused_mlp(x, weights, biases, output_activation=None):
         return x.new_zeros(prefix + [out_dim])
     # (Function.forward runs with grad mode off: whether anything will be differentiated is decided here)
     want_grad = torch.is_grad_enabled() and any(t.requires_grad for t in [x] + weights + biases)
-    outs = [_FusedMLP.apply(rows[i:i + MAX_ROWS], activation, n_hidden + 1, want_grad, *weights, *biases)
+    outs = [_FusedMLP.apply(rows[i:i + MAX_ROWS], activation, n_hidden + 1, want_grad, deterministic, *weights, *biases)
             for i in range(0, rows.shape[0], MAX_ROWS)]
     return (outs[0] if len(outs) == 1 else torch.cat(outs, 0)).view(prefix + [out_dim])
 
 
 class FusedMLP(nn.Module):
     """in_dim -> n_hidden x (Linear(width) + ReLU) -> Linear(out_dim) [-> sigmoid], run by fused_mlp.  The parameters are plain
-    nn.Linear modules with PyTorch's default init: state-dict keys layers.{i}.weight / layers.{i}.bias."""
+    nn.Linear modules with PyTorch's default init: state-dict keys layers.{i}.weight / layers.{i}.bias.  `deterministic` is a plain
+    attribute, handed to fused_mlp at every call."""
 
-    def __init__(self, in_dim, out_dim, width=64, n_hidden=2, output_activation=None):
+    def __init__(self, in_dim, out_dim, width=64, n_hidden=2, output_activation=None, deterministic=False):
         super().__init__()
         if width not in WIDTHS or not 1 <= n_hidden <= MAX_HIDDEN or not 1 <= in_dim <= MAX_IN_DIM or not 1 <= out_dim <= MAX_OUT_DIM \
                 or output_activation not in ACTIVATIONS:
@@ -130,11 +149,12 @@ class FusedMLP(nn.Module):
                              f"{out_dim}, {output_activation!r})")
         self.in_dim, self.out_dim, self.width, self.n_hidden = in_dim, out_dim, width, n_hidden
         self.output_activation = output_activation
+        self.deterministic = _flag(deterministic, "FusedMLP")
         self.layers = nn.ModuleList([nn.Linear(in_dim, width)] + [nn.Linear(width, width) for _ in range(n_hidden - 1)] +
                                     [nn.Linear(width, out_dim)])
 
     def forward(self, x):
-        return fused_mlp(x, [l.weight for l in self.layers], [l.bias for l in self.layers], self.output_activation)
+        return fused_mlp(x, [l.weight for l in self.layers], [l.bias for l in self.layers], self.output_activation, self.deterministic)
 
 
 def frequency_encode(x, freq):
@@ -163,10 +183,12 @@ class ImageFitNetwork(nn.Module):
     uv_encoder is a dict in the reference's config vocabulary: {"type": "frequency", "input_dim": 2, "freq": 10} (the default, 42
     channels) or {"type": "cuda_hashgrid", ...HashEncoder's arguments}.  The frequency encoding is computed in eager torch: it is 42
     floats per pixel, and the C positional-encoding entry is 3-D only.  The hash grid is called with normalize=False: uv is already in
-    [0, 1].  output_layer's nn.Sigmoid exists for key and structure parity and is not called: the kernel applies the sigmoid."""
+    [0, 1].  output_layer's nn.Sigmoid exists for key and structure parity and is not called: the kernel applies the sigmoid.
+    deterministic (a plain attribute) is fused_mlp's flag; a hash-grid encoder keeps its own, given in the uv_encoder dict."""
 
-    def __init__(self, D=4, W=128, uv_encoder=None, chunk_size=16384):
+    def __init__(self, D=4, W=128, uv_encoder=None, chunk_size=16384, deterministic=False):
         super().__init__()
+        self.deterministic = _flag(deterministic, "ImageFitNetwork")
         enc = dict(uv_encoder) if uv_encoder is not None else {"type": "frequency", "input_dim": 2, "freq": 10}
         kind = enc.pop("type", None)
         if kind == "frequency":
@@ -187,7 +209,8 @@ class ImageFitNetwork(nn.Module):
     def render(self, uv, batch=None):
         layers = list(self.backbone_layer) + [self.output_layer[0]]
         encoding = self.uv_encoder(uv, normalize=False) if isinstance(self.uv_encoder, nn.Module) else self.uv_encoder(uv)
-        rgb = fused_mlp(encoding, [l.weight for l in layers], [l.bias for l in layers], output_activation="sigmoid")
+        rgb = fused_mlp(encoding, [l.weight for l in layers], [l.bias for l in layers], output_activation="sigmoid",
+                        deterministic=self.deterministic)
         return {"rgb": rgb}
 
     def batchify(self, uv, batch):

@@ -25,7 +25,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .fused_mlp import MAX_ROWS, FusedMLP, fused_mlp
-from .hashgrid import EPS, HashEncoder, _as_offsets, hash_encode, level_scales
+from .hashgrid import EPS, HashEncoder, _as_offsets, _flag, hash_encode, level_scales
 
 GEO_DIM = 16                        # columns of the geometry feature: what the glue kernels move
 SH_DIM = 16                         # real spherical harmonics of degree 0..3
@@ -180,10 +180,13 @@ class HashField(nn.Module):
     bbox: 6 numbers, min xyz then max xyz; kept as the persistent fp32 buffer `wbounds`, so a checkpoint carries it.  encoder: a 3-D
     HashEncoder (default: L=16, C=2, H=16, T=19, desired_resolution=2048: 32 channels).  State-dict keys: encoder.embeddings,
     sigma_net.layers.{i}.{weight,bias}, color_net.layers.{i}.{weight,bias}, wbounds -- 11 parameter tensors with the defaults, one
-    FusedAdam group."""
+    FusedAdam group.  deterministic=True sets the flag on both networks (FusedMLP.deterministic: exact, order-independent weight and
+    bias gradients) and on the encoder when it is built here; an encoder that is passed in keeps its own.  With all three a training
+    step is the same bytes from run to run."""
 
-    def __init__(self, bbox, encoder=None, geo_dim=GEO_DIM, width=64, sigma_hidden=1, color_hidden=2):
+    def __init__(self, bbox, encoder=None, geo_dim=GEO_DIM, width=64, sigma_hidden=1, color_hidden=2, deterministic=False):
         super().__init__()
+        _flag(deterministic, "HashField")
         if geo_dim != GEO_DIM:
             raise ValueError(f"HashField: geo_dim = {GEO_DIM} is built (the glue kernels move 16-column rows), got {geo_dim!r}")
         try:
@@ -194,12 +197,12 @@ class HashField(nn.Module):
             raise ValueError(f"bbox must hold 6 finite numbers (min xyz, max xyz) with a positive extent on every axis, got {bbox!r}")
         if encoder is None:
             encoder = HashEncoder(input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=19,
-                                  desired_resolution=2048)
+                                  desired_resolution=2048, deterministic=deterministic)
         if not isinstance(encoder, HashEncoder) or encoder.input_dim != 3:
             raise TypeError("HashField: encoder must be a HashEncoder with input_dim = 3")
         self.encoder = encoder
-        self.sigma_net = FusedMLP(encoder.out_dim, GEO_DIM, width, sigma_hidden)
-        self.color_net = FusedMLP(GEO_DIM + SH_DIM, 3, width, color_hidden)
+        self.sigma_net = FusedMLP(encoder.out_dim, GEO_DIM, width, sigma_hidden, deterministic=deterministic)
+        self.color_net = FusedMLP(GEO_DIM + SH_DIM, 3, width, color_hidden, deterministic=deterministic)
         # Compositing takes relu(sigma): a field whose density starts negative everywhere renders the background, has a gradient of
         # exactly zero and never trains.  With embeddings near zero the initial density is one constant of random sign, so the bias
         # of the density column starts at 1 -- a uniform fog, whose gradient reaches every parameter.
@@ -227,10 +230,12 @@ class HashField(nn.Module):
         """x [M,3] in [0,1] -> the 16 columns of sigma_net."""
         enc = self.encoder
         feats = hash_encode(x, enc.embeddings, enc.offsets, enc.per_level_scale, enc.base_resolution, enc.deterministic)
-        return fused_mlp(feats, [l.weight for l in self.sigma_net.layers], [l.bias for l in self.sigma_net.layers])
+        return fused_mlp(feats, [l.weight for l in self.sigma_net.layers], [l.bias for l in self.sigma_net.layers],
+                         deterministic=self.sigma_net.deterministic)
 
     def _rgb(self, cin):
-        return fused_mlp(cin, [l.weight for l in self.color_net.layers], [l.bias for l in self.color_net.layers])
+        return fused_mlp(cin, [l.weight for l in self.color_net.layers], [l.bias for l in self.color_net.layers],
+                         deterministic=self.color_net.deterministic)
 
     def _check_fp32(self):
         for name, p in self.named_parameters():

@@ -7,6 +7,14 @@ keeps every sample.  Then the step time of examples/fit_image.py with and withou
 Writes profiles/fused_mlp_timing.json.  Needs an MI355X and the built library.
 
     python tools/time_fused_mlp.py [--rounds 7] [--inner 10] [--fit-steps 300] [--fit-rounds 3] [--out profiles/fused_mlp_timing.json]
+    python tools/time_fused_mlp.py --deterministic [--fit-rounds 9]         # writes profiles/fused_mlp_deterministic_timing.json
+
+--deterministic times the exact, order-independent weight and bias gradients (FusedMLP(deterministic=True))
+against the default path, which that mode does not touch: the "train" call of both workloads at both batch sizes, flag off and flag
+on alternately in one process under the protocol above, then a 4096-ray HashField training step (192 samples per ray, the default
+encoder; table and networks deterministic together) against the default one, and examples/fit_image.py --fused --deterministic
+beside the eager MLP for --fit-rounds alternating pairs: the PSNRs, and whether the deterministic runs end with the same parameters.
+The other record is left alone.
 
 FLOP are counted from the shapes.  "useful": 2 B n_out n_in per layer (forward), the same again for the transposed products the
 backward needs (all layers but the first, plus the first when x wants its gradient) and for the weight gradients.  "executed": what
@@ -66,16 +74,115 @@ def fit_image_ms(fused, steps):
     return float(m.group(2)), float(m.group(1))
 
 
+def fit_image_run(flags, steps):
+    """One fresh-process run of examples/fit_image.py -> (ms per step, PSNR, digest of the final parameters)."""
+    out = subprocess.run([sys.executable, os.path.join(REPO, "examples", "fit_image.py"), "--steps", str(steps)] + flags,
+                         capture_output=True, text=True, check=True).stdout
+    m = re.search(r"PSNR after \d+ steps: ([\d.]+) dB\s+\(([\d.]+) ms per step", out)
+    return float(m.group(2)), float(m.group(1)), re.search(r"parameters sha256: (\w+)", out).group(1)
+
+
+def deterministic(args):
+    """The --deterministic record: flag on against flag off."""
+    from nerf_replication_amd.training import FusedAdam, train_step
+    dev = torch.device("cuda")
+    rec = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "calls_per_window": args.inner,
+           "timer": "device events around whole calls (allocations, the workspace and the zeroing of gradients included); rounds "
+                    "alternate flag off and flag on in one process",
+           "baseline": "the same module with deterministic=False: fp32 atomic sums, the path this mode does not touch",
+           "cases": {}}
+    for name, (in_dim, width, n_hidden, out_dim, act) in WORKLOADS.items():
+        torch.manual_seed(0)
+        nets = {False: nerf.FusedMLP(in_dim, out_dim, width, n_hidden, act).to(dev)}
+        nets[True] = nerf.FusedMLP(in_dim, out_dim, width, n_hidden, act, deterministic=True).to(dev)
+        nets[True].load_state_dict(nets[False].state_dict())
+        for log2_b in (16, 20):
+            B = 1 << log2_b
+            gen = torch.Generator(device=dev).manual_seed(log2_b)
+            x = torch.rand(B, in_dim, device=dev, generator=gen).requires_grad_(True)
+            go = torch.randn(B, out_dim, device=dev, generator=gen)
+
+            def train(net):
+                x.grad = None
+                net.zero_grad(set_to_none=True)
+                net(x).backward(go)
+            grads = {}
+            for flag in (False, True):                 # the warm-up of both, and: the two sides compute the same thing
+                train(nets[flag])
+                grads[flag] = [p.grad.clone() for p in nets[flag].parameters()]
+            train(nets[True])
+            same = all(torch.equal(a, p.grad) for a, p in zip(grads[True], nets[True].parameters()))
+            err = max(float((a - b).abs().max() / b.abs().max().clamp_min(1e-30)) for a, b in zip(grads[False], grads[True]))
+            assert same and err < 1e-3, (same, err)
+            torch.cuda.synchronize()
+            ms = {False: [], True: []}
+            for _ in range(args.rounds):
+                for flag in (False, True):
+                    ms[flag].append(timed(lambda: train(nets[flag]), args.inner))
+            case = {"default_ms": stats(ms[False]), "deterministic_ms": stats(ms[True]),
+                    "ratio_median": statistics.median(ms[True]) / statistics.median(ms[False]),
+                    "guard_bits": int(nerf._lib.call("nerf_fused_mlp_exact_guard_bits", B)),
+                    "workspace_bytes": int(nerf._lib.call("nerf_fused_mlp_exact_workspace_bytes", in_dim, width, n_hidden, out_dim)),
+                    "parameter_grad_max_rel_between_the_two": err, "deterministic_run_to_run_equal": same}
+            rec["cases"][f"{name}/B=2^{log2_b}/train"] = case
+            print(f"{name}/B=2^{log2_b}/train", json.dumps(case), flush=True)
+            del x, go
+    # a 4096-ray HashField step, the whole field deterministic against the default
+    rays = torch.Generator(device=dev).manual_seed(3)
+    o = torch.nn.functional.normalize(torch.randn(4096, 3, device=dev, generator=rays), dim=1) * 4.0
+    d = torch.nn.functional.normalize(torch.randn(4096, 3, device=dev, generator=rays) * 0.5 - o, dim=1)
+    colors = torch.rand(4096, 3, device=dev, generator=rays)
+    steps = {}
+    for flag in (False, True):
+        torch.manual_seed(0)
+        field = nerf.HashField((-2.0, -2.0, -2.0, 2.0, 2.0, 2.0), deterministic=flag).to(dev)
+        ren = nerf.HashRenderer(field)
+        opt = FusedAdam(field.parameters(), lr=1e-2, eps=1e-15, clip_value=40.0)
+        steps[flag] = lambda ren=ren, opt=opt: train_step(ren, opt, o, d, colors)
+        steps[flag]()
+    torch.cuda.synchronize()
+    ms = {False: [], True: []}
+    for _ in range(args.rounds):
+        for flag in (False, True):
+            ms[flag].append(timed(steps[flag], args.inner))
+    rec["hashfield_step"] = {"rays": 4096, "samples_per_ray": 192, "what": "training.train_step on a default HashField with FusedAdam",
+                             "default_ms": stats(ms[False]), "deterministic_ms": stats(ms[True]),
+                             "difference_ms_median": statistics.median(ms[True]) - statistics.median(ms[False])}
+    print("hashfield_step", json.dumps(rec["hashfield_step"]), flush=True)
+    fit = {"eager": [], "deterministic": []}
+    for _ in range(args.fit_rounds):
+        fit["eager"].append(fit_image_run(["--digest"], args.fit_steps))
+        fit["deterministic"].append(fit_image_run(["--fused", "--deterministic"], args.fit_steps))
+    rec["fit_image"] = {"steps": args.fit_steps, "pairs": args.fit_rounds, "what": "examples/fit_image.py, a fresh process per run, the eager "
+                        "MLP and --fused --deterministic alternately, one seed",
+                        "psnr_eager_dB": [r[1] for r in fit["eager"]], "psnr_deterministic_dB": [r[1] for r in fit["deterministic"]],
+                        "eager_ms": stats([r[0] for r in fit["eager"]]), "deterministic_ms": stats([r[0] for r in fit["deterministic"]]),
+                        "distinct_final_parameters_eager": len({r[2] for r in fit["eager"]}),
+                        "distinct_final_parameters_deterministic": len({r[2] for r in fit["deterministic"]})}
+    print("fit_image", json.dumps(rec["fit_image"]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--inner", type=int, default=10, help="calls per timed window")
     ap.add_argument("--fit-steps", type=int, default=300)
     ap.add_argument("--fit-rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "fused_mlp_timing.json"))
+    ap.add_argument("--deterministic", action="store_true",
+                    help="time deterministic=True against the default path instead (writes profiles/fused_mlp_deterministic_timing.json)")
+    ap.add_argument("--out", default=None, help="default: profiles/fused_mlp_timing.json (--deterministic: "
+                                                "profiles/fused_mlp_deterministic_timing.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "fused_mlp_deterministic_timing.json" if args.deterministic else "fused_mlp_timing.json")
     assert torch.cuda.is_available(), "time_fused_mlp.py needs a GPU"
     assert args.rounds >= 5
+    if args.deterministic:
+        return deterministic(args)
     dev = torch.device("cuda")
     rec = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "calls_per_window": args.inner, "peak_fp32_mfma_TFLOPs": PEAK_TFLOPS,
            "timer": "device events around whole module calls (allocations and zeroing of gradients included); rounds alternate fused and eager",

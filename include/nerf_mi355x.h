@@ -126,6 +126,14 @@ int32_t nerf_mlp_forward_rays_for_compositing(const float* rays_o, const float* 
                                               int64_t t_ray_stride, int64_t n_rays, int32_t n_samples,
                                               const void* packed, float* raw, int32_t precision, void* stream);
 
+/* Dead k-step skipping (NERF_PREC_F32, the four inference entries above; exact): inside a 32-point tile, a step of a layer's
+ * reduction whose two input features are zero at all 32 points -- a ReLU output that is off tile-wide -- would add
+ * fma(w, +0, acc) = acc to every output, so the kernel does not issue its matrix instructions.  `raw` is bit-identical for
+ * finite weights (a NaN / Inf weight times such a zero would have been NaN: a checkpoint that renders NaN anyway may do so in
+ * fewer pixels).  How many steps are skipped is scene-dependent (17-30 % of them on the synthetic benchmark scene, close to
+ * none with white-noise weights).  NERF_DEAD_KSTEP_SKIP=0 in the environment makes the kernel issue every instruction, for
+ * A/B comparisons; the training entries below never skip. */
+
 /* ---- training path (BASELINE config 3; fp32 only) ------------------------------------------------
  * Forward with activation save: as nerf_mlp_forward_rays, and additionally stores, row-major per
  * point (P = n_rays*n_samples; floats): pe [P,64] and dpe [P,32] (encodings in the reference's channel

@@ -95,6 +95,8 @@ struct MlpArgs {
                            // hierarchical render / training step, whose colour is never read (volume_renderer.py:335 / SURVEY F6)
   const float* fold;       // fp32 kernels: packed + kOffFold, the fold region of `packed` (nerf_layout.h kFold*), written by
                            // nerf_pack_model (launch_mlp)
+  int skip_dead_ksteps;    // fp32 inference instances: a k-step whose ReLU-output activation register is zero in all 64 lanes
+                           // issues no MFMAs (gemm_tiles KSKIP; bit-identical raw).  launch_mlp: 1 unless NERF_DEAD_KSTEP_SKIP=0
 };
 
 // Training forward keeps what the backward pass needs, row-major per point (the layout the weight-

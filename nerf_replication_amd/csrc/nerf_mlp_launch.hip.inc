@@ -19,6 +19,14 @@ bool dead_tile_list_available(long long P, int precision) {
   return want && (precision == NERF_PREC_F32 || precision == NERF_PREC_F32X) && P % 32 == 0 && P / 32 <= 0x7fffffffLL;
 }
 
+// ------------------------------------------------------------------------------------ dead k-step skipping (fp32 inference instances)
+// On unless NERF_DEAD_KSTEP_SKIP=0: with 0 the kernel issues every MFMA (the A/B reference of the bit-identity tests, and the
+// price of the decision by itself).  Read per launch, like the switch above.
+int dead_kstep_skip_wanted() {
+  const char* env = getenv("NERF_DEAD_KSTEP_SKIP");
+  return !(env && env[0] == '0');
+}
+
 }  // namespace
 
 extern "C" {
@@ -72,6 +80,7 @@ static int launch_mlp(const MlpArgs& a_in, bool ray_mode, bool save, int precisi
   // density_only (ray mode): every precision has an instance that stops after the sigma head
   const MlpKernel k = f->inst[!ray_mode ? 3 : a.density_only ? 0 : a.skip_dead_colour ? 1 : 2];
   if (precision == NERF_PREC_F32) a.fold = a.packed + nerf::kOffFold;
+  a.skip_dead_ksteps = dead_kstep_skip_wanted();
   if (f->persistent) return launch(f->name, k, dim3(persistent_blocks(a.n_points, f->wg_pts)), dim3(f->threads), st, a);
   const long long blocks = (a.n_points + f->wg_pts - 1) / f->wg_pts;
   if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s: too many points for one launch", entry);

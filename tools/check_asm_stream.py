@@ -27,6 +27,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 # flags (nerf_kernels_x.hip says why); each unit is checked on the flags IT is built with.
 XFLAGS = "-mllvm -amdgpu-mfma-vgpr-form=1"
 CSRC = os.path.join(REPO, "nerf_replication_amd", "csrc")
+MAX_CNT = 64       # above every count an s_waitcnt can encode (vmcnt: 6 bits, lgkmcnt: 4 bits)
 UNITS = [{"src": os.path.join(CSRC, "nerf_kernels.hip"), "x": False}, {"src": os.path.join(CSRC, "nerf_kernels_x.hip"), "x": True}]
 
 
@@ -84,40 +85,49 @@ def check(K):
     loads = [idx for idx in range(len(ins)) if asm_load(idx)]
     hazards = []
 
-    def walk(idx, dst, younger, depth, seen, lds):
-        """Follow the control flow from instruction idx until a wait covers the load (at most `cnt` younger memory
-        operations outstanding); report every instruction on the way that touches dst."""
-        steps = 0
+    def walk(start, dst, lds):
+        """Follow EVERY control-flow path from instruction `start` until a wait covers the load (at most `cnt` younger
+        memory operations outstanding); report every instruction on the way that touches dst.  Both sides of every
+        conditional branch are followed, however many lie between a load and its wait (the k-step skipping of the fp32
+        inference kernels puts up to four more there): the states (instruction, younger operations) are memoised, and
+        `younger` never needs to exceed the largest wait count of the kernel, so the walk is finite without a depth limit.
+        A path that leaves the kernel's code without a wait is reported, not dropped."""
         pat = r"lgkmcnt\((\d+)\)" if lds else r"vmcnt\((\d+)\)"
-        while idx < len(ins) and steps < 6000:
-            steps += 1
-            if (idx, younger) in seen:
-                return
-            seen.add((idx, younger))
-            l = ins[idx][1]
-            m = re.search(pat, l) if l.startswith("s_waitcnt") else None
-            if m and younger >= int(m.group(1)):
-                return                                            # covered on this path
-            touched = vregs(l.split(",")[0]) if asm_load(idx) else vregs(l)
-            if touched & dst:
-                hazards.append(("touched before its wait", ld_text, l))
-                return
-            if (is_lds(l) if lds else is_vmem(l)):
-                younger += 1
-            if l.startswith("s_endpgm"):
-                if lds:
-                    hazards.append(("never waited for before the end of the program", ld_text, l))
-                return
-            if l.startswith("s_branch"):
-                idx = label_at[l.split()[1]]
-                continue
-            if l.startswith("s_cbranch") and depth < 12:
-                walk(label_at[l.split()[1]], dst, younger, depth + 1, seen, lds)
-            idx += 1
+        seen, todo = set(), [(start, 0)]
+        while todo:
+            idx, younger = todo.pop()
+            while True:
+                if idx >= len(ins):
+                    hazards.append(("path runs off the end of the kernel without a wait", ld_text, ""))
+                    break
+                younger = min(younger, MAX_CNT)                   # (every count a wait can ask for is <= MAX_CNT)
+                if (idx, younger) in seen:
+                    break
+                seen.add((idx, younger))
+                l = ins[idx][1]
+                m = re.search(pat, l) if l.startswith("s_waitcnt") else None
+                if m and younger >= int(m.group(1)):
+                    break                                         # covered on this path
+                touched = vregs(l.split(",")[0]) if asm_load(idx) else vregs(l)
+                if touched & dst:
+                    hazards.append(("touched before its wait", ld_text, l))
+                    break
+                if (is_lds(l) if lds else is_vmem(l)):
+                    younger += 1
+                if l.startswith("s_endpgm"):
+                    if lds:
+                        hazards.append(("never waited for before the end of the program", ld_text, l))
+                    break
+                if l.startswith("s_branch"):
+                    idx = label_at[l.split()[1]]
+                    continue
+                if l.startswith("s_cbranch"):
+                    todo.append((label_at[l.split()[1]], younger))
+                idx += 1
 
     for ld in loads:
         ld_text = ins[ld][1]
-        walk(ld + 1, vregs(ld_text.split(",")[0]), 0, 0, set(), bool(asm_lds_load(ld)))
+        walk(ld + 1, vregs(ld_text.split(",")[0]), bool(asm_lds_load(ld)))
     return len(loads), hazards
 
 

@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""CPU probe (torch, no GPU): how many k-steps of the fp32 render MLP multiply zeros tile-wide.
+
+The fp32 inference kernel (csrc/nerf_mlp_f32.hip.inc, gemm_tiles KSKIP) skips the MFMAs of a k-step whose activation register
+is zero in all 64 lanes: both features of the pair {act_feat(t, r, 0), act_feat(t, r, 1)} (csrc/nerf_layout.h) are off at all
+32 points of the tile.  This tool evaluates the coarse and the fine network of a checkpoint with the oracle on a seeded sample of
+rays of the bench frame (800 x 800, camera_pose(40)), cuts the samples of each ray into the kernel's 32-point tiles, and prints
+per ReLU-fed GEMM the fraction of dead k-steps and the MFMAs per tile that remain.  That is the prediction a measured A/B of
+NERF_DEAD_KSTEP_SKIP is set against, and what corrects bench.py's roofline figures (which count every MFMA as issued).
+
+    python tools/dead_ksteps.py --family base --rays 768
+"""
+import argparse
+import json
+import os
+import re
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+import nerf_oracle as orc            # noqa: E402
+from pack_reference import act_feat  # noqa: E402  (the pairing is taken from the layout's statement, not restated)
+
+TILE = 32
+# Every GEMM of a tile in issue order: (name, k-steps, output tiles, the ReLU output it consumes or None, colour branch?).
+# One k-step is one MFMA per output tile.  Training keeps the feature GEMM; the inference instances fold it into the views layer.
+GEMMS = (
+    ("L0 (PE)", 32, 8, None, False),
+    ("L1 (h0)", 128, 8, "h0", False), ("L2 (h1)", 128, 8, "h1", False), ("L3 (h2)", 128, 8, "h2", False),
+    ("L4 (h3)", 128, 8, "h3", False),
+    ("L5 (PE)", 32, 8, None, False), ("L5 (h4)", 128, 8, "h4", False),
+    ("L6 (h5)", 128, 8, "h5", False), ("L7 (h6)", 128, 8, "h6", False),
+    ("views, folded (h7)", 128, 4, "h7", True), ("views (dir PE)", 16, 4, None, True),
+)
+
+
+def kstep_pairs():
+    """[128, 2]: the two features one activation register holds, k-step s = 16 t + r (register r of input tile t)."""
+    return torch.tensor([[act_feat(s >> 4, s & 15, 0), act_feat(s >> 4, s & 15, 1)] for s in range(128)])
+
+
+def layout_mfmas():
+    """(trunk, colour branch) MFMAs of a tile as csrc/nerf_layout.h lays the two weight streams out: every 1-KiB block
+    (256 floats) feeds four MFMAs.  Read from the header's own constants."""
+    env = {"wsize": lambda ksteps, ntiles: (ksteps // 4) * ntiles * 64 * 4}
+    text = open(os.path.join(REPO, "nerf_replication_amd", "csrc", "nerf_layout.h")).read()
+    for name, expr in re.findall(r"constexpr\s+int64_t\s+(\w+)\s*=\s*([^;]+);", text):
+        try:
+            env[name] = eval(expr, {"__builtins__": {}}, env)      # noqa: S307 (the repository's own header)
+        except Exception:
+            pass                                                   # (expressions with C casts: not needed here)
+    return env["kOffFeat"] // 256 * 4, (env["kFoldOffBias"] - env["kFoldOffWvf"]) // 256 * 4
+
+
+def dead_ksteps(h):
+    """h [tiles, 32, 256] post-ReLU activations -> bool [tiles, 128]: the k-step's register is zero at every point."""
+    pairs = kstep_pairs()
+    off = (h == 0).all(dim=1)                                      # [tiles, 256]: feature off tile-wide
+    return off[:, pairs[:, 0]] & off[:, pairs[:, 1]]
+
+
+def tile_activations(sd, prefix, pts, viewdirs):
+    """pts [n, S, 3] (S a multiple of 32), viewdirs [n, 3] -> (raw [n*S/32, 32, 4], {name: [n*S/32, 32, C]}), fp32 on the CPU."""
+    n, S, _ = pts.shape
+    assert S % TILE == 0
+    emb = torch.cat([orc.freq_encode(pts.reshape(-1, 3), orc.XYZ_FREQS),
+                     orc.freq_encode(viewdirs[:, None].expand(n, S, 3).reshape(-1, 3), orc.DIR_FREQS)], -1)
+    outs, acts = [], {}
+    with torch.no_grad():
+        for i in range(0, emb.shape[0], 1 << 15):
+            raw, a = orc.nerf_mlp(sd, prefix, emb[i:i + (1 << 15)], return_activations=True)
+            outs.append(raw)
+            for k, v in a.items():
+                acts.setdefault(k, []).append(v)
+    tiles = lambda x: x.reshape(n * S // TILE, TILE, -1)
+    return tiles(torch.cat(outs)), {k: tiles(torch.cat(v)) for k, v in acts.items()}
+
+
+def count(raw, acts, density_only, skip_dead_colour):
+    """-> per-GEMM rows and totals for a set of tiles.  density_only: the coarse launch (stops after the sigma head);
+    skip_dead_colour: tiles without a sigma > 0 skip the colour branch (the fine launch of a render)."""
+    n_tiles = raw.shape[0]
+    colour = torch.ones(n_tiles, dtype=torch.bool)
+    if skip_dead_colour:
+        colour = (raw[..., 3] > 0).any(dim=1)
+    rows, total, left = [], 0.0, 0.0
+    for name, ksteps, ntiles, src, is_colour in GEMMS:
+        if is_colour and density_only:
+            continue
+        runs = colour if is_colour else torch.ones(n_tiles, dtype=torch.bool)
+        issued = ksteps * ntiles * runs.float().mean().item()                       # per mean tile, nothing skipped
+        frac_dead = frac_off = None
+        remain = issued
+        if src is not None:
+            dead = dead_ksteps(acts[src])
+            frac_dead = dead.float().mean().item()                                  # over all tiles (the table of the issue)
+            frac_off = (acts[src] == 0).all(dim=1).float().mean().item()
+            remain = ((~dead).float().sum(dim=1) * runs.float()).mean().item() * ntiles
+        rows.append(dict(gemm=name, ksteps=ksteps, ntiles=ntiles, feature_off=frac_off, kstep_dead=frac_dead,
+                         mfma=issued, mfma_left=remain))
+        total += issued
+        left += remain
+    return dict(tiles=n_tiles, colour_live=colour.float().mean().item(), rows=rows, mfma=total, mfma_left=left)
+
+
+def probe(sd, n_rays=768, seed=0, H=800, W=800, theta=40.0):
+    """Coarse (64 samples, density only) and fine (192 sorted samples, dead-colour skip) launches of a render of `n_rays` seeded
+    rays of the bench frame -> {"coarse": count(...), "fine": count(...)}."""
+    ids = torch.randperm(H * W, generator=torch.Generator().manual_seed(seed))[:n_rays]
+    o, d = orc.pinhole_rays(H, W, orc.camera_pose(theta), pixel_ids=ids)
+    with torch.no_grad():
+        _, _, parts = orc.render(sd, o[None], d[None], return_parts=True)
+    vd = parts["viewdirs"]
+    out = {}
+    for key, prefix, t, dens, dskip in (("coarse", "model", parts["t_coarse"], True, False),
+                                        ("fine", "model_fine", parts["t_sorted"], False, True)):
+        raw, acts = tile_activations(sd, prefix, orc.points_on_rays(o, d, t), vd)
+        out[key] = count(raw, acts, dens, dskip)
+    return out
+
+
+def load_family(ckpt, family):
+    ck = torch.load(ckpt, weights_only=True)
+    sd = {k: ck["net"][k] for k in orc.state_dict_keys()}
+    return sd if family in ("", "none", "as-is") else orc.weight_family(sd, family)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--ckpt", default=os.path.join(REPO, "tests", "golden", "synthetic_ckpt.pth"))
+    ap.add_argument("--family", default="base", help="oracle.WEIGHT_FAMILIES name, or 'none' for the checkpoint as stored")
+    ap.add_argument("--rays", type=int, default=768)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--json", help="also write the figures to this file")
+    args = ap.parse_args()
+    res = probe(load_family(args.ckpt, args.family), args.rays, args.seed)
+    trunk, col = layout_mfmas()
+    print(f"{os.path.basename(args.ckpt)} family={args.family} rays={args.rays} seed={args.seed}; "
+          f"a full tile issues {trunk} + {col} MFMAs (nerf_layout.h)")
+    for key in ("coarse", "fine"):
+        r = res[key]
+        print(f"\n{key}: {r['tiles']} tiles, colour branch runs in {100 * r['colour_live']:.1f} %")
+        print(f"  {'GEMM':<20} {'feature off':>11} {'k-step dead':>11} {'MFMA/tile':>10} {'left':>10}")
+        for row in r["rows"]:
+            f = lambda x: "     -" if x is None else f"{x:6.3f}"
+            print(f"  {row['gemm']:<20} {f(row['feature_off']):>11} {f(row['kstep_dead']):>11} {row['mfma']:10.1f} {row['mfma_left']:10.1f}")
+        print(f"  {'total':<20} {'':>11} {'':>11} {r['mfma']:10.1f} {r['mfma_left']:10.1f}   ({100 * (1 - r['mfma_left'] / r['mfma']):.1f} % skipped)")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(ckpt=os.path.basename(args.ckpt), family=args.family, rays=args.rays, seed=args.seed, **res), f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -190,6 +190,18 @@ NN_EXACT_SIGNATURES = _parse_table(_TABLE_NN_EXACT)
 NN_EXACT_EXPORTS = tuple(NN_EXACT_SIGNATURES)
 _NN_EXACT_PROTOS = _protos(NN_EXACT_SIGNATURES)
 
+# The unit orders of the fp32 render MLP, one line per entry of include/nerf_mi355x_order.h (the sixth header of the same library; the
+# five tables above are pinned at their sizes).  tests/test_unit_order_cpu.py compares this table with that header.  The matching is
+# pure host: its two arrays are host arrays and its int32 status comes back unchecked (call() checks entries that take a stream).
+_TABLE_ORDER = """
+nerf_pack_model_ordered  status : f32*[24] u8* void* i32 stream
+nerf_unit_order_stats  status : f32* i64 i32* stream
+nerf_unit_order_match  i32 : i32[65536] i32[256]
+"""
+ORDER_SIGNATURES = _parse_table(_TABLE_ORDER)
+ORDER_EXPORTS = tuple(ORDER_SIGNATURES)
+_ORDER_PROTOS = _protos(ORDER_SIGNATURES)
+
 _lib = None
 
 
@@ -217,7 +229,7 @@ def load():
                 "there is no CPU fallback for the render path")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_PROTOS.items()) + list(_NN_PROTOS.items()) + list(_FIELD_PROTOS.items()) +
-                                  list(_HASHGRID_PROTOS.items()) + list(_NN_EXACT_PROTOS.items())):
+                                  list(_HASHGRID_PROTOS.items()) + list(_NN_EXACT_PROTOS.items()) + list(_ORDER_PROTOS.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.nerf_abi_version() != 3:
@@ -242,9 +254,9 @@ class strided:
 def call(name, *args):
     """Call entry `name` of the library with `args` as its header lists them, minus the stream: tensors (None: NULL) for device
     pointers, numbers for scalars, sequences or ctypes arrays for host arrays.  Every argument is checked against the entry's kinds
-    in SIGNATURES (or, looked up in this order, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
+    in SIGNATURES (or, looked up in this order, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES, ORDER_SIGNATURES) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
     is checked (NerfLibraryError with nerf_last_error's text); any other return value comes back as it is."""
-    for table in (SIGNATURES, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES):
+    for table in (SIGNATURES, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES, ORDER_SIGNATURES):
         if name in table:
             break
     ret, kinds = table[name]

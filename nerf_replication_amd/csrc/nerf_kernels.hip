@@ -29,7 +29,8 @@
 #include "nerf_timing_guard.h"         // after the kernel includes: refuses a build with a stray timing switch
 
 // ---- the core: kernels and entries, one file per subsystem
-#include "nerf_pack.hip.inc"             // nerf_pack_model[_bwd], nerf_packed_*_bytes
+#include "nerf_pack.hip.inc"             // nerf_pack_model[_bwd], nerf_pack_model_ordered, nerf_packed_*_bytes
+#include "nerf_unit_order.hip.inc"       // nerf_unit_order_stats / _match (include/nerf_mi355x_order.h)
 #include "nerf_sampling.hip.inc"         // nerf_sample_fine*, nerf_stratified_samples, nerf_compact_valid
 #include "nerf_composite.hip.inc"        // nerf_composite[_backward]
 #include "nerf_mlp_launch.hip.inc"       // nerf_mlp_forward*: inference and SAVE

@@ -1,5 +1,7 @@
 // Packed weight streams (nerf_layout.h): the pack kernels of every precision, the fold of feature_linear into the views layer, the
-// transposed streams of the backward chain, and their entries nerf_pack_model / nerf_pack_model_bwd / nerf_packed_*_bytes.
+// transposed streams of the backward chain, and their entries nerf_pack_model / nerf_pack_model_ordered / nerf_pack_model_bwd /
+// nerf_packed_*_bytes.
+#include "../../include/nerf_mi355x_order.h"
 #include "nerf_host.h"
 #include "nerf_mlp_common.h"
 
@@ -11,9 +13,15 @@ struct PackArgs {
   float* out;
 };
 
+// Unit orders (include/nerf_mi355x_order.h): order[l][position] = the original unit of h_l at `position` of the permuted network,
+// whose stream the fp32 pack kernel writes; a null table is the identity (every other pack kernel passes none).
+__device__ __forceinline__ int ordered_unit(const uint8_t* order, int l, int position) {
+  return order ? (int)order[l * nerf::kHidden + position] : position;
+}
+
 __device__ __forceinline__ float pack_weight_elem(const PackArgs& a, long long rel, int ntiles,
                                                   int which /*0 L0,1 hidden,2 L5a,3 L5b,4 feat,5 views*/,
-                                                  int layer) {
+                                                  int layer, const uint8_t* order) {
   using namespace nerf;
   const int q = (int)(rel & 3);
   const int lane = (int)((rel >> 2) & 63);
@@ -23,12 +31,12 @@ __device__ __forceinline__ float pack_weight_elem(const PackArgs& a, long long r
   const int s = 4 * g + q, t = s >> 4, r = s & 15, h = lane >> 5;
   const int out = 32 * j + (lane & 31);
   switch (which) {
-    case 0: { const int c = pe_xyz_feat(s, h); return c < 0 ? 0.f : a.p[P_W0][out * 63 + c]; }
-    case 1: return a.p[2 * layer][out * 256 + act_feat(t, r, h)];
-    case 2: { const int c = pe_xyz_feat(s, h); return c < 0 ? 0.f : a.p[10][out * 319 + c]; }
-    case 3: return a.p[10][out * 319 + 63 + act_feat(t, r, h)];
-    case 4: return a.p[P_WF][out * 256 + act_feat(t, r, h)];
-    default: {
+    case 0: { const int c = pe_xyz_feat(s, h); return c < 0 ? 0.f : a.p[P_W0][ordered_unit(order, 0, out) * 63 + c]; }
+    case 1: return a.p[2 * layer][ordered_unit(order, layer, out) * 256 + ordered_unit(order, layer - 1, act_feat(t, r, h))];
+    case 2: { const int c = pe_xyz_feat(s, h); return c < 0 ? 0.f : a.p[10][ordered_unit(order, 5, out) * 319 + c]; }
+    case 3: return a.p[10][ordered_unit(order, 5, out) * 319 + 63 + ordered_unit(order, 4, act_feat(t, r, h))];
+    case 4: return a.p[P_WF][out * 256 + ordered_unit(order, 7, act_feat(t, r, h))];
+    default: {                                      // (its inputs are feature_linear's outputs and the direction: not permuted)
       if (t < 8) return a.p[P_WV][out * 283 + act_feat(t, r, h)];
       const int c = pe_dir_feat(r, h);
       return c < 0 ? 0.f : a.p[P_WV][out * 283 + 256 + c];
@@ -42,12 +50,22 @@ __device__ __forceinline__ float act_order_value(const float* x, int rel) {
   const int h = rel >> LOG2, slot = rel & ((1 << LOG2) - 1);
   return x[nerf::act_feat(slot >> 4, slot & 15, h)];
 }
+// the same over the units of h_l in `order` (the fp32 pack kernel alone: the other kernels' helpers stay as they were)
+template <int LOG2>
+__device__ __forceinline__ float act_order_value_ordered(const float* x, int rel, const uint8_t* order, int l) {
+  const int h = rel >> LOG2, slot = rel & ((1 << LOG2) - 1);
+  return x[ordered_unit(order, l, nerf::act_feat(slot >> 4, slot & 15, h))];
+}
 // The blocks the streams share beside w_alpha (act_order_value<7>): biases [layer 0..8][h][j*16 + r], w_rgb [c][h][t*16 + r] (t < 4)
 // and the head biases b_rgb[3], b_alpha.  (The weight pointer, not PackArgs, where a kernel also picks a weight matrix by a
 // run-time index: a reference to the arguments there made the compiler copy them to scratch.)
 __device__ __forceinline__ float pack_bias_value(const PackArgs& a, int rel) {
   const int layer = rel >> 8;
   return act_order_value<7>(layer < 8 ? a.p[2 * layer + 1] : a.p[nerf::P_BF], rel & 255);
+}
+__device__ __forceinline__ float pack_bias_value_ordered(const PackArgs& a, int rel, const uint8_t* order) {
+  const int layer = rel >> 8;                     // (feature_linear's outputs, layer 8, are not permuted)
+  return layer < 8 ? act_order_value_ordered<7>(a.p[2 * layer + 1], rel & 255, order, layer) : act_order_value<7>(a.p[nerf::P_BF], rel & 255);
 }
 __device__ __forceinline__ float pack_w_rgb_value(const float* w_rgb, int rel) {
   return act_order_value<6>(w_rgb + 128 * (rel >> 7), rel & 127);
@@ -56,22 +74,22 @@ __device__ __forceinline__ float pack_head_bias_value(const PackArgs& a, int rel
   return rel < 3 ? a.p[nerf::P_BR][rel] : a.p[nerf::P_BA][0];
 }
 
-__global__ void nerf_pack_kernel(PackArgs a) {
+__global__ void nerf_pack_kernel(PackArgs a, const uint8_t* __restrict__ order) {
   using namespace nerf;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= kUnfoldedFloats) return;
   constexpr long long WS = wsize(128, 8);
   float v;
-  if (i < kOffL1) v = pack_weight_elem(a, i - kOffL0, 8, 0, 0);
-  else if (i < kOffL5a) { const long long rel = i - kOffL1; v = pack_weight_elem(a, rel % WS, 8, 1, 1 + (int)(rel / WS)); }
-  else if (i < kOffL5b) v = pack_weight_elem(a, i - kOffL5a, 8, 2, 5);
-  else if (i < kOffL6) v = pack_weight_elem(a, i - kOffL5b, 8, 3, 5);
-  else if (i < kOffFeat) { const long long rel = i - kOffL6; v = pack_weight_elem(a, rel % WS, 8, 1, 6 + (int)(rel / WS)); }
-  else if (i < kOffViews) v = pack_weight_elem(a, i - kOffFeat, 8, 4, 0);
-  else if (i < kOffBias) v = pack_weight_elem(a, i - kOffViews, 4, 5, 0);
-  else if (i < kOffBiasViews) v = pack_bias_value(a, (int)(i - kOffBias));
+  if (i < kOffL1) v = pack_weight_elem(a, i - kOffL0, 8, 0, 0, order);
+  else if (i < kOffL5a) { const long long rel = i - kOffL1; v = pack_weight_elem(a, rel % WS, 8, 1, 1 + (int)(rel / WS), order); }
+  else if (i < kOffL5b) v = pack_weight_elem(a, i - kOffL5a, 8, 2, 5, order);
+  else if (i < kOffL6) v = pack_weight_elem(a, i - kOffL5b, 8, 3, 5, order);
+  else if (i < kOffFeat) { const long long rel = i - kOffL6; v = pack_weight_elem(a, rel % WS, 8, 1, 6 + (int)(rel / WS), order); }
+  else if (i < kOffViews) v = pack_weight_elem(a, i - kOffFeat, 8, 4, 0, order);
+  else if (i < kOffBias) v = pack_weight_elem(a, i - kOffViews, 4, 5, 0, order);
+  else if (i < kOffBiasViews) v = pack_bias_value_ordered(a, (int)(i - kOffBias), order);
   else if (i < kOffWAlpha) v = act_order_value<6>(a.p[P_BV], (int)(i - kOffBiasViews));      // [h][j*16 + r], j < 4
-  else if (i < kOffWRgb) v = act_order_value<7>(a.p[P_WA], (int)(i - kOffWAlpha));
+  else if (i < kOffWRgb) v = act_order_value_ordered<7>(a.p[P_WA], (int)(i - kOffWAlpha), order, 7);
   else if (i < kOffHeadBias) v = pack_w_rgb_value(a.p[P_WR], (int)(i - kOffWRgb));
   else v = pack_head_bias_value(a, (int)(i - kOffHeadBias));
   a.out[i] = v;
@@ -356,6 +374,13 @@ static int32_t fill_pack_args(const char* entry, const float* const params[24], 
   return NERF_OK;
 }
 
+// the fp32 stream: the permuted parameters (order: device [8][256] or null = identity), then the fold computed from them
+static int32_t pack_f32(const PackArgs& a, const uint8_t* order, hipStream_t st) {
+  const unsigned blocks = (unsigned)((nerf::kUnfoldedFloats + 255) / 256);
+  if (const int rc = NERF_LAUNCH(nerf_pack_kernel, dim3(blocks), dim3(256), st, a, order)) return rc;
+  return NERF_LAUNCH(nerf_fold_f32_kernel, dim3(kFoldBlocks), dim3(256), st, (const float*)a.out, a.out + nerf::kOffFold);
+}
+
 int32_t nerf_pack_model(const float* const params[24], void* packed, int32_t precision, void* stream) {
   PackArgs a;
   if (const int rc = fill_pack_args("nerf_pack_model", params, packed, a)) return rc;
@@ -373,9 +398,15 @@ int32_t nerf_pack_model(const float* const params[24], void* packed, int32_t pre
     return NERF_LAUNCH(nerf_pack_f16_kernel<true>, grid, dim3(threads), st, ax);
   }
   if (precision != NERF_PREC_F32) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_pack_model: unknown precision");
-  const unsigned blocks = (unsigned)((nerf::kUnfoldedFloats + threads - 1) / threads);
-  if (const int rc = NERF_LAUNCH(nerf_pack_kernel, dim3(blocks), dim3(threads), (hipStream_t)stream, a)) return rc;
-  return NERF_LAUNCH(nerf_fold_f32_kernel, dim3(kFoldBlocks), dim3(256), (hipStream_t)stream, (const float*)a.out, a.out + nerf::kOffFold);
+  return pack_f32(a, nullptr, (hipStream_t)stream);
+}
+
+// include/nerf_mi355x_order.h: the fp32 stream of the network permuted by `order` (null: nerf_pack_model's bytes)
+int32_t nerf_pack_model_ordered(const float* const params[24], const uint8_t* order, void* packed, int32_t precision, void* stream) {
+  PackArgs a;
+  if (const int rc = fill_pack_args("nerf_pack_model_ordered", params, packed, a)) return rc;
+  if (precision != NERF_PREC_F32) return fail(NERF_ERR_UNSUPPORTED, "%s", "nerf_pack_model_ordered: f32 only");
+  return pack_f32(a, order, (hipStream_t)stream);
 }
 
 int64_t nerf_packed_bwd_bytes(int32_t precision) {

@@ -95,24 +95,78 @@ class Network(nn.Module):
         self.model_fine = mk()
         self.precision = "f32"
         self._packed = {}       # tag -> (key, tensor)
+        self._orders = {}       # "" / "fine" -> (key, uint8 [8, 256] device tensor): unit orders
+        self._large_renders = {}   # "" / "fine" -> key of the weights the last large no-grad render read
 
     # ---- packed weight stream (csrc/nerf_layout.h) -------------------------------------------
+    def _stream_key(self, model):
+        """(tag, parameters, cache key) of the coarse ("") or fine model: the key changes whenever the precision or a parameter's
+        storage or version does (load_state_dict, .to(), optimizer.step())."""
+        tag = "fine" if model == "fine" else ""
+        params = (self.model_fine if tag == "fine" else self.model).ordered_params()
+        if params[0].device.type != "cuda":
+            raise _lib.NerfLibraryError("Network parameters are on the CPU: call .cuda() first; the render path is "
+                                        "HIP-only (no CPU fallback)")
+        return tag, params, (_lib.PRECISIONS[self.precision],) + tuple((p.data_ptr(), p._version) for p in params)
+
+    def unit_order(self, model=""):
+        """The unit order of the model's current weights (uint8 [8, 256] on the device, include/nerf_mi355x_order.h), or None: there
+        is none, or the weights or the precision changed since it was set."""
+        tag, _, key = self._stream_key(model)
+        hit = self._orders.get(tag)
+        return hit[1] if hit is not None and hit[0] == key else None
+
+    def rendered_before(self, model=""):
+        """Book-keeping of the renderer's automatic calibration: records that a large no-grad render reads the model's current
+        weights, and says whether one did before -- the evidence that these weights are rendered again and again (an evaluation
+        render inside a training loop never is: its weights moved since the last one)."""
+        tag, _, key = self._stream_key(model)
+        seen = self._large_renders.get(tag) == key
+        self._large_renders[tag] = key
+        return seen
+
+    def set_unit_order(self, model, order):
+        """Attach `order` ([8, 256], every row a permutation of 0..255; None removes it) to the model's current weights.  Only
+        packed_inference() looks at it, and only in precision 'f32'."""
+        tag, params, key = self._stream_key(model)
+        self._packed.pop("inf" + tag, None)
+        if order is None:
+            self._orders.pop(tag, None)
+            return
+        host = torch.as_tensor(order).detach().cpu().to(torch.int64)          # (checked on the host: no device kernel, one copy up)
+        if host.shape != (8, 256) or not bool((host.sort(dim=1).values == torch.arange(256)).all()):
+            raise ValueError("a unit order is [8, 256] with every row a permutation of 0..255")
+        self._orders[tag] = (key, host.to(torch.uint8).contiguous().to(params[0].device))
+
+    def packed_inference(self, model=""):
+        """The stream the no-grad render launches read: the model's weights permuted by its unit order (nerf_pack_model_ordered,
+        cached like packed()) when there is one for the current weights and the precision is 'f32', else packed(model).  The two
+        streams are the same network; raw differs in the last bits only.  Everything that saves rows or takes gradients
+        (training, Network.forward under autograd, the gradient part of render_geometry, mesh.py, occupancy.py) stays on packed()
+        and packed_bwd(): its rows and gradients are in parameter order."""
+        order = self.unit_order(model) if _lib.PRECISIONS[self.precision] == _lib.PREC_F32 else None
+        if order is None:
+            return self.packed(model)
+        tag, params, key = self._stream_key(model)
+        hit = self._packed.get("inf" + tag)
+        if hit is not None and hit[0] == key and hit[2] is order:
+            return hit[1]
+        out = torch.empty(_lib.packed_model_bytes(_lib.PREC_F32), dtype=torch.uint8, device=params[0].device)
+        _lib.call("nerf_pack_model_ordered", [p.detach().contiguous() for p in params], order, out, _lib.PREC_F32)
+        self._packed["inf" + tag] = (key, out, order)
+        return out
+
     def _stream(self, model, bwd):
         """The cached weight stream of the coarse ("") or fine model, forward or transposed: repacked on the device whenever the
         precision or a parameter's storage or version changed (load_state_dict, .to(), optimizer.step())."""
-        tag = "fine" if model == "fine" else ""
-        params = (self.model_fine if tag == "fine" else self.model).ordered_params()
+        tag, params, key = self._stream_key(model)
         dev = params[0].device
-        if dev.type != "cuda":
-            raise _lib.NerfLibraryError("Network parameters are on the CPU: call .cuda() first; the render path is "
-                                        "HIP-only (no CPU fallback)")
         prec = _lib.PRECISIONS[self.precision]
         if bwd:
             nbytes = int(_lib.call("nerf_packed_bwd_bytes", prec))
             if nbytes <= 0:
                 raise NotImplementedError(f"the data-gradient chain runs in precision 'f32' or 'f32x', not {self.precision!r}")
             tag = "bwd" + tag
-        key = (prec,) + tuple((p.data_ptr(), p._version) for p in params)
         hit = self._packed.get(tag)
         if hit is not None and hit[0] == key:
             return hit[1]

@@ -37,6 +37,10 @@ def _reference_cfg():
     return getattr(mod, "cfg", None) if mod is not None else None
 
 
+UNIT_ORDER_SAMPLE_RAYS = 16          # rays of the call that calibration evaluates: indices floor((2 k + 1) n / 32)
+UNIT_ORDER_MIN_RAYS = 160000         # 4 x (one-off cost 7.1 ms / gain 0.180 us per ray) = 158 k rays, LAB_NOTEBOOK.md "unit orders"
+
+
 class Renderer:
     def __init__(self, net):
         cfg = _reference_cfg()
@@ -68,6 +72,14 @@ class Renderer:
         # render_geometry works ray block by ray block: a block's scratch is ~3.9 MB per ray (the saved rows and gradient
         # rows of its 192 points), so 4096 rays -- a training step's batch -- are about 16 GB
         self.geometry_block_rays = 4096
+        # unit orders: "auto" = the second fp32 no-grad render() of one weights version with at least
+        # unit_order_min_rays rays calibrates an order on 16 of its rays, and from then on the whole-frame launches read the
+        # ordered stream (Network.packed_inference) for as long as the weights stay; a first large call alone is no sign that the
+        # weights will be rendered again.  "off" (or NERF_UNIT_ORDER=0 in the environment) = the identity stream, always.  The
+        # threshold is four times the number of rays whose gain pays for one calibration (measured, LAB_NOTEBOOK "unit orders"):
+        # a small call never pays it
+        self.unit_order = "auto"
+        self.unit_order_min_rays = UNIT_ORDER_MIN_RAYS
         if self.N_samples != _lib.N_SAMPLES or self.N_importance not in (0, _lib.N_IMPORTANCE):
             raise ValueError("HIP renderer is built for N_samples=64 and N_importance in {0,128}")
 
@@ -141,12 +153,92 @@ class Renderer:
         kw = {} if grid is None else {"occupancy": grid}
         return _sibling("training").render_with_grad(self, o, d, *draws, **kw)
 
+    # ---- unit orders
+    def _unit_order_on(self):
+        if self.unit_order not in ("auto", "off"):
+            raise ValueError(f"Renderer.unit_order must be 'auto' or 'off', got {self.unit_order!r}")
+        return (self.unit_order == "auto" and os.environ.get("NERF_UNIT_ORDER") != "0"
+                and _lib.PRECISIONS[modes.precision_of(self.net)] == _lib.PREC_F32)
+
+    def _models(self):
+        return ("", "fine") if self.N_importance > 0 else ("",)
+
+    def _inference_streams(self, o=None, d=None):
+        """(coarse, fine or None): the streams of the no-grad render launches.  With rays (the whole-frame paths of render()) a
+        call of at least unit_order_min_rays rays, when an earlier such call read the same weights, first calibrates whatever
+        model has no order for them -- never while the stream is capturing: a capture uses what exists."""
+        if not self._unit_order_on():
+            return self.net.packed(""), self.net.packed("fine") if self.N_importance > 0 else None
+        if (o is not None and o.shape[0] >= self.unit_order_min_rays and not torch.cuda.is_current_stream_capturing()
+                and any(self.net.unit_order(m) is None for m in self._models())
+                and all([self.net.rendered_before(m) for m in self._models()])):
+            self._calibrate(o, d)
+        return self.net.packed_inference(""), self.net.packed_inference("fine") if self.N_importance > 0 else None
+
+    def calibrate_unit_order(self, batch):
+        """Calibrate the unit orders of the current weights on 16 rays of `batch` now, whatever its size (render() does it by
+        itself from unit_order_min_rays rays on).  fp32 only, never during a graph capture; returns the {model: order} set."""
+        if modes.precision_of(self.net) not in ("f32", "fp32"):
+            raise NotImplementedError("unit orders exist for precision 'f32' only")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("calibrate_unit_order synchronises: not during a graph capture")
+        rays_o, rays_d = batch["rays_o"], batch["rays_d"]
+        o = rays_o.detach().reshape(-1, 3).to(torch.float32).contiguous()
+        d = rays_d.detach().reshape(-1, 3).to(torch.float32).contiguous()
+        if o.shape[0] == 0:
+            raise ValueError("calibrate_unit_order needs at least one ray")
+        return self._calibrate(o, d)
+
+    def _calibrate(self, o, d):
+        """16 rays of the call through the render's own stages on the IDENTITY streams, with activation save: coarse forward ->
+        nerf_sample_fine -> fine forward; per model the co-dead counts of its 32-sample tiles (nerf_unit_order_stats), the
+        matching on the host (nerf_unit_order_match) and the order handed to the network.  One synchronisation (the counts come
+        to the host); the ~45 MB of saved rows are freed on return."""
+        import ctypes
+        n, dev = o.shape[0], o.device
+        k = UNIT_ORDER_SAMPLE_RAYS
+        # (row copies, not an index kernel: calibration launches nothing of ATen's, whose first use in a process costs far more
+        # than everything here)
+        os_, ds_ = torch.empty((k, 3), dtype=torch.float32, device=dev), torch.empty((k, 3), dtype=torch.float32, device=dev)
+        for i in range(k):
+            r = (2 * i + 1) * n // (2 * k)
+            os_[i].copy_(o[r])
+            ds_[i].copy_(d[r])
+        t_c, u = self._get_tables(dev)
+        prec = _lib.PREC_F32
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        S_c, S = _lib.N_SAMPLES, _lib.N_SAMPLES + _lib.N_IMPORTANCE
+        counts = {}
+        raw_c, save = new(k, S_c, 4), new(int(_lib.call("nerf_train_save_floats", k * S_c)))
+        _lib.call("nerf_mlp_forward_rays_save", os_, ds_, t_c, 0, k, S_c, self.net.packed(""), raw_c, save, prec)
+        counts[""] = torch.empty((8, 256, 256), dtype=torch.int32, device=dev)
+        _lib.call("nerf_unit_order_stats", save, k * S_c, counts[""])
+        if self.N_importance > 0:
+            t_sorted, raw_f = new(k, S), new(k, S, 4)
+            _lib.call("nerf_sample_fine", raw_c, t_c, u, k, t_sorted, None, None, 0.0, 0.0)
+            save = None
+            save = new(int(_lib.call("nerf_train_save_floats", k * S)))
+            _lib.call("nerf_mlp_forward_rays_save", os_, ds_, t_sorted, S, k, S, self.net.packed("fine"), raw_f, save, prec)
+            counts["fine"] = torch.empty((8, 256, 256), dtype=torch.int32, device=dev)
+            _lib.call("nerf_unit_order_stats", save, k * S, counts["fine"])
+        orders = {}
+        for model, c in counts.items():
+            host = c.cpu().numpy()
+            order = torch.empty((8, 256), dtype=torch.int32)
+            for l in range(8):
+                out = (ctypes.c_int32 * 256)()
+                _lib.check(_lib.call("nerf_unit_order_match", (ctypes.c_int32 * 65536).from_buffer(host[l]), out),
+                           "nerf_unit_order_match")
+                order[l] = torch.tensor(list(out), dtype=torch.int32)
+            self.net.set_unit_order(model, order)
+            orders[model] = self.net.unit_order(model)
+        return orders
+
     def _frame_arguments(self, facts, o, d):
         """What the three whole-frame entries have in common: (rays, models, tables), (modes), fast, and the outputs."""
         n, dev = o.shape[0], o.device
         t_c, u = self._get_tables(dev)
-        pk_c = self.net.packed("")
-        pk_f = self.net.packed("fine") if self.N_importance > 0 else None
+        pk_c, pk_f = self._inference_streams(o, d)
         rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
         depth = torch.empty((n,), dtype=torch.float32, device=dev)
         fast = int(bool(self.fast_sampling) and self.N_importance > 0)       # (0 when stochastic: refused)
@@ -210,8 +302,12 @@ class Renderer:
         t_c, u = self._get_tables(dev)
         fine = self.N_importance > 0
         model = "fine" if fine else ""
-        pk_c = self.net.packed("")
-        pk = self.net.packed(model)                      # the composited network, and its transposed stream for the chain
+        # the forward launches read the streams render() reads (rgb and depth stay bit-equal to it, with or without a unit
+        # order; an order is used when one exists, never calibrated here); the gradient chain saves rows in parameter order and
+        # stays on the identity stream and its transpose
+        pk_c, pk_fwd = self._inference_streams()
+        pk_fwd = pk_fwd if fine else pk_c
+        pk = self.net.packed(model)
         pk_b = self.net.packed_bwd(model)
         S_c, S = _lib.N_SAMPLES, _lib.N_SAMPLES + (_lib.N_IMPORTANCE if fine else 0)
         nb_max = min(block, n)
@@ -226,7 +322,7 @@ class Renderer:
             if fine:
                 _lib.call("nerf_mlp_forward_rays_density", ob, db, t_c, 0, nb, S_c, pk_c, raw_c, prec)
                 _lib.call("nerf_sample_fine", raw_c, t_c, u, nb, t_sorted, None, None, 0.0, 0.0)
-                _lib.call("nerf_mlp_forward_rays_for_compositing", ob, db, t_sorted, S, nb, S, pk, raw_f, prec)
+                _lib.call("nerf_mlp_forward_rays_for_compositing", ob, db, t_sorted, S, nb, S, pk_fwd, raw_f, prec)
                 raw, tv, stride = raw_f, t_sorted, S
             else:
                 _lib.call("nerf_mlp_forward_rays", ob, db, t_c, 0, nb, S_c, pk_c, raw_c, prec)

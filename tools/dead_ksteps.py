@@ -9,6 +9,11 @@ per ReLU-fed GEMM the fraction of dead k-steps and the MFMAs per tile that remai
 NERF_DEAD_KSTEP_SKIP is set against, and what corrects bench.py's roofline figures (which count every MFMA as issued).
 
     python tools/dead_ksteps.py --family base --rays 768
+
+--calibrate-rays N adds the re-paired column: unit orders matched from the co-dead counts of N other rays
+(seed + 1) with the library's rule in its restatement (tests/unit_order_reference.py), evaluated on the same tiles as today's.
+
+    python tools/dead_ksteps.py --family base --rays 256 --calibrate-rays 16
 """
 import argparse
 import json
@@ -24,6 +29,7 @@ for p in (os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
         sys.path.insert(0, p)
 import nerf_oracle as orc            # noqa: E402
 from pack_reference import act_feat  # noqa: E402  (the pairing is taken from the layout's statement, not restated)
+import unit_order_reference as uor   # noqa: E402  (the matching rule, likewise)
 
 TILE = 32
 # Every GEMM of a tile in issue order: (name, k-steps, output tiles, the ReLU output it consumes or None, colour branch?).
@@ -80,47 +86,61 @@ def tile_activations(sd, prefix, pts, viewdirs):
     return tiles(torch.cat(outs)), {k: tiles(torch.cat(v)) for k, v in acts.items()}
 
 
-def count(raw, acts, density_only, skip_dead_colour):
+def count(raw, acts, density_only, skip_dead_colour, orders=None):
     """-> per-GEMM rows and totals for a set of tiles.  density_only: the coarse launch (stops after the sigma head);
-    skip_dead_colour: tiles without a sigma > 0 skip the colour branch (the fine launch of a render)."""
+    skip_dead_colour: tiles without a sigma > 0 skip the colour branch (the fine launch of a render).  orders: {"h0".."h7": order
+    [256]} adds the figures of the re-paired network (kstep_dead_repaired, mfma_left_repaired)."""
     n_tiles = raw.shape[0]
     colour = torch.ones(n_tiles, dtype=torch.bool)
     if skip_dead_colour:
         colour = (raw[..., 3] > 0).any(dim=1)
-    rows, total, left = [], 0.0, 0.0
+    rows, total, left, left_re = [], 0.0, 0.0, 0.0
     for name, ksteps, ntiles, src, is_colour in GEMMS:
         if is_colour and density_only:
             continue
         runs = colour if is_colour else torch.ones(n_tiles, dtype=torch.bool)
         issued = ksteps * ntiles * runs.float().mean().item()                       # per mean tile, nothing skipped
-        frac_dead = frac_off = None
-        remain = issued
+        frac_dead = frac_off = frac_re = None
+        remain = remain_re = issued
         if src is not None:
             dead = dead_ksteps(acts[src])
             frac_dead = dead.float().mean().item()                                  # over all tiles (the table of the issue)
             frac_off = (acts[src] == 0).all(dim=1).float().mean().item()
-            remain = ((~dead).float().sum(dim=1) * runs.float()).mean().item() * ntiles
+            remain = remain_re = ((~dead).float().sum(dim=1) * runs.float()).mean().item() * ntiles
+            if orders is not None:
+                dead_re = dead_ksteps(acts[src][:, :, torch.as_tensor(orders[src], dtype=torch.long)])
+                frac_re = dead_re.float().mean().item()
+                remain_re = ((~dead_re).float().sum(dim=1) * runs.float()).mean().item() * ntiles
         rows.append(dict(gemm=name, ksteps=ksteps, ntiles=ntiles, feature_off=frac_off, kstep_dead=frac_dead,
-                         mfma=issued, mfma_left=remain))
+                         mfma=issued, mfma_left=remain, kstep_dead_repaired=frac_re, mfma_left_repaired=remain_re))
         total += issued
         left += remain
-    return dict(tiles=n_tiles, colour_live=colour.float().mean().item(), rows=rows, mfma=total, mfma_left=left)
+        left_re += remain_re
+    return dict(tiles=n_tiles, colour_live=colour.float().mean().item(), rows=rows, mfma=total, mfma_left=left,
+                mfma_left_repaired=left_re)
 
 
-def probe(sd, n_rays=768, seed=0, H=800, W=800, theta=40.0):
-    """Coarse (64 samples, density only) and fine (192 sorted samples, dead-colour skip) launches of a render of `n_rays` seeded
-    rays of the bench frame -> {"coarse": count(...), "fine": count(...)}."""
+def launch_tiles(sd, n_rays, seed, H=800, W=800, theta=40.0):
+    """{"coarse" / "fine": (raw, acts)} of the two launches of a render of `n_rays` seeded rays of the bench frame."""
     ids = torch.randperm(H * W, generator=torch.Generator().manual_seed(seed))[:n_rays]
     o, d = orc.pinhole_rays(H, W, orc.camera_pose(theta), pixel_ids=ids)
     with torch.no_grad():
         _, _, parts = orc.render(sd, o[None], d[None], return_parts=True)
     vd = parts["viewdirs"]
-    out = {}
-    for key, prefix, t, dens, dskip in (("coarse", "model", parts["t_coarse"], True, False),
-                                        ("fine", "model_fine", parts["t_sorted"], False, True)):
-        raw, acts = tile_activations(sd, prefix, orc.points_on_rays(o, d, t), vd)
-        out[key] = count(raw, acts, dens, dskip)
-    return out
+    return {key: tile_activations(sd, prefix, orc.points_on_rays(o, d, t), vd)
+            for key, prefix, t in (("coarse", "model", parts["t_coarse"]), ("fine", "model_fine", parts["t_sorted"]))}
+
+
+def probe(sd, n_rays=768, seed=0, H=800, W=800, theta=40.0, calibrate_rays=0):
+    """Coarse (64 samples, density only) and fine (192 sorted samples, dead-colour skip) launches of a render of `n_rays` seeded
+    rays of the bench frame -> {"coarse": count(...), "fine": count(...)}.  calibrate_rays > 0: with the unit orders matched from
+    that many rays of seed + 1, as Renderer.calibrate_unit_order forms them (per model, from its own launch's tiles)."""
+    tiles = launch_tiles(sd, n_rays, seed, H, W, theta)
+    orders = {"coarse": None, "fine": None}
+    if calibrate_rays > 0:
+        cal = launch_tiles(sd, calibrate_rays, seed + 1, H, W, theta)
+        orders = {key: {h: uor.match(uor.co_dead_counts(cal[key][1][h]).numpy()) for h in uor.RELU_FED} for key in cal}
+    return {key: count(*tiles[key], key == "coarse", key == "fine", orders[key]) for key in ("coarse", "fine")}
 
 
 def load_family(ckpt, family):
@@ -135,23 +155,32 @@ def main():
     ap.add_argument("--family", default="base", help="oracle.WEIGHT_FAMILIES name, or 'none' for the checkpoint as stored")
     ap.add_argument("--rays", type=int, default=768)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--calibrate-rays", type=int, default=0, metavar="N",
+                    help="also print the re-paired column: unit orders matched from N rays of seed + 1")
     ap.add_argument("--json", help="also write the figures to this file")
     args = ap.parse_args()
-    res = probe(load_family(args.ckpt, args.family), args.rays, args.seed)
+    res = probe(load_family(args.ckpt, args.family), args.rays, args.seed, calibrate_rays=args.calibrate_rays)
     trunk, col = layout_mfmas()
     print(f"{os.path.basename(args.ckpt)} family={args.family} rays={args.rays} seed={args.seed}; "
           f"a full tile issues {trunk} + {col} MFMAs (nerf_layout.h)")
     for key in ("coarse", "fine"):
         r = res[key]
         print(f"\n{key}: {r['tiles']} tiles, colour branch runs in {100 * r['colour_live']:.1f} %")
-        print(f"  {'GEMM':<20} {'feature off':>11} {'k-step dead':>11} {'MFMA/tile':>10} {'left':>10}")
+        re_paired = args.calibrate_rays > 0
+        print(f"  {'GEMM':<20} {'feature off':>11} {'k-step dead':>11} {'MFMA/tile':>10} {'left':>10}"
+              + (f" {'re-paired':>10} {'left':>10}" if re_paired else ""))
         for row in r["rows"]:
             f = lambda x: "     -" if x is None else f"{x:6.3f}"
-            print(f"  {row['gemm']:<20} {f(row['feature_off']):>11} {f(row['kstep_dead']):>11} {row['mfma']:10.1f} {row['mfma_left']:10.1f}")
-        print(f"  {'total':<20} {'':>11} {'':>11} {r['mfma']:10.1f} {r['mfma_left']:10.1f}   ({100 * (1 - r['mfma_left'] / r['mfma']):.1f} % skipped)")
+            print(f"  {row['gemm']:<20} {f(row['feature_off']):>11} {f(row['kstep_dead']):>11} {row['mfma']:10.1f} {row['mfma_left']:10.1f}"
+                  + (f" {f(row['kstep_dead_repaired']):>10} {row['mfma_left_repaired']:10.1f}" if re_paired else ""))
+        print(f"  {'total':<20} {'':>11} {'':>11} {r['mfma']:10.1f} {r['mfma_left']:10.1f}"
+              + (f" {'':>10} {r['mfma_left_repaired']:10.1f}" if re_paired else "")
+              + f"   ({100 * (1 - r['mfma_left'] / r['mfma']):.1f} % skipped"
+              + (f", re-paired {100 * (1 - r['mfma_left_repaired'] / r['mfma']):.1f} %)" if re_paired else ")"))
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(dict(ckpt=os.path.basename(args.ckpt), family=args.family, rays=args.rays, seed=args.seed, **res), f, indent=1)
+            json.dump(dict(ckpt=os.path.basename(args.ckpt), family=args.family, rays=args.rays, seed=args.seed,
+                           calibrate_rays=args.calibrate_rays, **res), f, indent=1)
     return 0
 
 

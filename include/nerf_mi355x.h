@@ -132,7 +132,13 @@ int32_t nerf_mlp_forward_rays_for_compositing(const float* rays_o, const float* 
  * finite weights (a NaN / Inf weight times such a zero would have been NaN: a checkpoint that renders NaN anyway may do so in
  * fewer pixels).  How many steps are skipped is scene-dependent (17-30 % of them on the synthetic benchmark scene, close to
  * none with white-noise weights).  NERF_DEAD_KSTEP_SKIP=0 in the environment makes the kernel issue every instruction, for
- * A/B comparisons; the training entries below never skip. */
+ * A/B comparisons; the training entries below never skip.
+ * Leading dead groups (same entries; exact): the steps are issued in groups of four, and where the groups a trunk layer's
+ * reduction starts with are dead as a whole -- under a unit order (nerf_mi355x_order.h) the deadest steps come first -- the kernel
+ * steps over that run without waiting for, or fetching, its weights, and fetches from the first group that runs.  A stepped-over
+ * group adds nothing, exactly as its four skipped steps: `raw` is bit-identical.  Trunk layers 1-7 only: the views layer keeps the
+ * per-step decisions alone (DESIGN.md section 2.1 says why).  NERF_DEAD_GROUP_SKIP=0 switches this path off
+ * and leaves the per-step decisions as they are (its own A/B switch); NERF_DEAD_KSTEP_SKIP=0 switches off both. */
 
 /* ---- training path (BASELINE config 3; fp32 only) ------------------------------------------------
  * Forward with activation save: as nerf_mlp_forward_rays, and additionally stores, row-major per

@@ -97,6 +97,8 @@ struct MlpArgs {
                            // nerf_pack_model (launch_mlp)
   int skip_dead_ksteps;    // fp32 inference instances: a k-step whose ReLU-output activation register is zero in all 64 lanes
                            // issues no MFMAs (gemm_tiles KSKIP; bit-identical raw).  launch_mlp: 1 unless NERF_DEAD_KSTEP_SKIP=0
+  int skip_dead_groups;    // with skip_dead_ksteps: the leading run of all-dead 4-k-step groups of such a GEMM costs no wait, no
+                           // loads and no row branches (gemm_tiles `prefix`).  launch_mlp: 1 unless NERF_DEAD_GROUP_SKIP=0
 };
 
 // Training forward keeps what the backward pass needs, row-major per point (the layout the weight-

@@ -137,6 +137,45 @@ __device__ __forceinline__ void astream_load_one(AStream& as, int first, int slo
   asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3"
                : "=&v"(as.ring[(slot0 + K) % kRing]) : "v"(as.voff), "s"(b), "n"((K & 3) * 1024) : "memory");
 }
+// Group P > 0 of a GEMM is the first to run after a prefix of dead groups (gemm_tiles): its eight blocks into its own ring
+// half, slots 0..7 for even P and 8..15 for odd P, as the static slots of the group's code expect.  P = 0: nothing (group 0
+// was prefetched by the previous GEMM).  ONE asm statement with its branches inside, once per GEMM, so the compiler sees
+// straight-line code in which every slot passes through a read-write operand: with the loads in a conditional block of their
+// own it copied the slots where the paths join, while the loads were in flight.  Everything older is waited for first -- the
+// prefetch for group 0, issued before the decision was possible, may still be in flight into the same slots (it was issued
+// a group earlier: normally free).  P comes back opaque: the groups' `g < P` tests stay one scalar compare each.
+__device__ __forceinline__ void astream_fetch_from(AStream& as, unsigned& P) {
+  const char* b0 = as.base + (long long)P * (8 * 1024);
+  const char* b1 = b0 + 4096;
+  asm volatile("s_cmp_eq_u32 %[P], 0\n\t"
+               "s_cbranch_scc1 .Lpre_done_%=\n\t"
+               "s_waitcnt vmcnt(0)\n\t"
+               "s_bitcmp1_b32 %[P], 0\n\t"
+               "s_cbranch_scc1 .Lpre_odd_%=\n\t"
+               "global_load_dwordx4 %0, %[vo], %[b0]\n\t"
+               "global_load_dwordx4 %1, %[vo], %[b0] offset:1024\n\t"
+               "global_load_dwordx4 %2, %[vo], %[b0] offset:2048\n\t"
+               "global_load_dwordx4 %3, %[vo], %[b0] offset:3072\n\t"
+               "global_load_dwordx4 %4, %[vo], %[b1]\n\t"
+               "global_load_dwordx4 %5, %[vo], %[b1] offset:1024\n\t"
+               "global_load_dwordx4 %6, %[vo], %[b1] offset:2048\n\t"
+               "global_load_dwordx4 %7, %[vo], %[b1] offset:3072\n\t"
+               "s_branch .Lpre_done_%=\n"
+               ".Lpre_odd_%=:\n\t"
+               "global_load_dwordx4 %8, %[vo], %[b0]\n\t"
+               "global_load_dwordx4 %9, %[vo], %[b0] offset:1024\n\t"
+               "global_load_dwordx4 %10, %[vo], %[b0] offset:2048\n\t"
+               "global_load_dwordx4 %11, %[vo], %[b0] offset:3072\n\t"
+               "global_load_dwordx4 %12, %[vo], %[b1]\n\t"
+               "global_load_dwordx4 %13, %[vo], %[b1] offset:1024\n\t"
+               "global_load_dwordx4 %14, %[vo], %[b1] offset:2048\n\t"
+               "global_load_dwordx4 %15, %[vo], %[b1] offset:3072\n"
+               ".Lpre_done_%=:"
+               : "+v"(as.ring[0]), "+v"(as.ring[1]), "+v"(as.ring[2]), "+v"(as.ring[3]), "+v"(as.ring[4]), "+v"(as.ring[5]),
+                 "+v"(as.ring[6]), "+v"(as.ring[7]), "+v"(as.ring[8]), "+v"(as.ring[9]), "+v"(as.ring[10]), "+v"(as.ring[11]),
+                 "+v"(as.ring[12]), "+v"(as.ring[13]), "+v"(as.ring[14]), "+v"(as.ring[15]), [P] "+s"(P)
+               : [vo] "v"(as.voff), [b0] "s"(b0), [b1] "s"(b1) : "memory", "scc");
+}
 // the N ring slots from slot0 on are about to be read: one wait for everything but the CNT newest vector-memory
 // operations (normally the kPF blocks issued for the next group; fewer at the end of a tile's stream)
 template <int N, int CNT = 8>
@@ -197,13 +236,51 @@ __device__ __forceinline__ void wstream_start(AStream& as, const f32x4* p_lane0,
 __device__ __forceinline__ unsigned long long kstep_live(float x, unsigned kthr) {
   return __builtin_amdgcn_ballot_w64(__float_as_uint(x) >= kthr);
 }
+#ifndef NERF_F32_ASM_OVERRUN
+#define NERF_F32_ASM_OVERRUN 0      // 1 re-creates the prefetch past the stream end (a known hazard: self-test of tools/check_asm_stream.py)
+#endif
+// -> group g of a GEMM is dead: none of its four k-steps is alive in any lane
+__device__ __forceinline__ bool group_dead(const unsigned long long (&live4)[4]) {
+  return ((live4[0] | live4[1]) | (live4[2] | live4[3])) == 0ull;
+}
 template <int KT, int NT, bool LAST = false, class TAP = NoTap, bool KSKIP = false>
-__device__ __forceinline__ void gemm_tiles(f32x16 (&acc)[NT], const f32x16 (&X)[KT], AStream& as, TAP tap = TAP(), unsigned kthr = 0u) {
+__device__ __forceinline__ void gemm_tiles(f32x16 (&acc)[NT], const f32x16 (&X)[KT], AStream& as, TAP tap = TAP(), unsigned kthr = 0u,
+                                           bool prefix = false) {
   static_assert(kRing == 16 && kPF == 8, "interleaved form: ring 16, 8 blocks in flight");
   static_assert(!KSKIP || !TAP::kIsTap, "k-step skipping: inference instances only");
   static_assert((KT * 4 * NT) % kRing == 0, "layer steps must be a multiple of the ring");
   static_assert(!LAST || (kPF % NT == 0 && KT * 4 * NT >= 2 * kPF), "tail handling: whole groups");
   constexpr int kBlocks = KT * 4 * NT;
+  // Leading dead groups (KSKIP, spread form).  P, the length of the run of all-dead groups this GEMM's input starts with, is
+  // counted here, before the first group: four decisions per group until the first that has a live row.  Groups g < P are
+  // stepped over with nothing issued -- no wait, no loads, no row branches, one scalar compare -- and group P first finds its
+  // own eight blocks fetched into its own (static) slots (astream_fetch_from); from there the code is the one it always was.
+  // The last group is never counted in (P <= 31): it always runs and issues the next GEMM's prefetch, so the stream never stalls
+  // across a layer boundary, and in a LAST call it is the stream end: nothing is fetched past it.  `prefix` is only ever set
+  // with kthr != 0 (MlpArgs::skip_dead_groups).
+  constexpr bool kPrefix = KSKIP && NT == 8 && !(LAST && NERF_F32_ASM_OVERRUN);
+  unsigned P = 0u;
+  if constexpr (kPrefix) {
+    // The fetch's slots are read-write operands, which would keep the whole ring alive across the layer boundary in front of
+    // this call (+32 registers there: the full instances spilled).  Only slots 0..7 hold anything then, the prefetch for group
+    // 0; the upper half was consumed by the last group of the previous GEMM and nothing is in flight into it: cut it off.
+    // That rests on the assert above, not on the order of the calls: every call consumes a multiple of kRing blocks, so every
+    // call starts at slot 0, and a call with NT = 8 (all that precede a call with a prefix in the packed stream) therefore
+    // has an even number of groups and ends in slots 8..15; its last group prefetches this call's group 0 into slots 0..7.
+#pragma unroll
+    for (int k = kRing / 2; k < kRing; ++k) asm volatile("" : "=v"(as.ring[k]));
+    if (prefix) {
+#pragma unroll
+      for (int g = 0; g + 1 < KT * 4; ++g) {
+        unsigned long long live4[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) live4[q] = kstep_live(X[g >> 2][(g & 3) * 4 + q], kthr);
+        if (!group_dead(live4)) break;
+        P = g + 1;
+      }
+    }
+    astream_fetch_from(as, P);
+  }
   if constexpr (KSKIP) {
     // the accumulators (just initialised from the LDS bias reads) are made ready HERE, once: with every row behind a branch
     // the compiler cannot tell which row first touches an accumulator, and repeats the `s_waitcnt lgkmcnt` ladder of those
@@ -215,9 +292,6 @@ __device__ __forceinline__ void gemm_tiles(f32x16 (&acc)[NT], const f32x16 (&X)[
   }
 #pragma unroll
   for (int g = 0; g < KT * 4; ++g) {
-#ifndef NERF_F32_ASM_OVERRUN
-#define NERF_F32_ASM_OVERRUN 0      // 1 re-creates the prefetch past the stream end (a known hazard: self-test of tools/check_asm_stream.py)
-#endif
     if constexpr (NT == 8 && !TAP::kIsTap && !(LAST && NERF_F32_ASM_OVERRUN)) {      // (GEMMs with a storing tap: the spread form measured 2.8 % SLOWER)
       // Spread form (the 8-out-tile GEMMs = 90 % of the MFMAs): the eight loads of the NEXT group are not issued back to
       // back at the group start -- 8 x ~16 cycles of vector-memory issue during which this wave, alone on its SIMD,
@@ -225,9 +299,12 @@ __device__ __forceinline__ void gemm_tiles(f32x16 (&acc)[NT], const f32x16 (&X)[
       // The group's own blocks were the last loads issued (during the previous group): the wait is vmcnt(0) -- also in the
       // LAST GEMM of a stream, whose final group simply issues nothing (layer 7 of the inference instances).
       const bool kMore = !LAST || g * NT + kPF < kBlocks;      // (g is a constant once the loop is unrolled)
+      const int t = g >> 2, r0 = (g & 3) * 4;
+      if constexpr (KSKIP) {
+        if (g + 1 < KT * 4 && (unsigned)g < P) continue;      // leading dead group (P = 0 with the path off)
+      }
       astream_wait<NT, 0>(as, (g * NT) % kRing);
       __builtin_amdgcn_sched_barrier(0);
-      const int t = g >> 2, r0 = (g & 3) * 4;
       tap(t, g & 3, X[t]);
       // KSKIP: the four decisions of the group are taken here, behind the previous group's last MFMA, into four scalar pairs;
       // a row then costs one s_cmp and one branch.  Decided row by row (v_cmp -> vcc -> s_cbranch_vccz in front of each row)
@@ -512,6 +589,7 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   // fed by a ReLU output -- not in the PE / direction GEMMs, whose inputs are not ReLU outputs, and not in the training forward
   constexpr bool kKSkip = !SAVE;
   const unsigned kthr = a.skip_dead_ksteps ? 1u : 0u;                // (wave-uniform kernel argument)
+  const bool kpre = a.skip_dead_ksteps && a.skip_dead_groups;       // leading dead groups of each such GEMM are stepped over
   using TrunkTap = decltype(save_tap<SAVE, kTapBits>(srow, &sb));
 
   f32x16 X[8], Y[8];
@@ -531,12 +609,12 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
     if (pr == 2) {                                     // skip connection: cat([pts63, h]) (network.py:58)
       gemm_tiles<2, 8>(Y, PE, ws);
     }
-    gemm_tiles<8, 8, false, TrunkTap, kKSkip>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 2 * pr), &sb), kthr);
+    gemm_tiles<8, 8, false, TrunkTap, kKSkip>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 2 * pr), &sb), kthr, kpre);
     tap_bits_done(2 * pr);
     relu8(Y, 1 + 2 * pr);
     // Y -> X : L2, L4, L6   (consumes h1, h3, h5)
     load_bias<8>(X, bias + (2 + 2 * pr) * 256);
-    gemm_tiles<8, 8, false, TrunkTap, kKSkip>(X, Y, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 1 + 2 * pr), &sb), kthr);
+    gemm_tiles<8, 8, false, TrunkTap, kKSkip>(X, Y, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 1 + 2 * pr), &sb), kthr, kpre);
     tap_bits_done(1 + 2 * pr);
     relu8(X, 2 + 2 * pr);
   }
@@ -547,7 +625,7 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
     // prefetch past it (the compiler reuses ring registers it sees as dead).  Nothing downstream of h7 exists here, so
     // (SAVE) its row and sign bits are stored directly.  The sigma arithmetic is the full instance's, bit for bit.
     load_bias<8>(Y, bias + 7 * 256);
-    gemm_tiles<8, 8, true, TrunkTap, kKSkip>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 6), &sb), kthr);
+    gemm_tiles<8, 8, true, TrunkTap, kKSkip>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 6), &sb), kthr, kpre);
     tap_bits_done(6);
     relu8(Y, 7);
     lds_cf32x4* wa = reinterpret_cast<lds_cf32x4*>(tail + (kOffWAlpha - kOffBias) + h * 128);
@@ -584,7 +662,7 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   // The training forward still runs the feature layer from the packed stream -- the backward pass needs its row -- so
   // there layer 7 keeps prefetching and the feature GEMM is the last of the stream.
   load_bias<8>(Y, bias + 7 * 256);
-  gemm_tiles<8, 8, !SAVE, TrunkTap, kKSkip>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 6), &sb), kthr);
+  gemm_tiles<8, 8, !SAVE, TrunkTap, kKSkip>(Y, X, ws, save_tap<SAVE, kTapBits>(srow + TrainSave::off_h(a.n_points, 6), &sb), kthr, kpre);
   tap_bits_done(6);
   relu8(Y, 7);
   stream_drain(ws);

@@ -27,6 +27,13 @@ int dead_kstep_skip_wanted() {
   return !(env && env[0] == '0');
 }
 
+// Leading dead groups (gemm_tiles `prefix`): on unless NERF_DEAD_GROUP_SKIP=0, which leaves the row decisions above alone -- the
+// A/B switch of this path by itself.  NERF_DEAD_KSTEP_SKIP=0 switches both off.
+int dead_group_skip_wanted() {
+  const char* env = getenv("NERF_DEAD_GROUP_SKIP");
+  return dead_kstep_skip_wanted() && !(env && env[0] == '0');
+}
+
 }  // namespace
 
 extern "C" {
@@ -81,6 +88,7 @@ static int launch_mlp(const MlpArgs& a_in, bool ray_mode, bool save, int precisi
   const MlpKernel k = f->inst[!ray_mode ? 3 : a.density_only ? 0 : a.skip_dead_colour ? 1 : 2];
   if (precision == NERF_PREC_F32) a.fold = a.packed + nerf::kOffFold;
   a.skip_dead_ksteps = dead_kstep_skip_wanted();
+  a.skip_dead_groups = dead_group_skip_wanted();
   if (f->persistent) return launch(f->name, k, dim3(persistent_blocks(a.n_points, f->wg_pts)), dim3(f->threads), st, a);
   const long long blocks = (a.n_points + f->wg_pts - 1) / f->wg_pts;
   if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s: too many points for one launch", entry);

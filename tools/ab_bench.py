@@ -18,7 +18,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 CSRC = os.path.join(REPO, "nerf_replication_amd", "csrc")
 VDIR = os.path.join(CSRC, "variants")
-FLAGS = "-O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize --offload-arch=gfx950 -shared -fPIC -DNERF_TIMING_BUILD"
+FLAGS = "-O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mllvm -large-interval-freq-threshold=100000000 --offload-arch=gfx950 -shared -fPIC -DNERF_TIMING_BUILD"
 XFLAGS = "-mllvm -amdgpu-mfma-vgpr-form=1"        # csrc/Makefile: what nerf_kernels_x.hip is compiled with on top
 
 

@@ -9,6 +9,8 @@ spill, copy or reuse them -- it believes the asm's outputs are ready immediately
 ISA and verifies exactly that for every asm load; csrc/Makefile runs it on every build of the library (with the
 build's own flags; a hazard fails the build) and tests/test_abi_symbols.py runs it with a negative self-test.
 
+It also holds the fp32 inference instances to "no scratch" and a code-size limit (RESOURCE_RULE below).
+
     python tools/check_asm_stream.py        # exit status 0 = no hazard
 """
 import bisect
@@ -21,7 +23,7 @@ import tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # code-generation flags: the Makefile passes ITS OWN ($(CXXFLAGS)) through --flags, so the ISA checked here is the ISA
 # of the library being built; the default below mirrors csrc/Makefile for stand-alone runs
-FLAGS = "-O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize --offload-arch=gfx950"
+FLAGS = "-O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mllvm -large-interval-freq-threshold=100000000 --offload-arch=gfx950"
 HIPCC = "/opt/rocm/bin/hipcc"
 # The library is two translation units (csrc/Makefile): the split-fp16 kernels are compiled with XFLAGS on top of the common
 # flags (nerf_kernels_x.hip says why); each unit is checked on the flags IT is built with.
@@ -55,12 +57,45 @@ def kernels(lines):
     return sorted(out)
 
 
+# The fp32 inference instances (nerf_mlp_f32_kernel<*, SAVE = false, ...>) run one wave per SIMD on the whole register file and
+# must not spill: a spill of a ring register is exactly the hazard above, and scratch traffic at the MFMA issue limit is time.
+# That property hangs on a register-coalescer option of the build (csrc/Makefile, -large-interval-freq-threshold): without it
+# the same source compiles to 290-310 KB of accumulator copies with 512 registers and 20-44 bytes of scratch, silently.  So
+# every run also reads the compiler's own resource lines: scratch must be 0 and the code below 128 KiB (84-108 KB with the
+# option; a tripwire far from both, twice the 64-KiB instruction cache, not a tuned figure).
+RESOURCE_RULE = re.compile(r"^_Z19nerf_mlp_f32_kernelILb[01]ELb0E")
+MAX_CODE_BYTES = 128 * 1024
+
+
+def check_resources(lines):
+    """-> [(kernel, what is wrong)] for the kernels RESOURCE_RULE names; none of them found is an error too."""
+    name, code, found, bad = None, None, 0, []
+    for l in lines:
+        m = re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", l)
+        if m:
+            name, code = m.group(1), None
+        m = re.match(r"^; codeLenInByte = (\d+)", l)
+        if m:
+            code = int(m.group(1))
+        m = re.match(r"^; ScratchSize: (\d+)", l)
+        if m and name is not None and RESOURCE_RULE.match(name):
+            found += 1
+            scratch = int(m.group(1))
+            print(f"{name}: {code} code bytes, {scratch} scratch bytes")
+            if scratch != 0:
+                bad.append((name, f"{scratch} bytes of scratch (must be 0)"))
+            if code is None or code > MAX_CODE_BYTES:
+                bad.append((name, f"{code} code bytes (limit {MAX_CODE_BYTES})"))
+            name = None
+    return found, bad
+
+
 def check(K):
     """K: the code lines of one kernel.  -> (number of inline-asm loads, hazards)"""
     ins, label_at = [], {}
     for i, l in enumerate(K):
         t = l.strip()
-        if re.match(r"^\.LBB\d+_\d+:", t):
+        if re.match(r"^\.L\w+:", t):                                  # the compiler's blocks, and labels inside asm statements
             label_at[t.split(":")[0]] = len(ins)                 # index of the first instruction after the label
         elif t and not t.startswith((";", ".")):
             ins.append((i, t))
@@ -91,6 +126,9 @@ def check(K):
         conditional branch are followed, however many lie between a load and its wait (the k-step skipping of the fp32
         inference kernels puts up to four more there): the states (instruction, younger operations) are memoised, and
         `younger` never needs to exceed the largest wait count of the kernel, so the walk is finite without a depth limit.
+        Labels and branches inside an asm statement are followed like the compiler's (the leading-dead-group fetch of the fp32
+        inference kernels is one asm statement with a branch around its loads), and a branch is followed both ways whatever it
+        tests: paths the kernel cannot take (a group stepped over after the prefix was left) are proven hazard-free as well.
         A path that leaves the kernel's code without a wait is reported, not dropped."""
         pat = r"lgkmcnt\((\d+)\)" if lds else r"vmcnt\((\d+)\)"
         seen, todo = set(), [(start, 0)]
@@ -114,9 +152,8 @@ def check(K):
                     break
                 if (is_lds(l) if lds else is_vmem(l)):
                     younger += 1
-                if l.startswith("s_endpgm"):
-                    if lds:
-                        hazards.append(("never waited for before the end of the program", ld_text, l))
+                if l.startswith("s_endpgm"):                      # no load may be outstanding when the wave ends
+                    hazards.append(("never waited for before the end of the program", ld_text, l))
                     break
                 if l.startswith("s_branch"):
                     idx = label_at[l.split()[1]]
@@ -160,6 +197,13 @@ def main():
                 for kind, ld, use in hz[:10]:
                     print("   ", kind, "|", ld, "|", use)
                 bad += len(hz)
+            if not u["x"]:                                     # the unit of the fp32 kernels: scratch and code size
+                found, wrong = check_resources(lines)
+                for k, what in wrong:
+                    print("   ", k, "|", what)
+                if found != 4:
+                    print(f"    ({found} fp32 inference instances found, 4 expected: RESOURCE_RULE no longer names them)")
+                bad += len(wrong) + (found != 4)
             if checked == 0:                                   # both units have such kernels: their loads were not recognised
                 print(f"    (no kernel with an inline-asm load found in {os.path.basename(u['src'])})")
                 bad += 1

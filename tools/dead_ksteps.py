@@ -69,6 +69,23 @@ def dead_ksteps(h):
     return off[:, pairs[:, 0]] & off[:, pairs[:, 1]]
 
 
+def dead_groups(dead):
+    """dead bool [tiles, 128] (dead_ksteps) -> (all_dead, leading, runs), int64 [tiles] each, over the 32 four-k-step groups of a
+    GEMM: groups whose four k-steps are all dead; the length of the run of such groups the GEMM starts with (the kernel steps
+    over it: gemm_tiles, leading dead groups -- but never over the last group, which is counted here all the same); and the
+    number of maximal runs of such groups."""
+    g = dead.reshape(dead.shape[0], -1, 4).all(dim=-1)                              # [tiles, 32]
+    leading = g.long().cumprod(dim=1).sum(dim=1)
+    starts = g & ~torch.cat([torch.zeros_like(g[:, :1]), g[:, :-1]], dim=1)
+    return g.long().sum(dim=1), leading, starts.long().sum(dim=1)
+
+
+def stepped_over(leading):
+    """The groups the kernel really steps over, from dead_groups' leading run: the last group of a GEMM always runs (it issues
+    the next GEMM's prefetch), so a wholly dead input counts 31, not 32.  Trunk GEMMs only: the views GEMM has no group path."""
+    return leading.clamp(max=31)
+
+
 def tile_activations(sd, prefix, pts, viewdirs):
     """pts [n, S, 3] (S a multiple of 32), viewdirs [n, 3] -> (raw [n*S/32, 32, 4], {name: [n*S/32, 32, C]}), fp32 on the CPU."""
     n, S, _ = pts.shape
@@ -102,8 +119,12 @@ def count(raw, acts, density_only, skip_dead_colour, orders=None):
         issued = ksteps * ntiles * runs.float().mean().item()                       # per mean tile, nothing skipped
         frac_dead = frac_off = frac_re = None
         remain = remain_re = issued
+        grp = {}                                                                    # per mean tile, over all tiles (as kstep_dead)
+        mean_run = lambda x: x.float().mean().item()
         if src is not None:
             dead = dead_ksteps(acts[src])
+            grp.update(zip(("groups_dead", "groups_leading", "group_runs"), map(mean_run, dead_groups(dead))))
+            grp["groups_stepped"] = 0.0 if is_colour else mean_run(stepped_over(dead_groups(dead)[1]))
             frac_dead = dead.float().mean().item()                                  # over all tiles (the table of the issue)
             frac_off = (acts[src] == 0).all(dim=1).float().mean().item()
             remain = remain_re = ((~dead).float().sum(dim=1) * runs.float()).mean().item() * ntiles
@@ -111,8 +132,11 @@ def count(raw, acts, density_only, skip_dead_colour, orders=None):
                 dead_re = dead_ksteps(acts[src][:, :, torch.as_tensor(orders[src], dtype=torch.long)])
                 frac_re = dead_re.float().mean().item()
                 remain_re = ((~dead_re).float().sum(dim=1) * runs.float()).mean().item() * ntiles
+                grp.update(zip(("groups_dead_repaired", "groups_leading_repaired", "group_runs_repaired"),
+                               map(mean_run, dead_groups(dead_re))))
+                grp["groups_stepped_repaired"] = 0.0 if is_colour else mean_run(stepped_over(dead_groups(dead_re)[1]))
         rows.append(dict(gemm=name, ksteps=ksteps, ntiles=ntiles, feature_off=frac_off, kstep_dead=frac_dead,
-                         mfma=issued, mfma_left=remain, kstep_dead_repaired=frac_re, mfma_left_repaired=remain_re))
+                         mfma=issued, mfma_left=remain, kstep_dead_repaired=frac_re, mfma_left_repaired=remain_re, **grp))
         total += issued
         left += remain
         left_re += remain_re
@@ -177,6 +201,21 @@ def main():
               + (f" {'':>10} {r['mfma_left_repaired']:10.1f}" if re_paired else "")
               + f"   ({100 * (1 - r['mfma_left'] / r['mfma']):.1f} % skipped"
               + (f", re-paired {100 * (1 - r['mfma_left_repaired'] / r['mfma']):.1f} %)" if re_paired else ")"))
+        # all-dead 4-k-step groups (of 32 per GEMM) per mean tile: all of them, those in the GEMM's leading run, number of runs
+        # and "stepped": what the kernel steps over -- the leading run without a GEMM's last group, trunk GEMMs only
+        print(f"  {'groups (of 32)':<20} {'all dead':>9} {'leading':>9} {'runs':>6} {'stepped':>8}"
+              + (f"   {'re-paired:':>10} {'all dead':>9} {'leading':>9} {'runs':>6} {'stepped':>8}" if re_paired else ""))
+        tot = [0.0] * 8
+        for row in r["rows"]:
+            if "groups_dead" not in row:
+                continue
+            v = [row["groups_dead"], row["groups_leading"], row["group_runs"], row["groups_stepped"]]
+            v += [row.get(k + "_repaired", 0.0) for k in ("groups_dead", "groups_leading", "group_runs", "groups_stepped")]
+            tot = [a + b for a, b in zip(tot, v)]
+            print(f"  {row['gemm']:<20} {v[0]:9.2f} {v[1]:9.2f} {v[2]:6.2f} {v[3]:8.2f}"
+                  + (f"   {'':>10} {v[4]:9.2f} {v[5]:9.2f} {v[6]:6.2f} {v[7]:8.2f}" if re_paired else ""))
+        print(f"  {'sum':<20} {tot[0]:9.2f} {tot[1]:9.2f} {tot[2]:6.2f} {tot[3]:8.2f}"
+              + (f"   {'':>10} {tot[4]:9.2f} {tot[5]:9.2f} {tot[6]:6.2f} {tot[7]:8.2f}" if re_paired else ""))
     if args.json:
         with open(args.json, "w") as f:
             json.dump(dict(ckpt=os.path.basename(args.ckpt), family=args.family, rays=args.rays, seed=args.seed,

@@ -160,7 +160,7 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
     const bool exact_coarse = fp16 && fast_sampling && n_importance;
     rc = forward_rays(entry, o, d, tc, tcs, nb, NERF_N_SAMPLES, exact_coarse ? (const char*)packed_coarse + nerf::kF16PackedBytes : packed_coarse,
                       w.raw_c, false, nullptr, n_importance != 0, false, exact_coarse ? NERF_PREC_F32X : precision, stream,
-                      cull_c ? w.index_c : nullptr, cull_c ? w.count : nullptr);
+                      cull_c ? w.index_c : nullptr, cull_c ? w.count : nullptr, kRenderTileRaysLog2);
     if (rc) return rc;
     rc = tally(0, cull_c, nb * NERF_N_SAMPLES);
     if (rc) return rc;
@@ -197,7 +197,8 @@ static int32_t render_frame(const char* entry, const float* rays_o, const float*
       if (rc) return rc;
     }
     if (!fast_sampling && !cull_f) {
-      rc = forward_rays(entry, o, d, w.t_sorted, S, nb, (int32_t)S, packed_fine, w.raw_f, false, nullptr, false, true, precision, stream);
+      rc = forward_rays(entry, o, d, w.t_sorted, S, nb, (int32_t)S, packed_fine, w.raw_f, false, nullptr, false, true, precision, stream, nullptr,
+                        nullptr, kRenderTileRaysLog2);
       if (rc) return rc;
       if (guard) {
         rc = far_plane_guard(w.t_sorted, S, (int32_t)S, packed_fine, w.raw_f);

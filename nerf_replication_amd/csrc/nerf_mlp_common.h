@@ -85,6 +85,10 @@ struct MlpArgs {
   long long t_ray_stride;  // 0: all rays share one t table
   long long n_points;      // P = N*S
   int n_samples;           // S
+  int tile_rays_log2;      // fp32 inference ray instances without a list: a tile is (1 << lg) neighbouring rays by (32 >> lg) consecutive
+                           // samples instead of 32 consecutive samples of one ray (0) -- shorter along the ray, so more k-steps are dead
+                           // tile-wide; raw is bit-identical.  forward_rays: 0 unless (32 >> lg) divides n_samples.
+                           // Sits in what was padding behind n_samples: no other field moves and no other kernel's ISA changes
   const float* packed;     // nerf_layout.h packed model
   float* raw;              // [P,4] = (r,g,b,sigma) pre-activation
   const int* index;        // optional (ray mode): compacted list of point ids to evaluate (masked fine pass)

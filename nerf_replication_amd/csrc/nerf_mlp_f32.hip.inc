@@ -449,16 +449,37 @@ void nerf_mlp_f32_kernel(MlpArgs a) {
   const int wave = threadIdx.x >> 6;
   const int h = lane >> 5;
   const long long n_points = a.index ? (long long)*a.count : a.n_points;   // masked pass: device-side count
-  const long long base = ((long long)blockIdx.x * (blockDim.x >> 6) + wave) * kTilePts;
-  if (base >= n_points) return;                        // whole wave idle (no barriers in this kernel)
-  {
+  const long long tile = (long long)blockIdx.x * (blockDim.x >> 6) + wave;
+  const long long base = tile * kTilePts;
+  // Tile shape (MlpArgs::tile_rays_log2, inference ray instances, no list): tile T holds R = 1 << lg neighbouring rays by
+  // sps = 32 >> lg consecutive samples; q = n_samples / sps tiles cover one group of R rays.  Everything below the prologue
+  // sees (p, ray, s, valid) per lane and nothing else, so the shape changes which k-steps are dead, never a value.
+  const int lg = (RAY_MODE && !SAVE) ? a.tile_rays_log2 : 0;
   const long long pl = base + (lane & 31);
-  const bool valid = pl < n_points;
-  const long long plc = valid ? pl : n_points - 1;
-  const long long p = a.index ? (long long)a.index[plc] : plc;     // global point id (output slot)
+  long long p, ray;                                    // global point id (output slot), its ray
+  int s;
+  bool valid;
+  if (lg != 0) {
+    const long long n_rays = n_points / a.n_samples;
+    const int q = a.n_samples >> (5 - lg);
+    const long long g = tile / q;                      // ray group
+    if ((g << lg) >= n_rays) return;                   // whole wave idle: T >= ceil(n_rays / R) * q
+    const int j = lane & 31;
+    const long long r = (g << lg) + (j >> (5 - lg));
+    valid = r < n_rays;
+    ray = valid ? r : n_rays - 1;                      // ragged group: repeat the last ray's point, store nothing
+    s = ((int)(tile - g * q) << (5 - lg)) + (j & ((32 >> lg) - 1));
+    p = ray * a.n_samples + s;
+  } else {
+    if (base >= n_points) return;                      // whole wave idle (no barriers in this kernel)
+    valid = pl < n_points;
+    const long long plc = valid ? pl : n_points - 1;
+    p = a.index ? (long long)a.index[plc] : plc;
+    ray = p / a.n_samples;
+    s = (int)(p - ray * a.n_samples);
+  }
+  {
   const long long pc = p;
-  const long long ray = pc / a.n_samples;
-  const int s = (int)(pc - ray * a.n_samples);
 
   // 12 KiB per wave of the workgroup, + 1 KiB behind it for the folded views bias (instances with a colour branch)
   constexpr int kTailLds = kTailFloats + (DENS ? 0 : 256);

@@ -34,6 +34,21 @@ int dead_group_skip_wanted() {
   return dead_kstep_skip_wanted() && !(env && env[0] == '0');
 }
 
+// ------------------------------------------------------------------------------------ tile shape (fp32 inference ray instances)
+// NERF_TILE_RAYS = 1, 2, 4, 8, 16 or 32: rays per 32-point tile (MlpArgs::tile_rays_log2), read per launch.  Unset (or any other
+// value): the caller's default -- render_frame's dense launches ask for kRenderTileRaysLog2, the direct entries for one-ray tiles.
+constexpr int kRenderTileRaysLog2 = 3;
+int tile_rays_log2_wanted(int dflt) {
+  const char* env = getenv("NERF_TILE_RAYS");
+  if (!env) return dflt;
+  for (int lg = 0; lg <= 5; ++lg) {
+    char want[4];
+    snprintf(want, sizeof want, "%d", 1 << lg);
+    if (!strcmp(env, want)) return lg;
+  }
+  return dflt;
+}
+
 }  // namespace
 
 extern "C" {
@@ -90,7 +105,13 @@ static int launch_mlp(const MlpArgs& a_in, bool ray_mode, bool save, int precisi
   a.skip_dead_ksteps = dead_kstep_skip_wanted();
   a.skip_dead_groups = dead_group_skip_wanted();
   if (f->persistent) return launch(f->name, k, dim3(persistent_blocks(a.n_points, f->wg_pts)), dim3(f->threads), st, a);
-  const long long blocks = (a.n_points + f->wg_pts - 1) / f->wg_pts;
+  // shaped tiles (forward_rays): ceil(n_rays / R) ray groups of n_samples / (32 >> lg) tiles, i.e. the points of whole groups
+  long long grid_pts = a.n_points;
+  if (a.tile_rays_log2) {
+    const long long R = 1LL << a.tile_rays_log2;
+    grid_pts = (a.n_points / a.n_samples + R - 1) / R * R * a.n_samples;
+  }
+  const long long blocks = (grid_pts + f->wg_pts - 1) / f->wg_pts;
   if (blocks > 0x7fffffffLL) return fail(NERF_ERR_INVALID_ARG, "%s: too many points for one launch", entry);
   return launch(f->name, k, dim3((unsigned)blocks), dim3(f->threads), st, a);
 }
@@ -100,7 +121,8 @@ static int launch_mlp(const MlpArgs& a_in, bool ray_mode, bool save, int precisi
 // index / count (masked): rows of index[j] at slot j, `raw` at the id (every instance honours both).
 static int forward_rays(const char* entry, const float* rays_o, const float* rays_d, const float* tvals, int64_t t_ray_stride, int64_t n_rays,
                         int32_t n_samples, const void* packed, float* raw, bool want_save, float* save, bool density_only,
-                        bool for_compositing, int32_t precision, void* stream, const int* index = nullptr, const int* count = nullptr) {
+                        bool for_compositing, int32_t precision, void* stream, const int* index = nullptr, const int* count = nullptr,
+                        int tile_rays_log2 = 0) {
   if (n_rays < 0 || n_samples <= 0 || t_ray_stride < 0) return fail(NERF_ERR_INVALID_ARG, "%s: bad size", entry);
   if (n_rays == 0) return NERF_OK;
   if (!rays_o || !rays_d || !tvals || !packed || !raw || (want_save && !save)) return fail(NERF_ERR_INVALID_ARG, "%s: null argument", entry);
@@ -109,6 +131,9 @@ static int forward_rays(const char* entry, const float* rays_o, const float* ray
   a.n_points = n_rays * n_samples; a.n_samples = n_samples; a.packed = (const float*)packed; a.raw = raw; a.save = save;
   a.density_only = density_only; a.skip_dead_colour = for_compositing;
   a.index = index; a.count = count;
+  // tile shape: the fp32 inference instances without a list, and only where a tile's samples divide the ray
+  const int lg = tile_rays_log2_wanted(tile_rays_log2);
+  a.tile_rays_log2 = precision == NERF_PREC_F32 && !index && !want_save && n_samples % (32 >> lg) == 0 ? lg : 0;
   if (want_save) {
     // without dead-tile skipping in the backward pass every row must exist: fall back to the full store (the SAME helper decides
     // for the backward pass).  The buffer is stamped with what is done here: 1 = the rows of density-free tiles are NOT stored

@@ -14,6 +14,12 @@ NERF_DEAD_KSTEP_SKIP is set against, and what corrects bench.py's roofline figur
 (seed + 1) with the library's rule in its restatement (tests/unit_order_reference.py), evaluated on the same tiles as today's.
 
     python tools/dead_ksteps.py --family base --rays 256 --calibrate-rays 16
+
+--tile-rays R (2, 4, 8, 16, 32) cuts the tiles as the kernel does under NERF_TILE_RAYS=R ("Tile shape"): the
+evaluation rays come as seeded runs of R consecutive pixels, and a tile is R neighbouring rays by 32 / R consecutive samples.  The
+calibration rays stay scattered and their tiles one-ray, as the library forms unit orders.
+
+    python tools/dead_ksteps.py --family base --rays 512 --calibrate-rays 16 --tile-rays 4
 """
 import argparse
 import json
@@ -86,7 +92,16 @@ def stepped_over(leading):
     return leading.clamp(max=31)
 
 
-def tile_activations(sd, prefix, pts, viewdirs):
+def regroup(x, n, S, tile_rays=1):
+    """x [n * S, C], point (ray, sample) at row ray * S + sample -> [n * S / 32, 32, C] in the kernel's tiles: tile T of ray group
+    g = T // q (q = S / s, s = 32 / R) holds rays g R .. g R + R - 1 by samples c s .. c s + s - 1 (c = T - g q), lane slot
+    j = (ray - g R) s + (sample - c s).  R = 1: 32 consecutive samples of one ray."""
+    R, s = tile_rays, TILE // tile_rays
+    assert TILE % R == 0 and n % R == 0 and S % s == 0
+    return x.reshape(n // R, R, S // s, s, -1).permute(0, 2, 1, 3, 4).reshape(n * S // TILE, TILE, -1)
+
+
+def tile_activations(sd, prefix, pts, viewdirs, tile_rays=1):
     """pts [n, S, 3] (S a multiple of 32), viewdirs [n, 3] -> (raw [n*S/32, 32, 4], {name: [n*S/32, 32, C]}), fp32 on the CPU."""
     n, S, _ = pts.shape
     assert S % TILE == 0
@@ -99,7 +114,7 @@ def tile_activations(sd, prefix, pts, viewdirs):
             outs.append(raw)
             for k, v in a.items():
                 acts.setdefault(k, []).append(v)
-    tiles = lambda x: x.reshape(n * S // TILE, TILE, -1)
+    tiles = lambda x: regroup(x, n, S, tile_rays)
     return tiles(torch.cat(outs)), {k: tiles(torch.cat(v)) for k, v in acts.items()}
 
 
@@ -144,22 +159,36 @@ def count(raw, acts, density_only, skip_dead_colour, orders=None):
                 mfma_left_repaired=left_re)
 
 
-def launch_tiles(sd, n_rays, seed, H=800, W=800, theta=40.0):
-    """{"coarse" / "fine": (raw, acts)} of the two launches of a render of `n_rays` seeded rays of the bench frame."""
-    ids = torch.randperm(H * W, generator=torch.Generator().manual_seed(seed))[:n_rays]
+def pixel_runs(n_rays, seed, tile_rays=1, H=800, W=800):
+    """Pixel ids of `n_rays` seeded rays: n_rays / R runs of R consecutive pixels of one image row (R = 1: scattered pixels)."""
+    R = tile_rays
+    assert n_rays % R == 0 and W % R == 0
+    starts = torch.randperm(H * W // R, generator=torch.Generator().manual_seed(seed))[:n_rays // R] * R
+    return (starts[:, None] + torch.arange(R)).reshape(-1)
+
+
+def launch_tiles(sd, n_rays, seed, H=800, W=800, theta=40.0, tile_rays=1, run_rays=None):
+    """{"coarse" / "fine": (raw, acts)} of the two launches of a render of `n_rays` seeded rays of the bench frame, in tiles of
+    `tile_rays` rays (regroup).  The rays are runs of `run_rays` consecutive pixels (default: tile_rays; a multiple of it lets
+    two tile shapes be compared on the same rays)."""
+    run_rays = tile_rays if run_rays is None else run_rays
+    assert run_rays % tile_rays == 0
+    ids = pixel_runs(n_rays, seed, run_rays, H, W)
     o, d = orc.pinhole_rays(H, W, orc.camera_pose(theta), pixel_ids=ids)
     with torch.no_grad():
         _, _, parts = orc.render(sd, o[None], d[None], return_parts=True)
     vd = parts["viewdirs"]
-    return {key: tile_activations(sd, prefix, orc.points_on_rays(o, d, t), vd)
+    return {key: tile_activations(sd, prefix, orc.points_on_rays(o, d, t), vd, tile_rays)
             for key, prefix, t in (("coarse", "model", parts["t_coarse"]), ("fine", "model_fine", parts["t_sorted"]))}
 
 
-def probe(sd, n_rays=768, seed=0, H=800, W=800, theta=40.0, calibrate_rays=0):
+def probe(sd, n_rays=768, seed=0, H=800, W=800, theta=40.0, calibrate_rays=0, tile_rays=1, run_rays=None):
     """Coarse (64 samples, density only) and fine (192 sorted samples, dead-colour skip) launches of a render of `n_rays` seeded
     rays of the bench frame -> {"coarse": count(...), "fine": count(...)}.  calibrate_rays > 0: with the unit orders matched from
-    that many rays of seed + 1, as Renderer.calibrate_unit_order forms them (per model, from its own launch's tiles)."""
-    tiles = launch_tiles(sd, n_rays, seed, H, W, theta)
+    that many rays of seed + 1, as Renderer.calibrate_unit_order forms them (per model, from its own launch's one-ray tiles).
+    tile_rays: the evaluation tiles are that many neighbouring rays by 32 / tile_rays samples (NERF_TILE_RAYS); run_rays as in
+    launch_tiles."""
+    tiles = launch_tiles(sd, n_rays, seed, H, W, theta, tile_rays, run_rays)
     orders = {"coarse": None, "fine": None}
     if calibrate_rays > 0:
         cal = launch_tiles(sd, calibrate_rays, seed + 1, H, W, theta)
@@ -181,11 +210,15 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--calibrate-rays", type=int, default=0, metavar="N",
                     help="also print the re-paired column: unit orders matched from N rays of seed + 1")
+    ap.add_argument("--tile-rays", type=int, default=1, choices=(1, 2, 4, 8, 16, 32), metavar="R",
+                    help="evaluate on tiles of R neighbouring rays by 32 / R samples (runs of R consecutive pixels)")
     ap.add_argument("--json", help="also write the figures to this file")
     args = ap.parse_args()
-    res = probe(load_family(args.ckpt, args.family), args.rays, args.seed, calibrate_rays=args.calibrate_rays)
+    res = probe(load_family(args.ckpt, args.family), args.rays, args.seed, calibrate_rays=args.calibrate_rays,
+                tile_rays=args.tile_rays)
     trunk, col = layout_mfmas()
-    print(f"{os.path.basename(args.ckpt)} family={args.family} rays={args.rays} seed={args.seed}; "
+    print(f"{os.path.basename(args.ckpt)} family={args.family} rays={args.rays} seed={args.seed}"
+          + (f" tile={args.tile_rays} rays x {TILE // args.tile_rays} samples" if args.tile_rays != 1 else "") + "; "
           f"a full tile issues {trunk} + {col} MFMAs (nerf_layout.h)")
     for key in ("coarse", "fine"):
         r = res[key]
@@ -219,7 +252,8 @@ def main():
     if args.json:
         with open(args.json, "w") as f:
             json.dump(dict(ckpt=os.path.basename(args.ckpt), family=args.family, rays=args.rays, seed=args.seed,
-                           calibrate_rays=args.calibrate_rays, **res), f, indent=1)
+                           calibrate_rays=args.calibrate_rays,
+                           **({"tile_rays": args.tile_rays} if args.tile_rays != 1 else {}), **res), f, indent=1)
     return 0
 
 

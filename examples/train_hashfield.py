@@ -5,10 +5,13 @@ teacher setup of examples/train_synthetic.py (renders of tests/golden/synthetic_
 
     python examples/train_hashfield.py --steps 600
     python examples/train_hashfield.py --steps 600 --occupancy 64 --refresh-every 16      # cull empty space while training
+    python examples/train_hashfield.py --steps 600 --n-samples 64 --importance 64 --perturb   # resample from the field's own density
 
 --occupancy N rebuilds an N^3 occupancy grid from the field itself (HashField.occupancy_grid) every --refresh-every steps; a grid made
 from fields carries no staleness key, so this loop owns the schedule; the first --occupancy-from steps run unculled.  Prints ms per
-step and the held-out PSNR.  --deterministic-table sums the hash table's gradient exactly and order-independently
+step and the held-out PSNR.  --n-samples Sc --importance Sf renders every ray on Sc coarse depths plus Sf depths drawn from the weights
+of a density-only coarse pass (HashRenderer.N_importance); --perturb jitters the coarse depths inside their strata and draws random u
+while training (the held-out evaluation renders with perturb off).  --deterministic-table sums the hash table's gradient exactly and order-independently
 (HashEncoder(deterministic=True)); the two networks' weight and bias gradients then keep their fp32 atomics.  --deterministic turns
 on the table and both networks together (HashField(deterministic=True)): every sum of the step is exact and order-independent, and
 two runs from one seed end with the same parameters, byte for byte -- the last line printed is then a digest of them.
@@ -40,7 +43,13 @@ def main():
                     help="training views on the ring (train_synthetic.py uses 16: enough for the MLP's smooth prior, while a hash grid "
                          "fits 16 views to 45 dB and the held-out one to 15)")
     ap.add_argument("--res", type=int, default=200)
-    ap.add_argument("--samples", type=int, default=192, help="depths per ray (HashRenderer.N_samples, 1..192)")
+    ap.add_argument("--samples", "--n-samples", dest="samples", type=int, default=192,
+                    help="depths per ray (HashRenderer.N_samples, 1..192); with --importance the coarse count")
+    ap.add_argument("--importance", type=int, default=0, metavar="SF",
+                    help="fine depths per ray, resampled from the coarse pass's weights (HashRenderer.N_importance; "
+                         "--n-samples + SF <= 192)")
+    ap.add_argument("--perturb", action="store_true",
+                    help="train on jittered coarse depths and random u (HashRenderer.perturb); evaluation stays deterministic")
     ap.add_argument("--levels", type=int, default=16)
     ap.add_argument("--log2-hashmap-size", type=int, default=19)
     ap.add_argument("--lr", type=float, default=1e-2)
@@ -82,9 +91,9 @@ def main():
     half = float(args.half_extent)
     field = nerf.HashField((-half, -half, -half, half, half, half), encoder=encoder, deterministic=args.deterministic).cuda()
     ren = nerf.HashRenderer(field)                             # the held-out evaluation: never culled
-    ren.N_samples = args.samples
+    ren.N_samples, ren.N_importance = args.samples, args.importance
     train_ren = nerf.HashRenderer(field)
-    train_ren.N_samples = args.samples
+    train_ren.N_samples, train_ren.N_importance, train_ren.perturb = args.samples, args.importance, args.perturb
     if args.occupancy:
         train_ren.stats = []
     opt = FusedAdam(field.parameters(), lr=args.lr, eps=1e-15, clip_value=40.0)

@@ -202,6 +202,18 @@ ORDER_SIGNATURES = _parse_table(_TABLE_ORDER)
 ORDER_EXPORTS = tuple(ORDER_SIGNATURES)
 _ORDER_PROTOS = _protos(ORDER_SIGNATURES)
 
+# Where the samples of a hash-field ray lie, one line per entry of include/nerf_mi355x_sampling.h (one more header of the same library,
+# next to nerf_mi355x_field.h; the six tables above are pinned at their sizes).  tests/test_hashfield_sampling_cpu.py compares this
+# table with that header.
+_TABLE_SAMPLING = """
+nerf_field_sample_importance  status : f32* f32* i64 f32* i64 i64 i32 i32 f32* f32* stream
+nerf_field_stratified_depths  status : f32* f32* i64 i32 f32* stream
+nerf_field_density_scatter  status : f32* i64 i32* i64 i64 f32* stream
+"""
+SAMPLING_SIGNATURES = _parse_table(_TABLE_SAMPLING)
+SAMPLING_EXPORTS = tuple(SAMPLING_SIGNATURES)
+_SAMPLING_PROTOS = _protos(SAMPLING_SIGNATURES)
+
 _lib = None
 
 
@@ -229,7 +241,8 @@ def load():
                 "there is no CPU fallback for the render path")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_PROTOS.items()) + list(_NN_PROTOS.items()) + list(_FIELD_PROTOS.items()) +
-                                  list(_HASHGRID_PROTOS.items()) + list(_NN_EXACT_PROTOS.items()) + list(_ORDER_PROTOS.items())):
+                                  list(_HASHGRID_PROTOS.items()) + list(_NN_EXACT_PROTOS.items()) + list(_ORDER_PROTOS.items()) +
+                                  list(_SAMPLING_PROTOS.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.nerf_abi_version() != 3:
@@ -254,9 +267,11 @@ class strided:
 def call(name, *args):
     """Call entry `name` of the library with `args` as its header lists them, minus the stream: tensors (None: NULL) for device
     pointers, numbers for scalars, sequences or ctypes arrays for host arrays.  Every argument is checked against the entry's kinds
-    in SIGNATURES (or, looked up in this order, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES, ORDER_SIGNATURES) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
+    in SIGNATURES (or, looked up in this order, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES, ORDER_SIGNATURES,
+    SAMPLING_SIGNATURES) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
     is checked (NerfLibraryError with nerf_last_error's text); any other return value comes back as it is."""
-    for table in (SIGNATURES, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES, ORDER_SIGNATURES):
+    for table in (SIGNATURES, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES, ORDER_SIGNATURES,
+                  SAMPLING_SIGNATURES):
         if name in table:
             break
     ret, kinds = table[name]

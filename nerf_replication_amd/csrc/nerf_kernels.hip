@@ -55,6 +55,8 @@
 #include "nerf_fused_mlp_exact.hip.inc"
 // ---- hash-grid radiance field, the ray-side glue (include/nerf_mi355x_nn.h): nerf_sh4_encode, nerf_field_*
 #include "nerf_hashfield.hip.inc"
+// ---- where its samples lie (include/nerf_mi355x_sampling.h): nerf_field_sample_importance, nerf_field_stratified_depths
+#include "nerf_field_sampling.hip.inc"
 
 extern "C" {
 

@@ -10,7 +10,9 @@ The encoder runs on hash_encode, the two networks on fused_mlp, the grid lookup 
 image on nerf_composite, all as they are; what lies between them on the ray side (sample positions, the SH basis, the colour
 network's input rows, the scatter into `raw`) are the HIP kernels of csrc/nerf_hashfield.hip.inc (include/nerf_mi355x_nn.h has every
 formula).  The spatial adjoint of that glue -- the density gradient, the geometry outputs, gradients with respect to the rays --
-is DESIGN.md section 2.14.1, its formulas in include/nerf_mi355x_field.h.  No ATen op computes on the render path: torch allocates,
+is DESIGN.md section 2.14.1, its formulas in include/nerf_mi355x_field.h.  Where the samples of a ray lie -- one shared table, or
+depths resampled from the field's own density (HashRenderer.N_importance) with stratified jitter (HashRenderer.perturb) -- is
+DESIGN.md section 2.14.2, include/nerf_mi355x_sampling.h; the random draws of perturb are torch.rand.  No other ATen op computes on the render path: torch allocates,
 zero-fills and slices.  fp32 only; CPU tensors raise NerfLibraryError: there is no eager fallback.
 
 One host synchronisation per chunk on the culled path (HashRenderer.occupancy set): the number of surviving samples is read back,
@@ -72,15 +74,15 @@ class _RayInputs(torch.autograd.Function):
     takes (g_x, g_sh) and writes g_o and g_d once: nerf_sh4_encode_backward, then nerf_field_points_backward with its view term."""
 
     @staticmethod
-    def forward(ctx, o, d, t, index, M, S, frame):
+    def forward(ctx, o, d, t, index, M, S, frame, stride=0):
         o, d = o.detach().contiguous(), d.detach().contiguous()
         n = o.shape[0]
         x = torch.empty(M, 3, dtype=torch.float32, device=o.device)
-        _lib.call("nerf_field_points", o, d, t, 0, n, S, index, M, *frame, x)
+        _lib.call("nerf_field_points", o, d, t, stride, n, S, index, M, *frame, x)
         sh = torch.empty(n, SH_DIM, dtype=torch.float32, device=o.device)
         _lib.call("nerf_sh4_encode", d, n, sh)
         ctx.save_for_backward(o, d, t)
-        ctx.index, ctx.M, ctx.S, ctx.frame = index, M, S, frame
+        ctx.index, ctx.M, ctx.S, ctx.frame, ctx.stride = index, M, S, frame, stride
         ctx.set_materialize_grads(False)
         return x, sh
 
@@ -95,8 +97,8 @@ class _RayInputs(torch.autograd.Function):
             _lib.call("nerf_sh4_encode_backward", d, g_sh.contiguous(), n, g_view)
         g_x = torch.zeros(M, 3, dtype=torch.float32, device=o.device) if g_x is None else g_x.contiguous()
         g_o, g_d = torch.empty_like(o), torch.empty_like(d)
-        _lib.call("nerf_field_points_backward", o, d, t, 0, n, ctx.S, ctx.index, M, *ctx.frame, g_x, g_view, 0, None, g_o, g_d)
-        return g_o, g_d, None, None, None, None, None
+        _lib.call("nerf_field_points_backward", o, d, t, ctx.stride, n, ctx.S, ctx.index, M, *ctx.frame, g_x, g_view, 0, None, g_o, g_d)
+        return g_o, g_d, None, None, None, None, None, None
 
 
 class _ColorInputs(torch.autograd.Function):
@@ -147,17 +149,17 @@ class _RawScatter(torch.autograd.Function):
 
 class _Composite(torch.autograd.Function):
     """raw [n,S,4] -> (rgb [n,3], depth [n]) by nerf_composite; the backward is nerf_composite_backward with g_t = NULL (the depths
-    are constants)."""
+    are constants, also where they are a table per ray: stride = S)."""
 
     @staticmethod
-    def forward(ctx, raw, tvals, white):
+    def forward(ctx, raw, tvals, white, stride=0):
         raw = raw.detach()
         n, S = raw.shape[0], raw.shape[1]
         rgb = torch.empty(n, 3, dtype=torch.float32, device=raw.device)
         depth = torch.empty(n, dtype=torch.float32, device=raw.device)
-        _lib.call("nerf_composite", raw, tvals, 0, n, S, white, rgb, depth, None)
+        _lib.call("nerf_composite", raw, tvals, stride, n, S, white, rgb, depth, None)
         ctx.save_for_backward(raw, tvals)
-        ctx.white = white
+        ctx.white, ctx.stride = white, stride
         ctx.set_materialize_grads(False)
         return rgb, depth
 
@@ -169,8 +171,8 @@ class _Composite(torch.autograd.Function):
         g_rgb = torch.zeros(n, 3, dtype=torch.float32, device=raw.device) if g_rgb is None else g_rgb.contiguous()
         g_depth = None if g_depth is None else g_depth.contiguous()
         g_raw = torch.empty_like(raw)
-        _lib.call("nerf_composite_backward", raw, tvals, 0, n, S, ctx.white, g_rgb, g_depth, g_raw, None)
-        return g_raw, None, None
+        _lib.call("nerf_composite_backward", raw, tvals, ctx.stride, n, S, ctx.white, g_rgb, g_depth, g_raw, None)
+        return g_raw, None, None, None
 
 
 class HashField(nn.Module):
@@ -390,8 +392,15 @@ class HashRenderer:
     """Renderer's call surface over a HashField: render(batch) -> (rgb [B*N,3], depth [B*N]) with batch["rays_o"], batch["rays_d"]
     [B,N,3] on the GPU.
 
-    N_samples (192; any int in [1, 192]) depths per ray, one shared table linspace(t_near, t_far, N_samples); no hierarchical pass
-    and no jitter.  white_bkgd (True).  occupancy: None, or an OccupancyGrid with a fine bitfield (HashField.occupancy_grid): the
+    N_samples (192; any int in [1, 192]) depths per ray, one shared table linspace(t_near, t_far, N_samples).  N_importance (0; with
+    Sf = N_importance > 0, N_samples = Sc >= 3 is the coarse count and Sc + Sf <= 192): a coarse pass under no_grad -- the density
+    network alone on the Sc depths, nerf_composite's weights -- then nerf_field_sample_importance draws Sf more depths per ray from
+    those weights (u = linspace(0, 1, Sf)), and the image is rendered on the Sc + Sf merged depths.  The merged depths are constants:
+    no gradient reaches the coarse pass, the fine pass trains the one field.  perturb (False; True: the coarse depths are jittered
+    inside their strata, nerf_field_stratified_depths, and u is random; both come from _rand, drawn once per render() for all rays,
+    so torch.manual_seed controls the image and chunk_rays does not).  samples: None, or a list that receives (t_coarse,
+    weights_coarse, t_merged) per chunk with N_importance > 0.
+    white_bkgd (True).  occupancy: None, or an OccupancyGrid with a fine bitfield (HashField.occupancy_grid): the
     samples in empty cells are not evaluated and keep raw = 0 -- at the price of ONE HOST SYNCHRONISATION PER CHUNK, the count of the
     surviving samples.  stats: None, or a list that receives (evaluated, total) samples per chunk on the culled path.  chunk_rays
     (16384): rays per launch chain; the result does not depend on it.
@@ -408,6 +417,9 @@ class HashRenderer:
             raise TypeError("HashRenderer needs a HashField")
         self.field = field
         self.N_samples = MAX_SAMPLES
+        self.N_importance = 0
+        self.perturb = False
+        self.samples = None
         self.t_near, self.t_far = 2.0, 6.0
         self.white_bkgd = True
         self.occupancy = None
@@ -416,6 +428,7 @@ class HashRenderer:
         self.ray_gradients = False
         self.stats = None
         self._tables = {}
+        self._u_table = None
 
     @property
     def net(self):
@@ -429,11 +442,34 @@ class HashRenderer:
             t = self._tables[key] = torch.linspace(self.t_near, self.t_far, self.N_samples).to(dev)
         return t
 
+    def _get_u(self, dev):
+        """The u of the deterministic resampling, linspace(0, 1, N_importance), built on the CPU like the depth table."""
+        key = (dev, int(self.N_importance))
+        if self._u_table is None or self._u_table[0] != key:
+            self._u_table = (key, torch.linspace(0.0, 1.0, self.N_importance).to(dev))
+        return self._u_table[1]
+
+    def _rand(self, shape, device):
+        """The random draws of perturb = True (Renderer._rand's signature): torch.rand on the rays' device, so torch.manual_seed
+        controls the samples.  Overridable: tests replay recorded draws through it."""
+        return torch.rand(*shape, device=device)
+
     def _check(self, rays_o, rays_d, geometry=False):
         """Everything that is refused, before any launch or allocation -> the grid or None."""
         S = self.N_samples
         if isinstance(S, bool) or not isinstance(S, int) or not 1 <= S <= MAX_SAMPLES:
             raise ValueError(f"HashRenderer.N_samples must be an int in [1, {MAX_SAMPLES}], got {S!r}")
+        Sf = self.N_importance
+        if isinstance(Sf, bool) or not isinstance(Sf, int) or not 0 <= Sf <= MAX_SAMPLES - S:
+            raise ValueError(f"HashRenderer.N_importance must be an int in [0, {MAX_SAMPLES} - N_samples], got {Sf!r}")
+        if Sf > 0 and S < 3:
+            raise ValueError(f"HashRenderer.N_importance > 0 needs N_samples >= 3 coarse depths (one interior weight at least), got {S!r}")
+        if not isinstance(self.perturb, bool):
+            raise ValueError(f"HashRenderer.perturb must be a bool, got {self.perturb!r}")
+        if geometry and self.perturb:
+            raise NotImplementedError("HashRenderer.render_geometry: perturb = True is not supported (geometry is rendered on the "
+                                      "deterministic depths)")
+        S = S + Sf
         if isinstance(self.chunk_rays, bool) or not isinstance(self.chunk_rays, int) or self.chunk_rays < 1:
             raise ValueError(f"HashRenderer.chunk_rays must be an int >= 1 (rays), got {self.chunk_rays!r}")
         if not isinstance(self.ray_gradients, bool):
@@ -457,6 +493,9 @@ class HashRenderer:
             if not self.ray_gradients:
                 raise NotImplementedError("HashRenderer: rays that require grad are not supported (the ray adjoint runs only with "
                                           "HashRenderer.ray_gradients = True)")
+            if Sf > 0:
+                raise NotImplementedError("HashRenderer: rays that require grad are not supported with N_importance > 0 (the ray "
+                                          "adjoint through resampled depths is not built)")
         self.field._check_fp32()
         if not rays_o.is_cuda or not rays_d.is_cuda:
             raise _lib.NerfLibraryError("HashRenderer needs rays on a GPU (cuda) device; got a CPU tensor (there is no CPU fallback)")
@@ -464,7 +503,7 @@ class HashRenderer:
             raise ValueError(f"the occupancy grid is on {grid.device}, the rays on {rays_o.device}")
         return grid
 
-    def _survivors(self, o, d, t, S, grid):
+    def _survivors(self, o, d, t, S, grid, stride=0):
         """(index, M) of a chunk: the ascending list of the point ids in occupied cells and their number, (None, n * S) without a
         grid.  With a grid this is the chunk's host synchronisation, and `stats` gets its (evaluated, total)."""
         dev, n = o.device, o.shape[0]
@@ -472,7 +511,7 @@ class HashRenderer:
         if grid is None:
             return None, P
         valid = torch.empty(n, S, dtype=torch.uint8, device=dev)
-        _lib.call("nerf_occupancy_mark", o, d, t, 0, n, S, grid.bits["fine"], *grid.lookup_args(), 0, valid)
+        _lib.call("nerf_occupancy_mark", o, d, t, stride, n, S, grid.bits["fine"], *grid.lookup_args(), 0, valid)
         index = torch.empty(P, dtype=torch.int32, device=dev)
         count = torch.empty(1, dtype=torch.int32, device=dev)
         ws = torch.empty(int(_lib.call("nerf_compact_valid_workspace_bytes", P)), dtype=torch.uint8, device=dev)
@@ -482,27 +521,72 @@ class HashRenderer:
             self.stats.append((M, P))
         return index, M
 
-    def _chunk(self, o, d, t, S, grid, white):
-        """One chunk of n rays -> (rgb [n,3], depth [n]); every step is enqueued on the current stream."""
+    def _chunk(self, o, d, t, S, grid, white, stride=0):
+        """One chunk of n rays -> (rgb [n,3], depth [n]); every step is enqueued on the current stream.  t: the shared table [S]
+        (stride 0) or the chunk's own depths [n,S] (stride S)."""
         field, dev, n = self.field, o.device, o.shape[0]
-        index, M = self._survivors(o.detach(), d.detach(), t, S, grid)
+        index, M = self._survivors(o.detach(), d.detach(), t, S, grid, stride)
         if M == 0:
             raw = torch.zeros(n, S, 4, dtype=torch.float32, device=dev)
         else:
             if torch.is_grad_enabled() and (o.requires_grad or d.requires_grad):       # (only with ray_gradients: _check)
-                x, sh = _RayInputs.apply(o, d, t, index, M, S, field.frame())
+                x, sh = _RayInputs.apply(o, d, t, index, M, S, field.frame(), stride)
             else:
                 lo, hi, extent = field.frame()
                 x = torch.empty(M, 3, dtype=torch.float32, device=dev)
-                _lib.call("nerf_field_points", o, d, t, 0, n, S, index, M, lo, hi, extent, x)
+                _lib.call("nerf_field_points", o, d, t, stride, n, S, index, M, lo, hi, extent, x)
                 sh = torch.empty(n, SH_DIM, dtype=torch.float32, device=dev)
                 _lib.call("nerf_sh4_encode", d, n, sh)
             geo = field._geo(x)
             cin, sigma_rows = _ColorInputs.apply(geo, sh, index, M, n, S)
             raw = _RawScatter.apply(field._rgb(cin), sigma_rows, index, M, n, S)
-        return _Composite.apply(raw, t, white)
+        return _Composite.apply(raw, t, white, stride)
 
-    def _geometry_chunk(self, o, d, t, S, grid, white):
+    def _draws(self, n, dev):
+        """(jitter [n,Sc] or None, u, u's ray stride) of one render() call: with perturb the two _rand draws for ALL n rays, [n,Sc]
+        first, then [n,Sf] only if Sf > 0 (the chunks take slices, so the image does not depend on chunk_rays); without, no jitter
+        and the shared table linspace(0, 1, Sf).  u is None when N_importance is 0."""
+        Sc, Sf = self.N_samples, self.N_importance
+        if not self.perturb:
+            return None, (self._get_u(dev) if Sf > 0 else None), 0
+        jitter = self._rand((n, Sc), dev).to(torch.float32).contiguous()
+        u = self._rand((n, Sf), dev).to(torch.float32).contiguous() if Sf > 0 else None
+        return jitter, u, Sf
+
+    def _depths(self, o, d, table, jitter, u, grid, white):
+        """The depths one chunk of n rays is rendered on -> (t, S, ray stride), all constants (computed under no_grad).
+        jitter [n,Sc] (or None): the coarse depths are nerf_field_stratified_depths of the table.  u (None: N_importance == 0) [Sf]
+        or [n,Sf]: the coarse pass -- the survivors of the grid through nerf_field_points, hash_encode and sigma_net only, their
+        densities scattered into a raw [n,Sc,4] (nerf_field_density_scatter), nerf_composite's weights -- and
+        nerf_field_sample_importance, which gives the merged depths [n,Sc+Sf].  `samples` gets (t_coarse, weights, t_merged)."""
+        field, dev, n = self.field, o.device, o.shape[0]
+        Sc, Sf = self.N_samples, self.N_importance
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            o, d = o.detach(), d.detach()
+            t, stride = table, 0
+            if jitter is not None:
+                t, stride = new(n, Sc), Sc
+                _lib.call("nerf_field_stratified_depths", table, jitter, n, Sc, t)
+            if u is None:
+                return t, Sc, stride
+            index, M = self._survivors(o, d, t, Sc, grid, stride)
+            raw = new(n, Sc, 4) if index is None else torch.zeros(n, Sc, 4, dtype=torch.float32, device=dev)
+            if M > 0:
+                x = new(M, 3)
+                _lib.call("nerf_field_points", o, d, t, stride, n, Sc, index, M, *field.frame(), x)
+                _lib.call("nerf_field_density_scatter", field._geo(x), GEO_DIM, index, M, n * Sc, raw)
+            weights, rgb, depth = new(n, Sc), new(n, 3), new(n)
+            _lib.call("nerf_composite", raw, t, stride, n, Sc, white, rgb, depth, weights)
+            t_merged = new(n, Sc + Sf)
+            _lib.call("nerf_field_sample_importance", weights, t, stride, u, 0 if u.dim() == 1 else Sf, n, Sc, Sf, t_merged, None)
+        if isinstance(self.samples, list):
+            self.samples.append((t, weights, t_merged))
+        return t_merged, Sc + Sf, Sc + Sf
+
+    def _geometry_chunk(self, o, d, t, S, grid, white, stride=0):
         """One chunk of n rays -> (rgb [n,3], depth [n], acc [n], normal [n,3]), detached: the launches of _chunk with the density
         network's `save` kept, then the gradient chain with positive_only on the surviving rows, scattered by id, and
         nerf_composite_normals."""
@@ -510,14 +594,14 @@ class HashRenderer:
 
         def new(*shape):
             return torch.empty(shape, dtype=torch.float32, device=dev)
-        index, M = self._survivors(o, d, t, S, grid)
+        index, M = self._survivors(o, d, t, S, grid, stride)
         grad = new(n, S, 3)                            # rows of culled samples stay unwritten: their raw sigma is 0, they are not used
         if M == 0:
             raw = torch.zeros(n, S, 4, dtype=torch.float32, device=dev)
         else:
             frame = field.frame()
             x = new(M, 3)
-            _lib.call("nerf_field_points", o, d, t, 0, n, S, index, M, *frame, x)
+            _lib.call("nerf_field_points", o, d, t, stride, n, S, index, M, *frame, x)
             geo, g_x = field._sigma_gradient(x, True)
             sh = new(n, SH_DIM)
             _lib.call("nerf_sh4_encode", d, n, sh)
@@ -525,10 +609,10 @@ class HashRenderer:
             _lib.call("nerf_field_color_inputs", geo, sh, index, M, n, S, cin, sigma_rows)
             raw = torch.zeros(n, S, 4, dtype=torch.float32, device=dev)
             _lib.call("nerf_field_raw_scatter", field._rgb(cin), sigma_rows, index, M, n * S, raw)
-            _lib.call("nerf_field_points_backward", o, d, t, 0, n, S, index, M, *frame, g_x, None, 1, grad, None, None)
+            _lib.call("nerf_field_points_backward", o, d, t, stride, n, S, index, M, *frame, g_x, None, 1, grad, None, None)
         rgb, depth, acc, normal = new(n, 3), new(n), new(n), new(n, 3)
-        _lib.call("nerf_composite", raw, t, 0, n, S, white, rgb, depth, None)
-        _lib.call("nerf_composite_normals", raw, t, 0, n, S, grad, normal, acc)
+        _lib.call("nerf_composite", raw, t, stride, n, S, white, rgb, depth, None)
+        _lib.call("nerf_composite_normals", raw, t, stride, n, S, grad, normal, acc)
         return rgb, depth, acc, normal
 
     def render_geometry(self, batch):
@@ -549,10 +633,15 @@ class HashRenderer:
             return new(0, 3), new(0), new(0), new(0, 3)
         o = rays_o.reshape(-1, 3).to(torch.float32).contiguous()
         d = rays_d.reshape(-1, 3).to(torch.float32).contiguous()
-        S, white, step = self.N_samples, int(bool(self.white_bkgd)), self.geometry_chunk_rays
-        t = self._get_table(dev)
+        white, step = int(bool(self.white_bkgd)), self.geometry_chunk_rays
+        table = self._get_table(dev)
+        _, u, _ = self._draws(n, dev)                              # (perturb is refused: the shared u table, or None)
+        outs = []
         with torch.no_grad():
-            outs = [self._geometry_chunk(o[i:i + step], d[i:i + step], t, S, grid, white) for i in range(0, n, step)]
+            for i in range(0, n, step):
+                oc, dc = o[i:i + step], d[i:i + step]
+                t, S, stride = self._depths(oc, dc, table, None, u, grid, white)
+                outs.append(self._geometry_chunk(oc, dc, t, S, grid, white, stride))
         if len(outs) == 1:
             return outs[0]
         return tuple(torch.cat([out[k] for out in outs], 0) for k in range(4))
@@ -566,10 +655,18 @@ class HashRenderer:
             return torch.empty(0, 3, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
         o = rays_o.reshape(-1, 3).to(torch.float32).contiguous()
         d = rays_d.reshape(-1, 3).to(torch.float32).contiguous()
-        S, white = self.N_samples, int(bool(self.white_bkgd))
+        S, white, step = self.N_samples, int(bool(self.white_bkgd)), self.chunk_rays
         t = self._get_table(dev)
-        outs = [self._chunk(o[i:i + self.chunk_rays], d[i:i + self.chunk_rays], t, S, grid, white)
-                for i in range(0, n, self.chunk_rays)]
+        if self.N_importance == 0 and not self.perturb:            # the launches of a renderer without these attributes
+            outs = [self._chunk(o[i:i + step], d[i:i + step], t, S, grid, white) for i in range(0, n, step)]
+        else:
+            jitter, u, u_stride = self._draws(n, dev)
+            outs = []
+            for i in range(0, n, step):
+                oc, dc = o[i:i + step], d[i:i + step]
+                tc, Sa, stride = self._depths(oc, dc, t, None if jitter is None else jitter[i:i + step],
+                                              u[i:i + step] if u_stride else u, grid, white)
+                outs.append(self._chunk(oc, dc, tc, Sa, grid, white, stride))
         if len(outs) == 1:
             return outs[0]
         return torch.cat([r for r, _ in outs], 0), torch.cat([z for _, z in outs], 0)

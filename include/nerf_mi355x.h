@@ -285,7 +285,9 @@ int32_t nerf_mlp_backward_masked(const float* rays_o, const float* rays_d, const
 
 /* Adjoint of nerf_composite (autograd of volume_renderer.py:414-432 with :67-96): g_rgb [n,3], g_depth [n]
  * (nullable) -> g_raw [n,S,4] and, if given, g_t [n,S] (the direct dependence of the image on the sample
- * depths through delta_k = t_{k+1}-t_k and the depth sum).  S <= 192.  Rows of g_raw are exactly zero wherever
+ * depths through delta_k = t_{k+1}-t_k and the depth sum; the last sample's delta is the constant 1e10).  S <= 192.  The relu
+ * mask (sigma > 0) and whether clamp(1 - alpha, 1e-10, 1) passes the gradient (1e-10 <= 1 - alpha <= 1) are decided in fp32 exactly
+ * as nerf_composite computes them; everything else is evaluated in float64 from the inputs.  Rows of g_raw are exactly zero wherever
  * sigma <= 0 (relu: alpha = 0, weight 0) -- what the dead-tile skipping of nerf_mlp_backward* feeds on. */
 int32_t nerf_composite_backward(const float* raw, const float* tvals, int64_t t_ray_stride, int64_t n_rays,
                                 int32_t n_samples, int32_t white_bkgd, const float* g_rgb, const float* g_depth,
@@ -293,7 +295,10 @@ int32_t nerf_composite_backward(const float* raw, const float* tvals, int64_t t_
 
 /* Adjoint of nerf_sample_fine (autograd of volume_renderer.py:126-154, :247-264, :349-356): gradient of the
  * merged depths g_t_sorted [n,192] -> g_raw_coarse [n,64,4] (channel 3 only; the reference does NOT detach
- * the coarse weights, so the coarse network trains through the sample positions). */
+ * the coarse weights, so the coarse network trains through the sample positions).  The bin of every fine sample, the
+ * `denom < 1e-5` branch, its slot in t_sorted (ties: coarse first) and the relu / clamp-pass masks are the forward's own fp32
+ * decisions; on them the adjoint is evaluated in float64 from the inputs.  The rgb channels of g_raw_coarse are written as 0, and
+ * those of raw_coarse are not read. */
 int32_t nerf_sample_fine_backward(const float* raw_coarse, const float* t_coarse, const float* u, int64_t n_rays,
                                   const float* t_sorted, const float* g_t_sorted, float* g_raw_coarse, void* stream);
 
@@ -324,7 +329,10 @@ int32_t nerf_wgrad(const float* dz, int64_t ldz, int32_t zc0, int32_t n_out, con
  * If `valid_sorted` [n,192] (uint8) is non-NULL the fast_sampling branch is evaluated too: ESS (coarse
  * weight < weights_threshold around the sample, strict for rays with max sigma > 0.5) and ERT (coarse
  * transmittance < ert_threshold) masks and the empty-ray test (:116-123, :132-133, :158-193), merged
- * through the sort with the always-valid coarse samples (:359-369). */
+ * through the sort with the always-valid coarse samples (:359-369).
+ * Rules of the merge: t_coarse and u are ascending, and with valid_sorted every depth is > 0 (the validity of a fine sample rides
+ * through the merge as the sign of its depth: a depth of 0 would come out invalid).  Where a fine depth equals a coarse depth the
+ * coarse sample comes first, in t_sorted's order and therefore in valid_sorted's; equal fine depths keep the order of their u. */
 int32_t nerf_sample_fine(const float* raw_coarse, const float* t_coarse, const float* u,
                          int64_t n_rays, float* t_sorted, float* t_fine, uint8_t* valid_sorted,
                          float weights_threshold, float ert_threshold, void* stream);

@@ -323,7 +323,8 @@ void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __rest
   static_assert(S == 64 && F == 128, "lane = coarse sample, two fine samples per lane");
   __shared__ float s_tab[RAYS ? 4 * S : S + F];
   __shared__ float s_cdf[4][S];
-  __shared__ double s_gcdf[4][S];          // adjoint of the cdf, accumulated in float64 (see below)
+  __shared__ double s_cdf64[4][S];         // the cdf again, smooth in float64 (see below)
+  __shared__ double s_gcdf[4][S];          // adjoint of the cdf
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long long ray_slot = (long long)blockIdx.x * 4 + wv;
   const bool ray_ok = ray_slot < n_rays;                       // a wave past the end recomputes the last ray and stores nothing
@@ -373,15 +374,34 @@ void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __rest
     }
   }
   s_cdf[wv][lane] = cdf_m;                                     // (lane 63: unused slot)
+  // ---- the same quantities as smooth functions of the inputs, in float64.  The decisions above -- relu, whether the clamp passes,
+  // the bin of every fine sample, `live`, the merged slot -- are the forward's and stay fp32; the gradient is that of the exact
+  // expressions on those decisions.  (With the fp32 values it was the gradient at a point up to 2^-25 / e away in every factor
+  // q = 1 - alpha = e, and on a bin of denom ~ 1e-5 at a denom 6e-3 relative away: per ray as far from a float64 evaluation as
+  // torch's fp32 autograd, but not the same accident, so the two were up to 7 x apart: tests/test_gpu_ray_side.py.)
+  const bool pass = om >= 1e-10f && om <= 1.0f;
+  const double delta64 = (i < S - 1) ? (double)tc[i + 1] - (double)tc[i] : 1e10;
+  const double e64 = exp(-(double)sigma * delta64);
+  const double alpha64 = 1.0 - e64;
+  const double om64 = 1.0 - alpha64;
+  const double q64 = pass ? om64 : fmin(fmax(om64, 1e-10), 1.0);
+  const double T64 = wave_shift<true>(wave_scan<true>(q64, lane, op_prod), lane, 1.0);
+  const double we64 = T64 * alpha64 + (double)1e-5f;           // the forward's eps, the float
+  double wsum64 = inner ? we64 : 0.0;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) wsum64 += __shfl_xor(wsum64, d);
+  // lane m: cdf[m] = sum of pdf over bins 0..m-1 = over lanes 1..m
+  s_cdf64[wv][lane] = wave_scan<true>(inner ? we64 / wsum64 : 0.0, lane, op_sum);
   __syncthreads();
   // ---- the two fine samples of this lane: bin, merged slot, adjoint into g_cdf
   const float* gts = g_tsorted + ray * (S + F);
   float* cdf = s_cdf[wv];
-  // Everything downstream of the (fp32, forward-identical) decisions is accumulated in float64: the terms num / denom^2 of an
-  // ill-conditioned ray (denom ~ 1e-5) are 1e5 x the result of the sums they enter, and the fp32 version of these sums (LDS float
-  // atomics + wave scans) was 10-20 x further from a float64 evaluation of the adjoint than torch's fp32 autograd on the same
-  // inputs (tests/test_gpu_train_steps.py, round 3).  The kernel is 20 us of a training step either way.
+  // Everything downstream of the (fp32, forward-identical) decisions is float64: the terms num / denom^2 of an ill-conditioned ray
+  // (denom ~ 1e-5) are 1e5 x the result of the sums they enter, and the fp32 version of these sums (LDS float atomics + wave scans)
+  // was 10-20 x further from a float64 evaluation of the adjoint than torch's fp32 autograd on the same inputs
+  // (tests/test_gpu_train_steps.py, round 3).  The kernel is 20 us of a training step either way.
   double* gcdf = s_gcdf[wv];
+  const double* cdf64 = s_cdf64[wv];
   int ic_carry = 0;
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
@@ -404,9 +424,11 @@ void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __rest
     ic = max(wave_scan<true>(ic, lane, op_max), ic_carry);
     ic_carry = __shfl(ic, 63);
     const double g = (double)gts[k + ic];                       // its slot in the merged array
-    const double g_frac = g * (double)__fsub_rn(ba, bb);
-    double g_cb = -g_frac / (double)denom, g_ca = 0.0;          // frac = (u - cb) / denom, denom = ca - cb when live
-    if (live) { const double gden = -g_frac * (double)num / ((double)denom * (double)denom); g_ca += gden; g_cb -= gden; }
+    const double bb64 = 0.5 * ((double)tc[below + 1] + (double)tc[below]), ba64 = 0.5 * ((double)tc[above + 1] + (double)tc[above]);
+    const double den64 = live ? cdf64[above] - cdf64[below] : 1.0, num64 = (double)u - cdf64[below];
+    const double g_frac = g * (ba64 - bb64);
+    double g_cb = -g_frac / den64, g_ca = 0.0;                  // frac = (u - cb) / denom, denom = ca - cb when live
+    if (live) { const double gden = -g_frac * num64 / (den64 * den64); g_ca += gden; g_cb -= gden; }
     atomicAdd(&gcdf[below], g_cb);
     atomicAdd(&gcdf[above], g_ca);
   }
@@ -416,16 +438,16 @@ void nerf_sample_bwd_kernel(const float* __restrict__ raw_c, const float* __rest
   const double gpdf_excl = wave_shift<false>(sfx, lane, 0.0);   // lane j: g_pdf_j = sum_{m>j} g_cdf[m]
   double gpdf_i = __shfl_up(gpdf_excl, 1);                      // lane i: g_pdf of bin i - 1 (the bin of sample i)
   if (!inner) gpdf_i = 0.0;
-  double dot = inner ? gpdf_i * (double)we : 0.0;
+  double dot = inner ? gpdf_i * we64 : 0.0;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) dot += __shfl_xor(dot, d);
-  const double g_w = inner ? (gpdf_i / (double)wsum - dot / ((double)wsum * (double)wsum)) : 0.0;
-  const double sf2 = wave_scan<false>(g_w * (double)alpha * (double)Ti, lane, op_sum);     // suf_i = sum_{m>i} g_w_m a_m T_m
+  const double g_w = inner ? (gpdf_i / wsum64 - dot / (wsum64 * wsum64)) : 0.0;
+  const double sf2 = wave_scan<false>(g_w * alpha64 * T64, lane, op_sum);     // suf_i = sum_{m>i} g_w_m a_m T_m
   const double suf = wave_shift<false>(sf2, lane, 0.0);
-  double g_alpha = g_w * (double)Ti;
-  if (om >= 1e-10f && om <= 1.0f) g_alpha -= suf / (double)q;
+  double g_alpha = g_w * T64;
+  if (pass) g_alpha -= suf / q64;
   f32x4 go = {0.f, 0.f, 0.f, 0.f};
-  go.w = s_raw > 0.0f ? (float)(g_alpha * (double)delta * (double)e) : 0.0f;
+  go.w = s_raw > 0.0f ? (float)(g_alpha * delta64 * e64) : 0.0f;
   if (ray_ok) reinterpret_cast<f32x4*>(g_raw_c)[ray * S + i] = go;
 }
 

@@ -7,6 +7,8 @@ Public surface mirrors rkin100g/Nerf-Replication (paths relative to the referenc
     ImageFitNetwork <- src/models/img_fit/network.py              (state_dict keys, render(uv, batch), forward(batch)); FusedMLP and
                        fused_mlp are the small fused ReLU MLP it runs on (include/nerf_mi355x_nn.h)
     HashField, HashRenderer: a hash-grid radiance field on those parts and its renderer (no counterpart that runs in the reference)
+    DNeRFNGP   <- src/models/encoding/hashencoder/hashgrid.py  (`encoder`, `feat`, forward(x, wbounds), compute_delta, compute_tv_loss):
+               the deformation field of a dynamic scene; HashField(bbox, encoder=DNeRFNGP(...)) renders and trains it
 The arithmetic runs in hand-written HIP kernels (csrc/) reached through the C ABI declared in
 include/nerf_mi355x.h; there is no CPU or eager-PyTorch fallback: without the built library or a
 GPU the product path raises.
@@ -33,13 +35,14 @@ _LAZY = {
     "HashEncoder": ".hashgrid", "TriPlane": ".hashgrid",
     "fused_mlp": ".fused_mlp", "FusedMLP": ".fused_mlp", "ImageFitNetwork": ".fused_mlp",
     "HashField": ".hashfield", "HashRenderer": ".hashfield",
+    "DNeRFNGP": ".deform",
 }
-_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy", "hashgrid", "modes", "hashfield")
+_SUBMODULES = ("_lib", "network", "volume_renderer", "rays", "evaluator", "checkpoint", "training", "dist", "mesh", "occupancy", "hashgrid", "modes", "hashfield", "deform")
 
 __all__ = ["NeRF", "Network", "Renderer", "Evaluator", "generate_rays", "load_network", "load_model", "save_model",
            "density_grid", "isosurface", "write_ply", "extract_mesh", "density_gradient", "vertex_normals",
            "mesh_components", "filter_components", "vertex_colors", "write_ply_colors", "OccupancyGrid", "HashEncoder", "TriPlane",
-           "fused_mlp", "FusedMLP", "ImageFitNetwork", "HashField", "HashRenderer"]
+           "fused_mlp", "FusedMLP", "ImageFitNetwork", "HashField", "HashRenderer", "DNeRFNGP"]
 
 
 def __getattr__(name):

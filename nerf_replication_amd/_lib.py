@@ -214,6 +214,21 @@ SAMPLING_SIGNATURES = _parse_table(_TABLE_SAMPLING)
 SAMPLING_EXPORTS = tuple(SAMPLING_SIGNATURES)
 _SAMPLING_PROTOS = _protos(SAMPLING_SIGNATURES)
 
+# The deformation field of a dynamic scene, one line per entry of include/nerf_mi355x_deform.h (one more header of the same library; the
+# seven tables above are pinned at their sizes).  tests/test_deform_cpu.py compares this table with that header.  The two byte counts
+# are pure host.
+_TABLE_DEFORM = """
+nerf_deform_packed_bytes  i64 : i32 i32 i32
+nerf_deform_table_bytes  i64 : i32 i32 i32
+nerf_deform_pack  status : f32*[3] i32 i32 i32 f32* stream
+nerf_deform_unpack_grad  status : f32* i32 i32 i32 f32*[3] stream
+nerf_deform_forward  status : f32* f32* i32* i64 i64 i32 f32* i32 i32 i32 f32* f32* stream
+nerf_deform_backward  status : f32* f32* i32* i64 i64 i32 f32* i32 i32 i32 f32* f32* f32* stream
+"""
+DEFORM_SIGNATURES = _parse_table(_TABLE_DEFORM)
+DEFORM_EXPORTS = tuple(DEFORM_SIGNATURES)
+_DEFORM_PROTOS = _protos(DEFORM_SIGNATURES)
+
 _lib = None
 
 
@@ -242,7 +257,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_PROTOS.items()) + list(_NN_PROTOS.items()) + list(_FIELD_PROTOS.items()) +
                                   list(_HASHGRID_PROTOS.items()) + list(_NN_EXACT_PROTOS.items()) + list(_ORDER_PROTOS.items()) +
-                                  list(_SAMPLING_PROTOS.items())):
+                                  list(_SAMPLING_PROTOS.items()) + list(_DEFORM_PROTOS.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.nerf_abi_version() != 3:
@@ -268,10 +283,10 @@ def call(name, *args):
     """Call entry `name` of the library with `args` as its header lists them, minus the stream: tensors (None: NULL) for device
     pointers, numbers for scalars, sequences or ctypes arrays for host arrays.  Every argument is checked against the entry's kinds
     in SIGNATURES (or, looked up in this order, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES, ORDER_SIGNATURES,
-    SAMPLING_SIGNATURES) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
+    SAMPLING_SIGNATURES, DEFORM_SIGNATURES) before the library is touched; the work goes to the current torch stream of the tensors' device.  A status return
     is checked (NerfLibraryError with nerf_last_error's text); any other return value comes back as it is."""
     for table in (SIGNATURES, NN_SIGNATURES, FIELD_SIGNATURES, HASHGRID_SIGNATURES, NN_EXACT_SIGNATURES, ORDER_SIGNATURES,
-                  SAMPLING_SIGNATURES):
+                  SAMPLING_SIGNATURES, DEFORM_SIGNATURES):
         if name in table:
             break
     ret, kinds = table[name]

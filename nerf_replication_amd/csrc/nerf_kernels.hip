@@ -57,6 +57,8 @@
 #include "nerf_hashfield.hip.inc"
 // ---- where its samples lie (include/nerf_mi355x_sampling.h): nerf_field_sample_importance, nerf_field_stratified_depths
 #include "nerf_field_sampling.hip.inc"
+// ---- the deformation field of a dynamic scene (include/nerf_mi355x_deform.h): nerf_deform_forward / _backward / _pack / _unpack_grad
+#include "nerf_deform.hip.inc"
 
 extern "C" {
 

@@ -15,6 +15,12 @@ depths resampled from the field's own density (HashRenderer.N_importance) with s
 DESIGN.md section 2.14.2, include/nerf_mi355x_sampling.h; the random draws of perturb are torch.rand.  No other ATen op computes on the render path: torch allocates,
 zero-fills and slices.  fp32 only; CPU tensors raise NerfLibraryError: there is no eager fallback.
 
+A DYNAMIC field is HashField(bbox, encoder=DNeRFNGP(num_frames, ...)) (deform.py): the normalised positions
+are warped by the frame number of their ray (batch["time"]: [B], [B,1] or [B,N]) in one more launch, nerf_deform_forward, between
+nerf_field_points and hash_encode; field.num_frames is None for a static field, which runs the launches it always ran.
+density(xyz, time=k) is frame k.  The spatial adjoint, the geometry outputs, occupancy grids and deterministic=True are refused for a
+dynamic field.
+
 One host synchronisation per chunk on the culled path (HashRenderer.occupancy set): the number of surviving samples is read back,
 because hash_encode and fused_mlp take their row count from the host.  Without a grid nothing synchronises.
 """
@@ -27,6 +33,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .fused_mlp import MAX_ROWS, FusedMLP, fused_mlp
+from .deform import DNeRFNGP
 from .hashgrid import EPS, HashEncoder, _as_offsets, _flag, hash_encode, level_scales
 
 GEO_DIM = 16                        # columns of the geometry feature: what the glue kernels move
@@ -200,8 +207,11 @@ class HashField(nn.Module):
         if encoder is None:
             encoder = HashEncoder(input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=19,
                                   desired_resolution=2048, deterministic=deterministic)
-        if not isinstance(encoder, HashEncoder) or encoder.input_dim != 3:
-            raise TypeError("HashField: encoder must be a HashEncoder with input_dim = 3")
+        if not isinstance(encoder, (HashEncoder, DNeRFNGP)) or encoder.input_dim != 3:
+            raise TypeError("HashField: encoder must be a HashEncoder with input_dim = 3, or a DNeRFNGP")
+        if isinstance(encoder, DNeRFNGP) and deterministic:
+            raise NotImplementedError("HashField(deterministic=True) is not built for a dynamic field: the deformation tables' "
+                                      "gradient is summed by atomics, so the promise of identical bytes would be false")
         self.encoder = encoder
         self.sigma_net = FusedMLP(encoder.out_dim, GEO_DIM, width, sigma_hidden, deterministic=deterministic)
         self.color_net = FusedMLP(GEO_DIM + SH_DIM, 3, width, color_hidden, deterministic=deterministic)
@@ -228,9 +238,19 @@ class HashField(nn.Module):
         lo, hi, _ = self.frame()
         return np.array(list(lo) + list(hi), dtype=np.float64)
 
+    @property
+    def num_frames(self):
+        """None for a static field; the frames of the deformation tables for a dynamic one (encoder = DNeRFNGP)."""
+        return self.encoder.num_frames if isinstance(self.encoder, DNeRFNGP) else None
+
+    def _static_only(self, what):
+        if self.num_frames is not None:
+            raise NotImplementedError(f"{what} is not built for a dynamic field (encoder = DNeRFNGP): the gradient of the warp "
+                                      "with respect to the position, and a grid per frame, are not built")
+
     def _geo(self, x):
-        """x [M,3] in [0,1] -> the 16 columns of sigma_net."""
-        enc = self.encoder
+        """x [M,3] in [0,1] (a dynamic field: already warped) -> the 16 columns of sigma_net."""
+        enc = self.encoder.encoder if isinstance(self.encoder, DNeRFNGP) else self.encoder
         feats = hash_encode(x, enc.embeddings, enc.offsets, enc.per_level_scale, enc.base_resolution, enc.deterministic)
         return fused_mlp(feats, [l.weight for l in self.sigma_net.layers], [l.bias for l in self.sigma_net.layers],
                          deterministic=self.sigma_net.deterministic)
@@ -255,15 +275,27 @@ class HashField(nn.Module):
             raise _lib.NerfLibraryError(f"HashField.{what} needs xyz on a GPU (cuda) device; got a CPU tensor (there is no CPU fallback)")
         return xyz.contiguous()
 
-    def density(self, xyz):
+    def density(self, xyz, time=None):
         """World points xyz [n,3] on the GPU -> the raw density [n,1]: the queryfn protocol of extract_mesh.  The positions are
         normalised by nerf_field_points in point mode; the parameters get gradients if they require them, and so does xyz (the
-        point-mode adjoint nerf_field_points_backward behind the encoder's and the network's input gradients)."""
+        point-mode adjoint nerf_field_points_backward behind the encoder's and the network's input gradients).
+        time: a dynamic field needs it, ONE frame number (a float) for all points: extract_mesh(lambda p: field.density(p, time=k),
+        ...) meshes frame k; its xyz must not require grad.  A static field takes no time."""
+        dynamic = self.num_frames is not None
+        if dynamic != (time is not None):
+            raise ValueError("HashField.density: a dynamic field needs time (one frame number), a static field takes none")
+        if dynamic and (isinstance(time, bool) or not isinstance(time, (int, float))):
+            raise ValueError(f"HashField.density: time must be one number, got {time!r}")
+        if dynamic and isinstance(xyz, torch.Tensor) and xyz.requires_grad:
+            raise NotImplementedError("HashField.density: the gradient of the warp with respect to the position is not built; xyz "
+                                      "that requires grad is refused for a dynamic field")
         xyz = self._check_points(xyz, "density")
         if xyz.shape[0] == 0:
             return xyz.new_zeros(0, 1)
         frame = self.frame()
         with_grad = xyz.requires_grad and torch.is_grad_enabled()
+        if dynamic:                                   # one "ray" holds every point of a launch chain: n_samples = 1 and n "rays"
+            frame_number = torch.full((min(xyz.shape[0], DENSITY_ROWS),), float(time), dtype=torch.float32, device=xyz.device)
         outs = []
         for i in range(0, xyz.shape[0], DENSITY_ROWS):
             pts = xyz[i:i + DENSITY_ROWS]
@@ -273,12 +305,14 @@ class HashField(nn.Module):
             else:
                 x = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
                 _lib.call("nerf_field_points", pts, None, None, 0, n, 1, None, n, *frame, x)
+            if dynamic:
+                x = self.encoder.warp(x, frame_number[:n])
             outs.append(self._geo(x)[:, :1].contiguous())       # a copy of one column: the [n,16] output is not kept alive
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
     def _levels(self):
         """(offsets, scales, L): the level tables as the host arrays nerf_hashgrid_* take (what hash_encode builds per call)."""
-        enc = self.encoder
+        enc = self.encoder.encoder if isinstance(self.encoder, DNeRFNGP) else self.encoder
         offsets = _as_offsets(enc.offsets)
         L = offsets.shape[0] - 1
         scales = level_scales(L, enc.per_level_scale, enc.base_resolution)
@@ -319,6 +353,7 @@ class HashField(nn.Module):
         gradient with respect to the world position (exactly zero on an axis along which the point lies outside the box: the
         normalisation clamps).  positive_only: grad is exactly zero wherever sigma <= 0.  Detached; no ATen op computes: the chain of
         _sigma_gradient between nerf_field_points and nerf_field_points_backward in point mode, in chunks of GRADIENT_ROWS points."""
+        self._static_only("HashField.density_gradient")
         xyz = self._check_points(xyz, "density_gradient").detach()
         n_all = xyz.shape[0]
         sigma = torch.empty(n_all, dtype=torch.float32, device=xyz.device)
@@ -338,6 +373,7 @@ class HashField(nn.Module):
         """Unit outward normals [V,3] of an iso-surface of the density at its vertices [V,3]: -grad sigma / |grad sigma|, the zero
         vector where the gradient is zero or not finite -- mesh.vertex_normals' semantics on density_gradient (every point, whatever
         the sign of sigma); the normalisation of the [V,3] result is three torch operations."""
+        self._static_only("HashField.vertex_normals")
         _, g = self.density_gradient(self._as_points(vertices, "vertex_normals"), positive_only=False)
         nrm = g.norm(dim=-1, keepdim=True)
         ok = torch.isfinite(nrm) & (nrm > 0)
@@ -349,6 +385,7 @@ class HashField(nn.Module):
         normal is zero) -- mesh.vertex_colors' semantics.  The rows go through nerf_field_points (point mode), nerf_sh4_encode and
         nerf_field_color_inputs with n_samples = 1; the sigmoid of the [V,3] result is one torch operation."""
         from .mesh import _head_on
+        self._static_only("HashField.vertex_colors")
         if isinstance(vertices, torch.Tensor) and viewdirs is not None and \
                 (not isinstance(viewdirs, torch.Tensor) or viewdirs.shape != vertices.shape):
             raise ValueError(f"viewdirs must be a tensor of the vertices' shape {tuple(vertices.shape)}")
@@ -382,6 +419,7 @@ class HashField(nn.Module):
         under no_grad, the grid in x-slabs.  The grid carries no staleness key: rebuild it on your own schedule while training."""
         from .mesh import _query_grid, grid_axes
         from .occupancy import OccupancyGrid
+        self._static_only("HashField.occupancy_grid")
         bbox = self.bbox
         axes, _, _ = grid_axes(bbox, N)
         field = _query_grid(self.density, axes, self.wbounds.device)
@@ -454,8 +492,16 @@ class HashRenderer:
         controls the samples.  Overridable: tests replay recorded draws through it."""
         return torch.rand(*shape, device=device)
 
-    def _check(self, rays_o, rays_d, geometry=False):
-        """Everything that is refused, before any launch or allocation -> the grid or None."""
+    def _check(self, rays_o, rays_d, geometry=False, batch=None):
+        """Everything that is refused, before any launch or allocation -> the grid or None.  batch: render()'s, whose "time" a
+        dynamic field needs."""
+        if self.field.num_frames is not None:
+            if geometry:
+                self.field._static_only("HashRenderer.render_geometry")
+            if self.occupancy is not None:
+                self.field._static_only("HashRenderer.occupancy")
+            if isinstance(rays_o, torch.Tensor) and isinstance(rays_d, torch.Tensor) and (rays_o.requires_grad or rays_d.requires_grad):
+                self.field._static_only("HashRenderer.ray_gradients (rays that require grad)")
         S = self.N_samples
         if isinstance(S, bool) or not isinstance(S, int) or not 1 <= S <= MAX_SAMPLES:
             raise ValueError(f"HashRenderer.N_samples must be an int in [1, {MAX_SAMPLES}], got {S!r}")
@@ -496,6 +542,8 @@ class HashRenderer:
             if Sf > 0:
                 raise NotImplementedError("HashRenderer: rays that require grad are not supported with N_importance > 0 (the ray "
                                           "adjoint through resampled depths is not built)")
+        if batch is not None and self.field.num_frames is not None:
+            self._check_time(batch, rays_o)
         self.field._check_fp32()
         if not rays_o.is_cuda or not rays_d.is_cuda:
             raise _lib.NerfLibraryError("HashRenderer needs rays on a GPU (cuda) device; got a CPU tensor (there is no CPU fallback)")
@@ -521,9 +569,34 @@ class HashRenderer:
             self.stats.append((M, P))
         return index, M
 
-    def _chunk(self, o, d, t, S, grid, white, stride=0):
+    def _check_time(self, batch, rays_o):
+        """batch["time"] of a dynamic field: frame numbers [B], [B,1] or [B,N], fp32, on the rays' device -> that tensor."""
+        time = batch.get("time") if hasattr(batch, "get") else None
+        B, N = rays_o.shape[0], rays_o.shape[1]
+        if not isinstance(time, torch.Tensor):
+            raise ValueError('HashRenderer.render: a dynamic field needs batch["time"], a tensor of frame numbers [B], [B,1] or [B,N]')
+        if time.dtype != torch.float32 or time.device != rays_o.device:
+            raise ValueError(f'HashRenderer.render: batch["time"] must be float32 on the rays\' device {rays_o.device}, got '
+                             f"{time.dtype} on {time.device}")
+        if tuple(time.shape) not in ((B,), (B, 1), (B, N)):
+            raise ValueError(f'HashRenderer.render: batch["time"] must be [B], [B,1] or [B,N] = [{B}], [{B},1] or [{B},{N}], got '
+                             f"{tuple(time.shape)}")
+        if time.requires_grad:
+            raise NotImplementedError("HashRenderer.render: the gradient with respect to the frame numbers is not built")
+        return time
+
+    def _time(self, batch, rays_o):
+        """The frame number per ray [B*N] of a dynamic field, expanded from batch["time"] (validated by _check) without a
+        synchronisation; None for a static field, which ignores the key."""
+        if self.field.num_frames is None:
+            return None
+        B, N = rays_o.shape[0], rays_o.shape[1]
+        return batch["time"].detach().reshape(B, -1).expand(B, N).reshape(-1).contiguous()
+
+    def _chunk(self, o, d, t, S, grid, white, stride=0, time=None):
         """One chunk of n rays -> (rgb [n,3], depth [n]); every step is enqueued on the current stream.  t: the shared table [S]
-        (stride 0) or the chunk's own depths [n,S] (stride S)."""
+        (stride 0) or the chunk's own depths [n,S] (stride S).  time [n] (a dynamic field): the positions are warped
+        (nerf_deform_forward) between nerf_field_points and the encoder."""
         field, dev, n = self.field, o.device, o.shape[0]
         index, M = self._survivors(o.detach(), d.detach(), t, S, grid, stride)
         if M == 0:
@@ -537,6 +610,8 @@ class HashRenderer:
                 _lib.call("nerf_field_points", o, d, t, stride, n, S, index, M, lo, hi, extent, x)
                 sh = torch.empty(n, SH_DIM, dtype=torch.float32, device=dev)
                 _lib.call("nerf_sh4_encode", d, n, sh)
+            if time is not None:
+                x = field.encoder.warp(x, time, index, n, S)
             geo = field._geo(x)
             cin, sigma_rows = _ColorInputs.apply(geo, sh, index, M, n, S)
             raw = _RawScatter.apply(field._rgb(cin), sigma_rows, index, M, n, S)
@@ -553,7 +628,7 @@ class HashRenderer:
         u = self._rand((n, Sf), dev).to(torch.float32).contiguous() if Sf > 0 else None
         return jitter, u, Sf
 
-    def _depths(self, o, d, table, jitter, u, grid, white):
+    def _depths(self, o, d, table, jitter, u, grid, white, time=None):
         """The depths one chunk of n rays is rendered on -> (t, S, ray stride), all constants (computed under no_grad).
         jitter [n,Sc] (or None): the coarse depths are nerf_field_stratified_depths of the table.  u (None: N_importance == 0) [Sf]
         or [n,Sf]: the coarse pass -- the survivors of the grid through nerf_field_points, hash_encode and sigma_net only, their
@@ -577,6 +652,8 @@ class HashRenderer:
             if M > 0:
                 x = new(M, 3)
                 _lib.call("nerf_field_points", o, d, t, stride, n, Sc, index, M, *field.frame(), x)
+                if time is not None:
+                    x = field.encoder.warp(x, time, index, n, Sc)
                 _lib.call("nerf_field_density_scatter", field._geo(x), GEO_DIM, index, M, n * Sc, raw)
             weights, rgb, depth = new(n, Sc), new(n, 3), new(n)
             _lib.call("nerf_composite", raw, t, stride, n, Sc, white, rgb, depth, weights)
@@ -648,7 +725,8 @@ class HashRenderer:
 
     def render(self, batch):
         rays_o, rays_d = batch["rays_o"], batch["rays_d"]
-        grid = self._check(rays_o, rays_d)
+        grid = self._check(rays_o, rays_d, batch=batch)
+        tm = self._time(batch, rays_o)                             # None: a static field
         dev = rays_o.device
         n = rays_o.shape[0] * rays_o.shape[1]
         if n == 0:
@@ -658,15 +736,19 @@ class HashRenderer:
         S, white, step = self.N_samples, int(bool(self.white_bkgd)), self.chunk_rays
         t = self._get_table(dev)
         if self.N_importance == 0 and not self.perturb:            # the launches of a renderer without these attributes
-            outs = [self._chunk(o[i:i + step], d[i:i + step], t, S, grid, white) for i in range(0, n, step)]
+            # time by keyword, and only for a dynamic field: a static field makes the calls it always made (tests replace
+            # _chunk and _depths by functions with the static signature)
+            outs = [self._chunk(o[i:i + step], d[i:i + step], t, S, grid, white, **({} if tm is None else {"time": tm[i:i + step]}))
+                    for i in range(0, n, step)]
         else:
             jitter, u, u_stride = self._draws(n, dev)
             outs = []
             for i in range(0, n, step):
                 oc, dc = o[i:i + step], d[i:i + step]
+                extra = () if tm is None else (tm[i:i + step],)     # (a static field makes the calls it always made)
                 tc, Sa, stride = self._depths(oc, dc, t, None if jitter is None else jitter[i:i + step],
-                                              u[i:i + step] if u_stride else u, grid, white)
-                outs.append(self._chunk(oc, dc, tc, Sa, grid, white, stride))
+                                              u[i:i + step] if u_stride else u, grid, white, *extra)
+                outs.append(self._chunk(oc, dc, tc, Sa, grid, white, stride, *extra))
         if len(outs) == 1:
             return outs[0]
         return torch.cat([r for r, _ in outs], 0), torch.cat([z for _, z in outs], 0)

@@ -464,13 +464,17 @@ class FusedAdam(torch.optim.Optimizer):
         return loss
 
 
-def train_step(renderer, optimizer, rays_o, rays_d, colors, clip_value=40.0, group=None):
+def train_step(renderer, optimizer, rays_o, rays_d, colors, clip_value=40.0, group=None, time=None):
     """One step of the reference's intended loop (trainer.py:53-60 with trainers/nerf.py:27-33): render,
     MSE on the fine RGB, backward, [data-parallel: one gradient all-reduce], clip_grad_value_(40),
-    optimizer.step().  Returns the loss tensor."""
+    optimizer.step().  Returns the loss tensor.  time (None, or the frame number per ray [n]): passed on as
+    batch["time"], which a HashRenderer over a dynamic field needs."""
     from .dist import allreduce_gradients
     optimizer.zero_grad(set_to_none=True)
-    rgb, _ = renderer.render({"rays_o": rays_o[None], "rays_d": rays_d[None]})
+    batch = {"rays_o": rays_o[None], "rays_d": rays_d[None]}
+    if time is not None:
+        batch["time"] = time[None]
+    rgb, _ = renderer.render(batch)
     loss = torch.nn.functional.mse_loss(rgb, colors)
     loss.backward()
     allreduce_gradients(renderer.net.parameters(), group)

@@ -305,11 +305,21 @@ int32_t nerf_sample_fine_backward(const float* raw_coarse, const float* t_coarse
 /* Fused gradient clipping + Adam over up to 48 tensors in one launch.  Replaces
  * clip_grad_value_(parameters, 40) (src/train/trainers/trainer.py:59) followed by torch.optim.Adam.step()
  * as configured in src/train/optimizer.py:21-24 (betas (0.9, 0.999), no amsgrad; weight decay added to the
- * gradient).  The pointer arrays are HOST arrays of DEVICE pointers; `step` is the 1-based step count
- * (bias corrections are computed on the host in double); clip_value <= 0 disables clipping. */
+ * gradient).  The pointer arrays are HOST arrays of DEVICE pointers; `step` is the 1-based step count;
+ * clip_value <= 0 disables clipping.  The six hyper-parameters are doubles (Python floats): the fp32 constants of
+ * the update are formed in double on the host, as torch forms them, and rounded once:
+ *     w1 = (float)(1 - beta1), b2 = (float)beta2, w2 = (float)(1 - beta2), bc2s = (float)sqrt(1 - beta2^step),
+ *     s = (float)-(lr / (1 - beta1^step)), and eps, weight_decay, clip_value each rounded to fp32.
+ * Per element, every operation correctly rounded fp32 on its own, denormals kept:
+ *     g = clamp(g, -clip, clip) (a NaN gradient stays NaN, as clamp_; +-inf becomes +-clip);  g = g + wd * p (wd != 0);
+ *     m = m + (g - m) * w1 if w1 < 0.5, else g - (g - m) * (1 - w1)  (the two forms of torch's lerp: beta1 <= 0.5 takes the second);
+ *     v = v * b2 + (g * g) * w2;  denom = sqrt(v) / bc2s + eps;  p = p + s * (m / denom).
+ * A tensor with numel[i] == 0 is stepped over and its four pointers are not examined (an empty device tensor has a null data
+ * pointer); numel[i] < 0, n_tensors outside 1..48 and step <= 0 are NERF_ERR_INVALID_ARG ("bad size"), a null pointer of a tensor
+ * with elements is NERF_ERR_INVALID_ARG ("null tensor"); nothing is launched then.  grads are read only. */
 int32_t nerf_adam_step(int32_t n_tensors, float* const params[], const float* const grads[], float* const exp_avg[],
-                       float* const exp_avg_sq[], const int64_t numel[], float lr, float beta1, float beta2, float eps,
-                       float weight_decay, float clip_value, int64_t step, void* stream);
+                       float* const exp_avg_sq[], const int64_t numel[], double lr, double beta1, double beta2, double eps,
+                       double weight_decay, double clip_value, int64_t step, void* stream);
 
 /* Weight / bias gradient of one nn.Linear (or a column block of it): for o < n_out, i < n_in
  *     dw[o*ldw + wc0 + i] += sum_p dz[p*ldz + zc0 + o] * hin[p*ldh + hc0 + i],   db[o] += sum_p dz[p*ldz + zc0 + o]

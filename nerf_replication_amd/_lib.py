@@ -48,7 +48,7 @@ nerf_mlp_forward_rays_for_compositing  status : f32* f32* f32* i64 i64 i32 void*
 nerf_mlp_forward_rays_density  status : f32* f32* f32* i64 i64 i32 void* f32* i32 stream
 nerf_composite_backward  status : f32* f32* i64 i64 i32 i32 f32* f32* f32* f32* stream
 nerf_sample_fine_backward  status : f32* f32* f32* i64 f32* f32* f32* stream
-nerf_adam_step  status : i32 f32*[] f32*[] f32*[] f32*[] i64[] f32 f32 f32 f32 f32 f32 i64 stream
+nerf_adam_step  status : i32 f32*[] f32*[] f32*[] f32*[] i64[] f64 f64 f64 f64 f64 f64 i64 stream
 nerf_train_grad_floats  i64 : i64
 nerf_train_live_count_offset  i64 : i64
 nerf_packed_bwd_bytes  i64 : i32

@@ -229,35 +229,44 @@ __global__ void nerf_check_stamp_kernel(const float* __restrict__ stamp, float* 
 
 // ------------------------------------------------------------------------------------ fused clip + Adam (section 8f-4)
 // One launch over all 48 parameter tensors: clip_grad_value_ (trainer.py:59) + torch.optim.Adam's update
-// (optimizer.py:21-24: Adam(lr, weight_decay, eps), betas (0.9, 0.999), no amsgrad) in torch's operation
-// order (lerp for exp_avg, sqrt(v)/sqrt(bc2) + eps for the denominator).
+// (optimizer.py:21-24: Adam(lr, weight_decay, eps), betas (0.9, 0.999), no amsgrad) in the operation order of torch's
+// device kernels, every operation rounded on its own:
+//     g = clamp(g, -clip, clip)  (NaN stays NaN, +-inf becomes +-clip);   g = g + wd * p  (wd != 0)
+//     m = m + (g - m) * w1  (w1 < 0.5)   or   g - (g - m) * (1 - w1)  (w1 >= 0.5: the two forms of torch's lerp)
+//     v = v * b2 + (g * g) * w2;   denom = sqrt(v) / bc2s + eps;   p = p + s * (m / denom)
+// The constants are formed in double on the host, as torch forms them from Python floats, and rounded to fp32 once:
+//     w1 = 1 - beta1, b2 = beta2, w2 = 1 - beta2, bc2s = sqrt(1 - beta2^step), s = -(lr / (1 - beta1^step)).
+// sqrtf and __fdiv_rn are the correctly rounded forms here (__fsqrt_rn would be the bare 1-ulp v_sqrt_f32, nerf_normals.hip.inc);
+// tests/adam_reference.py restates the step and tests/test_gpu_adam.py holds the kernel to it bit for bit.
 constexpr int kAdamMaxTensors = 48;
 struct AdamArgs {
   float* p[kAdamMaxTensors];
   const float* g[kAdamMaxTensors];
   float* m[kAdamMaxTensors];
   float* v[kAdamMaxTensors];
-  long long end[kAdamMaxTensors];      // exclusive prefix ends of the flattened index space
-  int n_tensors;
-  float lr, beta1, beta2, eps, weight_decay, clip, bc1, bc2_sqrt;
+  long long end[kAdamMaxTensors];      // exclusive prefix ends of the flattened index space (a zero-element tensor repeats its
+  int n_tensors;                       // predecessor's end: the search below never lands on it)
+  float w1, b2, w2, bc2s, s, eps, weight_decay, clip;
 };
 __global__ __launch_bounds__(256)
 void nerf_adam_kernel(AdamArgs a) {
   const long long total = a.end[a.n_tensors - 1];
+  const float w1c = __fsub_rn(1.0f, a.w1);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     int lo = 0, hi = a.n_tensors - 1;
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (i < a.end[mid]) hi = mid; else lo = mid + 1; }
     const long long j = i - (lo ? a.end[lo - 1] : 0);
     float g = a.g[lo][j];
-    if (a.clip > 0.0f) g = fminf(fmaxf(g, -a.clip), a.clip);
+    if (a.clip > 0.0f) { if (g < -a.clip) g = -a.clip; if (g > a.clip) g = a.clip; }     // two comparisons: NaN passes, as clamp_
     const float p = a.p[lo][j];
     if (a.weight_decay != 0.0f) g = __fadd_rn(g, __fmul_rn(a.weight_decay, p));
     float m = a.m[lo][j], v = a.v[lo][j];
-    m = __fadd_rn(m, __fmul_rn(__fsub_rn(g, m), 1.0f - a.beta1));                       // exp_avg.lerp_(grad, 1 - beta1)
-    v = __fadd_rn(__fmul_rn(v, a.beta2), __fmul_rn(__fmul_rn(g, g), 1.0f - a.beta2));   // mul_(beta2).addcmul_(g, g, 1 - beta2)
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), a.bc2_sqrt), a.eps);
+    const float d = __fsub_rn(g, m);                                                    // exp_avg.lerp_(grad, 1 - beta1)
+    m = a.w1 < 0.5f ? __fadd_rn(m, __fmul_rn(d, a.w1)) : __fsub_rn(g, __fmul_rn(d, w1c));
+    v = __fadd_rn(__fmul_rn(v, a.b2), __fmul_rn(__fmul_rn(g, g), a.w2));                // mul_(beta2).addcmul_(g, g, 1 - beta2)
+    const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), a.bc2s), a.eps);
     a.m[lo][j] = m; a.v[lo][j] = v;
-    a.p[lo][j] = __fadd_rn(p, __fmul_rn(-(a.lr / a.bc1), __fdiv_rn(m, denom)));         // addcdiv_(m, denom, value=-step_size)
+    a.p[lo][j] = __fadd_rn(p, __fmul_rn(a.s, __fdiv_rn(m, denom)));                     // addcdiv_(m, denom, value=-step_size)
   }
 }
 
@@ -626,21 +635,26 @@ int32_t nerf_mlp_backward_masked(const float* rays_o, const float* rays_d, const
 }
 
 int32_t nerf_adam_step(int32_t n_tensors, float* const params[], const float* const grads[], float* const exp_avg[],
-                       float* const exp_avg_sq[], const int64_t numel[], float lr, float beta1, float beta2, float eps,
-                       float weight_decay, float clip_value, int64_t step, void* stream) {
+                       float* const exp_avg_sq[], const int64_t numel[], double lr, double beta1, double beta2, double eps,
+                       double weight_decay, double clip_value, int64_t step, void* stream) {
   if (n_tensors <= 0 || n_tensors > kAdamMaxTensors || step <= 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_adam_step: bad size");
   if (!params || !grads || !exp_avg || !exp_avg_sq || !numel) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_adam_step: null argument");
   AdamArgs a;
   long long run = 0;
   for (int i = 0; i < n_tensors; ++i) {
-    if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_adam_step: null tensor");
+    if (numel[i] < 0) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_adam_step: bad size");
+    // a zero-element tensor (an empty device tensor has a null data pointer) is stepped over: its pointers are not examined
+    if (numel[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i])) return fail(NERF_ERR_INVALID_ARG, "%s", "nerf_adam_step: null tensor");
     a.p[i] = params[i]; a.g[i] = grads[i]; a.m[i] = exp_avg[i]; a.v[i] = exp_avg_sq[i];
     run += numel[i]; a.end[i] = run;
   }
   if (run == 0) return NERF_OK;
-  a.n_tensors = n_tensors; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.clip = clip_value;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  // the constants as torch.optim.Adam forms them: in double from the double hyper-parameters, each rounded to fp32 once
+  a.n_tensors = n_tensors;
+  a.w1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.w2 = (float)(1.0 - beta2);
+  a.bc2s = (float)sqrt(1.0 - pow(beta2, (double)step));
+  a.s = (float)-(lr / (1.0 - pow(beta1, (double)step)));
+  a.eps = (float)eps; a.weight_decay = (float)weight_decay; a.clip = (float)clip_value;
   long long blocks = (run + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   return NERF_LAUNCH(nerf_adam_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, a);

@@ -369,7 +369,14 @@ class FusedAdam(torch.optim.Optimizer):
     clip_grad_value_(40).  It IS a torch.optim.Optimizer (param_groups, state, state_dict in torch.optim.Adam's layout),
     so the reference's schedulers (ExponentialLR / MultiStepLR of src/utils/optimizer/lr_scheduler.py, built by
     make_lr_scheduler) and its save_model / load_model (net_utils.py:288-343) drive it unchanged, and a checkpoint
-    moves freely between this optimizer and torch.optim.Adam."""
+    moves freely between this optimizer and torch.optim.Adam.
+
+    The arithmetic is fp32 in the operation order of torch's device kernels, every operation rounded on its own, with the constants
+    formed in double on the host, as torch forms them from these Python floats (1 - beta1, 1 - beta2, sqrt(1 - beta2^step),
+    -(lr / (1 - beta1^step)), each rounded to fp32 once; include/nerf_mi355x.h has the formulas).  Both forms of torch's lerp are
+    followed, so beta1 <= 0.5 is served.  A NaN gradient stays NaN through the clip, as clamp_ leaves it, and makes its parameter
+    NaN; +-inf is clipped.  Parameters whose grad is None are left alone with their state; a zero-element parameter is stepped
+    over.  tests/adam_reference.py restates the step; tests/test_gpu_adam.py holds the kernel to it bit for bit."""
 
     def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_value=40.0):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, clip_value=clip_value,
